@@ -167,6 +167,57 @@ def emit(full, path=None):
     print(compact_record(full), flush=True)
 
 
+# ---- --dump-outputs DIR ---------------------------------------------------------------------------------------------------------------
+# What the timed path computed in its last step, one DIR/<name>.npy per array (float64 stays float64, every other dtype becomes float32), so that two
+# builds run with the same arguments can be compared output for output.  At most DUMP_LIMIT_BYTES in all: small arrays are written whole, the budget
+# left over is shared evenly by the large ones, and an array beyond its share keeps a sorted sample of its flattened elements whose indices depend
+# only on its name and size (the same elements in every run).
+DUMP_LIMIT_BYTES = 60 * 10 ** 6         # (below 64 MB counted either way, with room for the .npy headers)
+
+
+def dump_sample_indices(name, numel, keep):
+    """sorted flat indices of the `keep`-element sample of an array called `name` with `numel` elements (a seeded draw, duplicates dropped)"""
+    import zlib
+    rng = np.random.default_rng(zlib.crc32(name.encode()) ^ numel)
+    return np.unique(rng.integers(0, numel, size=keep, dtype=np.int64))
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """arrays: {name: tensor or ndarray}.  Writes path/<name>.npy for each, within `limit` bytes in all; returns {name: None if written whole, else
+    the flat indices of the sample written}."""
+    os.makedirs(path, exist_ok=True)
+    items = []
+    for name, a in arrays.items():
+        t = a.detach() if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))
+        t = t.reshape(-1).to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        items.append((name, tuple(a.shape), t))
+    left, written = limit, {}
+    for i, (name, shape, t) in enumerate(sorted(items, key=lambda x: x[2].numel())):
+        share = left // (len(items) - i)
+        keep = min(t.numel(), share // t.element_size())
+        idx = None
+        if keep < t.numel():
+            idx = dump_sample_indices(name, t.numel(), keep)
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        else:
+            t = t.reshape(shape)
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+        left -= t.numel() * t.element_size()
+        written[name] = idx
+    return written
+
+
+def trained_parameters(**modules):
+    """{<module>.<parameter name>: parameter} of every parameter an optimisation step updates, each once (both models share the planes)"""
+    out, seen = {}, set()
+    for tag, m in modules.items():
+        for n, p in m.named_parameters():
+            if p.requires_grad and id(p) not in seen:
+                seen.add(id(p))
+                out[tag + "." + n] = p
+    return out
+
+
 class Opt:
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -620,6 +671,8 @@ def bench_train(args, nvsr_amd, dist, dev, rank, world):
         train_partition_check(nvsr_amd, dist, dev, rank, world, mc, mf, sid, scfg, opts, pose, H, W, focal, N, Nc, Nf, planes, dec, what)
 
     elapsed = _sync_time(dist, dev, one, args.warmup, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trained_parameters(coarse=mc, fine=mf))
     value = world * N * args.steps / elapsed
     host_issue_ms = 1e3 * _sync_time.issue_s / args.steps
     label = "planes + decoder gradients" if "decoder" in what else "plane gradients (Feature_Planes_Only.yml: what = ['LR_planes'])"
@@ -749,6 +802,8 @@ def bench_sr(args, nvsr_amd, dist, dev, rank, world):
         if not same:
             sys.exit(3)
     elapsed = _sync_time(dist, dev, one, args.warmup, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"sr_plane_" + n: sr.SR_planes[n] for n in names})
     value = (1 if bands else world) * 3 * args.steps / elapsed
     mode = nvsr_amd.capi.get_conv_arithmetic()
     arith = ARITHMETIC[mode]
@@ -950,6 +1005,8 @@ def bench_refine(args, nvsr_amd, dist, dev, rank, world):
         return m
 
     elapsed = _sync_time(dist, dev, one, args.warmup, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trained_parameters(sr=sr, coarse=mc, fine=mf))
     host_issue_ms = 1e3 * _sync_time.issue_s / args.steps
     if world > 1 and os.environ.get("NVSR_BENCH_REHEARSAL", "0") == "1":
         # rehearsal (tests/test_hip_round5.py): every rank started from the same parameters and stepped on the same averaged gradients -- a sample of
@@ -1140,7 +1197,14 @@ def main():
                     help="also write the full record (every key; the stdout line is its compact form, <= 4 KB) to PATH")
     ap.add_argument("--no-other-workloads", action="store_true",
                     help="--workload render, N = 1: do not append the short train / sr runs (`other_workloads` of the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0; float32 / float64, <= 64 MB in all, a seeded "
+                         "sample of larger outputs): render = the coarse and fine images, sr = the super-resolved planes, train / refine = every "
+                         "parameter the step updates.  render and sr repeat bit for bit; train and refine do not (their gradients are sums of "
+                         "float atomics)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: become the launcher.  Nothing in this process has touched the GPU yet (no HIP call, no
@@ -1258,6 +1322,9 @@ def main():
         t = torch.tensor([elapsed], device=dev if dist.get_backend() == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # "view": eval_nerf's (rgb_coarse, .., .., rgb_fine, ..) of this rank's view; "frame" / "rows": the assembled (coarse, fine) frame(s)
+        dump_outputs(args.dump_outputs, {"rgb_coarse": out[0], "rgb_fine": out[3] if partition == "view" else out[1]})
 
     rays_per_step = H * W                                            # per GPU and step ("frame": of the whole job)
     frames_per_step = 1 if partition == "frame" else world
@@ -1413,6 +1480,7 @@ def main():
             sub = argparse.Namespace(**vars(args))
             # their CPU legs share one convolution probe and one render probe per sample count (sub.cpu_cache), ~25 s of host time in all
             sub.no_cpu_baseline, sub.no_modes, sub.cpu_cache = args.no_cpu_baseline, False, {}
+            sub.dump_outputs = None                # (the dump is the headline render's)
             other = {}
             for wl, fn, steps, warm, extra in (("train", bench_train, 30, 5, {"train_what": "planes"}),
                                                ("train_decoder", bench_train, 20, 3, {"train_what": "planes+decoder"}),

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """Golden-vector generator (BUILD CONTAINER ONLY).
 
-Imports the upstream reference from /root/reference (read-only, pure PyTorch) behind the
+Imports the upstream reference (a checkout of the original project, pure PyTorch, read-only) behind the
 shims documented in SURVEY.md Appendix A, runs its hot-path functions on small seeded
 inputs on the CPU, and writes inputs + expected outputs as .npz fixtures next to this
 script.  The fixtures are data only; nothing of the reference travels with the repo.
 
-Re-run:  python tests/golden/gen_golden.py          (needs /root/reference)
+Re-run:  NVSR_REFERENCE_DIR=<upstream checkout> python tests/golden/gen_golden.py [g01 g02 ...]
 
 Fixture index:
   g01_raybundle.npz   get_ray_bundle                    nerf_helpers.py:507-549
@@ -46,10 +46,12 @@ import torch
 import torch.nn as nn
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = "/root/reference"
+REF = os.environ.get("NVSR_REFERENCE_DIR", "")
 
 
 def import_reference():
+    if not os.path.isdir(REF):
+        sys.exit("gen_golden.py: set NVSR_REFERENCE_DIR to a checkout of the upstream project")
     for m in ["cv2", "torchvision", "imageio", "magic", "deepdiff"]:
         sys.modules[m] = types.ModuleType(m)
     sys.modules["magic"].from_file = lambda *a, **k: None

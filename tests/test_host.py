@@ -646,6 +646,33 @@ def test_bench_emit_prints_the_compact_line_last(tmp_path, capsys, monkeypatch):
     assert cap.err.startswith("BENCH_FULL_RECORD {") and json.load(open(tmp_path / "bench_full.json")) == full
 
 
+def test_bench_dump_outputs_stays_within_its_budget_and_samples_the_same_elements(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): one <name>.npy per array, float64 kept and everything else float32; arrays that fit are written whole,
+    the rest as a seeded sample of the flattened array that is the same in every run; all files together stay within the limit"""
+    import bench
+    g = torch.Generator().manual_seed(0)
+    arrays = {"small": torch.randn(4, 5, generator=g), "wide": torch.randn(3000, generator=g, dtype=torch.float64),
+              "big": torch.randn(100, 100, generator=g), "half": torch.randn(64, generator=g).half()}
+    limit = 40000
+    for d in ("a", "b"):
+        written = bench.dump_outputs(str(tmp_path / d), arrays, limit=limit)
+        assert set(written) == set(arrays) and sorted(os.listdir(tmp_path / d)) == sorted(n + ".npy" for n in arrays)
+    total = 0
+    for n, a in arrays.items():
+        got, again = np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy"))
+        assert np.array_equal(got, again) and got.dtype == (np.float64 if n == "wide" else np.float32)
+        total += got.nbytes
+        flat = a.reshape(-1).double().numpy()
+        idx = written[n]
+        if idx is None:
+            assert got.shape == tuple(a.shape) and np.array_equal(got.reshape(-1), flat.astype(got.dtype))
+        else:
+            assert got.ndim == 1 and 0 < got.size == idx.size < a.numel() and (np.diff(idx) > 0).all()
+            assert np.array_equal(got, flat[idx].astype(got.dtype))
+    assert total <= limit
+    assert written["small"] is None and written["half"] is None and written["big"] is not None and written["wide"] is not None
+
+
 def test_fused_optimizer_steps_bump_the_version_counters():
     """Every derived copy of the parameters (packed decoder / EDSR blobs, channel-last plane copies, the f16 range cache) is keyed on
     (data_ptr, tensor._version); torch's fused optimizers write the parameters WITHOUT bumping the counters (checked here: if torch ever changes
