@@ -344,6 +344,32 @@ int nvsr_positional_encoding(int64_t P, int D, const float* x, int L, int includ
 int nvsr_flexible_nerf_forward(int64_t P, const float* x, int dim_xyz, int dim_dir, int hidden, int num_layers, int skip_every,
                                const float* blob, float* out, nvsr_stream_t stream);
 
+/* ---- the Mip-NeRF baseline (MipNeRF_baseline.yml; csrc/mip.hip) -------------------------------------------------------------
+ * FlexibleNeRFModel(include_input_xyz=False) with the constructor defaults (train_nerf.py:342-348 passes only the encoding arguments):
+ * layer1 36->128 (linear), 3 x ReLU(128->128), ReLU(fc_feat) 128->128, fc_alpha 128->1, ReLU(layers_dir(cat(feat, dir))) 155->64, fc_rgb 64->3.
+ * natural = state-dict order (layer1, layers_xyz.0-2, layers_dir.0, fc_alpha, fc_rgb, fc_feat, each {weight[out,in], bias}).
+ * rays [N,11] (nvsr_pack_rays), edges [N,S+1] (the S intervals of each ray), radius = ds 0.00135 2 / sqrt(12) (train_utils.py:19-27).
+ * arithmetic: NVSR_ARITH_F32 or NVSR_ARITH_BF16X3 (NVSR_ARITH_INHERIT = the decoder default); a request for NVSR_ARITH_F16X2 runs
+ * NVSR_ARITH_BF16X3 -- this model has no f16 range check, and the 3 bf16 limbs have no range limit. */
+#define NVSR_MIP_NERF_NATURAL_FLOATS 81092
+#define NVSR_MIP_NERF_RECORD_FLOATS 767        /* per point: [enc 36 | dir 27 | h1 | h2 | h3 | h4 | feat (128 each) | hd 64] */
+#define NVSR_MIP_NERF_GRAD_RECORD_FLOATS 708   /* per point: pre-activation gradients [layer1 | x0 | x1 | x2 | feat (128 each) | alpha | dir 64 | rgb 3] */
+/* cast_rays + IntegratedPositionalEncoding (mip.py:9-44,154-199; degrees 2^0..2^5) and positional_encoding(viewdir, 4):
+ * -> out [N*S, 63] = [18 sin | 18 cos (IPE, (degree, axis) with the degree major) | 27 direction columns] */
+int nvsr_mip_encode(int64_t N, int S, const float* rays, const float* edges, double radius, float* out, nvsr_stream_t stream);
+/* encoding + model on one 32-interval tile per wave, the encoded rows never leave the chip -> raw [N,S,4] (16-byte aligned);
+ * record [N*S, NVSR_MIP_NERF_RECORD_FLOATS] or NULL: every layer input and ReLU output, for the backward */
+int nvsr_mip_nerf_forward_arith(int64_t N, int S, const float* rays, const float* edges, double radius, const float* natural, float* raw,
+                                float* record, int arithmetic, nvsr_stream_t stream);
+/* g_raw [P,4] -> grad_record [P, NVSR_MIP_NERF_GRAD_RECORD_FLOATS] (the gradient of every layer's pre-activation output) */
+int nvsr_mip_nerf_backward_arith(int64_t P, const float* natural, const float* record, const float* g_raw, float* grad_record, int arithmetic,
+                                 nvsr_stream_t stream);
+/* grad_natural [NVSR_MIP_NERF_NATURAL_FLOATS] = sum over the P points of every layer's G^T X and G (overwritten, not accumulated).
+ * Exact-f32 products, partial sums per slab of points in workspace [nvsr_mip_nerf_wgrad_workspace_floats(P)] added in a fixed order:
+ * no float atomics, the same inputs give the same bits. */
+int64_t nvsr_mip_nerf_wgrad_workspace_floats(int64_t P);
+int nvsr_mip_nerf_weight_grad(int64_t P, const float* record, const float* grad_record, float* workspace, float* grad_natural, nvsr_stream_t stream);
+
 /* ---- training: gradient with respect to the feature planes -------------------------------------------------------------
  * The reference differentiates run_one_iter_of_nerf with torch.autograd (train_nerf.py:860-903); with the decoder frozen
  * (Feature_Planes_Only.yml) the leaves are the planes.  z_samples carry no gradient (`.detach()`, train_utils.py:153). */

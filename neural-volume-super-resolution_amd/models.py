@@ -1056,6 +1056,35 @@ class FlexibleNeRFModel(nn.Module):
             if l.in_features != expect:
                 raise NotImplementedError("this num_layers / skip_connect_every combination is inconsistent in the reference as well")
 
+    arithmetic = "bf16x3"     # of the Mip-NeRF path (mip_forward): 'f32' | 'bf16x3'; 'f16x2' runs 'bf16x3' (include/nvsr.h)
+
+    def _layers(self):
+        return [self.layer1] + list(self.layers_xyz) + [self.layers_dir[0], self.fc_alpha, self.fc_rgb, self.fc_feat]
+
+    def natural_blob(self, differentiable=False):
+        """parameters in state-dict order, one flat f32 tensor; differentiable=True keeps the graph to every nn.Linear, otherwise the blob is
+        cached against the parameters' versions"""
+        params = [t for m in self._layers() for t in (m.weight, m.bias)]
+        if differentiable:
+            return torch.cat([t.reshape(-1).float() for t in params])
+        key = tuple((p.data_ptr(), p._version) for p in params)
+        cache = self.__dict__.get("_natural_cache")
+        if cache is None or cache[0] != key:
+            cache = self.__dict__["_natural_cache"] = (key, torch.cat([t.detach().reshape(-1).float() for t in params]))
+        return cache[1]
+
+    def mip_forward(self, rays, edges, radius):
+        """The Mip-NeRF baseline's model call (train_utils.py:19-64 with mip_nerf=True, then forward): packed rays [N,11], interval edges
+        [N,S+1], the cone radius -> raw [N,S,4].  The integrated positional encoding happens inside the kernel; with gradients enabled,
+        loss.backward() reaches every nn.Linear of the model."""
+        if self.dim_xyz != 36 or self.dim_dir != 27 or self.hidden_size != 128 or self.num_layers != 4:
+            raise NotImplementedError("the Mip-NeRF kernels are built for FlexibleNeRFModel(include_input_xyz=False) with the constructor defaults")
+        grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        nat = self.natural_blob(differentiable=grad)
+        capi.require_cuda(nat)
+        raw, _ = torch.ops.nvsr.mip_nerf(rays, edges, float(radius), nat, grad, capi.arith_code(self.arithmetic))
+        return raw
+
     def forward(self, x):
         x = capi.f32c(x)
         assert x.shape[-1] == self.dim_xyz + self.dim_dir

@@ -506,6 +506,100 @@ def _(record, N, S, arithmetic):
 
 
 # =====================================================================================================================================
+# the Mip-NeRF baseline (mip.py, models.py:14-108; csrc/mip.hip): integrated positional encoding + FlexibleNeRFModel, forward and training
+# =====================================================================================================================================
+@custom_op("nvsr::mip_encode", mutates_args=(), device_types="cuda")
+def mip_encode(rays: Tensor, edges: Tensor, radius: float) -> Tensor:
+    """rays [N,11], edges [N,S+1] -> [N*S, 63] = [36 IPE columns | 27 direction columns] (what the fused forward computes on chip)"""
+    rays, edges = _c(rays), _c(edges)
+    N, S = edges.shape[0], edges.shape[1] - 1
+    out = _f(N * S, 63, like=rays)
+    if N:
+        capi.call("nvsr_mip_encode", N, S, capi.ptr(rays), capi.ptr(edges), float(radius), capi.ptr(out), capi.stream())
+    return out
+
+
+@mip_encode.register_fake
+def _(rays, edges, radius):
+    return rays.new_empty((edges.shape[0] * (edges.shape[1] - 1), 63))
+
+
+@custom_op("nvsr::mip_nerf", mutates_args=(), device_types="cuda")
+def mip_nerf(rays: Tensor, edges: Tensor, radius: float, natural: Tensor, want_record: bool, arithmetic: int) -> Tuple[Tensor, Tensor]:
+    """encoding + FlexibleNeRFModel over the S intervals of every ray -> raw [N,S,4], record [N*S, MIP_NERF_RECORD_FLOATS] (empty unless
+    want_record).  Differentiable in `natural` (state-dict order) when want_record."""
+    rays, edges, natural = _c(rays), _c(edges), _c(natural)
+    assert natural.numel() == capi.MIP_NERF_NATURAL_FLOATS
+    N, S = edges.shape[0], edges.shape[1] - 1
+    raw = _f(N, S, 4, like=rays)
+    rec = _f(N * S, capi.MIP_NERF_RECORD_FLOATS, like=rays) if want_record else _f(0, like=rays)
+    if N:
+        capi.call("nvsr_mip_nerf_forward_arith", N, S, capi.ptr(rays), capi.ptr(edges), float(radius), capi.ptr(natural), capi.ptr(raw),
+                  capi.ptr(rec) if want_record else None, arithmetic, capi.stream())
+    return raw, rec
+
+
+@mip_nerf.register_fake
+def _(rays, edges, radius, natural, want_record, arithmetic):
+    N, S = edges.shape[0], edges.shape[1] - 1
+    return rays.new_empty((N, S, 4)), rays.new_empty((N * S, capi.MIP_NERF_RECORD_FLOATS) if want_record else (0,))
+
+
+@custom_op("nvsr::mip_nerf_backward", mutates_args=(), device_types="cuda")
+def mip_nerf_backward(natural: Tensor, record: Tensor, g_raw: Tensor, arithmetic: int) -> Tensor:
+    """g_raw [P,4] (any shape with P * 4 elements) -> the pre-activation gradient of every layer [P, MIP_NERF_GRAD_RECORD_FLOATS]"""
+    natural, record, g_raw = _c(natural), _c(record), _c(g_raw)
+    P = record.shape[0]
+    assert g_raw.numel() == 4 * P
+    grec = _f(P, capi.MIP_NERF_GRAD_RECORD_FLOATS, like=record)
+    if P:
+        capi.call("nvsr_mip_nerf_backward_arith", P, capi.ptr(natural), capi.ptr(record), capi.ptr(g_raw), capi.ptr(grec), arithmetic, capi.stream())
+    return grec
+
+
+@mip_nerf_backward.register_fake
+def _(natural, record, g_raw, arithmetic):
+    return record.new_empty((record.shape[0], capi.MIP_NERF_GRAD_RECORD_FLOATS))
+
+
+@custom_op("nvsr::mip_nerf_weight_grad", mutates_args=(), device_types="cuda")
+def mip_nerf_weight_grad(record: Tensor, grad_record: Tensor) -> Tensor:
+    """sum over the points of every layer's G^T X and G -> the gradient of the natural blob (fixed summation order: bit-reproducible)"""
+    record, grad_record = _c(record), _c(grad_record)
+    P = record.shape[0]
+    g = _f(capi.MIP_NERF_NATURAL_FLOATS, like=record)
+    ws = _f(max(1, int(capi.lib().nvsr_mip_nerf_wgrad_workspace_floats(P))), like=record)
+    capi.call("nvsr_mip_nerf_weight_grad", P, capi.ptr(record), capi.ptr(grad_record), capi.ptr(ws), capi.ptr(g), capi.stream())
+    return g
+
+
+@mip_nerf_weight_grad.register_fake
+def _(record, grad_record):
+    return record.new_empty((capi.MIP_NERF_NATURAL_FLOATS,))
+
+
+def _mip_nerf_setup(ctx, inputs, output):
+    rays, edges, radius, natural, want_record, arithmetic = inputs
+    ctx.save_for_backward(natural, output[1])
+    ctx.want_record, ctx.arithmetic = want_record, arithmetic
+    ctx.mark_non_differentiable(output[1])
+
+
+def _mip_nerf_bwd(ctx, g_raw, g_rec):
+    natural, record = ctx.saved_tensors
+    if not ctx.want_record:
+        raise RuntimeError("nvsr::mip_nerf was called with want_record=False: no record for its backward")
+    g_nat = None
+    if ctx.needs_input_grad[3] and g_raw is not None:
+        grec = torch.ops.nvsr.mip_nerf_backward(natural, record, g_raw, ctx.arithmetic)
+        g_nat = torch.ops.nvsr.mip_nerf_weight_grad(record, grec)
+    return None, None, None, g_nat, None, None
+
+
+mip_nerf.register_autograd(_mip_nerf_bwd, setup_context=_mip_nerf_setup)
+
+
+# =====================================================================================================================================
 # compositing (volume_rendering_utils.py:6-51)
 # =====================================================================================================================================
 @custom_op("nvsr::composite", mutates_args=(), device_types="cuda")

@@ -536,6 +536,11 @@ def run_one_iter_of_nerf(H, W, focal, model_coarse, model_fine, batch_rays, opti
     """train_utils.py:185-282 -> (rgb_coarse, disp_coarse, acc_coarse, rgb_fine, disp_fine, acc_fine, None, None, None)
     ray_grid_width (not in the reference): the rays are whole rows of a row-major pixel grid of this width (eval_nerf, the row-sharded
     renders) -- an evaluation pass then renders them in patch order (patch_order) and returns the results in the caller's order."""
+    if isinstance(model_coarse, models.FlexibleNeRFModel):
+        if _cfg(options.nerf, "encode_position_fn", None) != "mip":
+            raise NotImplementedError("FlexibleNeRFModel runs as the Mip-NeRF baseline only (nerf.encode_position_fn: mip); the plain "
+                                      "positional-encoding NeRF is not supported")
+        return _run_mip(H, W, focal, model_coarse, model_fine, batch_rays, options, scene_id, mode, scene_config, randoms)
     if not isinstance(model_coarse, models.TwoDimPlanesModel):
         raise NotImplementedError("only the tri-plane model is on the accelerated path")
     if not options.nerf.use_viewdirs:
@@ -628,6 +633,71 @@ def run_one_iter_of_nerf(H, W, focal, model_coarse, model_fine, batch_rays, opti
     if inv is not None:
         out = tuple(None if t is None else t.index_select(0, inv) for t in out)
     return out
+
+
+def mip_radius(scene_id):
+    """the cone radius of the Mip-NeRF baseline (train_utils.py:19-27): ds 0.00135 2 / sqrt(12), ds = the scene id's trailing _DS<d>"""
+    import re
+    import numpy as np
+    m = re.search(r"(?<=_DS)(\d)+(?=$)", str(scene_id))
+    if m is None:
+        raise ValueError("Mip-NeRF needs the downsampling factor at the end of the scene id (e.g. 'lego_DS8'); got %r" % (scene_id,))
+    return int(m.group(0)) * 0.00135 * 2 / np.sqrt(12.0)
+
+
+def _run_mip(H, W, focal, model_coarse, model_fine, batch_rays, options, scene_id, mode, scene_config, randoms):
+    """run_one_iter_of_nerf + predict_and_render_radiance with mip_nerf=True (train_utils.py:71-282): Nc + 1 coarse edges, the fused
+    encoding + model kernel per pass, the interval compositor, sample_pdf_2 on the mid-points of the mid-points with weights[..., 1:-1],
+    Nf + 1 samples, sort(cat(edges, samples)).  Gradients reach both models (the coarse pass's optional_no_grad is a null context upstream);
+    the depths are detached."""
+    if not options.nerf.use_viewdirs:
+        raise NotImplementedError("the Mip-NeRF kernels expect use_viewdirs=True (MipNeRF_baseline.yml)")
+    from . import nerf_helpers
+    radius = mip_radius(scene_id)
+    rays = pack_rays(batch_rays[0], batch_rays[1], _cfg(scene_config, "near"), _cfg(scene_config, "far"), H, W, focal,
+                     no_ndc=_cfg(scene_config, "no_ndc"))
+    N = rays.shape[0]
+    m = _cfg(options.nerf, mode)
+    Nc, Nf, std = int(m.num_coarse), int(m.num_fine), float(m.radiance_field_noise_std)
+    if randoms is None and (m.perturb or std > 0.0):
+        # per reference ray chunk (chunksize // 4 with mip, train_utils.py:228-235), in the reference's order: t_rand, coarse noise, u, fine noise
+        parts = []
+        chunk = max(1, int(m.chunksize) // 4)
+        for a in range(0, N, chunk):
+            n = min(a + chunk, N) - a
+            p = {}
+            if m.perturb:
+                p["t_rand"] = torch.rand([n, Nc + 1])
+            if std > 0.0:
+                p["noise_coarse"] = torch.randn([n, Nc]) * std
+            if Nf > 0 and m.perturb != 0.0:
+                p["u"] = torch.rand([n, Nf + 1])
+            if Nf > 0 and std > 0.0:
+                p["noise_fine"] = torch.randn([n, Nc + Nf + 1]) * std
+            parts.append(p)
+        randoms = {k: torch.cat([p[k] for p in parts], 0) for k in parts[0]} if parts else {}
+    r = randoms or {}
+    dev = rays.device
+    t_rand, u, n_c, n_f = (None if r.get(k) is None else capi.f32c(r[k].to(dev)) for k in ("t_rand", "u", "noise_coarse", "noise_fine"))
+    if not m.perturb:
+        t_rand = None
+    white, lindisp = bool(m.white_background), bool(m.lindisp)
+    nv = torch.ops.nvsr
+    if N == 0:
+        e = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
+        return (e(0, 3), e(0), e(0)) + ((e(0, 3), e(0), e(0)) if Nf > 0 else (None, None, None)) + (None, None, None)
+    rd = rays[:, 3:6].contiguous()
+    edges_c = nv.coarse_z(rays, Nc + 1, lindisp, t_rand)
+    raw_c = model_coarse.mip_forward(rays, edges_c, radius)
+    rgb_c, disp_c, acc_c, w_c, _ = nv.composite(raw_c, edges_c, rd, n_c, white, True)
+    rgb_f = disp_f = acc_f = None
+    if Nf > 0:
+        mid = lambda z: 0.5 * (z[..., 1:] + z[..., :-1])
+        samples = nerf_helpers.sample_pdf_2(mid(mid(edges_c)), w_c.detach()[..., 1:-1].contiguous(), Nf + 1, det=(m.perturb == 0.0), u=u)
+        edges_f = nerf_helpers.sort_depths(torch.cat((edges_c, samples), dim=-1))
+        raw_f = model_fine.mip_forward(rays, edges_f, radius)
+        rgb_f, disp_f, acc_f, _, _ = nv.composite(raw_f, edges_f, rd, n_f, white, True)
+    return rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f, None, None, None
 
 
 def eval_nerf(height, width, focal_length, model_coarse, model_fine, ray_origins, ray_directions, options, scene_id,
