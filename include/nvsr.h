@@ -370,6 +370,30 @@ int nvsr_mip_nerf_backward_arith(int64_t P, const float* natural, const float* r
 int64_t nvsr_mip_nerf_wgrad_workspace_floats(int64_t P);
 int nvsr_mip_nerf_weight_grad(int64_t P, const float* record, const float* grad_record, float* workspace, float* grad_natural, nvsr_stream_t stream);
 
+/* ---- the positional-encoding NeRF baseline (MipNeRF_baseline.yml with encode_position_fn: positional_encoding; csrc/pe.hip) ------------
+ * FlexibleNeRFModel(num_encoding_fn_xyz=6, num_encoding_fn_dir=4, include_input_xyz=True, include_input_dir=True) with the constructor
+ * defaults (train_nerf.py:338-348): the Mip-NeRF model above with layer1 39->128.  Same natural order, the same layer engine (csrc/nerf_mlp.h).
+ * rays [N,11] (nvsr_pack_rays), z [N,S] (the S sample depths of each ray); arithmetic as for the Mip-NeRF baseline. */
+#define NVSR_PE_NERF_NATURAL_FLOATS 81476
+#define NVSR_PE_NERF_RECORD_FLOATS 770         /* per point: [enc 39 | dir 27 | h1 | h2 | h3 | h4 | feat (128 each) | hd 64] */
+#define NVSR_PE_NERF_GRAD_RECORD_FLOATS 708    /* per point: pre-activation gradients, the layout of NVSR_MIP_NERF_GRAD_RECORD_FLOATS */
+/* pts = ro + rd z (train_utils.py:111,156; two f32 roundings) -> positional_encoding(pts, 6, True) and positional_encoding(viewdir, 4, True)
+ * (nerf_helpers.py:552-575): out [N*S, 66] = [x | sin(2^0 x) | cos(2^0 x) | .. | sin(2^5 x) | cos(2^5 x) (3 columns each) | 27 direction columns] */
+int nvsr_pe_encode(int64_t N, int S, const float* rays, const float* z, float* out, nvsr_stream_t stream);
+/* run_network + FlexibleNeRFModel.forward (train_utils.py:15-64 with mip_nerf=False, models.py:83-108): encoding + model on one 32-point
+ * tile per wave, the encoded rows never leave the chip -> raw [N,S,4] (16-byte aligned);
+ * record [N*S, NVSR_PE_NERF_RECORD_FLOATS] or NULL: every layer input and ReLU output, for the backward */
+int nvsr_pe_nerf_forward_arith(int64_t N, int S, const float* rays, const float* z, const float* natural, float* raw, float* record, int arithmetic,
+                               nvsr_stream_t stream);
+/* the backward of FlexibleNeRFModel.forward (models.py:83-108): g_raw [P,4] -> grad_record [P, NVSR_PE_NERF_GRAD_RECORD_FLOATS] */
+int nvsr_pe_nerf_backward_arith(int64_t P, const float* natural, const float* record, const float* g_raw, float* grad_record, int arithmetic,
+                                nvsr_stream_t stream);
+/* the nn.Linear weight and bias gradients of FlexibleNeRFModel (models.py:14-108): grad_natural [NVSR_PE_NERF_NATURAL_FLOATS] (overwritten),
+ * fixed-order sums over slabs of points in workspace [nvsr_pe_nerf_wgrad_workspace_floats(P)]: no float atomics, the same inputs give the
+ * same bits. */
+int64_t nvsr_pe_nerf_wgrad_workspace_floats(int64_t P);
+int nvsr_pe_nerf_weight_grad(int64_t P, const float* record, const float* grad_record, float* workspace, float* grad_natural, nvsr_stream_t stream);
+
 /* ---- training: gradient with respect to the feature planes -------------------------------------------------------------
  * The reference differentiates run_one_iter_of_nerf with torch.autograd (train_nerf.py:860-903); with the decoder frozen
  * (Feature_Planes_Only.yml) the leaves are the planes.  z_samples carry no gradient (`.detach()`, train_utils.py:153). */

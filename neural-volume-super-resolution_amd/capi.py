@@ -22,6 +22,9 @@ DECODER_PACKED_BWD_FLOATS = 487424
 MIP_NERF_NATURAL_FLOATS = 81092      # NVSR_MIP_NERF_NATURAL_FLOATS
 MIP_NERF_RECORD_FLOATS = 767         # NVSR_MIP_NERF_RECORD_FLOATS
 MIP_NERF_GRAD_RECORD_FLOATS = 708    # NVSR_MIP_NERF_GRAD_RECORD_FLOATS
+PE_NERF_NATURAL_FLOATS = 81476       # NVSR_PE_NERF_NATURAL_FLOATS
+PE_NERF_RECORD_FLOATS = 770          # NVSR_PE_NERF_RECORD_FLOATS
+PE_NERF_GRAD_RECORD_FLOATS = 708     # NVSR_PE_NERF_GRAD_RECORD_FLOATS
 MSE_PAIR_MAX_ELEMS = 1 << 22          # NVSR_MSE_PAIR_MAX_ELEMS
 
 _STATUS = {1: "NVSR_ERR_SHAPE (argument out of the supported range)", 2: "NVSR_ERR_LAUNCH (kernel launch failed)",
@@ -201,6 +204,12 @@ _PROTOS_OPTIONAL = {   # feature-plane super-resolution (csrc/sr.hip)
     "nvsr_mip_nerf_backward_arith": ([_i64, _vp, _vp, _vp, _vp, _i, _vp], _i),
     "nvsr_mip_nerf_wgrad_workspace_floats": ([_i64], _i64),
     "nvsr_mip_nerf_weight_grad": ([_i64, _vp, _vp, _vp, _vp, _vp], _i),
+    # the positional-encoding NeRF baseline (csrc/pe.hip)
+    "nvsr_pe_encode": ([_i64, _i, _vp, _vp, _vp, _vp], _i),
+    "nvsr_pe_nerf_forward_arith": ([_i64, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp], _i),
+    "nvsr_pe_nerf_backward_arith": ([_i64, _vp, _vp, _vp, _vp, _i, _vp], _i),
+    "nvsr_pe_nerf_wgrad_workspace_floats": ([_i64], _i64),
+    "nvsr_pe_nerf_weight_grad": ([_i64, _vp, _vp, _vp, _vp, _vp], _i),
 }
 
 _lib = None

@@ -1056,7 +1056,7 @@ class FlexibleNeRFModel(nn.Module):
             if l.in_features != expect:
                 raise NotImplementedError("this num_layers / skip_connect_every combination is inconsistent in the reference as well")
 
-    arithmetic = "bf16x3"     # of the Mip-NeRF path (mip_forward): 'f32' | 'bf16x3'; 'f16x2' runs 'bf16x3' (include/nvsr.h)
+    arithmetic = "bf16x3"     # of the fused paths (mip_forward, pe_forward): 'f32' | 'bf16x3'; 'f16x2' runs 'bf16x3' (include/nvsr.h)
 
     def _layers(self):
         return [self.layer1] + list(self.layers_xyz) + [self.layers_dir[0], self.fc_alpha, self.fc_rgb, self.fc_feat]
@@ -1083,6 +1083,25 @@ class FlexibleNeRFModel(nn.Module):
         nat = self.natural_blob(differentiable=grad)
         capi.require_cuda(nat)
         raw, _ = torch.ops.nvsr.mip_nerf(rays, edges, float(radius), nat, grad, capi.arith_code(self.arithmetic))
+        return raw
+
+    def is_pe_baseline(self):
+        """the geometry the positional-encoding kernels are built for: num_encoding_fn_xyz=6, num_encoding_fn_dir=4, include_input_xyz and
+        include_input_dir, the constructor defaults otherwise (dim_xyz 39 and dim_dir 27 admit no other encoding counts)"""
+        return (self.dim_xyz == 39 and self.dim_dir == 27 and self.hidden_size == 128 and self.num_layers == 4
+                and all(l.in_features == 128 for l in self.layers_xyz))
+
+    def pe_forward(self, rays, z):
+        """The positional-encoding baseline's model call (train_utils.py:15-64 with mip_nerf=False, then forward): packed rays [N,11], sample
+        depths z [N,S] -> raw [N,S,4].  The points ro + rd z and their positional encoding happen inside the kernel; with gradients enabled,
+        loss.backward() reaches every nn.Linear of the model."""
+        if not self.is_pe_baseline():
+            raise NotImplementedError("the positional-encoding kernels are built for FlexibleNeRFModel(num_encoding_fn_xyz=6, num_encoding_fn_dir=4, "
+                                      "include_input_xyz=True, include_input_dir=True) with the constructor defaults")
+        grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        nat = self.natural_blob(differentiable=grad)
+        capi.require_cuda(nat)
+        raw, _ = torch.ops.nvsr.pe_nerf(rays, z, nat, grad, capi.arith_code(self.arithmetic))
         return raw
 
     def forward(self, x):

@@ -600,6 +600,101 @@ mip_nerf.register_autograd(_mip_nerf_bwd, setup_context=_mip_nerf_setup)
 
 
 # =====================================================================================================================================
+# the positional-encoding NeRF baseline (train_utils.py:71-182 with mip_nerf=False, nerf_helpers.py:552-575, models.py:14-108;
+# csrc/pe.hip): points ro + rd z, positional encoding + FlexibleNeRFModel, forward and training
+# =====================================================================================================================================
+@custom_op("nvsr::pe_encode", mutates_args=(), device_types="cuda")
+def pe_encode(rays: Tensor, z: Tensor) -> Tensor:
+    """rays [N,11], z [N,S] -> [N*S, 66] = [39 position columns | 27 direction columns] (what the fused forward computes on chip)"""
+    rays, z = _c(rays), _c(z)
+    N, S = z.shape
+    out = _f(N * S, 66, like=rays)
+    if N:
+        capi.call("nvsr_pe_encode", N, S, capi.ptr(rays), capi.ptr(z), capi.ptr(out), capi.stream())
+    return out
+
+
+@pe_encode.register_fake
+def _(rays, z):
+    return rays.new_empty((z.shape[0] * z.shape[1], 66))
+
+
+@custom_op("nvsr::pe_nerf", mutates_args=(), device_types="cuda")
+def pe_nerf(rays: Tensor, z: Tensor, natural: Tensor, want_record: bool, arithmetic: int) -> Tuple[Tensor, Tensor]:
+    """encoding + FlexibleNeRFModel at the S depths of every ray -> raw [N,S,4], record [N*S, PE_NERF_RECORD_FLOATS] (empty unless
+    want_record).  Differentiable in `natural` (state-dict order) when want_record."""
+    rays, z, natural = _c(rays), _c(z), _c(natural)
+    assert natural.numel() == capi.PE_NERF_NATURAL_FLOATS
+    N, S = z.shape
+    raw = _f(N, S, 4, like=rays)
+    rec = _f(N * S, capi.PE_NERF_RECORD_FLOATS, like=rays) if want_record else _f(0, like=rays)
+    if N:
+        capi.call("nvsr_pe_nerf_forward_arith", N, S, capi.ptr(rays), capi.ptr(z), capi.ptr(natural), capi.ptr(raw),
+                  capi.ptr(rec) if want_record else None, arithmetic, capi.stream())
+    return raw, rec
+
+
+@pe_nerf.register_fake
+def _(rays, z, natural, want_record, arithmetic):
+    N, S = z.shape
+    return rays.new_empty((N, S, 4)), rays.new_empty((N * S, capi.PE_NERF_RECORD_FLOATS) if want_record else (0,))
+
+
+@custom_op("nvsr::pe_nerf_backward", mutates_args=(), device_types="cuda")
+def pe_nerf_backward(natural: Tensor, record: Tensor, g_raw: Tensor, arithmetic: int) -> Tensor:
+    """g_raw [P,4] (any shape with P * 4 elements) -> the pre-activation gradient of every layer [P, PE_NERF_GRAD_RECORD_FLOATS]"""
+    natural, record, g_raw = _c(natural), _c(record), _c(g_raw)
+    P = record.shape[0]
+    assert g_raw.numel() == 4 * P
+    grec = _f(P, capi.PE_NERF_GRAD_RECORD_FLOATS, like=record)
+    if P:
+        capi.call("nvsr_pe_nerf_backward_arith", P, capi.ptr(natural), capi.ptr(record), capi.ptr(g_raw), capi.ptr(grec), arithmetic, capi.stream())
+    return grec
+
+
+@pe_nerf_backward.register_fake
+def _(natural, record, g_raw, arithmetic):
+    return record.new_empty((record.shape[0], capi.PE_NERF_GRAD_RECORD_FLOATS))
+
+
+@custom_op("nvsr::pe_nerf_weight_grad", mutates_args=(), device_types="cuda")
+def pe_nerf_weight_grad(record: Tensor, grad_record: Tensor) -> Tensor:
+    """sum over the points of every layer's G^T X and G -> the gradient of the natural blob (fixed summation order: bit-reproducible)"""
+    record, grad_record = _c(record), _c(grad_record)
+    P = record.shape[0]
+    g = _f(capi.PE_NERF_NATURAL_FLOATS, like=record)
+    ws = _f(max(1, int(capi.lib().nvsr_pe_nerf_wgrad_workspace_floats(P))), like=record)
+    capi.call("nvsr_pe_nerf_weight_grad", P, capi.ptr(record), capi.ptr(grad_record), capi.ptr(ws), capi.ptr(g), capi.stream())
+    return g
+
+
+@pe_nerf_weight_grad.register_fake
+def _(record, grad_record):
+    return record.new_empty((capi.PE_NERF_NATURAL_FLOATS,))
+
+
+def _pe_nerf_setup(ctx, inputs, output):
+    rays, z, natural, want_record, arithmetic = inputs
+    ctx.save_for_backward(natural, output[1])
+    ctx.want_record, ctx.arithmetic = want_record, arithmetic
+    ctx.mark_non_differentiable(output[1])
+
+
+def _pe_nerf_bwd(ctx, g_raw, g_rec):
+    natural, record = ctx.saved_tensors
+    if not ctx.want_record:
+        raise RuntimeError("nvsr::pe_nerf was called with want_record=False: no record for its backward")
+    g_nat = None
+    if ctx.needs_input_grad[2] and g_raw is not None:
+        grec = torch.ops.nvsr.pe_nerf_backward(natural, record, g_raw, ctx.arithmetic)
+        g_nat = torch.ops.nvsr.pe_nerf_weight_grad(record, grec)
+    return None, None, g_nat, None, None
+
+
+pe_nerf.register_autograd(_pe_nerf_bwd, setup_context=_pe_nerf_setup)
+
+
+# =====================================================================================================================================
 # compositing (volume_rendering_utils.py:6-51)
 # =====================================================================================================================================
 @custom_op("nvsr::composite", mutates_args=(), device_types="cuda")

@@ -537,10 +537,15 @@ def run_one_iter_of_nerf(H, W, focal, model_coarse, model_fine, batch_rays, opti
     ray_grid_width (not in the reference): the rays are whole rows of a row-major pixel grid of this width (eval_nerf, the row-sharded
     renders) -- an evaluation pass then renders them in patch order (patch_order) and returns the results in the caller's order."""
     if isinstance(model_coarse, models.FlexibleNeRFModel):
-        if _cfg(options.nerf, "encode_position_fn", None) != "mip":
-            raise NotImplementedError("FlexibleNeRFModel runs as the Mip-NeRF baseline only (nerf.encode_position_fn: mip); the plain "
-                                      "positional-encoding NeRF is not supported")
-        return _run_mip(H, W, focal, model_coarse, model_fine, batch_rays, options, scene_id, mode, scene_config, randoms)
+        encode = _cfg(options.nerf, "encode_position_fn", None)
+        if encode == "mip":
+            return _run_mip(H, W, focal, model_coarse, model_fine, batch_rays, options, scene_id, mode, scene_config, randoms)
+        if encode != "positional_encoding" or not all(mdl.is_pe_baseline() for mdl in (model_coarse, model_fine)):
+            raise NotImplementedError("FlexibleNeRFModel runs as the Mip-NeRF baseline (nerf.encode_position_fn: mip) or as the positional-encoding "
+                                      "NeRF (nerf.encode_position_fn: positional_encoding) with num_encoding_fn_xyz=6, num_encoding_fn_dir=4, "
+                                      "include_input_xyz=True, include_input_dir=True and the constructor defaults; got %r with dim_xyz %d"
+                                      % (encode, model_coarse.dim_xyz))
+        return _run_pe(H, W, focal, model_coarse, model_fine, batch_rays, options, mode, scene_config, randoms)
     if not isinstance(model_coarse, models.TwoDimPlanesModel):
         raise NotImplementedError("only the tri-plane model is on the accelerated path")
     if not options.nerf.use_viewdirs:
@@ -697,6 +702,61 @@ def _run_mip(H, W, focal, model_coarse, model_fine, batch_rays, options, scene_i
         edges_f = nerf_helpers.sort_depths(torch.cat((edges_c, samples), dim=-1))
         raw_f = model_fine.mip_forward(rays, edges_f, radius)
         rgb_f, disp_f, acc_f, _, _ = nv.composite(raw_f, edges_f, rd, n_f, white, True)
+    return rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f, None, None, None
+
+
+def _run_pe(H, W, focal, model_coarse, model_fine, batch_rays, options, mode, scene_config, randoms):
+    """run_one_iter_of_nerf + predict_and_render_radiance with mip_nerf=False (train_utils.py:71-282) for the positional-encoding NeRF: Nc
+    coarse depths, the fused points + encoding + model kernel per pass, the compositor, sample_pdf_2 on the mid-points with weights[..., 1:-1],
+    Nf samples, sort(cat(z, samples)).  Gradients reach both models (the coarse pass's optional_no_grad is a null context upstream); the
+    depths are detached."""
+    if not options.nerf.use_viewdirs:
+        raise NotImplementedError("the positional-encoding kernels expect use_viewdirs=True (MipNeRF_baseline.yml)")
+    from . import nerf_helpers
+    rays = pack_rays(batch_rays[0], batch_rays[1], _cfg(scene_config, "near"), _cfg(scene_config, "far"), H, W, focal,
+                     no_ndc=_cfg(scene_config, "no_ndc"))
+    N = rays.shape[0]
+    m = _cfg(options.nerf, mode)
+    Nc, Nf, std = int(m.num_coarse), int(m.num_fine), float(m.radiance_field_noise_std)
+    if randoms is None and (m.perturb or std > 0.0):
+        # per reference ray chunk (chunksize, train_utils.py:228-235: the // 4 is Mip's only), in the reference's order: t_rand, coarse noise,
+        # u, fine noise
+        parts = []
+        chunk = max(1, int(m.chunksize))
+        for a in range(0, N, chunk):
+            n = min(a + chunk, N) - a
+            p = {}
+            if m.perturb:
+                p["t_rand"] = torch.rand([n, Nc])
+            if std > 0.0:
+                p["noise_coarse"] = torch.randn([n, Nc]) * std
+            if Nf > 0 and m.perturb != 0.0:
+                p["u"] = torch.rand([n, Nf])
+            if Nf > 0 and std > 0.0:
+                p["noise_fine"] = torch.randn([n, Nc + Nf]) * std
+            parts.append(p)
+        randoms = {k: torch.cat([p[k] for p in parts], 0) for k in parts[0]} if parts else {}
+    r = randoms or {}
+    dev = rays.device
+    t_rand, u, n_c, n_f = (None if r.get(k) is None else capi.f32c(r[k].to(dev)) for k in ("t_rand", "u", "noise_coarse", "noise_fine"))
+    if not m.perturb:
+        t_rand = None
+    white, lindisp = bool(m.white_background), bool(m.lindisp)
+    nv = torch.ops.nvsr
+    if N == 0:
+        e = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
+        return (e(0, 3), e(0), e(0)) + ((e(0, 3), e(0), e(0)) if Nf > 0 else (None, None, None)) + (None, None, None)
+    rd = rays[:, 3:6].contiguous()
+    z_c = nv.coarse_z(rays, Nc, lindisp, t_rand)
+    raw_c = model_coarse.pe_forward(rays, z_c)
+    rgb_c, disp_c, acc_c, w_c, _ = nv.composite(raw_c, z_c, rd, n_c, white, False)
+    rgb_f = disp_f = acc_f = None
+    if Nf > 0:
+        mid = 0.5 * (z_c[..., 1:] + z_c[..., :-1])
+        samples = nerf_helpers.sample_pdf_2(mid, w_c.detach()[..., 1:-1].contiguous(), Nf, det=(m.perturb == 0.0), u=u)
+        z_f = nerf_helpers.sort_depths(torch.cat((z_c, samples), dim=-1))
+        raw_f = model_fine.pe_forward(rays, z_f)
+        rgb_f, disp_f, acc_f, _, _ = nv.composite(raw_f, z_f, rd, n_f, white, False)
     return rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f, None, None, None
 
 
