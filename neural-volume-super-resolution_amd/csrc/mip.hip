@@ -61,20 +61,12 @@ using namespace nvsr;
 extern "C" {
 
 int nvsr_mip_encode(int64_t N, int S, const float* rays, const float* edges, double radius, float* out, nvsr_stream_t stream) {
-    if (N < 0 || S < 1) return NVSR_ERR_SHAPE;
-    if (N == 0) return NVSR_OK;
-    if (!rays || !edges || !out) return NVSR_ERR_NULL;
-    return nerf_encode_launch((long)(N * S), MipEncoder{rays, edges, S, (float)(radius * radius)}, out, (hipStream_t)stream);
+    return nerf_encode_launch(N, S, rays, edges, MipEncoder{rays, edges, S, (float)(radius * radius)}, out, (hipStream_t)stream);
 }
 
 int nvsr_mip_nerf_forward_arith(int64_t N, int S, const float* rays, const float* edges, double radius, const float* natural, float* raw,
                                 float* record, int arithmetic, nvsr_stream_t stream) {
-    int arith;
-    if (N < 0 || S < 1 || nerf_arith(arithmetic, &arith)) return NVSR_ERR_SHAPE;
-    if (N == 0) return NVSR_OK;
-    if (!rays || !edges || !natural || !raw) return NVSR_ERR_NULL;
-    if (reinterpret_cast<uintptr_t>(raw) % 16) return NVSR_ERR_ALIGN;
-    return nerf_forward_launch((long)(N * S), MipEncoder{rays, edges, S, (float)(radius * radius)}, natural, raw, record, arith,
+    return nerf_forward_launch(N, S, rays, edges, MipEncoder{rays, edges, S, (float)(radius * radius)}, natural, raw, record, arithmetic,
                                (hipStream_t)stream);
 }
 

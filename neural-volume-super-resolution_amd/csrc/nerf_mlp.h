@@ -291,16 +291,27 @@ static inline int nerf_arith(int arithmetic, int* out) {
     return NVSR_OK;
 }
 
+// The bodies of nvsr_{mip,pe}_encode and nvsr_{mip,pe}_nerf_forward_arith: argument checks, then the launch.  `depths` is the encoder's
+// per-ray array (Mip: the S + 1 interval edges; PE: the S sample depths), checked for null beside the rays.
 template <class E>
-static int nerf_encode_launch(long P, const E& enc, float* out, hipStream_t stream) {
-    const long n = P * (E::ENC + NERF_DIR);
-    hipLaunchKernelGGL(nerf_encode_kernel<E>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, P, enc, out);
+static int nerf_encode_launch(int64_t N, int S, const float* rays, const float* depths, const E& enc, float* out, hipStream_t stream) {
+    if (N < 0 || S < 1) return NVSR_ERR_SHAPE;
+    if (N == 0) return NVSR_OK;
+    if (!rays || !depths || !out) return NVSR_ERR_NULL;
+    const long n = (long)(N * S) * (E::ENC + NERF_DIR);
+    hipLaunchKernelGGL(nerf_encode_kernel<E>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (long)(N * S), enc, out);
     return NVSR_CHECK_LAUNCH();
 }
 
-// (arguments checked by the caller; P > 0, raw 16-byte aligned)
 template <class E>
-static int nerf_forward_launch(long P, const E& enc, const float* natural, float* raw, float* record, int arith, hipStream_t stream) {
+static int nerf_forward_launch(int64_t N, int S, const float* rays, const float* depths, const E& enc, const float* natural, float* raw,
+                               float* record, int arithmetic, hipStream_t stream) {
+    int arith;
+    if (N < 0 || S < 1 || nerf_arith(arithmetic, &arith)) return NVSR_ERR_SHAPE;
+    if (N == 0) return NVSR_OK;
+    if (!rays || !depths || !natural || !raw) return NVSR_ERR_NULL;
+    if (reinterpret_cast<uintptr_t>(raw) % 16) return NVSR_ERR_ALIGN;
+    const long P = (long)(N * S);
     const dim3 grid((unsigned)((P + 32 * MIP_WAVES - 1) / (32 * MIP_WAVES)));
     if (arith == NVSR_ARITH_F32)
         hipLaunchKernelGGL((nerf_forward_kernel<E, NVSR_ARITH_F32>), grid, dim3(64 * MIP_WAVES), 0, stream, P, enc, natural, raw, record);

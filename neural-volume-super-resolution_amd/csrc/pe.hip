@@ -47,20 +47,12 @@ using namespace nvsr;
 extern "C" {
 
 int nvsr_pe_encode(int64_t N, int S, const float* rays, const float* z, float* out, nvsr_stream_t stream) {
-    if (N < 0 || S < 1) return NVSR_ERR_SHAPE;
-    if (N == 0) return NVSR_OK;
-    if (!rays || !z || !out) return NVSR_ERR_NULL;
-    return nerf_encode_launch((long)(N * S), PeEncoder{rays, z, S}, out, (hipStream_t)stream);
+    return nerf_encode_launch(N, S, rays, z, PeEncoder{rays, z, S}, out, (hipStream_t)stream);
 }
 
 int nvsr_pe_nerf_forward_arith(int64_t N, int S, const float* rays, const float* z, const float* natural, float* raw, float* record, int arithmetic,
                                nvsr_stream_t stream) {
-    int arith;
-    if (N < 0 || S < 1 || nerf_arith(arithmetic, &arith)) return NVSR_ERR_SHAPE;
-    if (N == 0) return NVSR_OK;
-    if (!rays || !z || !natural || !raw) return NVSR_ERR_NULL;
-    if (reinterpret_cast<uintptr_t>(raw) % 16) return NVSR_ERR_ALIGN;
-    return nerf_forward_launch((long)(N * S), PeEncoder{rays, z, S}, natural, raw, record, arith, (hipStream_t)stream);
+    return nerf_forward_launch(N, S, rays, z, PeEncoder{rays, z, S}, natural, raw, record, arithmetic, (hipStream_t)stream);
 }
 
 int nvsr_pe_nerf_backward_arith(int64_t P, const float* natural, const float* record, const float* g_raw, float* grad_record, int arithmetic,

@@ -1073,23 +1073,26 @@ class FlexibleNeRFModel(nn.Module):
             cache = self.__dict__["_natural_cache"] = (key, torch.cat([t.detach().reshape(-1).float() for t in params]))
         return cache[1]
 
-    def mip_forward(self, rays, edges, radius):
-        """The Mip-NeRF baseline's model call (train_utils.py:19-64 with mip_nerf=True, then forward): packed rays [N,11], interval edges
-        [N,S+1], the cone radius -> raw [N,S,4].  The integrated positional encoding happens inside the kernel; with gradients enabled,
-        loss.backward() reaches every nn.Linear of the model."""
-        if self.dim_xyz != 36 or self.dim_dir != 27 or self.hidden_size != 128 or self.num_layers != 4:
-            raise NotImplementedError("the Mip-NeRF kernels are built for FlexibleNeRFModel(include_input_xyz=False) with the constructor defaults")
-        grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-        nat = self.natural_blob(differentiable=grad)
-        capi.require_cuda(nat)
-        raw, _ = torch.ops.nvsr.mip_nerf(rays, edges, float(radius), nat, grad, capi.arith_code(self.arithmetic))
-        return raw
+    def is_mip_baseline(self):
+        """the geometry the Mip-NeRF kernels are built for: FlexibleNeRFModel(include_input_xyz=False), the constructor defaults otherwise"""
+        return self._is_baseline(36)
 
     def is_pe_baseline(self):
         """the geometry the positional-encoding kernels are built for: num_encoding_fn_xyz=6, num_encoding_fn_dir=4, include_input_xyz and
         include_input_dir, the constructor defaults otherwise (dim_xyz 39 and dim_dir 27 admit no other encoding counts)"""
-        return (self.dim_xyz == 39 and self.dim_dir == 27 and self.hidden_size == 128 and self.num_layers == 4
+        return self._is_baseline(39)
+
+    def _is_baseline(self, dim_xyz):
+        return (self.dim_xyz == dim_xyz and self.dim_dir == 27 and self.hidden_size == 128 and self.num_layers == 4
                 and all(l.in_features == 128 for l in self.layers_xyz))
+
+    def mip_forward(self, rays, edges, radius):
+        """The Mip-NeRF baseline's model call (train_utils.py:19-64 with mip_nerf=True, then forward): packed rays [N,11], interval edges
+        [N,S+1], the cone radius -> raw [N,S,4].  The integrated positional encoding happens inside the kernel; with gradients enabled,
+        loss.backward() reaches every nn.Linear of the model."""
+        if not self.is_mip_baseline():
+            raise NotImplementedError("the Mip-NeRF kernels are built for FlexibleNeRFModel(include_input_xyz=False) with the constructor defaults")
+        return self._fused_forward(torch.ops.nvsr.mip_nerf, rays, edges, float(radius))
 
     def pe_forward(self, rays, z):
         """The positional-encoding baseline's model call (train_utils.py:15-64 with mip_nerf=False, then forward): packed rays [N,11], sample
@@ -1098,18 +1101,21 @@ class FlexibleNeRFModel(nn.Module):
         if not self.is_pe_baseline():
             raise NotImplementedError("the positional-encoding kernels are built for FlexibleNeRFModel(num_encoding_fn_xyz=6, num_encoding_fn_dir=4, "
                                       "include_input_xyz=True, include_input_dir=True) with the constructor defaults")
+        return self._fused_forward(torch.ops.nvsr.pe_nerf, rays, z)
+
+    def _fused_forward(self, op, *inputs):
+        """op(*inputs, natural, want_record, arithmetic) -> raw, recording for the backward when a parameter wants a gradient"""
         grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         nat = self.natural_blob(differentiable=grad)
         capi.require_cuda(nat)
-        raw, _ = torch.ops.nvsr.pe_nerf(rays, z, nat, grad, capi.arith_code(self.arithmetic))
+        raw, _ = op(*inputs, nat, grad, capi.arith_code(self.arithmetic))
         return raw
 
     def forward(self, x):
         x = capi.f32c(x)
         assert x.shape[-1] == self.dim_xyz + self.dim_dir
         P = x.numel() // x.shape[-1]
-        mods = [self.layer1] + list(self.layers_xyz) + [self.layers_dir[0], self.fc_alpha, self.fc_rgb, self.fc_feat]
-        blob = torch.cat([t.detach().reshape(-1).float() for m in mods for t in (m.weight, m.bias)])
+        blob = self.natural_blob()
         capi.require_cuda(blob)
         out = torch.empty((P, 4), dtype=torch.float32, device=x.device)
         capi.call("nvsr_flexible_nerf_forward", P, capi.ptr(x), self.dim_xyz, self.dim_dir, self.hidden_size, self.num_layers,

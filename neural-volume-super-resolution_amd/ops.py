@@ -506,6 +506,50 @@ def _(record, N, S, arithmetic):
 
 
 # =====================================================================================================================================
+# the two NeRF baselines below share the layer engine (csrc/nerf_mlp.h): their backward, weight-gradient and autograd glue differ only in
+# the C prefix ("mip" / "pe"), the capi sizes and where `natural` sits among the forward op's inputs
+# =====================================================================================================================================
+def _nerf_backward(prefix, grad_record_floats, natural, record, g_raw, arithmetic):
+    natural, record, g_raw = _c(natural), _c(record), _c(g_raw)
+    P = record.shape[0]
+    assert g_raw.numel() == 4 * P
+    grec = _f(P, grad_record_floats, like=record)
+    if P:
+        capi.call("nvsr_%s_nerf_backward_arith" % prefix, P, capi.ptr(natural), capi.ptr(record), capi.ptr(g_raw), capi.ptr(grec), arithmetic,
+                  capi.stream())
+    return grec
+
+
+def _nerf_weight_grad(prefix, natural_floats, record, grad_record):
+    record, grad_record = _c(record), _c(grad_record)
+    P = record.shape[0]
+    g = _f(natural_floats, like=record)
+    ws = _f(max(1, int(getattr(capi.lib(), "nvsr_%s_nerf_wgrad_workspace_floats" % prefix)(P))), like=record)
+    capi.call("nvsr_%s_nerf_weight_grad" % prefix, P, capi.ptr(record), capi.ptr(grad_record), capi.ptr(ws), capi.ptr(g), capi.stream())
+    return g
+
+
+def _register_nerf_autograd(op, prefix, nat):
+    """autograd of nvsr::<prefix>_nerf, whose inputs are (..., natural, want_record, arithmetic) with `natural` at index `nat`"""
+    def setup(ctx, inputs, output):
+        ctx.save_for_backward(inputs[nat], output[1])
+        ctx.want_record, ctx.arithmetic = inputs[nat + 1], inputs[nat + 2]
+        ctx.mark_non_differentiable(output[1])
+
+    def backward(ctx, g_raw, g_rec):
+        natural, record = ctx.saved_tensors
+        if not ctx.want_record:
+            raise RuntimeError("nvsr::%s_nerf was called with want_record=False: no record for its backward" % prefix)
+        g_nat = None
+        if ctx.needs_input_grad[nat] and g_raw is not None:
+            grec = getattr(torch.ops.nvsr, prefix + "_nerf_backward")(natural, record, g_raw, ctx.arithmetic)
+            g_nat = getattr(torch.ops.nvsr, prefix + "_nerf_weight_grad")(record, grec)
+        return (None,) * nat + (g_nat, None, None)
+
+    op.register_autograd(backward, setup_context=setup)
+
+
+# =====================================================================================================================================
 # the Mip-NeRF baseline (mip.py, models.py:14-108; csrc/mip.hip): integrated positional encoding + FlexibleNeRFModel, forward and training
 # =====================================================================================================================================
 @custom_op("nvsr::mip_encode", mutates_args=(), device_types="cuda")
@@ -548,13 +592,7 @@ def _(rays, edges, radius, natural, want_record, arithmetic):
 @custom_op("nvsr::mip_nerf_backward", mutates_args=(), device_types="cuda")
 def mip_nerf_backward(natural: Tensor, record: Tensor, g_raw: Tensor, arithmetic: int) -> Tensor:
     """g_raw [P,4] (any shape with P * 4 elements) -> the pre-activation gradient of every layer [P, MIP_NERF_GRAD_RECORD_FLOATS]"""
-    natural, record, g_raw = _c(natural), _c(record), _c(g_raw)
-    P = record.shape[0]
-    assert g_raw.numel() == 4 * P
-    grec = _f(P, capi.MIP_NERF_GRAD_RECORD_FLOATS, like=record)
-    if P:
-        capi.call("nvsr_mip_nerf_backward_arith", P, capi.ptr(natural), capi.ptr(record), capi.ptr(g_raw), capi.ptr(grec), arithmetic, capi.stream())
-    return grec
+    return _nerf_backward("mip", capi.MIP_NERF_GRAD_RECORD_FLOATS, natural, record, g_raw, arithmetic)
 
 
 @mip_nerf_backward.register_fake
@@ -565,12 +603,7 @@ def _(natural, record, g_raw, arithmetic):
 @custom_op("nvsr::mip_nerf_weight_grad", mutates_args=(), device_types="cuda")
 def mip_nerf_weight_grad(record: Tensor, grad_record: Tensor) -> Tensor:
     """sum over the points of every layer's G^T X and G -> the gradient of the natural blob (fixed summation order: bit-reproducible)"""
-    record, grad_record = _c(record), _c(grad_record)
-    P = record.shape[0]
-    g = _f(capi.MIP_NERF_NATURAL_FLOATS, like=record)
-    ws = _f(max(1, int(capi.lib().nvsr_mip_nerf_wgrad_workspace_floats(P))), like=record)
-    capi.call("nvsr_mip_nerf_weight_grad", P, capi.ptr(record), capi.ptr(grad_record), capi.ptr(ws), capi.ptr(g), capi.stream())
-    return g
+    return _nerf_weight_grad("mip", capi.MIP_NERF_NATURAL_FLOATS, record, grad_record)
 
 
 @mip_nerf_weight_grad.register_fake
@@ -578,25 +611,7 @@ def _(record, grad_record):
     return record.new_empty((capi.MIP_NERF_NATURAL_FLOATS,))
 
 
-def _mip_nerf_setup(ctx, inputs, output):
-    rays, edges, radius, natural, want_record, arithmetic = inputs
-    ctx.save_for_backward(natural, output[1])
-    ctx.want_record, ctx.arithmetic = want_record, arithmetic
-    ctx.mark_non_differentiable(output[1])
-
-
-def _mip_nerf_bwd(ctx, g_raw, g_rec):
-    natural, record = ctx.saved_tensors
-    if not ctx.want_record:
-        raise RuntimeError("nvsr::mip_nerf was called with want_record=False: no record for its backward")
-    g_nat = None
-    if ctx.needs_input_grad[3] and g_raw is not None:
-        grec = torch.ops.nvsr.mip_nerf_backward(natural, record, g_raw, ctx.arithmetic)
-        g_nat = torch.ops.nvsr.mip_nerf_weight_grad(record, grec)
-    return None, None, None, g_nat, None, None
-
-
-mip_nerf.register_autograd(_mip_nerf_bwd, setup_context=_mip_nerf_setup)
+_register_nerf_autograd(mip_nerf, "mip", 3)
 
 
 # =====================================================================================================================================
@@ -643,13 +658,7 @@ def _(rays, z, natural, want_record, arithmetic):
 @custom_op("nvsr::pe_nerf_backward", mutates_args=(), device_types="cuda")
 def pe_nerf_backward(natural: Tensor, record: Tensor, g_raw: Tensor, arithmetic: int) -> Tensor:
     """g_raw [P,4] (any shape with P * 4 elements) -> the pre-activation gradient of every layer [P, PE_NERF_GRAD_RECORD_FLOATS]"""
-    natural, record, g_raw = _c(natural), _c(record), _c(g_raw)
-    P = record.shape[0]
-    assert g_raw.numel() == 4 * P
-    grec = _f(P, capi.PE_NERF_GRAD_RECORD_FLOATS, like=record)
-    if P:
-        capi.call("nvsr_pe_nerf_backward_arith", P, capi.ptr(natural), capi.ptr(record), capi.ptr(g_raw), capi.ptr(grec), arithmetic, capi.stream())
-    return grec
+    return _nerf_backward("pe", capi.PE_NERF_GRAD_RECORD_FLOATS, natural, record, g_raw, arithmetic)
 
 
 @pe_nerf_backward.register_fake
@@ -660,12 +669,7 @@ def _(natural, record, g_raw, arithmetic):
 @custom_op("nvsr::pe_nerf_weight_grad", mutates_args=(), device_types="cuda")
 def pe_nerf_weight_grad(record: Tensor, grad_record: Tensor) -> Tensor:
     """sum over the points of every layer's G^T X and G -> the gradient of the natural blob (fixed summation order: bit-reproducible)"""
-    record, grad_record = _c(record), _c(grad_record)
-    P = record.shape[0]
-    g = _f(capi.PE_NERF_NATURAL_FLOATS, like=record)
-    ws = _f(max(1, int(capi.lib().nvsr_pe_nerf_wgrad_workspace_floats(P))), like=record)
-    capi.call("nvsr_pe_nerf_weight_grad", P, capi.ptr(record), capi.ptr(grad_record), capi.ptr(ws), capi.ptr(g), capi.stream())
-    return g
+    return _nerf_weight_grad("pe", capi.PE_NERF_NATURAL_FLOATS, record, grad_record)
 
 
 @pe_nerf_weight_grad.register_fake
@@ -673,25 +677,7 @@ def _(record, grad_record):
     return record.new_empty((capi.PE_NERF_NATURAL_FLOATS,))
 
 
-def _pe_nerf_setup(ctx, inputs, output):
-    rays, z, natural, want_record, arithmetic = inputs
-    ctx.save_for_backward(natural, output[1])
-    ctx.want_record, ctx.arithmetic = want_record, arithmetic
-    ctx.mark_non_differentiable(output[1])
-
-
-def _pe_nerf_bwd(ctx, g_raw, g_rec):
-    natural, record = ctx.saved_tensors
-    if not ctx.want_record:
-        raise RuntimeError("nvsr::pe_nerf was called with want_record=False: no record for its backward")
-    g_nat = None
-    if ctx.needs_input_grad[2] and g_raw is not None:
-        grec = torch.ops.nvsr.pe_nerf_backward(natural, record, g_raw, ctx.arithmetic)
-        g_nat = torch.ops.nvsr.pe_nerf_weight_grad(record, grec)
-    return None, None, g_nat, None, None
-
-
-pe_nerf.register_autograd(_pe_nerf_bwd, setup_context=_pe_nerf_setup)
+_register_nerf_autograd(pe_nerf, "pe", 2)
 
 
 # =====================================================================================================================================

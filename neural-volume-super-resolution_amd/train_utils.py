@@ -5,6 +5,7 @@ ray-chunk and point-chunk Python loops of the reference collapse into one `nvsr_
 depths -> fused coarse pass -> inverse-CDF resampling + sort -> fused fine pass, all on the current stream."""
 import ctypes as C
 import os
+from typing import Callable, NamedTuple
 
 import torch
 
@@ -538,14 +539,13 @@ def run_one_iter_of_nerf(H, W, focal, model_coarse, model_fine, batch_rays, opti
     renders) -- an evaluation pass then renders them in patch order (patch_order) and returns the results in the caller's order."""
     if isinstance(model_coarse, models.FlexibleNeRFModel):
         encode = _cfg(options.nerf, "encode_position_fn", None)
-        if encode == "mip":
-            return _run_mip(H, W, focal, model_coarse, model_fine, batch_rays, options, scene_id, mode, scene_config, randoms)
-        if encode != "positional_encoding" or not all(mdl.is_pe_baseline() for mdl in (model_coarse, model_fine)):
-            raise NotImplementedError("FlexibleNeRFModel runs as the Mip-NeRF baseline (nerf.encode_position_fn: mip) or as the positional-encoding "
-                                      "NeRF (nerf.encode_position_fn: positional_encoding) with num_encoding_fn_xyz=6, num_encoding_fn_dir=4, "
-                                      "include_input_xyz=True, include_input_dir=True and the constructor defaults; got %r with dim_xyz %d"
-                                      % (encode, model_coarse.dim_xyz))
-        return _run_pe(H, W, focal, model_coarse, model_fine, batch_rays, options, mode, scene_config, randoms)
+        b = _NERF_BASELINES.get(encode)
+        if b is None or not all(b.fits(mdl) for mdl in (model_coarse, model_fine)):
+            raise NotImplementedError("FlexibleNeRFModel runs as the Mip-NeRF baseline (nerf.encode_position_fn: mip) with include_input_xyz=False, or "
+                                      "as the positional-encoding NeRF (nerf.encode_position_fn: positional_encoding) with num_encoding_fn_xyz=6, "
+                                      "num_encoding_fn_dir=4, include_input_xyz=True, include_input_dir=True; both with the constructor defaults "
+                                      "otherwise; got %r with dim_xyz %d / %d" % (encode, model_coarse.dim_xyz, model_fine.dim_xyz))
+        return _run_nerf_baseline(b, H, W, focal, model_coarse, model_fine, batch_rays, options, scene_id, mode, scene_config, randoms)
     if not isinstance(model_coarse, models.TwoDimPlanesModel):
         raise NotImplementedError("only the tri-plane model is on the accelerated path")
     if not options.nerf.use_viewdirs:
@@ -650,90 +650,63 @@ def mip_radius(scene_id):
     return int(m.group(0)) * 0.00135 * 2 / np.sqrt(12.0)
 
 
-def _run_mip(H, W, focal, model_coarse, model_fine, batch_rays, options, scene_id, mode, scene_config, randoms):
-    """run_one_iter_of_nerf + predict_and_render_radiance with mip_nerf=True (train_utils.py:71-282): Nc + 1 coarse edges, the fused
-    encoding + model kernel per pass, the interval compositor, sample_pdf_2 on the mid-points of the mid-points with weights[..., 1:-1],
-    Nf + 1 samples, sort(cat(edges, samples)).  Gradients reach both models (the coarse pass's optional_no_grad is a null context upstream);
-    the depths are detached."""
-    if not options.nerf.use_viewdirs:
-        raise NotImplementedError("the Mip-NeRF kernels expect use_viewdirs=True (MipNeRF_baseline.yml)")
-    from . import nerf_helpers
+class _NerfBaseline(NamedTuple):
+    """what differs between the two FlexibleNeRFModel baselines on the host (the reference's predict_and_render_radiance with mip_nerf=True /
+    False, train_utils.py:71-282)"""
+    name: str
+    fits: Callable          # FlexibleNeRFModel -> bool: the geometry its kernels are built for
+    extra: int              # Mip samples Nc + 1 interval edges and Nf + 1 samples (its noise_fine is Nc + Nf + 1 wide); PE Nc and Nf depths
+    chunk_div: int          # the reference draws its random numbers per chunksize // chunk_div rays (train_utils.py:228-235)
+    bins: Callable          # depths [N,S] -> the bins of sample_pdf_2
+    mip: bool               # the compositor's interval branch
+    model_call: Callable    # scene_id -> (model, packed rays, depths) -> raw
+
+
+def _mid(z):
+    return 0.5 * (z[..., 1:] + z[..., :-1])
+
+
+def _mip_call(scene_id):
     radius = mip_radius(scene_id)
-    rays = pack_rays(batch_rays[0], batch_rays[1], _cfg(scene_config, "near"), _cfg(scene_config, "far"), H, W, focal,
-                     no_ndc=_cfg(scene_config, "no_ndc"))
-    N = rays.shape[0]
-    m = _cfg(options.nerf, mode)
-    Nc, Nf, std = int(m.num_coarse), int(m.num_fine), float(m.radiance_field_noise_std)
-    if randoms is None and (m.perturb or std > 0.0):
-        # per reference ray chunk (chunksize // 4 with mip, train_utils.py:228-235), in the reference's order: t_rand, coarse noise, u, fine noise
-        parts = []
-        chunk = max(1, int(m.chunksize) // 4)
-        for a in range(0, N, chunk):
-            n = min(a + chunk, N) - a
-            p = {}
-            if m.perturb:
-                p["t_rand"] = torch.rand([n, Nc + 1])
-            if std > 0.0:
-                p["noise_coarse"] = torch.randn([n, Nc]) * std
-            if Nf > 0 and m.perturb != 0.0:
-                p["u"] = torch.rand([n, Nf + 1])
-            if Nf > 0 and std > 0.0:
-                p["noise_fine"] = torch.randn([n, Nc + Nf + 1]) * std
-            parts.append(p)
-        randoms = {k: torch.cat([p[k] for p in parts], 0) for k in parts[0]} if parts else {}
-    r = randoms or {}
-    dev = rays.device
-    t_rand, u, n_c, n_f = (None if r.get(k) is None else capi.f32c(r[k].to(dev)) for k in ("t_rand", "u", "noise_coarse", "noise_fine"))
-    if not m.perturb:
-        t_rand = None
-    white, lindisp = bool(m.white_background), bool(m.lindisp)
-    nv = torch.ops.nvsr
-    if N == 0:
-        e = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
-        return (e(0, 3), e(0), e(0)) + ((e(0, 3), e(0), e(0)) if Nf > 0 else (None, None, None)) + (None, None, None)
-    rd = rays[:, 3:6].contiguous()
-    edges_c = nv.coarse_z(rays, Nc + 1, lindisp, t_rand)
-    raw_c = model_coarse.mip_forward(rays, edges_c, radius)
-    rgb_c, disp_c, acc_c, w_c, _ = nv.composite(raw_c, edges_c, rd, n_c, white, True)
-    rgb_f = disp_f = acc_f = None
-    if Nf > 0:
-        mid = lambda z: 0.5 * (z[..., 1:] + z[..., :-1])
-        samples = nerf_helpers.sample_pdf_2(mid(mid(edges_c)), w_c.detach()[..., 1:-1].contiguous(), Nf + 1, det=(m.perturb == 0.0), u=u)
-        edges_f = nerf_helpers.sort_depths(torch.cat((edges_c, samples), dim=-1))
-        raw_f = model_fine.mip_forward(rays, edges_f, radius)
-        rgb_f, disp_f, acc_f, _, _ = nv.composite(raw_f, edges_f, rd, n_f, white, True)
-    return rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f, None, None, None
+    return lambda model, rays, edges: model.mip_forward(rays, edges, radius)
 
 
-def _run_pe(H, W, focal, model_coarse, model_fine, batch_rays, options, mode, scene_config, randoms):
-    """run_one_iter_of_nerf + predict_and_render_radiance with mip_nerf=False (train_utils.py:71-282) for the positional-encoding NeRF: Nc
-    coarse depths, the fused points + encoding + model kernel per pass, the compositor, sample_pdf_2 on the mid-points with weights[..., 1:-1],
-    Nf samples, sort(cat(z, samples)).  Gradients reach both models (the coarse pass's optional_no_grad is a null context upstream); the
-    depths are detached."""
+_NERF_BASELINES = {
+    "mip": _NerfBaseline("Mip-NeRF", models.FlexibleNeRFModel.is_mip_baseline, 1, 4, lambda z: _mid(_mid(z)), True, _mip_call),
+    "positional_encoding": _NerfBaseline("positional-encoding", models.FlexibleNeRFModel.is_pe_baseline, 0, 1, _mid, False,
+                                         lambda scene_id: lambda model, rays, z: model.pe_forward(rays, z)),
+}
+
+
+def _run_nerf_baseline(b, H, W, focal, model_coarse, model_fine, batch_rays, options, scene_id, mode, scene_config, randoms):
+    """run_one_iter_of_nerf + predict_and_render_radiance (train_utils.py:71-282) for the baseline b: Nc + b.extra coarse depths (Mip: the
+    interval edges), the fused encoding + model kernel per pass, the compositor, sample_pdf_2 on b.bins(depths) with weights[..., 1:-1],
+    Nf + b.extra samples, sort(cat(depths, samples)).  Gradients reach both models (the coarse pass's optional_no_grad is a null context
+    upstream); the depths are detached."""
     if not options.nerf.use_viewdirs:
-        raise NotImplementedError("the positional-encoding kernels expect use_viewdirs=True (MipNeRF_baseline.yml)")
+        raise NotImplementedError("the %s kernels expect use_viewdirs=True (MipNeRF_baseline.yml)" % b.name)
     from . import nerf_helpers
+    model_call = b.model_call(scene_id)
     rays = pack_rays(batch_rays[0], batch_rays[1], _cfg(scene_config, "near"), _cfg(scene_config, "far"), H, W, focal,
                      no_ndc=_cfg(scene_config, "no_ndc"))
     N = rays.shape[0]
     m = _cfg(options.nerf, mode)
-    Nc, Nf, std = int(m.num_coarse), int(m.num_fine), float(m.radiance_field_noise_std)
+    Nc, Nf, std, x = int(m.num_coarse), int(m.num_fine), float(m.radiance_field_noise_std), b.extra
     if randoms is None and (m.perturb or std > 0.0):
-        # per reference ray chunk (chunksize, train_utils.py:228-235: the // 4 is Mip's only), in the reference's order: t_rand, coarse noise,
-        # u, fine noise
+        # per reference ray chunk, in the reference's order: t_rand, coarse noise, u, fine noise
         parts = []
-        chunk = max(1, int(m.chunksize))
+        chunk = max(1, int(m.chunksize) // b.chunk_div)
         for a in range(0, N, chunk):
             n = min(a + chunk, N) - a
             p = {}
             if m.perturb:
-                p["t_rand"] = torch.rand([n, Nc])
+                p["t_rand"] = torch.rand([n, Nc + x])
             if std > 0.0:
                 p["noise_coarse"] = torch.randn([n, Nc]) * std
             if Nf > 0 and m.perturb != 0.0:
-                p["u"] = torch.rand([n, Nf])
+                p["u"] = torch.rand([n, Nf + x])
             if Nf > 0 and std > 0.0:
-                p["noise_fine"] = torch.randn([n, Nc + Nf]) * std
+                p["noise_fine"] = torch.randn([n, Nc + Nf + x]) * std
             parts.append(p)
         randoms = {k: torch.cat([p[k] for p in parts], 0) for k in parts[0]} if parts else {}
     r = randoms or {}
@@ -747,16 +720,15 @@ def _run_pe(H, W, focal, model_coarse, model_fine, batch_rays, options, mode, sc
         e = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
         return (e(0, 3), e(0), e(0)) + ((e(0, 3), e(0), e(0)) if Nf > 0 else (None, None, None)) + (None, None, None)
     rd = rays[:, 3:6].contiguous()
-    z_c = nv.coarse_z(rays, Nc, lindisp, t_rand)
-    raw_c = model_coarse.pe_forward(rays, z_c)
-    rgb_c, disp_c, acc_c, w_c, _ = nv.composite(raw_c, z_c, rd, n_c, white, False)
+    z_c = nv.coarse_z(rays, Nc + x, lindisp, t_rand)
+    raw_c = model_call(model_coarse, rays, z_c)
+    rgb_c, disp_c, acc_c, w_c, _ = nv.composite(raw_c, z_c, rd, n_c, white, b.mip)
     rgb_f = disp_f = acc_f = None
     if Nf > 0:
-        mid = 0.5 * (z_c[..., 1:] + z_c[..., :-1])
-        samples = nerf_helpers.sample_pdf_2(mid, w_c.detach()[..., 1:-1].contiguous(), Nf, det=(m.perturb == 0.0), u=u)
+        samples = nerf_helpers.sample_pdf_2(b.bins(z_c), w_c.detach()[..., 1:-1].contiguous(), Nf + x, det=(m.perturb == 0.0), u=u)
         z_f = nerf_helpers.sort_depths(torch.cat((z_c, samples), dim=-1))
-        raw_f = model_fine.pe_forward(rays, z_f)
-        rgb_f, disp_f, acc_f, _, _ = nv.composite(raw_f, z_f, rd, n_f, white, False)
+        raw_f = model_call(model_fine, rays, z_f)
+        rgb_f, disp_f, acc_f, _, _ = nv.composite(raw_f, z_f, rd, n_f, white, b.mip)
     return rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f, None, None, None
 
 

@@ -108,10 +108,9 @@ def main():
     dirs = dir_enc(rays[:, None, 8:11].expand(n, S, 3).reshape(-1, 3))
     out.update({"a.rays": npy(rays), "a.edges": npy(edges), "a.means": npy(means), "a.covs": npy(covs), "a.ipe": npy(enc), "a.dirs": npy(dirs)})
     # (b) two models on the rows of (a)
-    ms = [model(101), model(202)]
+    ms = [model(s) for s in mip_params.SEEDS]
     for i, m in enumerate(ms):
-        flat = np.concatenate([npy(v).reshape(-1).astype(np.float64) for v in m.state_dict().values()])
-        out["b.m%d.checksum" % i] = np.array([flat.sum(), (flat * flat).sum()])
+        out["b.m%d.checksum" % i] = mip_params.checksum({k: npy(v) for k, v in m.state_dict().items()})
         with torch.no_grad():
             out["b.m%d.raw" % i] = npy(m(torch.cat((enc, dirs), -1)))
     mc, mf = ms

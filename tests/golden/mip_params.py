@@ -14,17 +14,24 @@ SHAPES += [x for j in range(3) for x in (("layers_xyz.%d.weight" % j, (128, 128)
 SHAPES += [("layers_dir.0.weight", (64, 155)), ("layers_dir.0.bias", (64,)), ("fc_alpha.weight", (1, 128)), ("fc_alpha.bias", (1,)),
            ("fc_rgb.weight", (3, 64)), ("fc_rgb.bias", (3,)), ("fc_feat.weight", (128, 128)), ("fc_feat.bias", (128,))]
 KEEP = 1024
+SEEDS = (101, 202)       # coarse, fine
 
 
-def state_dict(seed):
-    """{name: float32 array} of the model with this seed"""
+def state_dict(seed, shapes=SHAPES):
+    """{name: float32 array} of the model with this seed (`shapes`: pe_params.SHAPES for the g24 models)"""
     rs = np.random.RandomState(seed)
     out = {}
-    for name, shape in SHAPES:
-        fan_in = dict(SHAPES)[name.rsplit(".", 1)[0] + ".weight"][1]
+    for name, shape in shapes:
+        fan_in = dict(shapes)[name.rsplit(".", 1)[0] + ".weight"][1]
         b = 1.0 / np.sqrt(fan_in)
         out[name] = rs.uniform(-b, b, size=shape).astype(np.float32)
     return out
+
+
+def checksum(sd):
+    """float64 sum and sum of squares of every parameter: what the fixtures store in place of the parameters"""
+    flat = np.concatenate([v.reshape(-1).astype(np.float64) for v in sd.values()])
+    return np.array([flat.sum(), (flat * flat).sum()])
 
 
 def kept_elements(name, numel):

@@ -11,7 +11,6 @@ Tolerances
                           of every gradient is checked against float64 in test_at_size_against_float64) as g13: coarse model relative L2 < 1e-4 and max <= 1e-4 max|ref|; fine model 1e-2 and 3e-2 max|ref|
   parameters after Adam . the same relative L2 bounds; per element <= 1e-3 max|ref| (check_grads: Adam's step does not shrink with the gradient)
 """
-import copy
 import sys
 
 import numpy as np
@@ -19,22 +18,15 @@ import pytest
 import torch
 
 from conftest import GOLDEN, load_golden
+from nerf_baseline_checks import DEV, N_, T, chain_abs_sum, check_grads, check_render, cpu_eval, scene
+import nerf_baseline_checks as checks
 
 if GOLDEN not in sys.path:
     sys.path.insert(0, GOLDEN)
 import mip_params  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 ARITHS = ["f32", "bf16x3"]
-
-
-def T(a):
-    return torch.as_tensor(np.ascontiguousarray(a), device=DEV)
-
-
-def N_(t):
-    return t.detach().cpu().numpy()
 
 
 @pytest.fixture(scope="module")
@@ -43,27 +35,11 @@ def g23():
 
 
 def models_from(hip, g, arith):
-    """the two g23 models (coarse, fine): parameters from mip_params, checked against the fixture's checksums"""
-    ms = []
-    for i, seed in enumerate((101, 202)):
-        sd = mip_params.state_dict(seed)
-        flat = np.concatenate([v.reshape(-1).astype(np.float64) for v in sd.values()])
-        np.testing.assert_allclose([flat.sum(), (flat * flat).sum()], g["b.m%d.checksum" % i], rtol=1e-12)
-        m = hip.models.FlexibleNeRFModel(include_input_xyz=False).to(DEV)
-        m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
-        m.arithmetic = arith
-        ms.append(m)
-    return ms
+    return checks.models_from(hip, g, arith, mip_params, include_input_xyz=False)
 
 
-def opts(perturb=False, noise=0.0, chunk=131072, nc=64, nf=64):
-    from types import SimpleNamespace as NS
-    mode = NS(chunksize=chunk, perturb=perturb, num_coarse=nc, num_fine=nf, white_background=False, radiance_field_noise_std=noise, lindisp=False)
-    return NS(nerf=NS(use_viewdirs=True, encode_position_fn="mip", train=mode, validation=mode))
-
-
-def scene(ndc):
-    return {"near": 0.0 if ndc else 2.0, "far": 1.0 if ndc else 6.0, "no_ndc": not ndc}
+def opts(**kw):
+    return checks.opts("mip", **kw)
 
 
 def run(hip, g, mc, mf, o, mode, ndc=False, randoms=None):
@@ -71,31 +47,6 @@ def run(hip, g, mc, mf, o, mode, ndc=False, randoms=None):
     rays = torch.stack((T(g["c.ro"]).reshape(-1, 3), T(g["c.rd"]).reshape(-1, 3)))
     return hip.train_utils.run_one_iter_of_nerf(int(H), int(W), float(focal), mc, mf, rays, o, "lego_DS8", mode=mode, scene_config=scene(ndc),
                                                 randoms=randoms)
-
-
-def check_render(out, g, tag):
-    ec = np.abs(N_(out[0]) - g[tag + "rgb_coarse"]).max()
-    assert ec <= 3e-5, "%s coarse rgb max|err| %.2e" % (tag, ec)
-    assert np.abs(N_(out[2]) - g[tag + "acc_coarse"]).max() <= 3e-5
-    ef = np.abs(N_(out[3]) - g[tag + "rgb_fine"]).max(-1)
-    mse = float(((N_(out[3]) - g[tag + "rgb_fine"]) ** 2).mean())
-    psnr = 10 * np.log10(1.0 / max(mse, 1e-30))
-    assert (ef <= 2e-4).mean() >= 0.95 and psnr >= 70, "%s fine: %.3f of rays within 2e-4, PSNR %.1f dB" % (tag, (ef <= 2e-4).mean(), psnr)
-
-
-def check_grads(ms, g, prefix):
-    for i, m in enumerate(ms):
-        rl2, rmax = (1e-4, 1e-4) if i == 0 else (1e-2, 3e-2)
-        if not prefix:
-            # parameters after Adam: each element moves by ~lr m / sqrt(v) whatever its gradient's size, so an element whose gradient is
-            # near zero moves by up to lr per step on a sign that rounding decides -- the per-element bound is 1e-3 of the largest parameter
-            rmax = max(rmax, 1e-3)
-        for k, p in m.named_parameters():
-            ref = g["%s.m%d.grad.%s" % (prefix, i, k)] if prefix else g["e.m%d.%s" % (i, k)]
-            got = mip_params.kept(k, N_(p.grad if prefix else p))
-            assert np.isfinite(got).all(), k
-            rel = np.linalg.norm(got - ref) / max(np.linalg.norm(ref), 1e-30)
-            assert rel < rl2 and np.abs(got - ref).max() <= rmax * np.abs(ref).max(), "model %d %s: relative L2 %.2e" % (i, k, rel)
 
 
 def test_mip_encode_matches_upstream(hip, g23):
@@ -112,29 +63,6 @@ def test_mip_encode_matches_upstream(hip, g23):
     assert np.abs(g["a.means"]).max() * 32 > 100
 
 
-def _chain_abs_sum(g, i, x):
-    """float64 sum over the layers of max_rows (|W||x| + |b|): the scale of the bf16x3 error bound"""
-    sd = mip_params.state_dict((101, 202)[i])
-    W = lambda k: np.abs(sd[k + ".weight"]).astype(np.float64)
-    Wr = lambda k: sd[k + ".weight"].astype(np.float64)
-    b = lambda k: sd[k + ".bias"].astype(np.float64)
-    relu = lambda v: np.maximum(v, 0)
-    xyz, view = x[:, :36].astype(np.float64), x[:, 36:].astype(np.float64)
-    tot = 0.0
-    h = xyz @ Wr("layer1").T + b("layer1")
-    tot += (np.abs(xyz) @ W("layer1").T).max()
-    for j in range(3):
-        tot += (np.abs(h) @ W("layers_xyz.%d" % j).T).max()
-        h = relu(h @ Wr("layers_xyz.%d" % j).T + b("layers_xyz.%d" % j))
-    tot += (np.abs(h) @ W("fc_feat").T).max() + (np.abs(h) @ W("fc_alpha").T).max()
-    feat = relu(h @ Wr("fc_feat").T + b("fc_feat"))
-    c = np.concatenate([feat, view], -1)
-    tot += (np.abs(c) @ W("layers_dir.0").T).max()
-    hd = relu(c @ Wr("layers_dir.0").T + b("layers_dir.0"))
-    tot += (np.abs(hd) @ W("fc_rgb").T).max()
-    return tot
-
-
 @pytest.mark.parametrize("arith", ARITHS)
 def test_fused_forward_matches_upstream_model(hip, g23, arith):
     g = g23
@@ -142,7 +70,7 @@ def test_fused_forward_matches_upstream_model(hip, g23, arith):
     for i, m in enumerate(models_from(hip, g, arith)):
         with torch.no_grad():
             raw = N_(m.mip_forward(T(g["a.rays"]), T(g["a.edges"]), float(g["radius"]))).reshape(n * S, 4)
-        tol = 1e-5 if arith == "f32" else 1e-5 + 1e-6 * _chain_abs_sum(g, i, np.concatenate([g["a.ipe"], g["a.dirs"]], -1))
+        tol = 1e-5 if arith == "f32" else 1e-5 + 1e-6 * chain_abs_sum(mip_params.state_dict(mip_params.SEEDS[i]), np.concatenate([g["a.ipe"], g["a.dirs"]], -1), 36)
         err = np.abs(raw - g["b.m%d.raw" % i]).max()
         assert err <= tol, "model %d (%s): max|err| %.2e > %.2e" % (i, arith, err, tol)
     # model(x) on already-encoded rows still runs the scalar kernel with its own values
@@ -226,25 +154,8 @@ def test_at_size_against_float64(hip, arith):
     (raw * g_raw).sum().backward()
     x = torch.ops.nvsr.mip_encode(rays, edges, radius).cpu().double()
     gr = g_raw.reshape(-1, 4).cpu().double()
-
-    def cpu_eval(dtype):
-        ref = copy.deepcopy(m).cpu().to(dtype)
-        for q in ref.parameters():
-            q.grad = None
-        with torch.enable_grad():
-            xyz, view = x[:, :36].to(dtype), x[:, 36:].to(dtype)
-            h = ref.layer1(xyz)
-            for l in ref.layers_xyz:
-                h = torch.relu(l(h))
-            feat = torch.relu(ref.fc_feat(h))
-            alpha = ref.fc_alpha(h)
-            hd = torch.relu(ref.layers_dir[0](torch.cat((feat, view), -1)))
-            out = torch.cat((ref.fc_rgb(hd), alpha), -1)
-            (out * gr.to(dtype)).sum().backward()
-        return out.detach().double(), {k: p.grad.double() for k, p in ref.named_parameters()}
-
-    out64, g64 = cpu_eval(torch.float64)
-    _, g32 = cpu_eval(torch.float32)          # the reference's own arithmetic: the scale of the summation error over 524 288 points
+    out64, g64 = cpu_eval(m, x, gr, 36, torch.float64)
+    _, g32 = cpu_eval(m, x, gr, 36, torch.float32)     # the reference's own arithmetic: the scale of the summation error over 524 288 points
     e_fwd = float((raw.detach().reshape(-1, 4).cpu().double() - out64).abs().max())
     report = ["forward max|err| %.2e" % e_fwd]
     assert e_fwd <= (1e-5 if arith == "f32" else 1e-4), report

@@ -1,14 +1,12 @@
 """CPU checks of the Mip-NeRF baseline (MipNeRF_baseline.yml; csrc/mip.hip): the g23 fixture, the C ABI of the new kernels, the model's
 dimensions and the errors of the configurations it does not run."""
-import os
-import re
 import sys
-import types
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT, load_golden
+from conftest import GOLDEN, load_golden
+from nerf_baseline_checks import HOST_SCENE, check_bad_arguments, check_entry_points, check_geometry_refused, host_opts
 
 if GOLDEN not in sys.path:
     sys.path.insert(0, GOLDEN)
@@ -22,12 +20,14 @@ def test_g23_fixture_keys_and_shapes():
     assert g["a.means"].shape == (n, S, 3) and g["a.covs"].shape == (n, S, 3)
     assert g["a.ipe"].shape == (n * S, 36) and g["a.dirs"].shape == (n * S, 27)
     import mip_params
-    for i, seed in enumerate((101, 202)):
+    assert mip_params.SEEDS == (101, 202)
+    for i, seed in enumerate(mip_params.SEEDS):
         sd = mip_params.state_dict(seed)
         assert sd["layer1.weight"].shape == (128, 36) and sd["layers_dir.0.weight"].shape == (64, 155)
         assert sum(v.size for v in sd.values()) == 81092
         flat = np.concatenate([v.reshape(-1).astype(np.float64) for v in sd.values()])
         np.testing.assert_allclose([flat.sum(), (flat * flat).sum()], g["b.m%d.checksum" % i], rtol=1e-12)   # the recipe is the fixture's
+        np.testing.assert_array_equal(mip_params.checksum(sd), [flat.sum(), (flat * flat).sum()])
         assert g["b.m%d.raw" % i].shape == (n * S, 4)
         for name, shape in mip_params.SHAPES:
             want = min(int(np.prod(shape)), mip_params.KEEP)
@@ -42,30 +42,24 @@ def test_g23_fixture_keys_and_shapes():
     assert np.diff(g["a.edges"][2]).max() < 2e-5
 
 
-def test_header_declares_the_mip_entry_points(pkg_capi):
-    text = open(os.path.join(ROOT, "include", "nvsr.h")).read()
-    for name in ("nvsr_mip_encode", "nvsr_mip_nerf_forward_arith", "nvsr_mip_nerf_backward_arith", "nvsr_mip_nerf_wgrad_workspace_floats",
-                 "nvsr_mip_nerf_weight_grad"):
-        assert re.search(r"\b%s\s*\(" % name, text), name
-        assert name in pkg_capi.exported_symbols(), name
-    for macro, value in (("NVSR_MIP_NERF_NATURAL_FLOATS", pkg_capi.MIP_NERF_NATURAL_FLOATS), ("NVSR_MIP_NERF_RECORD_FLOATS", pkg_capi.MIP_NERF_RECORD_FLOATS),
-                         ("NVSR_MIP_NERF_GRAD_RECORD_FLOATS", pkg_capi.MIP_NERF_GRAD_RECORD_FLOATS)):
-        assert int(re.search(r"#define %s (\d+)" % macro, text).group(1)) == value
-    lib = pkg_capi.lib()
-    assert lib.nvsr_mip_nerf_wgrad_workspace_floats(0) == 0
-    assert lib.nvsr_mip_nerf_wgrad_workspace_floats(8193) == 2 * pkg_capi.MIP_NERF_NATURAL_FLOATS
-
-
 @pytest.fixture(scope="module")
 def pkg_capi():
     import nvsr_amd
     return nvsr_amd.capi
 
 
+def test_header_declares_the_mip_entry_points(pkg_capi):
+    check_entry_points(pkg_capi, "mip", (81092, 767, 708))
+
+
+def test_mip_entry_points_refuse_bad_arguments_without_a_gpu(pkg_capi):
+    check_bad_arguments(pkg_capi, "mip")
+
+
 def test_flexible_nerf_without_input_xyz_has_the_baseline_dimensions():
     import nvsr_amd
     m = nvsr_amd.models.FlexibleNeRFModel(include_input_xyz=False)
-    assert (m.dim_xyz, m.dim_dir) == (36, 27)
+    assert (m.dim_xyz, m.dim_dir) == (36, 27) and m.is_mip_baseline() and not m.is_pe_baseline()
     assert m.layer1.in_features == 36 and m.layers_dir[0].in_features == 155
     assert m.natural_blob().numel() == nvsr_amd.capi.MIP_NERF_NATURAL_FLOATS
     assert sum(p.numel() for p in m.parameters()) == nvsr_amd.capi.MIP_NERF_NATURAL_FLOATS
@@ -80,12 +74,6 @@ def test_mip_radius_from_the_scene_id():
             nvsr_amd.train_utils.mip_radius(bad)
 
 
-def _opts(encode):
-    mode = types.SimpleNamespace(chunksize=1024, perturb=False, num_coarse=8, num_fine=8, white_background=False, radiance_field_noise_std=0.0,
-                                 lindisp=False)
-    return types.SimpleNamespace(nerf=types.SimpleNamespace(use_viewdirs=True, encode_position_fn=encode, train=mode, validation=mode))
-
-
 def test_unsupported_configurations_raise_clearly():
     """positional-encoding NeRF is refused before any GPU work; so is a Mip-NeRF scene id without _DS<d> (before the rays are packed)"""
     import torch
@@ -94,7 +82,20 @@ def test_unsupported_configurations_raise_clearly():
     m = nvsr_amd.models.FlexibleNeRFModel(include_input_xyz=False)
     rays = torch.zeros(2, 4, 3)
     with pytest.raises(NotImplementedError, match="positional-encoding"):
-        tu.run_one_iter_of_nerf(4, 4, 2.0, m, m, rays, _opts("positional_encoding"), "lego_DS8", mode="validation",
-                                scene_config={"near": 2.0, "far": 6.0, "no_ndc": True})
+        tu.run_one_iter_of_nerf(4, 4, 2.0, m, m, rays, host_opts("positional_encoding"), "lego_DS8", mode="validation", scene_config=HOST_SCENE)
     with pytest.raises(ValueError, match="_DS"):
-        tu.run_one_iter_of_nerf(4, 4, 2.0, m, m, rays, _opts("mip"), "lego", mode="validation", scene_config={"near": 2.0, "far": 6.0, "no_ndc": True})
+        tu.run_one_iter_of_nerf(4, 4, 2.0, m, m, rays, host_opts("mip"), "lego", mode="validation", scene_config=HOST_SCENE)
+
+
+@pytest.mark.parametrize("kwargs", [dict()] + [dict(include_input_xyz=False, **kw) for kw in (
+    dict(num_encoding_fn_xyz=5), dict(num_encoding_fn_xyz=10), dict(num_encoding_fn_dir=3), dict(include_input_dir=False), dict(hidden_size=64),
+    dict(num_layers=6), dict(skip_connect_every=2))])
+def test_unsupported_mip_geometries_raise_before_gpu_work(kwargs):
+    """any FlexibleNeRFModel geometry other than the shipped one (dict(): the default model, PE's geometry) is refused under mip, coarse or
+    fine, before the rays are packed and before any coarse depths exist; mip_forward refuses it too"""
+    import torch
+    import nvsr_amd
+    bad = nvsr_amd.models.FlexibleNeRFModel(**kwargs)
+    check_geometry_refused(nvsr_amd.models.FlexibleNeRFModel(include_input_xyz=False), bad, "mip", "lego_DS8", "Mip-NeRF")
+    with pytest.raises(NotImplementedError, match="Mip-NeRF"):
+        bad.mip_forward(torch.zeros(2, 11), torch.zeros(2, 5), 0.001)

@@ -10,7 +10,6 @@ Tolerances (those of tests/test_mip_nerf.py)
                           every element of every gradient is checked against float64 in test_at_size_against_float64)
   parameters after Adam . the same relative L2 bounds; per element <= 1e-3 max|ref|
 """
-import copy
 import sys
 
 import numpy as np
@@ -18,22 +17,15 @@ import pytest
 import torch
 
 from conftest import GOLDEN, load_golden
+from nerf_baseline_checks import DEV, N_, T, chain_abs_sum, check_grads, check_render, cpu_eval, scene
+import nerf_baseline_checks as checks
 
 if GOLDEN not in sys.path:
     sys.path.insert(0, GOLDEN)
 import pe_params  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 ARITHS = ["f32", "bf16x3"]
-
-
-def T(a):
-    return torch.as_tensor(np.ascontiguousarray(a), device=DEV)
-
-
-def N_(t):
-    return t.detach().cpu().numpy()
 
 
 @pytest.fixture(scope="module")
@@ -42,26 +34,11 @@ def g24():
 
 
 def models_from(hip, g, arith):
-    """the two g24 models (coarse, fine): parameters from pe_params, checked against the fixture's checksums"""
-    ms = []
-    for i, seed in enumerate(pe_params.SEEDS):
-        sd = pe_params.state_dict(seed)
-        np.testing.assert_allclose(pe_params.checksum(sd), g["b.m%d.checksum" % i], rtol=1e-12)
-        m = hip.models.FlexibleNeRFModel().to(DEV)
-        m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
-        m.arithmetic = arith
-        ms.append(m)
-    return ms
+    return checks.models_from(hip, g, arith, pe_params)
 
 
-def opts(perturb=False, noise=0.0, chunk=131072, nc=64, nf=64):
-    from types import SimpleNamespace as NS
-    mode = NS(chunksize=chunk, perturb=perturb, num_coarse=nc, num_fine=nf, white_background=False, radiance_field_noise_std=noise, lindisp=False)
-    return NS(nerf=NS(use_viewdirs=True, encode_position_fn="positional_encoding", train=mode, validation=mode))
-
-
-def scene(ndc):
-    return {"near": 0.0 if ndc else 2.0, "far": 1.0 if ndc else 6.0, "no_ndc": not ndc}
+def opts(**kw):
+    return checks.opts("positional_encoding", **kw)
 
 
 def run(hip, g, mc, mf, o, mode, ndc=False, randoms=None):
@@ -69,29 +46,6 @@ def run(hip, g, mc, mf, o, mode, ndc=False, randoms=None):
     rays = torch.stack((T(g["c.ro"]).reshape(-1, 3), T(g["c.rd"]).reshape(-1, 3)))
     return hip.train_utils.run_one_iter_of_nerf(int(H), int(W), float(focal), mc, mf, rays, o, str(g["scene_id"]), mode=mode,
                                                 scene_config=scene(ndc), randoms=randoms)
-
-
-def check_render(out, g, tag):
-    ec = np.abs(N_(out[0]) - g[tag + "rgb_coarse"]).max()
-    assert ec <= 3e-5, "%s coarse rgb max|err| %.2e" % (tag, ec)
-    assert np.abs(N_(out[2]) - g[tag + "acc_coarse"]).max() <= 3e-5
-    ef = np.abs(N_(out[3]) - g[tag + "rgb_fine"]).max(-1)
-    mse = float(((N_(out[3]) - g[tag + "rgb_fine"]) ** 2).mean())
-    psnr = 10 * np.log10(1.0 / max(mse, 1e-30))
-    assert (ef <= 2e-4).mean() >= 0.95 and psnr >= 70, "%s fine: %.3f of rays within 2e-4, PSNR %.1f dB" % (tag, (ef <= 2e-4).mean(), psnr)
-
-
-def check_grads(ms, g, prefix):
-    for i, m in enumerate(ms):
-        rl2, rmax = (1e-4, 1e-4) if i == 0 else (1e-2, 3e-2)
-        if not prefix:
-            rmax = max(rmax, 1e-3)      # (Adam moves an element by ~lr per step whatever its gradient's size: tests/test_mip_nerf.py)
-        for k, p in m.named_parameters():
-            ref = g["%s.m%d.grad.%s" % (prefix, i, k)] if prefix else g["e.m%d.%s" % (i, k)]
-            got = pe_params.kept(k, N_(p.grad if prefix else p))
-            assert np.isfinite(got).all(), k
-            rel = np.linalg.norm(got - ref) / max(np.linalg.norm(ref), 1e-30)
-            assert rel < rl2 and np.abs(got - ref).max() <= rmax * np.abs(ref).max(), "model %d %s: relative L2 %.2e" % (i, k, rel)
 
 
 @pytest.mark.parametrize("tag", ["a.", "a.ndc."])
@@ -105,29 +59,6 @@ def test_pe_encode_matches_upstream(hip, g24, tag):
     np.testing.assert_allclose(out[:, 39:], g[tag + "dirs"], rtol=0, atol=2e-6)
 
 
-def _chain_abs_sum(i, x):
-    """float64 sum over the layers of max_rows (|W||x| + |b|): the scale of the bf16x3 error bound"""
-    sd = pe_params.state_dict(pe_params.SEEDS[i])
-    W = lambda k: np.abs(sd[k + ".weight"]).astype(np.float64)
-    Wr = lambda k: sd[k + ".weight"].astype(np.float64)
-    b = lambda k: sd[k + ".bias"].astype(np.float64)
-    relu = lambda v: np.maximum(v, 0)
-    xyz, view = x[:, :39].astype(np.float64), x[:, 39:].astype(np.float64)
-    tot = 0.0
-    h = xyz @ Wr("layer1").T + b("layer1")
-    tot += (np.abs(xyz) @ W("layer1").T).max()
-    for j in range(3):
-        tot += (np.abs(h) @ W("layers_xyz.%d" % j).T).max()
-        h = relu(h @ Wr("layers_xyz.%d" % j).T + b("layers_xyz.%d" % j))
-    tot += (np.abs(h) @ W("fc_feat").T).max() + (np.abs(h) @ W("fc_alpha").T).max()
-    feat = relu(h @ Wr("fc_feat").T + b("fc_feat"))
-    c = np.concatenate([feat, view], -1)
-    tot += (np.abs(c) @ W("layers_dir.0").T).max()
-    hd = relu(c @ Wr("layers_dir.0").T + b("layers_dir.0"))
-    tot += (np.abs(hd) @ W("fc_rgb").T).max()
-    return tot
-
-
 @pytest.mark.parametrize("arith", ARITHS)
 def test_fused_forward_matches_upstream_model(hip, g24, arith):
     g = g24
@@ -137,7 +68,7 @@ def test_fused_forward_matches_upstream_model(hip, g24, arith):
         for i, m in enumerate(models_from(hip, g, arith)):
             with torch.no_grad():
                 raw = N_(m.pe_forward(T(g[tag + "rays"]), T(g[tag + "z"]))).reshape(n * S, 4)
-            tol = 1e-5 if arith == "f32" else 1e-5 + 1e-6 * _chain_abs_sum(i, x)
+            tol = 1e-5 if arith == "f32" else 1e-5 + 1e-6 * chain_abs_sum(pe_params.state_dict(pe_params.SEEDS[i]), x, 39)
             err = np.abs(raw - g["b.m%d.%s" % (i, key)]).max()
             assert err <= tol, "%s model %d (%s): max|err| %.2e > %.2e" % (tag, i, arith, err, tol)
     # model(x) on already-encoded rows still runs the scalar kernel with its own values
@@ -228,25 +159,8 @@ def test_at_size_against_float64(hip, arith):
     (raw * g_raw).sum().backward()
     x = torch.ops.nvsr.pe_encode(rays, z).cpu().double()
     gr = g_raw.reshape(-1, 4).cpu().double()
-
-    def cpu_eval(dtype):
-        ref = copy.deepcopy(m).cpu().to(dtype)
-        for q in ref.parameters():
-            q.grad = None
-        with torch.enable_grad():
-            xyz, view = x[:, :39].to(dtype), x[:, 39:].to(dtype)
-            h = ref.layer1(xyz)
-            for l in ref.layers_xyz:
-                h = torch.relu(l(h))
-            feat = torch.relu(ref.fc_feat(h))
-            alpha = ref.fc_alpha(h)
-            hd = torch.relu(ref.layers_dir[0](torch.cat((feat, view), -1)))
-            out = torch.cat((ref.fc_rgb(hd), alpha), -1)
-            (out * gr.to(dtype)).sum().backward()
-        return out.detach().double(), {k: p.grad.double() for k, p in ref.named_parameters()}
-
-    out64, g64 = cpu_eval(torch.float64)
-    _, g32 = cpu_eval(torch.float32)          # the reference's own arithmetic: the scale of the summation error over 524 288 points
+    out64, g64 = cpu_eval(m, x, gr, 39, torch.float64)
+    _, g32 = cpu_eval(m, x, gr, 39, torch.float32)     # the reference's own arithmetic: the scale of the summation error over 524 288 points
     e_fwd = float((raw.detach().reshape(-1, 4).cpu().double() - out64).abs().max())
     report = ["forward max|err| %.2e" % e_fwd]
     assert e_fwd <= (1e-5 if arith == "f32" else 1e-4), report

@@ -1,14 +1,12 @@
 """CPU checks of the positional-encoding NeRF baseline (MipNeRF_baseline.yml with encode_position_fn: positional_encoding; csrc/pe.hip): the
 g24 fixture, the C ABI of the new entry points, the model's dimensions and the errors of the geometries the kernels are not built for."""
-import os
-import re
 import sys
-import types
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT, load_golden
+from conftest import GOLDEN, load_golden
+from nerf_baseline_checks import HOST_SCENE, check_bad_arguments, check_entry_points, check_geometry_refused, host_opts
 
 if GOLDEN not in sys.path:
     sys.path.insert(0, GOLDEN)
@@ -47,45 +45,21 @@ def pkg_capi():
 
 
 def test_header_declares_the_pe_entry_points(pkg_capi):
-    text = open(os.path.join(ROOT, "include", "nvsr.h")).read()
-    for name in ("nvsr_pe_encode", "nvsr_pe_nerf_forward_arith", "nvsr_pe_nerf_backward_arith", "nvsr_pe_nerf_wgrad_workspace_floats",
-                 "nvsr_pe_nerf_weight_grad"):
-        assert re.search(r"\b%s\s*\(" % name, text), name
-        assert name in pkg_capi.exported_symbols(), name
-    for macro, value in (("NVSR_PE_NERF_NATURAL_FLOATS", 81476), ("NVSR_PE_NERF_RECORD_FLOATS", 770), ("NVSR_PE_NERF_GRAD_RECORD_FLOATS", 708)):
-        assert int(re.search(r"#define %s (\d+)" % macro, text).group(1)) == value
-        assert getattr(pkg_capi, macro[len("NVSR_"):]) == value
-    lib = pkg_capi.lib()
-    assert lib.nvsr_pe_nerf_wgrad_workspace_floats(0) == 0
-    assert lib.nvsr_pe_nerf_wgrad_workspace_floats(8192) == pkg_capi.PE_NERF_NATURAL_FLOATS
-    assert lib.nvsr_pe_nerf_wgrad_workspace_floats(8193) == 2 * pkg_capi.PE_NERF_NATURAL_FLOATS
+    check_entry_points(pkg_capi, "pe", (81476, 770, 708))
 
 
 def test_pe_entry_points_refuse_bad_arguments_without_a_gpu(pkg_capi):
-    """shape / arithmetic / null checks return before any launch"""
-    lib = pkg_capi.lib()
-    assert lib.nvsr_pe_encode(-1, 4, None, None, None, None) == 1                     # NVSR_ERR_SHAPE
-    assert lib.nvsr_pe_encode(0, 4, None, None, None, None) == 0                      # nothing to do
-    assert lib.nvsr_pe_nerf_forward_arith(1, 0, None, None, None, None, None, 0, None) == 1
-    assert lib.nvsr_pe_nerf_forward_arith(1, 4, None, None, None, None, None, 7, None) == 1
-    assert lib.nvsr_pe_nerf_backward_arith(-1, None, None, None, None, 0, None) == 1
-    assert lib.nvsr_pe_nerf_weight_grad(-1, None, None, None, None, None) == 1
+    check_bad_arguments(pkg_capi, "pe")
 
 
 def test_default_flexible_nerf_is_the_pe_baseline():
     import nvsr_amd
     m = nvsr_amd.models.FlexibleNeRFModel()
-    assert (m.dim_xyz, m.dim_dir) == (39, 27) and m.is_pe_baseline()
+    assert (m.dim_xyz, m.dim_dir) == (39, 27) and m.is_pe_baseline() and not m.is_mip_baseline()
     assert m.layer1.in_features == 39 and m.layers_dir[0].in_features == 155
     assert m.natural_blob().numel() == nvsr_amd.capi.PE_NERF_NATURAL_FLOATS
     assert sum(p.numel() for p in m.parameters()) == nvsr_amd.capi.PE_NERF_NATURAL_FLOATS
     assert not nvsr_amd.models.FlexibleNeRFModel(include_input_xyz=False).is_pe_baseline()
-
-
-def _opts(encode):
-    mode = types.SimpleNamespace(chunksize=1024, perturb=False, num_coarse=8, num_fine=8, white_background=False, radiance_field_noise_std=0.0,
-                                 lindisp=False)
-    return types.SimpleNamespace(nerf=types.SimpleNamespace(use_viewdirs=True, encode_position_fn=encode, train=mode, validation=mode))
 
 
 @pytest.mark.parametrize("kwargs", [dict(include_input_xyz=False), dict(num_encoding_fn_xyz=5), dict(num_encoding_fn_xyz=10),
@@ -96,14 +70,8 @@ def test_unsupported_pe_geometries_raise_before_gpu_work(kwargs):
     packed (these are CPU models and CPU rays: reaching a kernel would fail differently)"""
     import torch
     import nvsr_amd
-    tu = nvsr_amd.train_utils
-    good = nvsr_amd.models.FlexibleNeRFModel()
     bad = nvsr_amd.models.FlexibleNeRFModel(**kwargs)
-    rays = torch.zeros(2, 4, 3)
-    for mc, mf in ((bad, good), (good, bad)):
-        with pytest.raises(NotImplementedError, match="positional-encoding"):
-            tu.run_one_iter_of_nerf(4, 4, 2.0, mc, mf, rays, _opts("positional_encoding"), "lego", mode="validation",
-                                    scene_config={"near": 2.0, "far": 6.0, "no_ndc": True})
+    check_geometry_refused(nvsr_amd.models.FlexibleNeRFModel(), bad, "positional_encoding", "lego", "positional-encoding")
     with pytest.raises(NotImplementedError, match="positional-encoding"):
         bad.pe_forward(torch.zeros(2, 11), torch.zeros(2, 4))
 
@@ -113,5 +81,5 @@ def test_flexible_nerf_without_an_encoding_still_raises():
     import nvsr_amd
     m = nvsr_amd.models.FlexibleNeRFModel()
     with pytest.raises(NotImplementedError, match="positional-encoding"):
-        nvsr_amd.train_utils.run_one_iter_of_nerf(4, 4, 2.0, m, m, torch.zeros(2, 4, 3), _opts(None), "lego", mode="validation",
-                                                  scene_config={"near": 2.0, "far": 6.0, "no_ndc": True})
+        nvsr_amd.train_utils.run_one_iter_of_nerf(4, 4, 2.0, m, m, torch.zeros(2, 4, 3), host_opts(None), "lego", mode="validation",
+                                                  scene_config=HOST_SCENE)
