@@ -349,8 +349,14 @@ int nvsr_flexible_nerf_forward(int64_t P, const float* x, int dim_xyz, int dim_d
  * layer1 36->128 (linear), 3 x ReLU(128->128), ReLU(fc_feat) 128->128, fc_alpha 128->1, ReLU(layers_dir(cat(feat, dir))) 155->64, fc_rgb 64->3.
  * natural = state-dict order (layer1, layers_xyz.0-2, layers_dir.0, fc_alpha, fc_rgb, fc_feat, each {weight[out,in], bias}).
  * rays [N,11] (nvsr_pack_rays), edges [N,S+1] (the S intervals of each ray), radius = ds 0.00135 2 / sqrt(12) (train_utils.py:19-27).
- * arithmetic: NVSR_ARITH_F32 or NVSR_ARITH_BF16X3 (NVSR_ARITH_INHERIT = the decoder default); a request for NVSR_ARITH_F16X2 runs
- * NVSR_ARITH_BF16X3 -- this model has no f16 range check, and the 3 bf16 limbs have no range limit. */
+ * arithmetic: NVSR_ARITH_F32, NVSR_ARITH_BF16X3 or NVSR_ARITH_F16X2 (3 v_mfma_f32_32x32x16_f16 per product block on 2 round-to-nearest limbs,
+ * weights x 2^8 and activations x 2^4 as above, split where they are multiplied: the weights stay the natural f32 blob).  F16X2 has the range
+ * contract of the decoder kernels: a weight |W| >= 255 or an activation / encoding |x| >= 4094 enters the products as NaN (a ReLU keeps it),
+ * and a launch that writes a non-finite raw row or gradient ORs 1 into the range flag (nvsr_set_range_flag); a gradient chain that grows
+ * beyond the f16 range in the backward does the same.  The backward scales each point's chains by powers of two: the rgb chain by the one that
+ * puts max |dL/drgb| into [8, 16), the chain from fc_feat down (where dL/dalpha joins) by the one of max |dL/draw|; grad_record is written
+ * unscaled (a loss scaled by 2^k gives the same bits times 2^k).  NVSR_ARITH_INHERIT = the decoder default with NVSR_ARITH_F16X2 read as
+ * NVSR_ARITH_BF16X3: a caller who never names F16X2 runs what these entry points ran before they had it. */
 #define NVSR_MIP_NERF_NATURAL_FLOATS 81092
 #define NVSR_MIP_NERF_RECORD_FLOATS 767        /* per point: [enc 36 | dir 27 | h1 | h2 | h3 | h4 | feat (128 each) | hd 64] */
 #define NVSR_MIP_NERF_GRAD_RECORD_FLOATS 708   /* per point: pre-activation gradients [layer1 | x0 | x1 | x2 | feat (128 each) | alpha | dir 64 | rgb 3] */
@@ -373,7 +379,7 @@ int nvsr_mip_nerf_weight_grad(int64_t P, const float* record, const float* grad_
 /* ---- the positional-encoding NeRF baseline (MipNeRF_baseline.yml with encode_position_fn: positional_encoding; csrc/pe.hip) ------------
  * FlexibleNeRFModel(num_encoding_fn_xyz=6, num_encoding_fn_dir=4, include_input_xyz=True, include_input_dir=True) with the constructor
  * defaults (train_nerf.py:338-348): the Mip-NeRF model above with layer1 39->128.  Same natural order, the same layer engine (csrc/nerf_mlp.h).
- * rays [N,11] (nvsr_pack_rays), z [N,S] (the S sample depths of each ray); arithmetic as for the Mip-NeRF baseline. */
+ * rays [N,11] (nvsr_pack_rays), z [N,S] (the S sample depths of each ray); arithmetic (F16X2 and INHERIT included) as for the Mip-NeRF baseline. */
 #define NVSR_PE_NERF_NATURAL_FLOATS 81476
 #define NVSR_PE_NERF_RECORD_FLOATS 770         /* per point: [enc 39 | dir 27 | h1 | h2 | h3 | h4 | feat (128 each) | hd 64] */
 #define NVSR_PE_NERF_GRAD_RECORD_FLOATS 708    /* per point: pre-activation gradients, the layout of NVSR_MIP_NERF_GRAD_RECORD_FLOATS */

@@ -235,6 +235,16 @@ def resolve_decoder_arithmetic(mode=None):
     return lib().nvsr_get_decoder_arithmetic() if code == ARITH_INHERIT else code
 
 
+def resolve_nerf_arithmetic(mode=None):
+    """the concrete NVSR_ARITH_* code a call of the two FlexibleNeRFModel baselines (nvsr_{mip,pe}_nerf_*_arith) made now with `mode` runs in:
+    an explicit 'f16x2' runs f16x2; an INHERITED f16x2 default runs bf16x3 (csrc/nerf_mlp.h: nerf_arith, include/nvsr.h)"""
+    code = arith_code(mode)
+    if code != ARITH_INHERIT:
+        return code
+    code = lib().nvsr_get_decoder_arithmetic()
+    return ARITHMETIC["bf16x3"] if code == ARITHMETIC["f16x2"] else code
+
+
 def resolve_conv_arithmetic(mode=None):
     code = arith_code(mode)
     return lib().nvsr_get_conv_arithmetic() if code == ARITH_INHERIT else code

@@ -17,8 +17,10 @@
 // DESIGN.md 3.7 has the traffic this costs.
 //
 // Arithmetic: NVSR_ARITH_F32 = v_mfma_f32_32x32x2_f32 (exact products); NVSR_ARITH_BF16X3 = v_mfma_f32_32x32x16_bf16 on 3 truncation limbs of
-// both operands, 6 products (limb_core.h).  NVSR_ARITH_F16X2 runs BF16X3 (include/nvsr.h).  The weight gradients are exact-f32 MFMAs in
-// either case.
+// both operands, 6 products; NVSR_ARITH_F16X2 = v_mfma_f32_32x32x16_f16 on 2 round-to-nearest f16 limbs, 3 products, with the static scales
+// of limb_core.h (weights x 2^F16_SW, activations x 2^F16_SX; the backward's gradient operand carries one power of two per point instead).
+// Every operand is split where it is multiplied, the weights included: the weight stream stays the natural f32 blob.  An
+// F16X2 request that INHERITS the process default runs BF16X3 (include/nvsr.h).  The weight gradients are exact-f32 MFMAs in every case.
 #pragma once
 #include "limb_core.h"
 
@@ -71,7 +73,16 @@ __device__ __forceinline__ float dir_column(const float* __restrict__ r, int q) 
 // One dense layer of a 32-point tile: for every block of 32 outputs o, acc = W'[o][0..K) . X[point][0..K) on the matrix pipe, then
 // put(point n, output m, acc) for m < M.  W'[o][k] = W[o * ldw + k] (forward) or W[k * ldw + o] (TRANS: the transposed layer of the backward),
 // 0 outside o < M, k < K.  X: the wave's LDS rows (stride MIP_LD); its columns [K, K rounded up to the K-step) must hold zeros.
-template <int ARITH, bool TRANS, class Put>
+// F16X2: the weights go in as W 2^F16_SW and the activations as x 2^F16_SX (GRAD: as they are -- the backward's rows carry a power of two per
+// point), put() receives the unscaled sum.  Forward (not GRAD): a weight |W| >= 255 or an activation |x| >= 4094 enters the products as NaN.
+// Backward (GRAD): no compare per weight and use.  A weight whose W 2^8 rounds beyond the f16 range (|W| >= 255.97; up to there both limbs
+// are exact) has hi = inf and lo = RN(W 2^8 - inf) = -inf, so Wh x + Wl x = inf - inf = NaN for x != 0 and inf 0 = NaN for x = 0: the
+// overflow is its own poison, as in the tri-plane kernels (and a weight in [255, 255.97) has already made its forward NaN).  A gradient
+// operand beyond the f16 range overflows to inf the same way: the outputs it reaches are NaN, never a finite wrong number.
+// (Measured, profiles/nerf_baseline_time.txt: the backward without the weight compare is 4 % faster than the one with it, the forward 7 %
+// slower -- its schedule around the weight loads changes; each keeps its faster form.)
+constexpr float NERF_F16_W_MAX = 255.0f, NERF_F16_X_MAX = 4094.0f;
+template <int ARITH, bool TRANS, bool GRAD = false, class Put>
 __device__ __forceinline__ void tile_layer(const float* __restrict__ W, int ldw, int M, int K, const float* X, int lane, Put put) {
     const int n = lane & 31, h = lane >> 5;
 #pragma nounroll
@@ -87,6 +98,27 @@ __device__ __forceinline__ void tile_layer(const float* __restrict__ W, int ldw,
                 const float a = (o < M && k < K) ? (TRANS ? W[(long)k * ldw + o] : W[(long)o * ldw + k]) : 0.0f;
                 acc = mfma32(a, X[n * MIP_LD + k], acc);
             }
+        } else if constexpr (ARITH == NVSR_ARITH_F16X2) {
+#pragma unroll 2
+            for (int k0 = 0; k0 < K; k0 += 16) {
+                float a[8], b[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int k = k0 + 8 * h + j;
+                    const float wv = (o < M && k < K) ? (TRANS ? W[(long)k * ldw + o] : W[(long)o * ldw + k]) : 0.0f;
+                    const float xv = X[n * MIP_LD + k];
+                    a[j] = GRAD ? wv * F16_W_SCALE : (fabsf(wv) < NERF_F16_W_MAX ? wv * F16_W_SCALE : __builtin_nanf(""));
+                    b[j] = GRAD ? xv : (fabsf(xv) < NERF_F16_X_MAX ? xv * F16_X_SCALE : __builtin_nanf(""));
+                }
+                Limbs<2> wa, xb;
+                split_all<2>([&](int i) { return a[i]; }, wa);
+                split_all<2>([&](int i) { return b[i]; }, xb);
+#pragma unroll
+                for (int p = 0; p < 3; ++p) acc = mfma_limb<2>(wa.v[limb_w(2, p)], xb.v[limb_x(2, p)], acc);
+            }
+            constexpr float un = GRAD ? F16_ACC_UNSCALE : F16_ACC_UNSCALE * F16_HEAD_SCALE;      // 2^-SW, 2^-(SW + SX)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] *= un;
         } else {
 #pragma unroll 2
             for (int k0 = 0; k0 < K; k0 += 16) {
@@ -138,9 +170,11 @@ __global__ void nerf_encode_kernel(long P, E enc, float* __restrict__ out) {
 //   enc -> xa[0,48) (ENC..47 zero), dir -> xb[128,160) (155..159 zero)
 //   layer1: xa -> xb[0,128) h1;  x0: xb -> xa h2;  x1: xa -> xb h3;  x2: xb -> xa[0,128) h4
 //   fc_alpha: xa -> xa[131];  fc_feat: xa -> xb[0,128) feat (next to dir);  layers_dir: xb[0,160) -> xa[0,64) hd;  fc_rgb: xa -> xa[128,131)
+//   F16X2: a ReLU that keeps NaN (fmaxf(NaN, 0) is 0: an out-of-range hidden activation would vanish), and a lane that writes a non-finite raw
+//   row ORs 1 into the range flag (include/nvsr.h: nvsr_set_range_flag)
 template <class E, int ARITH>
 __global__ __launch_bounds__(64 * MIP_WAVES) void nerf_forward_kernel(long P, E enc, const float* __restrict__ w, float* __restrict__ raw,
-                                                                     float* __restrict__ rec) {
+                                                                     float* __restrict__ rec, unsigned* __restrict__ flag) {
     using L = NerfLayout<E::ENC>;
     __shared__ float lds[MIP_WAVES * 2 * 32 * MIP_LD];
     NVSR_RACE_PROBE_DELAY(lds);
@@ -163,7 +197,8 @@ __global__ __launch_bounds__(64 * MIP_WAVES) void nerf_forward_kernel(long P, E 
     auto dense = [&](int wo, int bo, int M, int K, const float* X, float* Y, int yoff, bool relu) {
         tile_layer<ARITH, false>(w + wo, K, M, K, X, lane, [&](int pt, int m, float a) {
             const float v = __fadd_rn(a, w[bo + m]);
-            Y[pt * MIP_LD + yoff + m] = relu ? fmaxf(v, 0.0f) : v;
+            if constexpr (ARITH == NVSR_ARITH_F16X2) Y[pt * MIP_LD + yoff + m] = (relu && !(v != v)) ? fmaxf(v, 0.0f) : v;
+            else Y[pt * MIP_LD + yoff + m] = relu ? fmaxf(v, 0.0f) : v;
         });
     };
     dense(L::W_L1, L::B_L1, MH, L::ENC, xa, xb, 0, false);
@@ -183,6 +218,9 @@ __global__ __launch_bounds__(64 * MIP_WAVES) void nerf_forward_kernel(long P, E 
     if (live && h == 0) {
         float4 o = {xa[n * MIP_LD + 128], xa[n * MIP_LD + 129], xa[n * MIP_LD + 130], xa[n * MIP_LD + 131]};
         reinterpret_cast<float4*>(raw)[p] = o;
+        if constexpr (ARITH == NVSR_ARITH_F16X2) {
+            if (flag && !(fabsf(o.x + o.y + o.z + o.w) <= 3.0e38f)) __hip_atomic_fetch_or(flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
     }
 }
 
@@ -190,10 +228,29 @@ __global__ __launch_bounds__(64 * MIP_WAVES) void nerf_forward_kernel(long P, E 
 //   G_rgb -> xa[0,3) (3..15 zero);  fc_rgb's input gradient gated by hd > 0 = G_dir -> xb[0,64)
 //   (G_dir W_dir)[0,128) gated by feat > 0 = G_feat -> xa[0,128);  G_feat W_feat + G_alpha W_alpha gated by h4 > 0 = G_x2 -> xb
 //   G_x2 W_x2 gated by h3 = G_x1 -> xa;  G_x1 W_x1 gated by h2 = G_x0 -> xb;  G_x0 W_x0 = G_1 (layer1 is linear) -> xa
+// F16X2: gradients span far more binades than f16's 5 exponent bits, but one chain of one point does not -- every layer of the backward is
+// linear in that point's dL/draw (the ReLU gates come from the record).  As in render_bwd_limb.hip (pow2_scales), a point carries two powers
+// of two: the rgb chain (G_rgb -> G_dir -> G_feat) is scaled by the one that puts max |dL/drgb| into [2^NERF_F16_UP, 2^(NERF_F16_UP+1)), and
+// from fc_feat's transposed product on (G_x2 .. G_1, where dL/dalpha joins) the chain runs at the scale of max |dL/draw|; the rgb part enters
+// there through an exact multiply by the ratio of the two (<= 1: what it shrinks below an f32 subnormal is below 2^-126 of the joint chain).
+// Behind a surface dL/dalpha and dL/drgb of one sample differ by many binades: one scale for both would leave the rgb chain in subnormal f16.
+// The rows are written unscaled (lane pt holds point pt's two undos; a row's is read with v_readlane).  Exact: a point is a column of every
+// product, and a loss scaled by 2^k gives the same bits times 2^k.  A lane that writes a non-finite gradient ORs 1 into the range flag (the
+// stored values are accumulated as v 0: NaN iff one of them is inf or NaN -- one FMA per value).
+constexpr int NERF_F16_UP = 3;
+__device__ __forceinline__ void nerf_pow2_scale(float m, float& sc, float& un) {
+    const int e = (int)((__float_as_uint(m) >> 23) & 0xffu);              // biased exponent of the largest magnitude (0: zero or subnormal)
+    // (clamped to [1 + UP, 253]: both factors stay normal numbers; a non-finite dL/draw keeps a scale of 1 and comes out non-finite)
+    const int eu = (e == 255 ? 127 + NERF_F16_UP : (e > 253 ? 253 : (e < 1 + NERF_F16_UP ? 1 + NERF_F16_UP : e))) - NERF_F16_UP;
+    sc = __uint_as_float((unsigned)(254 - eu) << 23);
+    un = __uint_as_float((unsigned)eu << 23);
+}
 template <int ENC, int ARITH>
 __global__ __launch_bounds__(64 * MIP_WAVES) void nerf_backward_kernel(long P, const float* __restrict__ w, const float* __restrict__ rec,
-                                                                      const float* __restrict__ g_raw, float* __restrict__ grec) {
+                                                                      const float* __restrict__ g_raw, float* __restrict__ grec,
+                                                                      unsigned* __restrict__ flag) {
     using L = NerfLayout<ENC>;
+    constexpr bool F16 = ARITH == NVSR_ARITH_F16X2;
     __shared__ float lds[MIP_WAVES * 2 * 32 * MIP_LD];
     NVSR_RACE_PROBE_DELAY(lds);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, n = lane & 31, h = lane >> 5;
@@ -203,31 +260,60 @@ __global__ __launch_bounds__(64 * MIP_WAVES) void nerf_backward_kernel(long P, c
     if (p0 >= P) return;
     const long p = p0 + n;
     const bool live = p < P;
-    const float g_alpha = live ? g_raw[p * 4 + 3] : 0.0f;
-    for (int c = h; c < 16; c += 2) xa[n * MIP_LD + c] = (live && c < 3) ? g_raw[p * 4 + c] : 0.0f;
+    const float g_alpha_in = live ? g_raw[p * 4 + 3] : 0.0f;
+    float sc_r = 1.0f, un_r = 1.0f, sc_m = 1.0f, un_m = 1.0f, join = 1.0f, chk = 0.0f;
+    if constexpr (F16) {
+        const float mr = live ? fmaxf(fmaxf(fabsf(g_raw[p * 4]), fabsf(g_raw[p * 4 + 1])), fabsf(g_raw[p * 4 + 2])) : 0.0f;
+        nerf_pow2_scale(mr, sc_r, un_r);
+        nerf_pow2_scale(fmaxf(mr, fabsf(g_alpha_in)), sc_m, un_m);
+        join = sc_m * un_r;                                                 // rgb chain -> joint chain, a power of two <= 1
+    }
+    const float g_alpha = F16 ? g_alpha_in * sc_m : g_alpha_in;
+    for (int c = h; c < 16; c += 2) xa[n * MIP_LD + c] = (live && c < 3) ? (F16 ? g_raw[p * 4 + c] * sc_r : g_raw[p * 4 + c]) : 0.0f;
     wave_sync();
-    store_rows(xa, 0, 3, grec, NERF_GREC, G_RGB, p0, P, lane);
-    if (live && h == 0) grec[p * NERF_GREC + G_A] = g_alpha;
+    auto store = [&](const float* X, int nc, int off, float un) {
+        if constexpr (F16) {
+            for (int pt = 0; pt < 32 && p0 + pt < P; ++pt) {
+                const float u = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(un), pt));
+                for (int c = lane; c < nc; c += 64) {
+                    const float v = X[pt * MIP_LD + c] * u;
+                    chk = fmaf(v, 0.0f, chk);
+                    grec[(p0 + pt) * NERF_GREC + off + c] = v;
+                }
+            }
+            wave_sync();
+        } else {
+            store_rows(X, 0, nc, grec, NERF_GREC, off, p0, P, lane);
+        }
+    };
+    store(xa, 3, G_RGB, un_r);
+    if (live && h == 0) grec[p * NERF_GREC + G_A] = g_alpha_in;
+    if constexpr (F16) { if (live && h == 0) chk = fmaf(g_alpha_in, 0.0f, chk); }
     // (a dead point's record row does not exist: its gate reads are skipped and its gradient rows are zeros)
     auto gate = [&](int off, int pt, int m) { return p0 + pt < P && rec[(p0 + pt) * L::REC + off + m] > 0.0f; };
-    tile_layer<ARITH, true>(w + L::W_RGB, MHD, MHD, 3, xa, lane, [&](int pt, int m, float a) {
+    tile_layer<ARITH, true, true>(w + L::W_RGB, MHD, MHD, 3, xa, lane, [&](int pt, int m, float a) {
         xb[pt * MIP_LD + m] = gate(L::R_HD, pt, m) ? a : 0.0f;
     });
-    store_rows(xb, 0, MHD, grec, NERF_GREC, G_DIR, p0, P, lane);
-    tile_layer<ARITH, true>(w + L::W_DIR, MH + NERF_DIR, MH, MHD, xb, lane, [&](int pt, int m, float a) {
+    store(xb, MHD, G_DIR, un_r);
+    tile_layer<ARITH, true, true>(w + L::W_DIR, MH + NERF_DIR, MH, MHD, xb, lane, [&](int pt, int m, float a) {
         xa[pt * MIP_LD + m] = gate(L::R_FEAT, pt, m) ? a : 0.0f;
     });
-    store_rows(xa, 0, MH, grec, NERF_GREC, G_FEAT, p0, P, lane);
-    tile_layer<ARITH, true>(w + L::W_F, MH, MH, MH, xa, lane, [&](int pt, int m, float a) {
-        xb[pt * MIP_LD + m] = gate(L::R_H4, pt, m) ? __fadd_rn(a, __fmul_rn(g_alpha, w[L::W_A + m])) : 0.0f;   // (lane (pt, h) holds point pt's g_alpha)
+    store(xa, MH, G_FEAT, un_r);
+    // (lane (pt, h) holds point pt's g_alpha and join)
+    tile_layer<ARITH, true, true>(w + L::W_F, MH, MH, MH, xa, lane, [&](int pt, int m, float a) {
+        if constexpr (F16) a *= join;
+        xb[pt * MIP_LD + m] = gate(L::R_H4, pt, m) ? __fadd_rn(a, __fmul_rn(g_alpha, w[L::W_A + m])) : 0.0f;
     });
-    store_rows(xb, 0, MH, grec, NERF_GREC, G_X2, p0, P, lane);
-    tile_layer<ARITH, true>(w + L::W_X2, MH, MH, MH, xb, lane, [&](int pt, int m, float a) { xa[pt * MIP_LD + m] = gate(L::R_H3, pt, m) ? a : 0.0f; });
-    store_rows(xa, 0, MH, grec, NERF_GREC, G_X1, p0, P, lane);
-    tile_layer<ARITH, true>(w + L::W_X1, MH, MH, MH, xa, lane, [&](int pt, int m, float a) { xb[pt * MIP_LD + m] = gate(L::R_H2, pt, m) ? a : 0.0f; });
-    store_rows(xb, 0, MH, grec, NERF_GREC, G_X0, p0, P, lane);
-    tile_layer<ARITH, true>(w + L::W_X0, MH, MH, MH, xb, lane, [&](int pt, int m, float a) { xa[pt * MIP_LD + m] = a; });
-    store_rows(xa, 0, MH, grec, NERF_GREC, G_L1, p0, P, lane);
+    store(xb, MH, G_X2, un_m);
+    tile_layer<ARITH, true, true>(w + L::W_X2, MH, MH, MH, xb, lane, [&](int pt, int m, float a) { xa[pt * MIP_LD + m] = gate(L::R_H3, pt, m) ? a : 0.0f; });
+    store(xa, MH, G_X1, un_m);
+    tile_layer<ARITH, true, true>(w + L::W_X1, MH, MH, MH, xa, lane, [&](int pt, int m, float a) { xb[pt * MIP_LD + m] = gate(L::R_H2, pt, m) ? a : 0.0f; });
+    store(xb, MH, G_X0, un_m);
+    tile_layer<ARITH, true, true>(w + L::W_X0, MH, MH, MH, xb, lane, [&](int pt, int m, float a) { xa[pt * MIP_LD + m] = a; });
+    store(xa, MH, G_L1, un_m);
+    if constexpr (F16) {
+        if (chk != 0.0f && flag) __hip_atomic_fetch_or(flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
 }
 
 // partial[slab][wo + m * K + k] = sum over the slab's points of G[p][m] X[p][k] (X = [X1 (K1 columns) | X2 (K - K1 columns)]),
@@ -283,10 +369,14 @@ __global__ void nerf_wgrad_reduce_kernel(int slabs, const float* __restrict__ pa
 
 // ---- host side: the launches behind the C entry points of mip.hip and pe.hip ----------------------------------------------------------
 
+// the arithmetic a call runs: an explicit F16X2 runs F16X2; NVSR_ARITH_INHERIT resolves to the decoder default with F16X2 read as BF16X3 (the
+// meaning these entry points had before they had an f16 path: a caller who never names F16X2 sees no change -- include/nvsr.h)
 static inline int nerf_arith(int arithmetic, int* out) {
-    if (arithmetic == NVSR_ARITH_INHERIT) arithmetic = nvsr_get_decoder_arithmetic();
+    const bool inherit = arithmetic == NVSR_ARITH_INHERIT;
+    if (inherit) arithmetic = nvsr_get_decoder_arithmetic();
     if (arithmetic == NVSR_ARITH_F32) *out = NVSR_ARITH_F32;
-    else if (arithmetic == NVSR_ARITH_BF16X3 || arithmetic == NVSR_ARITH_F16X2) *out = NVSR_ARITH_BF16X3;   // (include/nvsr.h)
+    else if (arithmetic == NVSR_ARITH_BF16X3) *out = NVSR_ARITH_BF16X3;
+    else if (arithmetic == NVSR_ARITH_F16X2) *out = inherit ? NVSR_ARITH_BF16X3 : NVSR_ARITH_F16X2;
     else return NVSR_ERR_SHAPE;
     return NVSR_OK;
 }
@@ -313,10 +403,14 @@ static int nerf_forward_launch(int64_t N, int S, const float* rays, const float*
     if (reinterpret_cast<uintptr_t>(raw) % 16) return NVSR_ERR_ALIGN;
     const long P = (long)(N * S);
     const dim3 grid((unsigned)((P + 32 * MIP_WAVES - 1) / (32 * MIP_WAVES)));
+    unsigned* flag = nullptr;
     if (arith == NVSR_ARITH_F32)
-        hipLaunchKernelGGL((nerf_forward_kernel<E, NVSR_ARITH_F32>), grid, dim3(64 * MIP_WAVES), 0, stream, P, enc, natural, raw, record);
+        hipLaunchKernelGGL((nerf_forward_kernel<E, NVSR_ARITH_F32>), grid, dim3(64 * MIP_WAVES), 0, stream, P, enc, natural, raw, record, flag);
+    else if (arith == NVSR_ARITH_BF16X3)
+        hipLaunchKernelGGL((nerf_forward_kernel<E, NVSR_ARITH_BF16X3>), grid, dim3(64 * MIP_WAVES), 0, stream, P, enc, natural, raw, record, flag);
     else
-        hipLaunchKernelGGL((nerf_forward_kernel<E, NVSR_ARITH_BF16X3>), grid, dim3(64 * MIP_WAVES), 0, stream, P, enc, natural, raw, record);
+        hipLaunchKernelGGL((nerf_forward_kernel<E, NVSR_ARITH_F16X2>), grid, dim3(64 * MIP_WAVES), 0, stream, P, enc, natural, raw, record,
+                           nvsr_get_range_flag());
     return NVSR_CHECK_LAUNCH();
 }
 
@@ -328,12 +422,16 @@ static int nerf_backward_launch(int64_t P, const float* natural, const float* re
     if (P == 0) return NVSR_OK;
     if (!natural || !record || !g_raw || !grad_record) return NVSR_ERR_NULL;
     const dim3 grid((unsigned)((P + 32 * MIP_WAVES - 1) / (32 * MIP_WAVES)));
+    unsigned* flag = nullptr;
     if (arith == NVSR_ARITH_F32)
         hipLaunchKernelGGL((nerf_backward_kernel<ENC, NVSR_ARITH_F32>), grid, dim3(64 * MIP_WAVES), 0, stream, (long)P, natural, record, g_raw,
-                           grad_record);
-    else
+                           grad_record, flag);
+    else if (arith == NVSR_ARITH_BF16X3)
         hipLaunchKernelGGL((nerf_backward_kernel<ENC, NVSR_ARITH_BF16X3>), grid, dim3(64 * MIP_WAVES), 0, stream, (long)P, natural, record, g_raw,
-                           grad_record);
+                           grad_record, flag);
+    else
+        hipLaunchKernelGGL((nerf_backward_kernel<ENC, NVSR_ARITH_F16X2>), grid, dim3(64 * MIP_WAVES), 0, stream, (long)P, natural, record, g_raw,
+                           grad_record, nvsr_get_range_flag());
     return NVSR_CHECK_LAUNCH();
 }
 

@@ -1056,7 +1056,10 @@ class FlexibleNeRFModel(nn.Module):
             if l.in_features != expect:
                 raise NotImplementedError("this num_layers / skip_connect_every combination is inconsistent in the reference as well")
 
-    arithmetic = "bf16x3"     # of the fused paths (mip_forward, pe_forward): 'f32' | 'bf16x3'; 'f16x2' runs 'bf16x3' (include/nvsr.h)
+    # of the fused paths (mip_forward, pe_forward): 'f32' | 'bf16x3' | 'f16x2' (2 f16 limbs, NaN and the range flag beyond their range:
+    # evaluation falls back to 'bf16x3' by itself, training raises -- train_utils._run_nerf_baseline, training.StepMetrics) | None (the process
+    # default, with 'f16x2' read as 'bf16x3': capi.resolve_nerf_arithmetic)
+    arithmetic = "bf16x3"
 
     def _layers(self):
         return [self.layer1] + list(self.layers_xyz) + [self.layers_dir[0], self.fc_alpha, self.fc_rgb, self.fc_feat]
@@ -1086,29 +1089,29 @@ class FlexibleNeRFModel(nn.Module):
         return (self.dim_xyz == dim_xyz and self.dim_dir == 27 and self.hidden_size == 128 and self.num_layers == 4
                 and all(l.in_features == 128 for l in self.layers_xyz))
 
-    def mip_forward(self, rays, edges, radius):
+    def mip_forward(self, rays, edges, radius, arithmetic=None):
         """The Mip-NeRF baseline's model call (train_utils.py:19-64 with mip_nerf=True, then forward): packed rays [N,11], interval edges
         [N,S+1], the cone radius -> raw [N,S,4].  The integrated positional encoding happens inside the kernel; with gradients enabled,
-        loss.backward() reaches every nn.Linear of the model."""
+        loss.backward() reaches every nn.Linear of the model.  arithmetic: this call's, instead of self.arithmetic."""
         if not self.is_mip_baseline():
             raise NotImplementedError("the Mip-NeRF kernels are built for FlexibleNeRFModel(include_input_xyz=False) with the constructor defaults")
-        return self._fused_forward(torch.ops.nvsr.mip_nerf, rays, edges, float(radius))
+        return self._fused_forward(torch.ops.nvsr.mip_nerf, rays, edges, float(radius), arithmetic=arithmetic)
 
-    def pe_forward(self, rays, z):
+    def pe_forward(self, rays, z, arithmetic=None):
         """The positional-encoding baseline's model call (train_utils.py:15-64 with mip_nerf=False, then forward): packed rays [N,11], sample
         depths z [N,S] -> raw [N,S,4].  The points ro + rd z and their positional encoding happen inside the kernel; with gradients enabled,
-        loss.backward() reaches every nn.Linear of the model."""
+        loss.backward() reaches every nn.Linear of the model.  arithmetic: this call's, instead of self.arithmetic."""
         if not self.is_pe_baseline():
             raise NotImplementedError("the positional-encoding kernels are built for FlexibleNeRFModel(num_encoding_fn_xyz=6, num_encoding_fn_dir=4, "
                                       "include_input_xyz=True, include_input_dir=True) with the constructor defaults")
-        return self._fused_forward(torch.ops.nvsr.pe_nerf, rays, z)
+        return self._fused_forward(torch.ops.nvsr.pe_nerf, rays, z, arithmetic=arithmetic)
 
-    def _fused_forward(self, op, *inputs):
+    def _fused_forward(self, op, *inputs, arithmetic=None):
         """op(*inputs, natural, want_record, arithmetic) -> raw, recording for the backward when a parameter wants a gradient"""
         grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         nat = self.natural_blob(differentiable=grad)
         capi.require_cuda(nat)
-        raw, _ = op(*inputs, nat, grad, capi.arith_code(self.arithmetic))
+        raw, _ = op(*inputs, nat, grad, capi.arith_code(self.arithmetic if arithmetic is None else arithmetic))
         return raw
 
     def forward(self, x):

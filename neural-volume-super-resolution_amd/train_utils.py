@@ -659,7 +659,7 @@ class _NerfBaseline(NamedTuple):
     chunk_div: int          # the reference draws its random numbers per chunksize // chunk_div rays (train_utils.py:228-235)
     bins: Callable          # depths [N,S] -> the bins of sample_pdf_2
     mip: bool               # the compositor's interval branch
-    model_call: Callable    # scene_id -> (model, packed rays, depths) -> raw
+    model_call: Callable    # scene_id -> (model, packed rays, depths, arithmetic or None) -> raw
 
 
 def _mid(z):
@@ -668,13 +668,13 @@ def _mid(z):
 
 def _mip_call(scene_id):
     radius = mip_radius(scene_id)
-    return lambda model, rays, edges: model.mip_forward(rays, edges, radius)
+    return lambda model, rays, edges, arith: model.mip_forward(rays, edges, radius, arithmetic=arith)
 
 
 _NERF_BASELINES = {
     "mip": _NerfBaseline("Mip-NeRF", models.FlexibleNeRFModel.is_mip_baseline, 1, 4, lambda z: _mid(_mid(z)), True, _mip_call),
     "positional_encoding": _NerfBaseline("positional-encoding", models.FlexibleNeRFModel.is_pe_baseline, 0, 1, _mid, False,
-                                         lambda scene_id: lambda model, rays, z: model.pe_forward(rays, z)),
+                                         lambda scene_id: lambda model, rays, z, arith: model.pe_forward(rays, z, arithmetic=arith)),
 }
 
 
@@ -720,16 +720,46 @@ def _run_nerf_baseline(b, H, W, focal, model_coarse, model_fine, batch_rays, opt
         e = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
         return (e(0, 3), e(0), e(0)) + ((e(0, 3), e(0), e(0)) if Nf > 0 else (None, None, None)) + (None, None, None)
     rd = rays[:, 3:6].contiguous()
-    z_c = nv.coarse_z(rays, Nc + x, lindisp, t_rand)
-    raw_c = model_call(model_coarse, rays, z_c)
-    rgb_c, disp_c, acc_c, w_c, _ = nv.composite(raw_c, z_c, rd, n_c, white, b.mip)
-    rgb_f = disp_f = acc_f = None
-    if Nf > 0:
-        samples = nerf_helpers.sample_pdf_2(b.bins(z_c), w_c.detach()[..., 1:-1].contiguous(), Nf + x, det=(m.perturb == 0.0), u=u)
-        z_f = nerf_helpers.sort_depths(torch.cat((z_c, samples), dim=-1))
-        raw_f = model_call(model_fine, rays, z_f)
-        rgb_f, disp_f, acc_f, _, _ = nv.composite(raw_f, z_f, rd, n_f, white, b.mip)
-    return rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f, None, None, None
+
+    def render(force):
+        # force: the arithmetic of the models that would run 'f16x2' (None: as configured)
+        call = lambda mdl, z: model_call(mdl, rays, z, force if force and capi.resolve_nerf_arithmetic(mdl.arithmetic) == f16 else None)
+        z_c = nv.coarse_z(rays, Nc + x, lindisp, t_rand)
+        raw_c = call(model_coarse, z_c)
+        rgb_c, disp_c, acc_c, w_c, _ = nv.composite(raw_c, z_c, rd, n_c, white, b.mip)
+        rgb_f = disp_f = acc_f = None
+        if Nf > 0:
+            samples = nerf_helpers.sample_pdf_2(b.bins(z_c), w_c.detach()[..., 1:-1].contiguous(), Nf + x, det=(m.perturb == 0.0), u=u)
+            z_f = nerf_helpers.sort_depths(torch.cat((z_c, samples), dim=-1))
+            raw_f = call(model_fine, z_f)
+            rgb_f, disp_f, acc_f, _, _ = nv.composite(raw_f, z_f, rd, n_f, white, b.mip)
+        return rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f, None, None, None
+
+    # An evaluation in 'f16x2' heals itself, as run_one_iter_of_nerf's does for the tri-plane model: the f16 limbs have ranges (|W| < 255,
+    # |activation| < 4094) beyond which the kernels write NaN and raise the range flag.  The flag is zeroed before the frame and read once after
+    # it; raised -> warned once, the frame is rendered again in 'bf16x3', and later frames of the same parameters (storage, version of both
+    # models') go there directly.  Training does not come here: its metrics raise (training.StepMetrics).
+    f16 = capi.ARITHMETIC["f16x2"]
+    ms = [mdl for mdl in (model_coarse, model_fine) if mdl is not None]
+    if mode == "train" or not any(capi.resolve_nerf_arithmetic(mdl.arithmetic) == f16 for mdl in ms):
+        return render(None)
+    key = tuple((p.data_ptr(), p._version) for mdl in ms for p in mdl.parameters())
+    owner = ms[-1]
+    if owner.__dict__.get("_nerf_f16_unfit") == key:
+        return render("bf16x3")
+    flag = capi.range_flag(dev)
+    flag.reset()
+    out = render(None)
+    if capi.RangeFlag.raised(flag.read_async()):
+        if not owner.__dict__.get("_nerf_f16_unfit_warned"):
+            import warnings
+            warnings.warn("weights or activations beyond NVSR_ARITH_F16X2's range (|W| < 255, |activation| < 4094): this %s model renders in "
+                          "'bf16x3' while its parameters stay as they are (set model.arithmetic = 'bf16x3' to render there in the first place)" % b.name)
+            owner.__dict__["_nerf_f16_unfit_warned"] = True
+        owner.__dict__["_nerf_f16_unfit"] = key
+        out = render("bf16x3")
+        flag.reset()
+    return out
 
 
 def eval_nerf(height, width, focal_length, model_coarse, model_fine, ray_origins, ray_directions, options, scene_id,

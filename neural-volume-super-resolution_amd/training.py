@@ -616,6 +616,7 @@ class GraphedTrainStep:
                     continue
                 m._packed_cache = None
                 m._packed_bwd_cache = None
+                m.__dict__.pop("_natural_cache", None)       # (FlexibleNeRFModel.natural_blob of a baseline model that is not trained)
                 for k in (getattr(m, "planes_", None) or {}):
                     models._PLANE_CACHE.pop(k, None)
                     models._PLANE_CACHE.pop(k + "/SR", None)

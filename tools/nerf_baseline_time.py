@@ -4,7 +4,8 @@
     python tools/nerf_baseline_time.py --child mip f32         # (what the parent runs)
 
 Per model and arithmetic, one JSON line: an 800 x 800 validation frame at 64 + 64 samples (run_one_iter_of_nerf: ms; the two model passes
-alone: kernel ms, ns per point and the fraction of the roof, FLOP per point on the f32 matrix pipe at 157.3 TF or the bf16 one at 2516.6 / 6 TF)
+alone: kernel ms, ns per point and the fraction of the roof, FLOP per point on the f32 matrix pipe at 157.3 TF, the bf16 one at 2516.6 / 6 TF or the
+f16 one at 2516.6 / 3 TF)
 and a 4096-ray training step (forward, backward, weight gradients: ms and the record bytes it moves).  Mip also times, as "before", the scalar
 flexible_nerf_kernel on the same 4096 x 193 points with pre-encoded input.  Without --model both models run, Mip first; the first failure
 ends the run."""
@@ -14,7 +15,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ROOF = {"f32": 157.3e12, "bf16x3": 2516.6e12 / 6}
+ROOF = {"f32": 157.3e12, "bf16x3": 2516.6e12 / 6, "f16x2": 2516.6e12 / 3}
 # per model: FlexibleNeRFModel arguments, encode_position_fn, scene id, FLOP per point (2 x multiply-adds), depths per ray of the coarse pass
 # (Mip: interval edges, one more than its samples), the capi prefix of the record sizes
 MODELS = {
@@ -110,7 +111,7 @@ def main():
     if args and (len(args) != 2 or args[0] != "--model" or args[1] not in MODELS):
         sys.exit("usage: nerf_baseline_time.py [--model mip|pe]")
     for model in [args[1]] if args else list(MODELS):
-        for arith in ("f32", "bf16x3"):
+        for arith in ("f32", "bf16x3", "f16x2"):
             p = subprocess.run(["timeout", "-k", "10", "600", sys.executable, os.path.abspath(__file__), "--child", model, arith])
             if p.returncode != 0:
                 print(json.dumps({"model": model, "arith": arith, "exit": p.returncode}))
