@@ -31,6 +31,11 @@ Other workloads of the same path (--workload; same JSON contract, their own metr
           --refine-what joint (what = ['LR_planes', 'decoder', 'SR'], the YAMLs' value; default) | sr (what = ['SR']); --refine-scene llff: configs[4] as
           written (LLFF-'fern'-like forward-facing 378x504 view, NDC rays, 64+128 samples; `other_workloads.refine_llff_ndc`).  The line carries the
           split of an iteration (regions of interest / SR forward / render / SR backward / optimizers) and the crops' algorithmic FLOP.
+
+A plain run does what its headline figure needs and no more: it sets up, warms up, times the K steps, writes --dump-outputs if asked, and prints
+the line.  --full adds everything else the benchmark measures or checks, after the timed steps: the live roofline kernel timings and HBM stage
+rates, the other arithmetic modes, the CPU baselines, the PSNR against the float64 checker, the other workloads of the default line, the SR
+training split and the refine iteration's phase split, and (N > 1) the comparison of the sharded frame with the one-GPU frame.
 """
 import argparse
 import json
@@ -695,7 +700,7 @@ def bench_train(args, nvsr_amd, dist, dev, rank, world):
                          "partition": par,
                          "parallelism": "rays sharded by rank; in-place asynchronous all-reduces of the %s (one per tensor, one wait) per step"
                                         % ("plane + decoder gradients" if "decoder" in what else "plane gradients (23 MB)")}}
-    if rank == 0:
+    if rank == 0 and args.full:
         # dominant kernel: gate-driven backward of the fine pass (transposed layers + plane scatter + gradient half of the record), S = 128
         batch = torch.stack(nvsr_amd.training.get_ray_bundle_at(H, W, focal, pose, torch.randint(0, H, (N, 2), device=dev)), 0)
         out = nvsr_amd.train_utils.run_one_iter_of_nerf(H, W, focal, mc, mf, batch, opts, sid, mode="train", scene_config=scfg, randoms={})
@@ -766,7 +771,7 @@ def bench_train(args, nvsr_amd, dist, dev, rank, world):
             result["cpu_baseline"] = {"value": n / t, "unit": "rays/s", "cores": 1, "kind": "port",
                                       "sample": "%d rays of the same step (forward + analytic backward: %s), %.1f s, C "
                                                 "oracle, double accumulation, single thread" % (n, label, t)}
-        return result
+    return result if rank == 0 else None
 
 
 def bench_sr(args, nvsr_amd, dist, dev, rank, world):
@@ -831,7 +836,7 @@ def bench_sr(args, nvsr_amd, dist, dev, rank, world):
                                             % ((2, "f16") if mode == "f16x2" else (3, "bf16")))
             result["roofline"]["sustained_pipe_rate"] = dict(SUSTAINED_BF16_MFMA, executed_over_sustained_16x16x32=ach * arith["products"] /
                                                              SUSTAINED_BF16_MFMA[("f16_" if mode == "f16x2" else "") + "tflops_random_operands_16x16x32_two_waves_per_simd"])
-        if world == 1 and not args.no_modes:
+        if world == 1 and args.full and not args.no_modes:
             modes = {}
             for m2 in ("f32", "bf16x3", "f16x2"):
                 nvsr_amd.capi.set_conv_arithmetic(m2)
@@ -862,7 +867,7 @@ def bench_sr(args, nvsr_amd, dist, dev, rank, world):
             result["sr_training_per_plane"] = {"forward_ms": 1e3 * tf, "backward_ms": 1e3 * tb,
                                                "algorithmic_tflop": {"forward": 6.74, "backward": 13.48},
                                                "achieved_tflops": {"forward": 6.74 / tf if tf else None, "backward": 13.48 / tb if tb else None}}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cv = cpu_conv_rate(args, 10.0)
             result["cpu_baseline"] = {"value": cv["flops"] / (flop_scene / 3), "unit": "planes/s", "cores": cv["cores"], "kind": "port",
                                       "sample": "%d x one 256->256 3x3 conv on a 66x66 tile (%.2f GFLOP each, %.1f s in total, C oracle fp32 OpenMP "
@@ -1041,7 +1046,7 @@ def bench_refine(args, nvsr_amd, dist, dev, rank, world):
                                         % (N, ", planes 23 MB + decoders 1 MB behind it" if joint else "")}}
     if rank != 0:
         return None
-    if getattr(args, "no_split", False):          # counter passes: the timed iteration only
+    if not args.full or args.no_split:            # a plain run, or counter passes: the timed iteration only
         return result
     # ---- the split of one iteration: events on the launch stream at the phase boundaries of one more (eager) iteration
     marks = {}
@@ -1186,17 +1191,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--res", type=int, default=800, help="image side (default 800 = BASELINE config)")
     ap.add_argument("--plane-res", type=int, default=800)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline figure (see the module docstring); off by "
+                         "default: a plain run sets up, warms up, times the steps, dumps its outputs if asked and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines and the checks against the float64 checker")
     ap.add_argument("--no-graph", action="store_true", help="train workload: launch the iteration kernel by kernel instead of replaying its HIP graph")
-    ap.add_argument("--no-modes", action="store_true", help="skip the per-arithmetic-mode frames (profiling passes)")
+    ap.add_argument("--no-modes", action="store_true", help="with --full: skip the per-arithmetic-mode frames (profiling passes)")
     ap.add_argument("--refine-scene", choices=["blender", "llff"], default="blender",
                     help="--workload refine: blender = 4096 rays of an 800x800 Lego-like view, 64+64 samples (the YAMLs' values); llff = BASELINE configs[4] as "
                          "written: an LLFF-'fern'-like forward-facing 378x504 view, NDC rays, 64+128 samples")
-    ap.add_argument("--no-split", action="store_true", help="--workload refine: skip the three probe iterations of the phase split (counter passes)")
+    ap.add_argument("--no-split", action="store_true", help="--workload refine with --full: skip the three probe iterations of the phase split (counter passes)")
     ap.add_argument("--full-record", default=None, metavar="PATH",
                     help="also write the full record (every key; the stdout line is its compact form, <= 4 KB) to PATH")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="--workload render, N = 1: do not append the short train / sr runs (`other_workloads` of the line)")
+                    help="--workload render, N = 1, with --full: do not append the short train / sr runs (`other_workloads` of the line)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0; float32 / float64, <= 64 MB in all, a seeded "
                          "sample of larger outputs): render = the coarse and fine images, sr = the super-resolved planes, train / refine = every "
@@ -1351,7 +1359,7 @@ def main():
                                            "one all_gather of the pixels per step"}[partition]},
         "decoder_evals_per_s_per_gpu": value * 256 / world,
     }
-    if rank == 0 and world > 1 and partition != "view":
+    if rank == 0 and world > 1 and partition != "view" and args.full:
         # BASELINE's metric asks for "PSNR vs ref at 1/2/4/8 MI355X": a sharded frame is the one-GPU frame BIT FOR BIT (same kernels on the same rays, only
         # the launch a ray sits in differs), so its PSNR against the checker is the N = 1 line's figure.  Checked here, outside the timed region and without
         # a collective: rank 0 renders view 0 alone and compares it with the frame the ranks assembled in the last timed step.
@@ -1360,7 +1368,7 @@ def main():
         got_c, got_f = (out[0][0], out[1][0]) if partition == "rows" else (out[0], out[1])
         result["sharded_frame_identical_to_one_gpu"] = bool(torch.equal(got_c, alone[0]) and torch.equal(got_f, alone[3]))
         result["psnr_note"] = "sharded frames equal the one-GPU frame bit for bit: psnr_vs_oracle_db is the N = 1 line's"
-    if rank == 0:
+    if rank == 0 and args.full:
         # dominant kernel: fused fine render pass (192 of the 256 evaluations per ray), render2.hip
         rays = nvsr_amd.train_utils.pack_rays(ro, rd, 2.0, 6.0)
         N = rays.shape[0]
@@ -1497,6 +1505,7 @@ def main():
                     other[wl] = {"error": "%s: %s" % (type(e).__name__, e)}
                 torch.cuda.empty_cache()
             result["other_workloads"] = other
+    if rank == 0:
         result["collectives"] = comm
         emit(result, args.full_record)
     if dist is not None:

@@ -1665,7 +1665,7 @@ def test_bench_two_rank_rehearsal(workload):
     env = dict(os.environ, NVSR_BENCH_REHEARSAL="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", workload,
-           "--res", "160", "--plane-res", "128", "--no-cpu-baseline", "--no-modes"]
+           "--res", "160", "--plane-res", "128", "--full", "--no-cpu-baseline", "--no-modes"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, "\n".join(l for l in p.stderr.splitlines() if "[rank" in l)[-4000:] or p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -1675,6 +1675,32 @@ def test_bench_two_rank_rehearsal(workload):
     per_gpu = r["config"]["planes_per_step_per_gpu" if workload == "sr" else "rays_per_step_per_gpu"]
     assert abs(r["value"] - 2 * per_gpu * 2 / (r["ms_per_step"] * 2e-3)) <= 1e-6 * r["value"]   # whole-job aggregate over both ranks
     assert "roofline" in r and "cpu_baseline" not in r
+
+
+@pytest.mark.parametrize("full", [False, True])
+def test_bench_plain_run_is_lean(full, tmp_path):
+    """A plain `bench.py --gpus 1` times its steps and prints the line: the contract's keys, and none of what --full measures after the steps
+    (live roofline, HBM stages, other arithmetic modes, CPU baseline, PSNR against the checker, other workloads).  --full adds them back."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "NVSR_BENCH_REHEARSAL"):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--res", "160", "--plane-res", "128",
+           "--full-record", str(tmp_path / "full.json")] + (["--full", "--no-cpu-baseline", "--no-modes"] if full else [])
+    p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    r = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert r.get(k) is not None, k
+    assert r["n_gpus"] == 1 and r["steps"] == 2 and r["warmup"] == 1 and r["unit"] == "rays/s" and r["higher_is_better"] is True
+    assert abs(r["value"] - 160 * 160 * 2 / (r["ms_per_step"] * 2e-3)) <= 1e-6 * r["value"]
+    rec = json.load(open(tmp_path / "full.json"))
+    assert ("hbm_stages" in rec) == full and (r["roofline"] is not None) == full
+    for k in ("cpu_baseline", "psnr_vs_oracle_db", "arithmetic_modes", "other_workloads"):
+        assert k not in rec, k
 
 
 def test_loaded_scenes_feed_the_render_path(hip, tmp_path):

@@ -504,8 +504,8 @@ def test_sharded_render_is_bit_identical_to_one_rank(partition, res, self_launch
     env = dict(os.environ, NVSR_BENCH_REHEARSAL="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    tail = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--res", str(res), "--plane-res", "128", "--no-cpu-baseline",
-            "--no-modes", "--partition", partition]
+    tail = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--res", str(res), "--plane-res", "128", "--full",
+            "--no-cpu-baseline", "--no-modes", "--partition", partition]
     if self_launch:
         cmd = [sys.executable] + tail
     else:

@@ -371,7 +371,7 @@ def test_refine_iteration_on_two_ranks():
     through distributed.allreduce_gradients behind it, then the three optimizers step; the run asserts that a sample of every parameter group is
     bit-identical on both ranks after its iterations and finishes with one line, finite, weak scaling."""
     from test_hip_round3 import _bench_rehearsal
-    r, err = _bench_rehearsal(["--workload", "refine", "--refine-what", "joint", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+    r, err = _bench_rehearsal(["--workload", "refine", "--refine-what", "joint", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"])
     for rank in (0, 1):
         assert "REFINE_PARAMS_IDENTICAL rank %d of 2 (overlapped gradient sync, 4 buckets)" % rank in err, err[-3000:]
     assert r["n_gpus"] == 2 and r["scaling"] == "weak" and r["config"]["rays_per_step_per_gpu"] == 4096

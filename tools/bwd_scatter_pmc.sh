@@ -5,7 +5,7 @@
 # x 3 planes x 4 taps x 192 B = 1.208 GB; WRITE_SIZE is in KB.
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 V=$R/gpurun_out/variants; mkdir -p $V
-export PMC_SCRIPT=../bench.py PMC_ARGS="--workload train --steps 3 --warmup 1 --no-cpu-baseline"
+export PMC_SCRIPT=../bench.py PMC_ARGS="--full --workload train --steps 3 --warmup 1 --no-cpu-baseline"
 for m in ${MODES:-0 1 2}; do
   rm -f $V/bl_scatter_$m.so
   NVSR_EXTRA_HIPCC_FLAGS="-DBL_SCATTER=$m" python3 -c "import sys; sys.path.insert(0, '$R'); import nvsr_amd; nvsr_amd.build_extension(out_path='$V/bl_scatter_$m.so')" > $V/bl_scatter_$m.log 2>&1 || { echo "BL_SCATTER=$m: build failed"; continue; }

@@ -66,7 +66,7 @@ if pm:
     traffic = (2.0 * pm["FETCH_SIZE"][0] + pm["WRITE_SIZE"][0]) * 1024.0
     latest.update({"kernel": "%s (fine pass, S=192)" % out.get("render", {}).get("roofline", {}).get("kernel", "render_pass kernel").split(" (")[0],
                    "decoder_arithmetic": out.get("render", {}).get("decoder_arithmetic", "f32"),
-                   "command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-modes (two separate passes)",
+                   "command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-modes (two separate passes)",
                    "fetch_size_kb": pm["FETCH_SIZE"][0], "write_size_kb": pm["WRITE_SIZE"][0],
                    "kernel_ms_under_pmc": [pm["FETCH_SIZE"][1], pm["WRITE_SIZE"][1]], "traffic_bytes": traffic})
     print("render: traffic per fine launch %.1f GB" % (traffic / 1e9))
@@ -85,7 +85,7 @@ if len(mf) == 3 and "traffic_bytes" in latest:
     latest["mfma"] = {"SQ_VALU_MFMA_BUSY_CYCLES": mf["SQ_VALU_MFMA_BUSY_CYCLES"][0], "GRBM_GUI_ACTIVE": mf["GRBM_GUI_ACTIVE"][0],
                       "SQ_INSTS_MFMA": mf["SQ_INSTS_MFMA"][0], "kernel_ms_under_pmc": mf["GRBM_GUI_ACTIVE"][1],
                       "mfma_busy_frac": mf["SQ_VALU_MFMA_BUSY_CYCLES"][0] / (1024.0 * cyc), "clock_ghz": cyc / (mf["GRBM_GUI_ACTIVE"][1] * 1e6),
-                      "command": "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_MFMA --kernel-trace -- python3 bench.py --steps 1 --warmup 0 "
+                      "command": "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_MFMA --kernel-trace -- python3 bench.py --full --steps 1 --warmup 0 "
                                  "--no-cpu-baseline --no-modes"}
     print("render: matrix pipe %.1f %% busy at %.2f GHz" % (100 * latest["mfma"]["mfma_busy_frac"], latest["mfma"]["clock_ghz"]))
 # train: the longest gate-driven backward launch = the fine pass (S = 128); sr: every convolution of one step
