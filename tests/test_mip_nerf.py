@@ -12,6 +12,7 @@ Tolerances
   parameters after Adam . the same relative L2 bounds; per element <= 1e-3 max|ref| (check_grads: Adam's step does not shrink with the gradient)
 """
 import sys
+from types import SimpleNamespace as NS
 
 import numpy as np
 import pytest
@@ -167,6 +168,48 @@ def test_at_size_against_float64(hip, arith):
         #  and for bf16x3 the limbs' 2^-20 per product through the chain, measured below 1.1e-3)
         assert rel <= 4 * rel32 + (np.sqrt(N * S) * 2.0 ** -24 if arith == "f32" else 2e-3), report
     print("mip at size (%s): " % arith + ", ".join(report))
+
+
+@pytest.fixture(scope="module")
+def fine_pass_at_size(hip):
+    """the Mip fine pass of a training step at 4096 rays: Nc + Nf + 1 = 129 intervals per ray, P = 528 384 points = 64.5 slabs of the weight
+    gradient.  The model, its inputs, dL/draw and their float64 evaluation, which does not depend on the arithmetic (computed once, on the
+    device: rocBLAS DGEMM, not the kernels under test); the torch f32 evaluation on the CPU, as in test_at_size_against_float64"""
+    torch.manual_seed(7)
+    m = hip.models.FlexibleNeRFModel(include_input_xyz=False).to(DEV)
+    N, S = 4096, 129
+    rays = hip.train_utils.pack_rays(torch.randn(N, 3, device=DEV), torch.randn(N, 3, device=DEV), 2.0, 6.0)
+    edges = torch.sort(2.0 + 4.0 * torch.rand(N, S + 1, device=DEV), -1)[0]
+    radius = hip.train_utils.mip_radius("lego_DS8")
+    g_raw = torch.randn(N, S, 4, device=DEV)
+    x = torch.ops.nvsr.mip_encode(rays, edges, radius).double()
+    gr = g_raw.reshape(-1, 4).double()
+    out64, g64 = cpu_eval(m, x, gr, 36, torch.float64, device=DEV)
+    _, g32 = cpu_eval(m, x.cpu(), gr.cpu(), 36, torch.float32)
+    rel32 = {k: float((g32[k] - g64[k].cpu()).norm() / g64[k].norm().clamp_min(1e-30)) for k in g64}
+    return NS(state={k: v.detach().clone() for k, v in m.state_dict().items()}, N=N, S=S, rays=rays, edges=edges, radius=radius, g_raw=g_raw,
+              out64=out64, g64=g64, rel32=rel32)
+
+
+@pytest.mark.parametrize("arith", ARITHS + ["f16x2"])
+def test_fine_pass_shape_against_float64(hip, fine_pass_at_size, arith):
+    """4096 rays x 129 intervals, the shape of the fine pass of every Mip training step (P is not a whole number of weight-gradient slabs):
+    forward and every parameter gradient of mip_forward + autograd against float64, with the tolerances of test_at_size_against_float64
+    (for f16x2 those of test_f16x2_at_size_against_float64, the same)"""
+    f = fine_pass_at_size
+    m = hip.models.FlexibleNeRFModel(include_input_xyz=False).to(DEV)
+    m.load_state_dict(f.state)
+    m.arithmetic = arith
+    raw = m.mip_forward(f.rays, f.edges, f.radius)
+    (raw * f.g_raw).sum().backward()
+    e_fwd = float((raw.detach().reshape(-1, 4).double() - f.out64).abs().max())
+    report = ["forward max|err| %.2e" % e_fwd]
+    assert e_fwd <= (1e-5 if arith == "f32" else 1e-4), report
+    for k, p in m.named_parameters():
+        rel = float((p.grad.double() - f.g64[k]).norm() / f.g64[k].norm().clamp_min(1e-30))
+        report.append("%s %.2e (torch f32 %.2e)" % (k, rel, f.rel32[k]))
+        assert rel <= 4 * f.rel32[k] + (np.sqrt(f.N * f.S) * 2.0 ** -24 if arith == "f32" else 2e-3), report
+    print("mip fine pass at size (%s): " % arith + ", ".join(report))
 
 
 def test_opcheck_mip_operators(hip, g23):
