@@ -128,6 +128,30 @@ int nvsr_set_decoder_arithmetic(int mode);
  * touch it (they have no range limit; a NaN they return was a NaN in their inputs). */
 int nvsr_set_range_flag(uint32_t* device_word);
 uint32_t* nvsr_get_range_flag(void);
+/* The two-phase render pass.  A fused limb pass (NVSR_ARITH_BF16X3 / _F16X2, N >= nvsr_fused_min_rays) whose caller does not ask for the
+ * raw decoder outputs runs as two launches: the DENSITY pass (render_pass3_density[_z]_kernel: planes 0..2, the density decoder, the whole
+ * compositing recurrence -- disp, acc, depth, the coarse weights) leaves, per ray, the list of its samples with a weight that is not zero
+ * (a NaN weight counts) and their number; the COLOUR pass (render_pass3_colour[_z]_kernel) runs the colour decoder on those entries only, as
+ * many steps as the longest list among a workgroup's 256 rays, and adds w sigmoid(raw) in sample order.  A sample with weight +0.0 added +0.0
+ * to every sum of the fused kernel, so the outputs are the fused kernel's bit for bit; the one difference lies beyond the F16X2 range: a NaN
+ * that only the colour decoder of a weightless sample produces no longer reaches the pixel (the pixel is then the correct finite value; a
+ * density-side overflow still gives NaN and raises the range flag -- the density pass checks acc, the colour pass rgb).
+ * NVSR_RENDER_ONE_PHASE=1 in the environment (read at every launch) keeps the fused kernel; it also runs when raw outputs are requested,
+ * while the stream is being captured into a graph, or when the scratch below cannot be allocated.
+ * Scratch: the lists take 2 N S floats + N ints (0.98 GB for the 800 x 800 x 192 fine pass).  They are NOT part of the caller's workspace
+ * (nvsr_render_workspace_floats is unchanged): the library owns one buffer per (device, stream), allocated with hipMalloc at the first
+ * two-phase launch on that stream and grown (never shrunk) when a larger pass arrives -- growing waits for the device.
+ * nvsr_render_rays and nvsr_render_rays_arith size it for the frame's larger pass (N (Nc + Nf) entries) before the coarse launch, so a frame
+ * grows it at most once; nvsr_render_rays_shared_arith's own path asks for raw outputs in every pass, runs the fused kernel and reserves nothing.
+ * The buffer stays allocated between frames (0.98 GB at the benchmark size that torch's caching allocator does not see) until it is released.
+ * nvsr_release_render_scratch frees every such buffer (the caller makes sure no render launch is still running); later launches allocate anew.
+ * nvsr_render_scratch_bytes returns what the library holds at the moment, over all devices and streams (0 until a two-phase launch has
+ * run: a caller, or a test, can tell that the two-phase route was taken).
+ * Contract: the buffers are keyed by the stream handle and never pruned -- the entry of a destroyed stream keeps its memory (torch's
+ * allocator does not see it) until nvsr_release_render_scratch; and only one host thread at a time may enqueue render launches on a given
+ * (device, stream): a second thread growing that entry would free the buffer under the first one's launch. */
+int nvsr_release_render_scratch(void);
+int64_t nvsr_render_scratch_bytes(void);
 /* The arithmetic primitive alone (test hook, one wavefront): Y[32][32] = W[32][K] X[K][32] (row-major f32, K a multiple of 16) with the
  * operands split and multiplied exactly as the kernels of `arithmetic` do it (NVSR_ARITH_F32 | _BF16X3 | _F16X2, incl. the static scales of
  * F16X2) -- lets a test put chosen mantissas / magnitudes through the products that replace models.py:381-421's nn.Linear GEMMs. */

@@ -906,6 +906,7 @@ int64_t nvsr_render_workspace_floats(int64_t N, int Nc, int Nf) {
 }
 
 extern "C" int nvsr_internal_resolve_decoder_arith(int arithmetic);      // render.hip
+extern "C" void nvsr_internal_reserve_render_scratch(int64_t N, int S, nvsr_stream_t stream);      // render3.hip
 extern "C" int nvsr_render_pass3_coarse_z_launch(int limbs, const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays,
                                                  int lindisp, const float* noise, int white_bkgd, float* rgb, float* disp, float* acc,
                                                  float* weights, float* depth, float* raw_out, nvsr_stream_t stream);
@@ -948,6 +949,8 @@ int nvsr_render_rays_arith(const nvsr_scene* scene, const float* packed_coarse, 
     // pass and the resampler compute them in registers, the [N,Nc] depth tensor (164 MB at 800 x 800 x 64) is never written or read
     const int arith = nvsr_internal_resolve_decoder_arith(arithmetic);
     const bool in_kernel_z = !t_rand && Nf > 0 && N >= NVSR_FUSED_MIN_RAYS && arith > 0 && !getenv("NVSR_RENDER_V1") && !getenv("NVSR_STORE_COARSE_Z");
+    // both passes on the fused limb kernels: the live-list scratch of the two-phase route is sized for the larger (fine) pass once
+    if (Nf > 0 && N >= NVSR_FUSED_MIN_RAYS && arith > 0 && !getenv("NVSR_RENDER_V1")) nvsr_internal_reserve_render_scratch(N, Nc + Nf, stream);
     if (in_kernel_z) {
         if (!scene || !packed_coarse || !rays || !rgb_c || !disp_c || !acc_c) return NVSR_ERR_NULL;
         for (int d = 0; d < 4; ++d) {

@@ -165,6 +165,27 @@ __device__ __forceinline__ void gather_roll(int slot, const GatherJob& jl, float
     });
 }
 
+// Rolling gather in two tap buffers and one blend buffer (the density pass of the two-phase render, render3.hip: both tiles' activations are
+// live beside the gathers, four tap buffers do not fit).  A plane gather is two halves -- taps (nw, ne), then (sw, se).  A block blends the
+// half HB of job jb, which the block before it loaded, in its first NS / 2 slots (channels in load order) and issues the 12 loads of half HL
+// of job jl in its last NS / 2 slots, a buffer pair at a time: every load is NS / 2 slots ahead of its use.  Operation for operation the
+// blend of gather_roll:  F = T0 nw;  F = fma(T1, ne, F);  F = fma(T2, sw, F);  F = fma(T3, se, F).
+template <int NS, bool LOADS, int HL, bool BLENDS, int HB>
+__device__ __forceinline__ void gather_half(int slot, const GatherJob& jl, const GatherJob& jb, float (&F)[HALF_C], int h, RawTaps2& rt) {
+    if constexpr (BLENDS)
+        spread<HALF_C, 0, NS / 2>(slot, [&](int c) {
+            const float a = rt.r0[c >> 2][c & 3], b = rt.r1[c >> 2][c & 3];
+            if (HB == 0) F[c] = fmaf(b, jb.t.ne, a * jb.t.nw);
+            else F[c] = fmaf(b, jb.t.se, fmaf(a, jb.t.sw, F[c]));
+        });
+    if constexpr (LOADS)
+        spread<12, NS / 2, NS>(slot, [&](int k) {
+            const int off = HL == 0 ? ((k & 1) ? jl.t.o01 : jl.t.o00) : ((k & 1) ? jl.t.o11 : jl.t.o10);
+            const f32x4 v = reinterpret_cast<const f32x4*>(jl.plane + off + HALF_C * h)[k >> 1];
+            if (k & 1) rt.r1[k >> 1] = v; else rt.r0[k >> 1] = v;
+        });
+}
+
 // ring wait with N younger vector-memory operations allowed in flight (vmcnt counts in issue order: the chunk issued before them has landed)
 template <int N>
 __device__ __forceinline__ void ring3_sync() {

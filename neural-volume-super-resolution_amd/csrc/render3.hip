@@ -11,6 +11,10 @@
 // Biases are not preloaded into the accumulators: the first MFMA of a layer takes C = 0 and act = max(acc + bias, 0).
 #include "pair_core.h"
 
+#include <cstdlib>
+#include <mutex>
+#include <vector>
+
 namespace nvsr {
 
 // =====================================================================================================================
@@ -18,16 +22,33 @@ namespace nvsr {
 // symbols in a rocprofv3 kernel trace -- a second template parameter on one kernel trips hipcc's host pass over the LDS-DMA builtins).
 // ZCOMP: the depths are the un-jittered coarse ones (train_utils.py:95-100) and are computed from the ray's near / far in registers
 // (coarse_depth, bit for bit what nvsr_coarse_z writes) instead of being read: `z` is NULL and `lindisp` selects the spacing
-// (ONE template parameter, LZ = LIMBS + 8 * ZCOMP: with a second one hipcc's host pass fails to resolve the LDS-DMA helpers inside the body)
+// (ONE template parameter, LZ = LIMBS + 8 * ZCOMP + 16 * PHASE: with a second one hipcc's host pass fails to resolve the LDS-DMA helpers inside the body)
+//
+// PHASE: 0 = the fused pass (both decoders on every sample: the path of raw_out != NULL and of NVSR_RENDER_ONE_PHASE=1).
+// The two-phase route runs the colour decoder only where it can reach the pixel -- w = alpha T is +0.0 exactly wherever sigma + noise <= 0,
+// and such a sample adds +0.0 to every accumulator:
+//   1 = density pass: planes 0..2 -> D, density layers 0..3, sigma head, the whole compositing recurrence of T, w, depth, acc (composite_weight:
+//       the operations of composite_sample) -- writes disp / acc / depth / weights and, per ray, the live list: (z or sample index, w) of every
+//       sample with !(w == 0) in sample order (rows of S entries, like z) and their count.  The gathers of sample s + 1 roll through the blocks of
+//       sample s in halves of two taps (gather_half, pair_core.h).
+//   2 = colour pass: the loop runs over k < trip = max live count of the workgroup's 256 rays (workgroup-uniform: the four waves share the
+//       ring); a lane evaluates its ray's k-th live sample -- today's rgb layer 0 (same K-block order), rgb layers 1..3, rgb head -- and adds
+//       w sigmoid(raw) with the operations of composite_sample.  A lane past its own count re-evaluates its last entry and KEEPS its
+//       accumulators (a select, no + 0 x: padding cannot inject a NaN).
+// Neither chain's K-order changes and dead samples contributed +0.0 to non-negative sums, so the pixels are bit for bit the fused pass's.
 template <int LZ>
 __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const float* __restrict__ packed, long N, int S,
                                                   const float* __restrict__ rays, const float* __restrict__ z, int lindisp,
                                                   const float* __restrict__ noise, int white,
                                                   float* __restrict__ rgb, float* __restrict__ disp,
                                                   float* __restrict__ acc, float* __restrict__ weights,
-                                                  float* __restrict__ depth, float* __restrict__ raw_out, unsigned* __restrict__ flag) {
+                                                  float* __restrict__ depth, float* __restrict__ raw_out, unsigned* __restrict__ flag,
+                                                  float* __restrict__ live_z = nullptr, float* __restrict__ live_w = nullptr,
+                                                  int* __restrict__ live_n = nullptr) {
     constexpr int LIMBS = LZ & 7;
     constexpr bool ZCOMP = (LZ & 8) != 0;
+    constexpr int PHASE = (LZ >> 4) & 3;
+    constexpr bool FUSED = PHASE == 0, DENSITY = PHASE == 1, COLOUR = PHASE == 2;
     using L = Lds3<LIMBS>;
     constexpr int NP = limb_products(LIMBS);
     constexpr int NSF = 3 * 4 * NP, NSH = 4 * 4 * NP;          // slots of a feature block / of half a hidden layer
@@ -79,8 +100,8 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
             reinterpret_cast<f32x4*>(rtp)[1] = f32x4{vt.nw, vt.ne, vt.sw, vt.se};
         }
     }
-    const float* zX = ZCOMP ? nullptr : z + rayX * S;
-    const float* zY = ZCOMP ? nullptr : z + rayY * S;
+    const float* zX = ZCOMP || COLOUR ? nullptr : z + rayX * S;
+    const float* zY = ZCOMP || COLOUR ? nullptr : z + rayY * S;
     auto depth_of = [&](const float* zp, const float* rc, int k) NVSR_INL {
         if constexpr (ZCOMP) return coarse_depth(rc[7], L::FAR >= 0 ? ldsf[L::FAR + rs.wave * 64 + (rs.lane & 31) + (rc == rcX ? 0 : 32)] : rc[16], k, S, lindisp);
         else return zp[k];
@@ -90,9 +111,38 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
     X.T = Y.T = 1.0f;
     X.cr = X.cg = X.cb = X.dep = X.ac = 0.0f;
     Y.cr = Y.cg = Y.cb = Y.dep = Y.ac = 0.0f;
-    if constexpr (ZCOMP) __syncthreads();   // (the ray cache is written by lanes 0..31 and read by all 64, see below)
-    X.zc = depth_of(zX, rcX, 0); Y.zc = depth_of(zY, rcY, 0);
+    // colour pass: the rays' live lists (rows of S entries; nX, nY entries are valid) and the workgroup's trip count
+    const float* lzX = COLOUR ? live_z + rayX * S : nullptr;
+    const float* lzY = COLOUR ? live_z + rayY * S : nullptr;
+    const float* lwX = COLOUR ? live_w + rayX * S : nullptr;
+    const float* lwY = COLOUR ? live_w + rayY * S : nullptr;
+    int nX = 0, nY = 0, trip = S;
+    float wX = 0.0f, wY = 0.0f, wXn = 0.0f, wYn = 0.0f;
+    // entry k of a live list, clamped to the last valid one; an empty list gives the ray's near depth and weight 0 (never composited)
+    auto live_depth = [&](const float* lzp, const float* rc, int n, int k) NVSR_INL -> float {
+        if (n == 0) return rc[7];
+        const float e = lzp[k < n ? k : n - 1];
+        if constexpr (ZCOMP) return depth_of(nullptr, rc, __float_as_int(e));      // (the density pass stored the sample index)
+        else return e;
+    };
+    auto live_weight = [](const float* lwp, int n, int k) NVSR_INL -> float { return n == 0 ? 0.0f : lwp[k < n ? k : n - 1]; };
+    if constexpr (COLOUR) {
+        __shared__ int trip_s[NW2];                   // (the colour kernels' alone: the other phases declare nothing)
+        nX = live_n[rayX]; nY = live_n[rayY];
+        int m = max(nX, nY);
+#pragma unroll
+        for (int o = 16; o >= 1; o >>= 1) m = max(m, __shfl_xor(m, o));
+        if (lane0 == 0) trip_s[rs.wave] = m;
+        __syncthreads();                              // the wave maxima; also the ray cache, written by lanes 0..31 and read by all 64
+        trip = __builtin_amdgcn_readfirstlane(max(max(trip_s[0], trip_s[1]), max(trip_s[2], trip_s[3])));
+        X.zc = live_depth(lzX, rcX, nX, 0); Y.zc = live_depth(lzY, rcY, nY, 0);
+        wX = live_weight(lwX, nX, 0); wY = live_weight(lwY, nY, 0);
+    } else {
+        if constexpr (ZCOMP) __syncthreads();         // (the ray cache is written by lanes 0..31 and read by all 64, see below)
+        X.zc = depth_of(zX, rcX, 0); Y.zc = depth_of(zY, rcY, 0);
+    }
     RawTaps4 rt;
+    RawTaps2 r2;      // (density pass)
 
     auto point_norm = [&](const float* rc, float zc, float& n0, float& n1, float& n2) NVSR_INL {
         const f32x4 c0 = reinterpret_cast<const f32x4*>(rc)[0], c1 = reinterpret_cast<const f32x4*>(rc)[1];
@@ -118,14 +168,39 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
                        // half above the writes (per lane there is no dependence)
     // The view-plane features (project_viewdir, models.py:312-326) depend on the ray only: gathered once.  They open every sample's rgb
     // layer 0, so that the first plane gathers of a sample have two blocks to land in.
+    if constexpr (!DENSITY) {
 #pragma unroll
-    for (int k2 = 0; k2 < 2; ++k2) {
-        Tile3& t = k2 ? Y : X;
-        const GatherJob vj = view_job(k2 ? rtY : rtX);
+        for (int k2 = 0; k2 < 2; ++k2) {
+            Tile3& t = k2 ? Y : X;
+            const GatherJob vj = view_job(k2 ? rtY : rtX);
 #pragma unroll
-        for (int k = 0; k < 12; ++k) gather4_load(k, vj, lane0 >> 5, rt);
+            for (int k = 0; k < 12; ++k) gather4_load(k, vj, lane0 >> 5, rt);
 #pragma unroll
-        for (int c = 0; c < HALF_C; ++c) gather4_blend(c, vj, rt, t.V);
+            for (int c = 0; c < HALF_C; ++c) gather4_blend(c, vj, rt, t.V);
+        }
+    } else {
+        // density pass: D of sample 0 (every later sample's is gathered during the sample before it) -- the operations of the rolling gather
+#pragma unroll
+        for (int k2 = 0; k2 < 2; ++k2) {
+            Tile3& t = k2 ? Y : X;
+            float n0, n1, n2;
+            point_norm(k2 ? rcY : rcX, t.zc, n0, n1, n2);
+#pragma unroll
+            for (int p = 0; p < 3; ++p) {
+                GatherJob pj;
+                pj.plane = sc.plane[p]; pj.t = pos_taps2(sc, p, n0, n1, n2); scale_taps(pj.t);
+#pragma unroll
+                for (int k = 0; k < 12; ++k) gather4_load(k, pj, lane0 >> 5, rt);
+#pragma unroll
+                for (int c = 0; c < HALF_C; ++c) gather4_blend(c, pj, rt, t.F);
+#pragma unroll
+                for (int c = 0; c < HALF_C; ++c) {
+                    t.D[c] = p == 0 ? t.F[c] : p == 1 ? __fadd_rn(t.D[c], t.F[c]) : div3(__fadd_rn(t.D[c], t.F[c]));
+                    asm volatile("" : "+v"(t.D[c]));
+                }
+                __builtin_amdgcn_sched_barrier(0);      // (one plane at a time: the scheduler would issue all six gathers' 144 loads first)
+            }
+        }
     }
     Limbs<LIMBS> cur, fa;
     f32x2_t nsc = {-F16_ACC_UNSCALE, -F16_ACC_UNSCALE};                  // relu_bias_step
@@ -134,12 +209,13 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
     float stamp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long tprev = __builtin_amdgcn_s_memtime();
 #endif
-    constexpr bool RESIDENT = L::RES_KB > 0;
-    constexpr int KB_FIRST = RESIDENT ? KB_RGB0 + 9 : KB_RGB0;      // the first chunk of a step that goes through the ring
+    constexpr bool RESIDENT = L::RES_KB > 0 && !DENSITY;             // (the density pass streams KB_DEN0 .. through the ring and keeps nothing resident)
+    constexpr int KB_FIRST = DENSITY ? KB_DEN0 : RESIDENT ? KB_RGB0 + 9 : KB_RGB0;      // the first chunk of a step that goes through the ring
     unsigned* const res = lds + L::RES;
     if constexpr (RESIDENT) ring3_load_resident<LIMBS, L::RES_KB>(rs, res, KB_RGB0);
     unsigned* cw = const_cast<unsigned*>(ring3_issue<LIMBS, 3>(rs, KB_FIRST));     // first ring chunk of sample 0; every later one is issued during the previous sample
-    for (int s = 0; s < S; ++s) {
+    const int steps = COLOUR ? trip : S;
+    for (int s = 0; s < steps; ++s) {
         asm volatile("" : "+v"(rs.voff), "+v"(rs.lane));
 #if R3_NO_VIEW_HOIST
         // The view features are loop-invariant and so are their limbs: hipcc hoists the two split_feat(V) of a step out of the sample loop
@@ -150,13 +226,16 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
 #endif
         const int lane = rs.lane, h = lane >> 5;
         const bool last = (s + 1 == S);
-        X.zn = depth_of(zX, rcX, last ? s : s + 1);            // (unconditional loads unless ZCOMP: ring3_sync<2> below counts them)
-        Y.zn = depth_of(zY, rcY, last ? s : s + 1);
-        const float nzX = noise ? noise[rayX * S + s] : 0.0f;
-        const float nzY = noise ? noise[rayY * S + s] : 0.0f;
+        if constexpr (!COLOUR) {
+            X.zn = depth_of(zX, rcX, last ? s : s + 1);        // (unconditional loads unless ZCOMP: ring3_sync<2> below counts them)
+            Y.zn = depth_of(zY, rcY, last ? s : s + 1);
+        }
+        const float nzX = !COLOUR && noise ? noise[rayX * S + s] : 0.0f;
+        const float nzY = !COLOUR && noise ? noise[rayY * S + s] : 0.0f;
         float xn0, xn1, xn2, yn0, yn1, yn2;
-        point_norm(rcX, X.zc, xn0, xn1, xn2);
-        point_norm(rcY, Y.zc, yn0, yn1, yn2);
+        // (density pass: the planes gathered during this step are the NEXT sample's; after the last sample they are gathered again and dropped)
+        point_norm(rcX, DENSITY ? X.zn : X.zc, xn0, xn1, xn2);
+        point_norm(rcY, DENSITY ? Y.zn : Y.zc, yn0, yn1, yn2);
         BiasPend4 bp;
         bp.slot = bounce_slot(ldsf + L::VTAPS + rs.wave * 64 * L::TAP_FLOATS + lane * 4);     // (f16 limbs: the wave's tap region, dead since the prologue)
         HeadPend<3> hp3;
@@ -177,10 +256,17 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
         // multiplies plane p - 1 of a tile loads plane p of the same tile, the next block blends it.
         GatherJob ja, jb;
         R3_MARK(0)      // loop top
-        ring3_sync<ZCOMP ? 0 : 2>();                             // the step's first ring chunk (issued during the previous sample) -- younger: the two z loads above
+        ring3_sync<(ZCOMP || COLOUR) ? 0 : 2>();                 // the step's first ring chunk (issued during the previous sample) -- younger: the two z loads above
+        if constexpr (COLOUR) {
+            // the next live entry, a whole step ahead of its use (issued behind the wait: no ring wait has to count these loads)
+            X.zn = live_depth(lzX, rcX, nX, s + 1); Y.zn = live_depth(lzY, rcY, nY, s + 1);
+            wXn = live_weight(lwX, nX, s + 1); wYn = live_weight(lwY, nY, s + 1);
+        }
         // RESIDENT (f16 limbs): view plane, planes 0 and 1 multiply out of the resident region; the ring chunk that has just landed is plane 2's,
         // and the blocks that issue gathers (B0 .. B5) issue no weight copy and need no ring wait
-        unsigned* nw = RESIDENT ? nullptr : ring3_take(rs);
+        unsigned* nw = (RESIDENT || DENSITY) ? nullptr : ring3_take(rs);
+        float hx[3] = {0.0f, 0.0f, 0.0f};
+        if constexpr (!DENSITY) {
         const unsigned* const w_view = RESIDENT ? res : cw;
         R3_MARK(1)      // first ring wait
         R3_RESET
@@ -263,6 +349,7 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
         R3_MARKB(7)
         cw = nw;
         R3_MARK(2)      // rgb layer 0
+        }
 
         // ---- hidden layers.  Layer l of a decoder = chunks a (K-blocks 0..3), b (4..7):
         //   X a | Y: act of layer l-1; tail Y kb 0        Y a | tail X kb 4        X b | tail Y kb 4        Y b | X: act of layer l; tail X kb 0
@@ -295,18 +382,28 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
 #define NVSR_HIDDEN_LAYER(VPREV, ...) NVSR_HIDDEN_LAYER_(ring3_sync<0>(), relu_side(Y, VPREV), VPREV, __VA_ARGS__)
         // rgb layers 1, 2: Y b | X relu, tail X kb 0
 #define NVSR_YB_PLAIN(VTHIS) (limb_block<LIMBS, 4, false, false>(cw, lane, Y.acc, cur, fa, hid(Y.act, 4), relu_side(X, VTHIS), tail_of(X.act, 0)))
+        if constexpr (!DENSITY) {
         NVSR_HIDDEN_LAYER(4, 5, KB_RGB1 + 4, 4, KB_RGB1 + 8, 4, NVSR_YB_PLAIN(5))
         NVSR_HIDDEN_LAYER(5, 6, KB_RGB1 + 12, 4, KB_RGB1 + 16, 4, NVSR_YB_PLAIN(6))
-        // rgb layer 3: Y b | X relu (no tail: X continues with the density decoder from X.D)
-        NVSR_HIDDEN_LAYER(6, 7, KB_RGB1 + 20, 4, KB_DEN0, 3,
-                          (limb_block<LIMBS, 4, false, false>(cw, lane, Y.acc, cur, fa, hid(Y.act, 4), relu_side(X, 7), NoTail{})))
+        // rgb layer 3: Y b | X relu (no tail: X continues with the density decoder from X.D).  The chunk issued last is the density decoder's
+        // first -- colour pass: chunk 0 of the NEXT step, and X's rgb heads follow its activation in the second half of the block
+        NVSR_HIDDEN_LAYER(6, 7, KB_RGB1 + 20, 4, (COLOUR ? KB_FIRST : KB_DEN0), 3,
+                          (limb_block<LIMBS, 4, false, false>(cw, lane, Y.acc, cur, fa, hid(Y.act, 4),
+                                                              [&](int slot) NVSR_INL {
+                                                                  if constexpr (COLOUR) {
+                                                                      spread<RELU_STEPS, 0, NSH / 2>(slot, [&](int k) NVSR_INL { relu_bias_step<LIMBS>(k, small + S_BIAS + 7 * HID, h, X.acc, X.act, bp, nsc); });
+                                                                      spread<64, NSH / 2, NSH>(slot, [&](int k) NVSR_INL { heads_side<3>(k >> 2, k & 3, small + S_RGB_W, h, X.act, hx, hp3); });
+                                                                  } else relu_side(X, 7)(slot);
+                                                              },
+                                                              NoTail{})))
+        }
 
         R3_MARK(3)      // rgb layers 1..3
+        if constexpr (FUSED) {
         // ---- density layer 0 (from D) -------------------------------------------------------------------------------------------
         ring3_sync<0>();
         nw = ring3_take(rs);
         // X density 0 | Y: act of rgb layer 3; X: rgb heads
-        float hx[3] = {0.0f, 0.0f, 0.0f};
         split_feat(X.D);
         limb_block<LIMBS, 3, true, true>(cw, lane, X.acc, cur, fa, feat(X.D),
                                          [&](int slot) NVSR_INL {
@@ -334,6 +431,87 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
         // ---- density layers 1..3 -------------------------------------------------------------------------------------------------
         NVSR_HIDDEN_LAYER(0, 1, KB_DEN1 + 4, 4, KB_DEN1 + 8, 4, NVSR_YB_PLAIN(1))
         NVSR_HIDDEN_LAYER(1, 2, KB_DEN1 + 12, 4, KB_DEN1 + 16, 4, NVSR_YB_PLAIN(2))
+        } else if constexpr (DENSITY) {
+        // ---- density pass: the whole density decoder, with the NEXT sample's six plane gathers (X planes 0..2, then Y planes 0..2) rolling
+        // through its blocks in halves (gather_half, pair_core.h: two tap buffers and ONE blend buffer -- both tiles' activations are live
+        // beside them): block i = 0..11 loads half i, block i + 1 blends it; a plane is complete behind every second block and goes into D
+        // there, in the order (F0 + F1) + F2, then div3.  A ring chunk is issued in the first half of an X block and waited for behind the Y
+        // block that follows it, whose 12 gather loads are younger than the chunk's last piece (ring3_sync<12>; the X block's own loads are
+        // blended by then).
+        float (&Fg)[HALF_C] = X.F;
+#define NVSR_HALF(JL, HL, JB, HB, LOADS, BLENDS, NS_) gather_half<NS_, LOADS, HL, BLENDS, HB>(slot, JL, JB, Fg, h, r2)
+#define NVSR_JOB(J, P, N0, N1, N2) J.plane = sc.plane[P]; J.t = pos_taps2(sc, P, N0, N1, N2); scale_taps(J.t);
+        // density layer 0
+        nw = ring3_take(rs);
+        NVSR_JOB(ja, 0, xn0, xn1, xn2)
+        split_feat(X.D);
+        limb_block<LIMBS, 3, true, true>(cw, lane, X.acc, cur, fa, feat(X.D),
+                                         [&](int slot) NVSR_INL { NVSR_HALF(ja, 0, ja, 0, true, false, NSF); dma_side<LIMBS, 4>(slot, rs, nw, KB_DEN1); }, NoTail{});
+        split_feat(Y.D);
+        limb_block<LIMBS, 3, true, false>(cw, lane, Y.acc, cur, fa, feat(Y.D),
+                                          [&](int slot) NVSR_INL {
+                                              spread<RELU_STEPS, 0, NSF>(slot, [&](int k) NVSR_INL { relu_bias_step<LIMBS>(k, small + S_BIAS + 0 * HID, h, X.acc, X.act, bp, nsc); });
+                                              NVSR_HALF(ja, 1, ja, 0, true, true, NSF);
+                                          },
+                                          tail_of(X.act, 0));
+        cw = nw;
+        // one hidden layer: X a | Y a | X b | Y b, each with the gather halves (JL, HL) it loads and (JB, HB) it blends, and the statements
+        // (D updates, the next job's taps) that go in front of it
+#define NVSR_DEN_LAYER(VPREV, KB_NEXT_A, KB_NEXT_B, NKB_B, PRE_XA, G_XA, PRE_YA, G_YA, PRE_XB, G_XB, PRE_YB, YB_SIDE, YB_TAIL)                      \
+        ring3_sync<12>();                                                                                                           \
+        nw = ring3_take(rs);                                                                                                        \
+        PRE_XA                                                                                                                      \
+        limb_block<LIMBS, 4, true, true>(cw, lane, X.acc, cur, fa, hid(X.act, 0),                                                   \
+                                         [&](int slot) NVSR_INL { relu_side(Y, VPREV)(slot); G_XA; dma_side<LIMBS, 4>(slot, rs, nw, KB_NEXT_A); }, tail_of(Y.act, 0)); \
+        PRE_YA                                                                                                                      \
+        limb_block<LIMBS, 4, true, false>(cw, lane, Y.acc, cur, fa, hid(Y.act, 0), [&](int slot) NVSR_INL { G_YA; }, tail_of(X.act, 4)); \
+        cw = nw;                                                                                                                    \
+        ring3_sync<12>();                                                                                                           \
+        nw = ring3_take(rs);                                                                                                        \
+        PRE_XB                                                                                                                      \
+        limb_block<LIMBS, 4, false, true>(cw, lane, X.acc, cur, fa, hid(X.act, 4),                                                  \
+                                          [&](int slot) NVSR_INL { G_XB; dma_side<LIMBS, NKB_B>(slot, rs, nw, KB_NEXT_B); }, tail_of(Y.act, 4)); \
+        PRE_YB                                                                                                                      \
+        limb_block<LIMBS, 4, false, false>(cw, lane, Y.acc, cur, fa, hid(Y.act, 4), [&](int slot) NVSR_INL { YB_SIDE; }, YB_TAIL);     \
+        cw = nw;
+        // (D is read by the NEXT iteration only: without the opaque statement the compiler sinks every blend and D update of the step into the
+        //  loop's last basic block, behind the list stores, and keeps all 144 tap registers of the step alive until there -- in scratch)
+#define NVSR_D_SET(T) _Pragma("unroll") for (int c = 0; c < HALF_C; ++c) { T.D[c] = Fg[c]; asm volatile("" : "+v"(T.D[c])); }
+#define NVSR_D_ADD(T) _Pragma("unroll") for (int c = 0; c < HALF_C; ++c) { T.D[c] = __fadd_rn(T.D[c], Fg[c]); asm volatile("" : "+v"(T.D[c])); }
+#define NVSR_D_AVG(T) _Pragma("unroll") for (int c = 0; c < HALF_C; ++c) { T.D[c] = div3(__fadd_rn(T.D[c], Fg[c])); asm volatile("" : "+v"(T.D[c])); }
+        // density layer 1: X p0 -> D, X p1, X p2 (first half)
+        NVSR_DEN_LAYER(0, KB_DEN1 + 4, KB_DEN1 + 8, 4,
+                       NVSR_JOB(jb, 1, xn0, xn1, xn2), NVSR_HALF(jb, 0, ja, 1, true, true, NSH),
+                       NVSR_D_SET(X), NVSR_HALF(jb, 1, jb, 0, true, true, NSH),
+                       NVSR_JOB(ja, 2, xn0, xn1, xn2), NVSR_HALF(ja, 0, jb, 1, true, true, NSH),
+                       NVSR_D_ADD(X), relu_side(X, 1)(slot); NVSR_HALF(ja, 1, ja, 0, true, true, NSH), tail_of(X.act, 0))
+        // density layer 2: X p2 -> D done; Y p0, Y p1
+        NVSR_DEN_LAYER(1, KB_DEN1 + 12, KB_DEN1 + 16, 4,
+                       NVSR_JOB(jb, 0, yn0, yn1, yn2), NVSR_HALF(jb, 0, ja, 1, true, true, NSH),
+                       NVSR_D_AVG(X), NVSR_HALF(jb, 1, jb, 0, true, true, NSH),
+                       NVSR_JOB(ja, 1, yn0, yn1, yn2), NVSR_HALF(ja, 0, jb, 1, true, true, NSH),
+                       NVSR_D_SET(Y), relu_side(X, 2)(slot); NVSR_HALF(ja, 1, ja, 0, true, true, NSH), tail_of(X.act, 0))
+        // density layer 3: Y p2 -> D done behind X b.  The chunk issued last is chunk 0 of the NEXT sample (after the last sample: a harmless
+        // copy); Y b | X: act, then the sigma head
+        float sx[1] = {0.0f};
+        auto sigma_side = [&](int slot) NVSR_INL {
+            spread<RELU_STEPS, 0, NSH / 2>(slot, [&](int k) NVSR_INL { relu_bias_step<LIMBS>(k, small + S_BIAS + 3 * HID, h, X.acc, X.act, bp, nsc); });
+            spread<64, NSH / 2, NSH>(slot, [&](int k) NVSR_INL { heads_side<1>(k >> 2, k & 3, small + S_ALPHA_W, h, X.act, sx, hp1); });
+        };
+        NVSR_DEN_LAYER(2, KB_DEN1 + 20, KB_FIRST, 3,
+                       NVSR_JOB(jb, 2, yn0, yn1, yn2), NVSR_HALF(jb, 0, ja, 1, true, true, NSH),
+                       NVSR_D_ADD(Y), NVSR_HALF(jb, 1, jb, 0, true, true, NSH),
+                       , NVSR_HALF(jb, 1, jb, 1, false, true, NSH),
+                       NVSR_D_AVG(Y), sigma_side(slot), NoTail{})
+#undef NVSR_DEN_LAYER
+#undef NVSR_D_SET
+#undef NVSR_D_ADD
+#undef NVSR_D_AVG
+#undef NVSR_HALF
+#undef NVSR_JOB
+        X.raw[3] = (sx[0] + __shfl_xor(sx[0], 32)) + small[S_HEAD_B];
+        }
+        if constexpr (FUSED) {
         // density layer 3: the chunk issued last is chunk 0 of the NEXT sample (after the last sample: a harmless copy);
         // Y b | X: act, then the sigma head
         float sx[1] = {0.0f};
@@ -344,13 +522,10 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
                                                                   spread<64, NSH / 2, NSH>(slot, [&](int k) NVSR_INL { heads_side<1>(k >> 2, k & 3, small + S_ALPHA_W, h, X.act, sx, hp1); });
                                                               },
                                                               NoTail{})))
-#undef NVSR_HIDDEN_LAYER
-#undef NVSR_HIDDEN_LAYER_
-#undef NVSR_ROLL
-#undef NVSR_ROLL_DMA
-#undef NVSR_YB_PLAIN
         X.raw[3] = (sx[0] + __shfl_xor(sx[0], 32)) + small[S_HEAD_B];
+        }
         R3_MARK(5)      // density layers 1..3
+        if constexpr (!COLOUR) {
 
         // ---- epilogue (exposed): Y's last activation + sigma head, both tiles' compositing -----------------------------------------
 #pragma unroll
@@ -364,12 +539,47 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
             if (validX) *reinterpret_cast<f32x4*>(raw_out + (rayX * S + s) * 4) = f32x4{X.raw[0], X.raw[1], X.raw[2], X.raw[3]};
             if (validY) *reinterpret_cast<f32x4*>(raw_out + (rayY * S + s) * 4) = f32x4{Y.raw[0], Y.raw[1], Y.raw[2], Y.raw[3]};
         }
-        composite_sample(X, reinterpret_cast<const f32x4*>(rcX)[1][2], nzX, last);
-        composite_sample(Y, reinterpret_cast<const f32x4*>(rcY)[1][2], nzY, last);
+        if constexpr (DENSITY) {
+            composite_weight(X, reinterpret_cast<const f32x4*>(rcX)[1][2], nzX, last);
+            composite_weight(Y, reinterpret_cast<const f32x4*>(rcY)[1][2], nzY, last);
+        } else {
+            composite_sample(X, reinterpret_cast<const f32x4*>(rcX)[1][2], nzX, last);
+            composite_sample(Y, reinterpret_cast<const f32x4*>(rcY)[1][2], nzY, last);
+        }
         if (weights && lane < 32) {
             if (validX) weights[rayX * S + s] = X.raw[3];
             if (validY) weights[rayY * S + s] = Y.raw[3];
         }
+        if constexpr (DENSITY) {
+            // the live list: every sample whose weight is not zero (a NaN weight is live), in sample order
+            const bool liveX = !(X.raw[3] == 0.0f), liveY = !(Y.raw[3] == 0.0f);
+            if (lane < 32) {
+                if (validX && liveX) { live_z[rayX * S + nX] = ZCOMP ? __int_as_float(s) : X.zc; live_w[rayX * S + nX] = X.raw[3]; }
+                if (validY && liveY) { live_z[rayY * S + nY] = ZCOMP ? __int_as_float(s) : Y.zc; live_w[rayY * S + nY] = Y.raw[3]; }
+            }
+            nX += liveX; nY += liveY;
+        }
+        } else {
+        // ---- colour pass epilogue (exposed): X's raw colours, Y's last activation + rgb heads, both tiles' w sigmoid(raw) ------------
+#pragma unroll
+        for (int c = 0; c < 3; ++c) X.raw[c] = (hx[c] + __shfl_xor(hx[c], 32)) + small[S_HEAD_B + 1 + c];
+#pragma unroll
+        for (int k = 0; k < RELU_STEPS; ++k) relu_bias_step<LIMBS>(k, small + S_BIAS + 7 * HID, h, Y.acc, Y.act, bp, nsc);
+        {
+            float hd[3];
+            head_dots<3>(small + S_RGB_W, h, Y.act, hd);        // (the fmaf chain and the half-wave sum of heads_side)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) Y.raw[c] = hd[c] + small[S_HEAD_B + 1 + c];
+        }
+        composite_colour(X, wX, s < nX);
+        composite_colour(Y, wY, s < nY);
+        wX = wXn; wY = wYn;
+        }
+#undef NVSR_HIDDEN_LAYER
+#undef NVSR_HIDDEN_LAYER_
+#undef NVSR_ROLL
+#undef NVSR_ROLL_DMA
+#undef NVSR_YB_PLAIN
         X.zc = X.zn; Y.zc = Y.zn;
         R3_MARK(6)      // epilogue
     }
@@ -387,14 +597,22 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
             const long ray = k ? rayY : rayX;
             if (!(k ? validY : validX)) continue;
             float cr = t.cr, cg = t.cg, cb = t.cb;
-            const float q = t.dep / t.ac;                       // NaN when acc == 0, like torch.max(1e-10, nan)
-            disp[ray] = 1.0f / ((q != q) ? q : fmaxf(1e-10f, q));
-            if (white) { const float bg = 1.0f - t.ac; cr += bg; cg += bg; cb += bg; }
-            rgb[ray * 3 + 0] = cr; rgb[ray * 3 + 1] = cg; rgb[ray * 3 + 2] = cb;
-            acc[ray] = t.ac;
+            const float ac = COLOUR ? acc[ray] : t.ac;          // (colour pass: the density pass wrote it)
+            if constexpr (!COLOUR) {
+                const float q = t.dep / t.ac;                   // NaN when acc == 0, like torch.max(1e-10, nan)
+                disp[ray] = 1.0f / ((q != q) ? q : fmaxf(1e-10f, q));
+                acc[ray] = t.ac;
+                if (depth) depth[ray] = t.dep;
+            }
+            if constexpr (DENSITY) {
+                live_n[ray] = k ? nY : nX;
+                cr = cg = cb = 0.0f;                            // (the range flag below then looks at acc alone; the colour pass looks at rgb)
+            } else {
+                if (white) { const float bg = 1.0f - ac; cr += bg; cg += bg; cb += bg; }
+                rgb[ray * 3 + 0] = cr; rgb[ray * 3 + 1] = cg; rgb[ray * 3 + 2] = cb;
+            }
             // range flag of the f16 limbs (nvsr.h: nvsr_set_range_flag): a non-finite colour / opacity is an operand beyond the static scales
-            if (LIMBS == 2 && flag && !(fabsf(cr + cg + cb + t.ac) <= 3.0e38f)) __hip_atomic_fetch_or(flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (depth) depth[ray] = t.dep;
+            if (LIMBS == 2 && flag && !(fabsf(cr + cg + cb + ac) <= 3.0e38f)) __hip_atomic_fetch_or(flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }
@@ -430,6 +648,50 @@ __global__ __launch_bounds__(TPB2, 1) void render_pass3_kernel(SceneDev sc, cons
                                                               float* __restrict__ acc, float* __restrict__ depth,
                                                               float* __restrict__ raw_out, unsigned* __restrict__ flag) {
     render_pass3_body<LIMBS>(sc, packed, N, S, rays, z, 0, noise, white, rgb, disp, acc, nullptr, depth, raw_out, flag);
+}
+
+// ---- the two-phase route: density pass, then the colour decoder on the live samples (PHASE 1 and 2 of the body) ---------------------
+// live_z / live_w: [N, S] rows (the first live_n[ray] entries are written), live_n: [N].  `_z`: the coarse pass of an inference frame
+// (depths in registers; live_z holds sample indices).  Device pass only, like the coarse_z kernel above.
+template <int LIMBS>
+__global__ __launch_bounds__(TPB2, 1) void render_pass3_density_kernel(SceneDev sc, const float* __restrict__ packed, long N, int S,
+                                                                      const float* __restrict__ rays, const float* __restrict__ z,
+                                                                      const float* __restrict__ noise, float* __restrict__ disp,
+                                                                      float* __restrict__ acc, float* __restrict__ weights,
+                                                                      float* __restrict__ depth, unsigned* __restrict__ flag,
+                                                                      float* __restrict__ live_z, float* __restrict__ live_w, int* __restrict__ live_n) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    render_pass3_body<LIMBS + 16>(sc, packed, N, S, rays, z, 0, noise, 0, nullptr, disp, acc, weights, depth, nullptr, flag, live_z, live_w, live_n);
+#endif
+}
+template <int LIMBS>
+__global__ __launch_bounds__(TPB2, 1) void render_pass3_density_z_kernel(SceneDev sc, const float* __restrict__ packed, long N, int S,
+                                                                        const float* __restrict__ rays, int lindisp,
+                                                                        const float* __restrict__ noise, float* __restrict__ disp,
+                                                                        float* __restrict__ acc, float* __restrict__ weights,
+                                                                        float* __restrict__ depth, unsigned* __restrict__ flag,
+                                                                        float* __restrict__ live_z, float* __restrict__ live_w, int* __restrict__ live_n) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    render_pass3_body<LIMBS + 8 + 16>(sc, packed, N, S, rays, nullptr, lindisp, noise, 0, nullptr, disp, acc, weights, depth, nullptr, flag, live_z, live_w, live_n);
+#endif
+}
+template <int LIMBS>
+__global__ __launch_bounds__(TPB2, 1) void render_pass3_colour_kernel(SceneDev sc, const float* __restrict__ packed, long N, int S,
+                                                                     const float* __restrict__ rays, int white, float* __restrict__ rgb,
+                                                                     float* __restrict__ acc, unsigned* __restrict__ flag,
+                                                                     float* __restrict__ live_z, float* __restrict__ live_w, int* __restrict__ live_n) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    render_pass3_body<LIMBS + 32>(sc, packed, N, S, rays, nullptr, 0, nullptr, white, rgb, nullptr, acc, nullptr, nullptr, nullptr, flag, live_z, live_w, live_n);
+#endif
+}
+template <int LIMBS>
+__global__ __launch_bounds__(TPB2, 1) void render_pass3_colour_z_kernel(SceneDev sc, const float* __restrict__ packed, long N, int S,
+                                                                       const float* __restrict__ rays, int lindisp, int white,
+                                                                       float* __restrict__ rgb, float* __restrict__ acc, unsigned* __restrict__ flag,
+                                                                       float* __restrict__ live_z, float* __restrict__ live_w, int* __restrict__ live_n) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    render_pass3_body<LIMBS + 8 + 32>(sc, packed, N, S, rays, nullptr, lindisp, nullptr, white, rgb, nullptr, acc, nullptr, nullptr, nullptr, flag, live_z, live_w, live_n);
+#endif
 }
 
 // ---- natural blob -> bf16 limb fragments (the tail of the packed blob) -----------------------------------------------------------
@@ -524,11 +786,97 @@ extern "C" int nvsr_pack_decoder_limbs_launch(const float* natural, float* packe
     return NVSR_CHECK_LAUNCH();
 }
 
+// ---- scratch of the two-phase route: the live lists, [N, S] depths + [N, S] weights + [N] counts ------------------------------------
+// Owned by the library, one buffer per (device, stream), grow-only: two launches on one stream are ordered, launches on two streams never
+// share a buffer.  Growing frees the old buffer with hipFree, which waits for the device -- no launch can still be using it.
+// Contract (include/nvsr.h): one host thread at a time enqueues render launches on a given (device, stream) -- the pointer is used after
+// the table's lock is dropped; the entry of a destroyed stream keeps its buffer until nvsr_release_render_scratch.
+namespace {
+struct LiveScratch { int device; hipStream_t stream; char* p; size_t bytes; };
+std::mutex g_live_mutex;
+std::vector<LiveScratch> g_live;
+
+char* live_scratch(hipStream_t stream, size_t bytes) {
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) return nullptr;
+    std::lock_guard<std::mutex> lock(g_live_mutex);
+    LiveScratch* e = nullptr;
+    for (LiveScratch& c : g_live)
+        if (c.device == device && c.stream == stream) e = &c;
+    if (!e) { g_live.push_back(LiveScratch{device, stream, nullptr, 0}); e = &g_live.back(); }
+    if (e->bytes < bytes) {
+        if (e->p) (void)hipFree(e->p);
+        e->p = nullptr; e->bytes = 0;
+        void* p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        e->p = static_cast<char*>(p); e->bytes = bytes;
+    }
+    return e->p;
+}
+
+// the two-phase route is taken unless the caller wants the raw decoder outputs, NVSR_RENDER_ONE_PHASE=1 is set (the A/B handle), the stream
+// is being captured (the scratch cannot grow inside a capture) or the scratch cannot be had -- then the fused kernel runs: same pixels
+struct LiveLists { float* z; float* w; int* n; };
+bool two_phase_lists(const float* raw_out, int64_t N, int S, hipStream_t stream, LiveLists& out) {
+    if (raw_out) return false;
+    const char* e = getenv("NVSR_RENDER_ONE_PHASE");
+    if (e && e[0] == '1') return false;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return false; }
+    const size_t rows = (size_t)N * (size_t)S * sizeof(float);
+    char* p = live_scratch(stream, 2 * rows + (size_t)N * sizeof(int));
+    if (!p) return false;
+    out.z = reinterpret_cast<float*>(p);
+    out.w = reinterpret_cast<float*>(p + rows);
+    out.n = reinterpret_cast<int*>(p + 2 * rows);
+    return true;
+}
+}  // namespace
+
+// a frame's driver knows its largest pass before the first launch: sizing the buffer for it up front keeps the growth (a device-wide
+// wait) out of the frame -- between the coarse and the fine pass (aux.hip).  Does nothing where the two-phase route would not be taken.
+extern "C" void nvsr_internal_reserve_render_scratch(int64_t N, int S, nvsr_stream_t stream) {
+    LiveLists ll;
+    (void)two_phase_lists(nullptr, N, S, (hipStream_t)stream, ll);
+}
+
+extern "C" int64_t nvsr_render_scratch_bytes(void) {
+    std::lock_guard<std::mutex> lock(g_live_mutex);
+    int64_t total = 0;
+    for (const LiveScratch& c : g_live) total += (int64_t)c.bytes;
+    return total;
+}
+
+extern "C" int nvsr_release_render_scratch(void) {
+    std::lock_guard<std::mutex> lock(g_live_mutex);
+    int prev = 0;
+    const bool have_prev = hipGetDevice(&prev) == hipSuccess;
+    int rc = NVSR_OK;
+    for (LiveScratch& c : g_live) {
+        if (!c.p) continue;
+        if (hipSetDevice(c.device) != hipSuccess || hipFree(c.p) != hipSuccess) rc = NVSR_ERR_LAUNCH;
+    }
+    g_live.clear();
+    if (have_prev) (void)hipSetDevice(prev);
+    return rc;
+}
+
 extern "C" int nvsr_render_pass3_launch(int limbs, const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays,
                                         const float* z, const float* noise, int white_bkgd, float* rgb, float* disp, float* acc,
                                         float* weights, float* depth, float* raw_out, nvsr_stream_t stream) {
     const int64_t grid = (N + RAYS2 - 1) / RAYS2;
     if (grid > 0x7fffffff || (limbs != 2 && limbs != 3)) return NVSR_ERR_SHAPE;
+    LiveLists ll;
+    if (two_phase_lists(raw_out, N, S, (hipStream_t)stream, ll)) {
+#define NVSR_LAUNCH3_2P(LIMBS_)                                                                                                            \
+        hipLaunchKernelGGL(render_pass3_density_kernel<LIMBS_>, dim3((unsigned)grid), dim3(TPB2), 0, (hipStream_t)stream, to_dev(scene),   \
+                           packed_decoder, (long)N, S, rays, z, noise, disp, acc, weights, depth, nvsr_get_range_flag(), ll.z, ll.w, ll.n); \
+        hipLaunchKernelGGL(render_pass3_colour_kernel<LIMBS_>, dim3((unsigned)grid), dim3(TPB2), 0, (hipStream_t)stream, to_dev(scene),    \
+                           packed_decoder, (long)N, S, rays, white_bkgd, rgb, acc, nvsr_get_range_flag(), ll.z, ll.w, ll.n)
+        if (limbs == 3) { NVSR_LAUNCH3_2P(3); } else { NVSR_LAUNCH3_2P(2); }
+#undef NVSR_LAUNCH3_2P
+        return NVSR_CHECK_LAUNCH();
+    }
 #define NVSR_LAUNCH3(LIMBS_)                                                                                                               \
     if (weights)                                                                                                                           \
         hipLaunchKernelGGL(render_pass3_coarse_kernel<LIMBS_>, dim3((unsigned)grid), dim3(TPB2), 0, (hipStream_t)stream, to_dev(scene),    \
@@ -547,6 +895,17 @@ extern "C" int nvsr_render_pass3_coarse_z_launch(int limbs, const nvsr_scene* sc
                                                  float* weights, float* depth, float* raw_out, nvsr_stream_t stream) {
     const int64_t grid = (N + RAYS2 - 1) / RAYS2;
     if (grid > 0x7fffffff || (limbs != 2 && limbs != 3) || !weights) return NVSR_ERR_SHAPE;
+    LiveLists ll;
+    if (two_phase_lists(raw_out, N, S, (hipStream_t)stream, ll)) {
+#define NVSR_LAUNCH3_2P(LIMBS_)                                                                                                            \
+        hipLaunchKernelGGL(render_pass3_density_z_kernel<LIMBS_>, dim3((unsigned)grid), dim3(TPB2), 0, (hipStream_t)stream, to_dev(scene), \
+                           packed_decoder, (long)N, S, rays, lindisp, noise, disp, acc, weights, depth, nvsr_get_range_flag(), ll.z, ll.w, ll.n); \
+        hipLaunchKernelGGL(render_pass3_colour_z_kernel<LIMBS_>, dim3((unsigned)grid), dim3(TPB2), 0, (hipStream_t)stream, to_dev(scene),  \
+                           packed_decoder, (long)N, S, rays, lindisp, white_bkgd, rgb, acc, nvsr_get_range_flag(), ll.z, ll.w, ll.n)
+        if (limbs == 3) { NVSR_LAUNCH3_2P(3); } else { NVSR_LAUNCH3_2P(2); }
+#undef NVSR_LAUNCH3_2P
+        return NVSR_CHECK_LAUNCH();
+    }
     if (limbs == 3)
         hipLaunchKernelGGL(render_pass3_coarse_z_kernel<3>, dim3((unsigned)grid), dim3(TPB2), 0, (hipStream_t)stream, to_dev(scene), packed_decoder,
                            (long)N, S, rays, lindisp, noise, white_bkgd, rgb, disp, acc, weights, depth, raw_out, nvsr_get_range_flag());

@@ -83,6 +83,29 @@ __device__ __forceinline__ void composite_sample(TileT& t, float nrm, float nois
     t.raw[3] = w;     // hand the weight back to the caller (stored when requested)
 }
 
+// The two halves of composite_sample for the two-phase render pass (render3.hip), operation for operation.
+// Density pass: T, w, depth and acc; the weight is handed back in raw[3].
+template <class TileT>
+__device__ __forceinline__ void composite_weight(TileT& t, float nrm, float noise, bool last) {
+    const float dist = __fmul_rn(last ? 1e10f : __fsub_rn(t.zn, t.zc), nrm);
+    const float sn = __fadd_rn(t.raw[3], noise);
+    const float sig = sn < 0.0f ? 0.0f : sn;
+    const float alpha = __fsub_rn(1.0f, expf(-__fmul_rn(sig, dist)));
+    const float w = __fmul_rn(alpha, t.T);
+    t.T = __fmul_rn(t.T, __fadd_rn(__fsub_rn(1.0f, alpha), 1e-10f));
+    t.dep = __fadd_rn(t.dep, __fmul_rn(w, t.zc));
+    t.ac = __fadd_rn(t.ac, w);
+    t.raw[3] = w;
+}
+// Colour pass: c += w sigmoid(raw) for a live entry; a lane past its ray's list keeps its sums (a select, never + 0 x)
+template <class TileT>
+__device__ __forceinline__ void composite_colour(TileT& t, float w, bool live) {
+    const float cr = __fadd_rn(t.cr, __fmul_rn(w, 1.0f / (1.0f + expf(-t.raw[0]))));
+    const float cg = __fadd_rn(t.cg, __fmul_rn(w, 1.0f / (1.0f + expf(-t.raw[1]))));
+    const float cb = __fadd_rn(t.cb, __fmul_rn(w, 1.0f / (1.0f + expf(-t.raw[2]))));
+    t.cr = live ? cr : t.cr; t.cg = live ? cg : t.cg; t.cb = live ? cb : t.cb;
+}
+
 __device__ __forceinline__ Taps pos_taps2(const SceneDev& sc, int d, float n0, float n1, float n2) {
     const float* M = sc.proj + 6 * d;
     return make_taps(sc, d, n0 * M[0] + n1 * M[2] + n2 * M[4], n0 * M[1] + n1 * M[3] + n2 * M[5]);
