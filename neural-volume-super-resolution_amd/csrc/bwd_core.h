@@ -259,9 +259,12 @@ __device__ __forceinline__ void scatter_plane_cached_v(const f32x16 (&acc2)[2], 
     const int o0 = sy ? x2 : x0, o1 = sy ? x3 : x1, o2 = sy ? x0 : x2, o3 = sy ? x1 : x3;
     const float a0 = sy ? y2 : y0, a1 = sy ? y3 : y1, a2 = sy ? y0 : y2, a3 = sy ? y1 : y3;
     // bit j: slot j holds another texel than at the previous point (point 0: every slot starts)
+    // (the four lane reads stand in front of the select, with every lane active: inside its `pt != 0` arm point 0's lanes are switched off,
+    //  ds_bpermute returns 0 for an inactive source lane, and point 1 compared its texels with offset 0 instead of point 0's -- a slot that
+    //  moved ONTO the plane's first texel at the second sample of a tile was never flushed and its sum landed on that texel)
     const int prev = (lane & 32) | (pt > 0 ? pt - 1 : 0);
-    const int fl = pt == 0 ? 15 : ((o0 != __shfl(o0, prev)) ? 1 : 0) | ((o1 != __shfl(o1, prev)) ? 2 : 0) | ((o2 != __shfl(o2, prev)) ? 4 : 0) |
-                                  ((o3 != __shfl(o3, prev)) ? 8 : 0);
+    const int p0_ = __shfl(o0, prev), p1_ = __shfl(o1, prev), p2_ = __shfl(o2, prev), p3_ = __shfl(o3, prev);
+    const int fl = pt == 0 ? 15 : ((o0 != p0_) ? 1 : 0) | ((o1 != p1_) ? 2 : 0) | ((o2 != p2_) ? 4 : 0) | ((o3 != p3_) ? 8 : 0);
     float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;              // this lane's channel of slot j
     float* const gl = gplane + lane;
 #if defined(BL_SCATTER_FALLTHROUGH) && BL_SCATTER_FALLTHROUGH
