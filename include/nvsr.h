@@ -688,6 +688,30 @@ int nvsr_planes_sr_backward_batch_marks(int B, int C, int R0, int R1, const floa
                                         float* grad_natural, float* const* d_lr, float* workspace, int arithmetic, int align_corners,
                                         int plane_interp, int n_marks, const int32_t* mark_layers, void* const* mark_events, nvsr_stream_t stream);
 
+/* ---- low-rank feature planes ---------------------------------------------------------------------------------------------------------------
+ * Replaces: `TwoDimPlanesModel.gen_plane` (models.py:223-230) -- with `plane_rank[name] = r` a position plane is stored as ONE parameter
+ * F [1,C,R,2r] (contiguous NCHW), U = F[..., :r], V = F[..., r:], and sampled as plane = U @ V^T per channel (torch.matmul + permute) -- and
+ * that product's autograd backward.  Square planes only; ranks and resolutions may differ between the planes of a call; r == R is legal.
+ *   factors[p]     device, [C][R][2r] f32 (4-byte alignment is enough: rows are 8r bytes)
+ *   planes[p]      device, CHANNEL-LAST [R][R][C]: written by nvsr_lowrank_planes; READ by nvsr_lowrank_planes_backward as dL/d plane
+ *   d_factors[p]   device, [C][R][2r]: written (every element, no accumulation) by nvsr_lowrank_planes_backward; unused by the forward
+ * Arithmetic: exact f32, no limb mode.  plane[y][x][c] = the fmaf chain over k = 0 .. r-1 ASCENDING from +0.0 (the f32 matrix instruction,
+ * k zero-padded to its step of 4); dU[c][y][k] = the fmaf chain over x ascending of G[y][x][c] V[c][x][k], dV[c][x][k] over y ascending of
+ * G[y][x][c] U[c][y][k].  No atomics and no split sums: the results are a function of the inputs alone, bit for bit run to run and whether a
+ * plane is alone in the call or not.  One kernel launch per call for all planes.
+ * NVSR_ERR_SHAPE (nothing is launched): num_planes outside 1 .. NVSR_MAX_POSITION_PLANES, channels < 1, a res or rank < 1. */
+typedef struct nvsr_lowrank_planes_args {
+    int32_t num_planes;                                   /* 1 .. NVSR_MAX_POSITION_PLANES */
+    int32_t channels;                                     /* C >= 1 (any; 48 in the shipped configs) */
+    const float* factors[NVSR_MAX_POSITION_PLANES];
+    float* planes[NVSR_MAX_POSITION_PLANES];
+    float* d_factors[NVSR_MAX_POSITION_PLANES];
+    int32_t res[NVSR_MAX_POSITION_PLANES];                /* R per plane */
+    int32_t rank[NVSR_MAX_POSITION_PLANES];               /* r per plane (the reference's plane_rank: ceil(planes_rank_ratio R), models.py:541) */
+} nvsr_lowrank_planes_args;
+int nvsr_lowrank_planes(nvsr_lowrank_planes_args args, nvsr_stream_t stream);
+int nvsr_lowrank_planes_backward(nvsr_lowrank_planes_args args, nvsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,13 @@ class SceneExt(C.Structure):
                 ("range", C.c_float * 5), ("proj", (C.c_float * 6) * MAX_POSITION_PLANES)]
 
 
+class LowrankPlanesArgs(C.Structure):
+    """struct nvsr_lowrank_planes_args (passed by value)"""
+    _fields_ = [("num_planes", C.c_int32), ("channels", C.c_int32), ("factors", C.c_void_p * MAX_POSITION_PLANES),
+                ("planes", C.c_void_p * MAX_POSITION_PLANES), ("d_factors", C.c_void_p * MAX_POSITION_PLANES),
+                ("res", C.c_int32 * MAX_POSITION_PLANES), ("rank", C.c_int32 * MAX_POSITION_PLANES)]
+
+
 class DecoderGeometry(C.Structure):
     """struct nvsr_decoder_geometry"""
     _fields_ = [(n, C.c_int32) for n in ("plane_channels", "viewdir_channels", "hidden", "density_layers", "rgb_layers", "skip_connect_every",
@@ -212,6 +219,9 @@ _PROTOS_OPTIONAL = {   # feature-plane super-resolution (csrc/sr.hip)
     "nvsr_pe_nerf_backward_arith": ([_i64, _vp, _vp, _vp, _vp, _i, _vp], _i),
     "nvsr_pe_nerf_wgrad_workspace_floats": ([_i64], _i64),
     "nvsr_pe_nerf_weight_grad": ([_i64, _vp, _vp, _vp, _vp, _vp], _i),
+    # low-rank feature planes (csrc/lowrank.hip)
+    "nvsr_lowrank_planes": ([LowrankPlanesArgs, _vp], _i),
+    "nvsr_lowrank_planes_backward": ([LowrankPlanesArgs, _vp], _i),
 }
 
 _lib = None

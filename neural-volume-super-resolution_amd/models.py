@@ -120,10 +120,50 @@ def from_channel_last(plane_hwc, like=None):
 _PLANE_CACHE = {}
 
 
+# ---- generated (low-rank) planes: models.py:223-230 -----------------------------------------------------------------------------------
+# With `plane_rank[name] = r` the parameter planes_[name] is a factor tensor F [1,C,R,2r] and the plane that is sampled is GENERATED from it
+# (torch.ops.nvsr.lowrank_planes).  The reference keeps generated planes in the dict `generated_planes`, shared by the coarse and the fine
+# model and cleared by PlanesOptimizer.step() / load_scene; here the dict is honoured the same way (an externally assigned attribute; clearing
+# it has the reference's effect), and on top of that an entry is only SERVED while it is valid: made from this factor tensor object, at its
+# current version, after the last clear_plane_cache().  Models that were given no dict share this one.
+#
+# All the rules, in one place.  An entry generated_planes[name] is served by gen_plane only if
+#   1. it was made from THIS factor tensor object (weak reference) at its CURRENT `_version`, with the current plane_rank[name]: an optimizer step,
+#      training.mark_updated, any in-place write and a replaced parameter retire it (_generated_valid);
+#   2. it was made after the last clear_plane_cache() (`_generation_epoch`: that call cannot reach dicts the caller assigned to models);
+#   3. for a caller that needs gradients: it carries a graph that no backward has walked yet (a hook on the plane sets `consumed`: autograd frees
+#      the graph, and a second iteration on the same factor version must generate again instead of failing).
+# Entries are REMOVED by generated_planes.clear() (the reference's PlanesOptimizer.step / load_scene), model.invalidate() (`.data` writes bump no
+# version), a model's move to another scene (set_cur_scene_id: only the current scene stays resident) and GraphedTrainStep before its capture.
+# A detached plane (gen_plane(detach=True), what assign_LR_planes hands to PlanesSR under detach_LR_planes) keeps the record of its source, so
+# that whoever holds it can apply rule 1: TwoDimPlanesModel._refresh_LR_planes does, right before every use of PlanesSR's LR planes.
+_GENERATED_PLANES = {}
+_generation_epoch = 0
+
+
+class _Generated:
+    """what a generated plane was made from (kept on the tensor as `_nvsr_generated`)"""
+    __slots__ = ("src", "version", "rank", "epoch", "state")
+
+    def __init__(self, src, rank, state):
+        self.src, self.version, self.rank, self.epoch, self.state = weakref.ref(src), src._version, rank, _generation_epoch, state
+
+
+def _generated_valid(plane, src, rank, need_grad):
+    meta = getattr(plane, "_nvsr_generated", None) if plane is not None else None
+    if meta is None or meta.src() is not src or meta.version != src._version or meta.rank != rank or meta.epoch != _generation_epoch:
+        return False
+    # a training step needs a plane that is part of the autograd graph, and one whose graph has not been walked yet (the backward frees it)
+    return not need_grad or (plane.requires_grad and not meta.state["consumed"])
+
+
 def clear_plane_cache(prefix=None, keep_scene=None):
     """drop every cached channel-last plane; with `prefix` only the entries whose name starts with it; with `keep_scene` every entry that
-    does not belong to that scene id"""
+    does not belong to that scene id.  Without arguments every generated (low-rank) plane is dropped as well, whichever dict holds it."""
     if prefix is None and keep_scene is None:
+        global _generation_epoch
+        _generation_epoch += 1
+        _GENERATED_PLANES.clear()
         _PLANE_CACHE.clear()
         return
     for name in list(_PLANE_CACHE):
@@ -254,6 +294,9 @@ class TwoDimPlanesModel(nn.Module):
             keep = scene_id if self.scene_coupler is None else None
             if keep is not None:
                 clear_plane_cache(keep_scene=keep)
+                gen = self._generated_dict()
+                for name in [n for n in gen if search("(?<=sc).*(?=_D)", n) and plane_name2scene(n) != keep]:
+                    gen.pop(name, None)                  # (generated low-rank planes of the scene that was left)
         self.cur_id = scene_id
 
     def invalidate(self):
@@ -267,6 +310,7 @@ class TwoDimPlanesModel(nn.Module):
             for k in self.planes_:
                 _PLANE_CACHE.pop(k, None)
                 _PLANE_CACHE.pop(k + "/SR", None)
+        self._generated_dict().clear()           # (a `.data` write leaves the factor's version where it was)
 
     def train(self, mode=True):
         """nn.Module.train, and on a CHANGE of mode the derived copies are dropped: a training loop may have updated the parameters through
@@ -283,8 +327,67 @@ class TwoDimPlanesModel(nn.Module):
             p.data = p.data.to("cpu")
         self.invalidate()
 
+    # ---- low-rank planes (models.py:223-244) ---------------------------------------------------------------------------------------
+    def _generated_dict(self):
+        """`generated_planes` when the caller assigned one (load_scene: one dict for all models of a scene), else the module's shared dict"""
+        g = self.__dict__.get("generated_planes")
+        return _GENERATED_PLANES if g is None else g
+
+    def _rank_of(self, plane_name):
+        rank = self.__dict__.get("plane_rank")
+        return int(rank[plane_name]) if rank and plane_name in rank else None
+
+    def gen_plane(self, plane_name, detach=False):
+        """models.py:223-231: the plane as stored, or -- with plane_rank[plane_name] = r -- the plane generated from its factors
+        F [1,C,R,2r], U @ V^T per channel, in channels_last memory (sampled in place).  ALL low-rank planes of the plane's scene that have
+        no valid entry are generated by the one operator call, and the entries are shared by every model that shares the dict: the coarse
+        and the fine pass of an iteration sample one generated plane, and both gradients reach F through its one autograd node."""
+        r = self._rank_of(plane_name)
+        if r is None:
+            plane = self.planes_[plane_name]
+            return plane.detach() if detach else plane
+        src = self.planes_[plane_name]
+        cache = self._generated_dict()
+        need_grad = torch.is_grad_enabled() and src.requires_grad and not detach
+        plane = cache.get(plane_name)
+        if not _generated_valid(plane, src, r, need_grad):
+            scene = search("(?<=sc).*(?=_D)", plane_name)
+            names = [plane_name]
+            for n in self.plane_rank:
+                if n == plane_name or n not in self.planes_ or len(names) == capi.MAX_POSITION_PLANES:
+                    continue
+                m = search("(?<=sc).*(?=_D)", n)
+                f = self.planes_[n]
+                if (m and scene and m.group(0) == scene.group(0) and f.shape[1] == src.shape[1] and f.is_cuda
+                        and not _generated_valid(cache.get(n), f, int(self.plane_rank[n]), torch.is_grad_enabled() and f.requires_grad)):
+                    names.append(n)
+            factors = [self.planes_[n] for n in names]
+            ranks = [int(self.plane_rank[n]) for n in names]
+            for n, f, k in zip(names, factors, ranks):
+                if f.dim() != 4 or f.shape[3] != 2 * k or f.shape[2] < 1:
+                    raise ValueError("low-rank plane %s: plane_rank %d needs a factor tensor [1,C,R,%d], got %s" % (n, k, 2 * k, list(f.shape)))
+            capi.require_cuda(*factors)
+            state = {"consumed": False}
+            for n, f, k, p in zip(names, factors, ranks, torch.ops.nvsr.lowrank_planes(factors, ranks)):
+                p._nvsr_generated = _Generated(f, k, state)
+                if p.requires_grad:
+                    p.register_hook(lambda g, state=state: state.__setitem__("consumed", True))
+                cache[n] = p
+            plane = cache[plane_name]
+        if detach:
+            meta, plane = plane._nvsr_generated, plane.detach()
+            plane._nvsr_generated = meta                 # (what holds the detached plane -- PlanesSR.LR_planes -- can tell when it is stale)
+        return plane
+
+    def raw_plane(self, plane_name, downsample=False, detach=False):
+        """models.py:233-244 (down-sampled planes -- 'HR_planes' -- are refused: _refuse_plane_downsampling)"""
+        if downsample:
+            raise NotImplementedError("plane down-sampling ('HR_planes' in nerf.train.what: models.py:231-238) is not implemented")
+        return self.gen_plane(plane_name, detach=detach)
+
     def assign_LR_planes(self, scene=None):
-        """models.py:426-434 (no plane down-sampling: `should_downsample` is always False in the supported configs)"""
+        """models.py:426-434 (no plane down-sampling: `should_downsample` is always False in the supported configs).  A low-rank LR plane is
+        handed over GENERATED, as part of the graph: refining through it trains the factors (unless detach_LR_planes)."""
         for k in self.planes_:
             if scene is not None and self.scene_coupler is not None and self.scene_coupler.scene2saved[scene] not in k:
                 continue
@@ -292,8 +395,7 @@ class TwoDimPlanesModel(nn.Module):
                 self._refuse_plane_downsampling(k, for_LR_loading=True)
             if not self.SR_model.SR_viewdir and get_plane_name(None, self.num_density_planes) in k:
                 continue
-            plane = self.planes_[k]
-            self.SR_model.set_LR_plane(plane.detach() if self.detach_LR_planes else plane, id=k, save_interpolated=False)
+            self.SR_model.set_LR_plane(self.raw_plane(k, detach=self.detach_LR_planes), id=k, save_interpolated=False)
 
     # ---- native path ---------------------------------------------------------------------------------------------------
     def is_native_geometry(self):
@@ -380,10 +482,6 @@ class TwoDimPlanesModel(nn.Module):
     def _refuse_plane_downsampling(self, plane_name, **kw):
         """models.py:231-238,273: with 'HR_planes' in nerf.train.what (SceneCoupler(planes_res='HR')) an LR scene samples its HR couple's planes
         DOWN-sampled.  Not mirrored (no shipped config trains HR planes): loud instead of sampling the HR plane as it is."""
-        rank = getattr(self, "plane_rank", None)
-        if rank:
-            # models.py:223-230 (PlanesOptimizer(planes_rank_ratio=...), which train_nerf.py never passes): planes stored as two low-rank factors
-            raise NotImplementedError("low-rank planes (plane_rank / planes_rank_ratio, models.py:223-230) are not implemented")
         sd = getattr(self.scene_coupler, "should_downsample", None)
         if sd is not None and sd(plane_name, **kw):
             raise NotImplementedError("plane down-sampling ('HR_planes' in nerf.train.what: models.py:231-238) is not implemented; "
@@ -397,8 +495,9 @@ class TwoDimPlanesModel(nn.Module):
         if self.scene_coupler is not None:
             plane_name = self.scene_coupler.scene_with_saved_plane(plane_name, plane_not_scene=True)
         if super_resolve:
+            self._refresh_LR_planes([plane_name])
             return plane_name + "/SR", self.SR_model(plane_name)
-        return plane_name, self.planes_[plane_name]
+        return plane_name, self.raw_plane(plane_name)
 
     def channel_last_plane(self, dim_num):
         name, src = self._plane_source(dim_num)
@@ -453,8 +552,9 @@ class TwoDimPlanesModel(nn.Module):
         sr_dims = []
         for d, name in enumerate(names):
             if not (d < self.num_density_planes and self._should_SR(name)):
-                out[d] = self.planes_[saved[d]]
+                out[d] = self.raw_plane(saved[d])
             elif not self.SR_model.training:
+                self._refresh_LR_planes([saved[d]])
                 out[d] = self.SR_model(saved[d])                       # full plane, cached (models.py:277: ROI only in training)
             else:
                 sr_dims.append(d)
@@ -466,9 +566,23 @@ class TwoDimPlanesModel(nn.Module):
                 dims, dev_rois = self.training_rois(rays, normalized_points)
                 assert dims == sr_dims
                 rois = dev_rois.detach().reshape(len(dims), 4).cpu().tolist()          # ONE host read for all planes
+            self._refresh_LR_planes([saved[d] for d in sr_dims])
             for d, plane in zip(sr_dims, self.SR_model.forward_many([(saved[d], rois[k]) for k, d in enumerate(sr_dims)])):
                 out[d] = plane
         return out
+
+    def _refresh_LR_planes(self, names):
+        """a generated LR plane the SR model holds belongs to ONE version of its factors: before the SR network runs in training, hand it the
+        current one (the reference re-assigns after every PlanesOptimizer step through generated_planes.clear() + assign_LR_planes)"""
+        for n in names:
+            if self._rank_of(n) is None or n not in self.SR_model.LR_planes:
+                continue
+            held, src = self.SR_model.LR_planes[n], self.planes_[n]
+            need = torch.is_grad_enabled() and src.requires_grad and not self.detach_LR_planes
+            if not _generated_valid(held, src, self._rank_of(n), need):
+                self.SR_model.LR_planes[n] = self.raw_plane(n, detach=self.detach_LR_planes)
+                self.SR_model.SR_planes.pop(n, None)            # (super-resolved from the stale plane)
+                _PLANE_CACHE.pop(n + "/SR", None)
 
     def _generic_forward(self, x, coord_noise=None):
         """forward through the generic kernels (any geometry); in training mode with gradients for the planes and the decoder.
@@ -494,13 +608,14 @@ class TwoDimPlanesModel(nn.Module):
                     n = 2 * (x[:, :3] - box[0, :3].float()) / (box[1, :3] - box[0, :3]).float() - 1
                     planes = self.training_planes(None, normalized_points=n if coord_noise is None else n + coord_noise)
                 else:
-                    planes = [self.planes_[n] for n in names]
+                    planes = [self.raw_plane(n) for n in names]
                 return _GenericDecodeFn.apply(self, x, self.natural_blob(differentiable=True) if dec else None, coord_noise, *planes)
         if hasattr(self, "SR_model") and not self.skip_SR_:
             names = [get_plane_name(self.cur_id, d) for d in range(self.num_density_planes)]
             names = [n for n in names if self._should_SR(n)]
             if self.scene_coupler is not None:
                 names = [self.scene_coupler.scene_with_saved_plane(n, plane_not_scene=True) for n in names]
+            self._refresh_LR_planes(names)
             self.SR_model.super_resolve_many(names)
         planes = [self.channel_last_plane(d) for d in range(self.num_density_planes + 1)]
         planes, consts = self.scene_args(planes=planes, check_native=False)
@@ -523,6 +638,7 @@ class TwoDimPlanesModel(nn.Module):
                 names = [n for n in names if self._should_SR(n)]
                 if self.scene_coupler is not None:
                     names = [self.scene_coupler.scene_with_saved_plane(n, plane_not_scene=True) for n in names]
+                self._refresh_LR_planes(names)
                 self.SR_model.super_resolve_many(names)
             planes = [self.channel_last_plane(d) for d in range(self.num_density_planes + 1)]
         # box and projection matrices as host floats: read back once per version (a device-to-host copy drains the queue, and this runs
@@ -565,13 +681,15 @@ class TwoDimPlanesModel(nn.Module):
         # the matrices the matrix pipe multiplies: the hidden / feature layers' weights (heads and biases stay f32 vector arithmetic)
         mats = [p for n, p in self.named_parameters() if n.endswith(".weight") and (n.startswith("density_dec.") or n.startswith("rgb_dec."))]
         for t, limit in [(w, self.F16_WEIGHT_LIMIT) for w in mats] + [(p, self.F16_FEATURE_LIMIT) for p in planes]:
+            # (the tensor OBJECT is part of the entry: a regenerated low-rank plane or a new super-resolved plane is a fresh tensor -- version 0, the
+            #  same shape, usually at the address the allocator has just got back -- and must not inherit its predecessor's verdict)
             key = (t.data_ptr(), t._version, tuple(t.shape))
             hit = cache.get(key)
-            if hit is None:
+            if hit is None or hit[0]() is not t:
                 if len(cache) > 64:
                     cache.clear()
-                hit = cache[key] = bool(torch.isfinite(t).all()) and float(t.detach().abs().max()) < limit if t.numel() else True
-            ok = ok and hit
+                hit = cache[key] = (weakref.ref(t), bool(torch.isfinite(t).all()) and float(t.detach().abs().max()) < limit if t.numel() else True)
+            ok = ok and hit[1]
         return ok
 
     def render_arithmetic(self, planes, training):
@@ -601,9 +719,9 @@ class TwoDimPlanesModel(nn.Module):
         assert coord_noise is None, "a jitter for a forward that does not jitter (point_coords_noise == 0 or evaluation mode)"
         if self.training and torch.is_grad_enabled() and not (hasattr(self, "SR_model") and not self.skip_SR_):
             names = [get_plane_name(self.cur_id, d) for d in range(self.num_density_planes + 1)]
-            planes = [self.planes_[n] for n in names]
             dec = any(p.requires_grad for p in self.decoder_parameters())
-            if dec or any(p.requires_grad for p in planes):
+            if dec or any(self.planes_[n].requires_grad for n in names):
+                planes = [self.raw_plane(n) for n in names]
                 # run_network's differentiable model call (train_utils.py:15-64): gradients for the planes and the decoder
                 # models.py:393 `np.random.randint(len(self.density_dec))`: the reference picks an ensemble member on every training-mode
                 # forward.  With ensemble_size == 1 (the only supported size) the call returns 0 WITHOUT drawing from NumPy's stream (a

@@ -1221,8 +1221,93 @@ def _cumprod_bwd(ctx, g):
 cumprod_exclusive.register_autograd(_cumprod_bwd, setup_context=_cumprod_setup)
 
 
+# =====================================================================================================================================
+# low-rank feature planes (models.py:223-230 gen_plane; csrc/lowrank.hip)
+# =====================================================================================================================================
+def _lowrank_check(factors, ranks):
+    """-> [(C, R, r)] of factors [1,C,R,2r] / [C,R,2r]; the kernels' own argument checks (plane count, C, R, r >= 1) stay in the library"""
+    assert len(factors) == len(ranks), "one rank per factor tensor"
+    dims = []
+    for f, r in zip(factors, ranks):
+        assert f.dim() in (3, 4) and (f.dim() == 3 or f.shape[0] == 1), "a factor tensor is [1,C,R,2r]"
+        Cc, R, W = f.shape[-3:]
+        assert W == 2 * int(r), "factor width %d is not 2 x rank %d" % (W, int(r))
+        dims.append((int(Cc), int(R), int(r)))
+    assert len({d[0] for d in dims}) <= 1, "the planes of one call have the same number of channels"
+    return dims
+
+
+def _lowrank_args(dims, factors, planes, d_factors=None):
+    a = capi.LowrankPlanesArgs()
+    a.num_planes, a.channels = len(dims), dims[0][0] if dims else 0
+    for p, (_, R, r) in enumerate(dims[:capi.MAX_POSITION_PLANES]):      # (a longer list is refused by the library's status)
+        a.factors[p], a.planes[p] = factors[p].data_ptr(), planes[p].data_ptr()
+        a.d_factors[p] = d_factors[p].data_ptr() if d_factors is not None else None
+        a.res[p], a.rank[p] = R, r
+    return a
+
+
+@custom_op("nvsr::lowrank_planes", mutates_args=(), device_types="cuda")
+def lowrank_planes(factors: Sequence[Tensor], ranks: Sequence[int]) -> List[Tensor]:
+    """factors [1,C,R,2r] (U | V along the last axis) -> planes [1,C,R,R], plane[0,c] = U[0,c] @ V[0,c]^T, in torch.channels_last memory (the
+    layout the render kernels sample: models.is_native_layout); all planes in one launch"""
+    dims = _lowrank_check(factors, ranks)
+    fs = [capi.f32c(f) for f in factors]
+    outs = [torch.empty((1, Cc, R, R), dtype=torch.float32, device=f.device, memory_format=torch.channels_last) for f, (Cc, R, _) in zip(fs, dims)]
+    capi.call("nvsr_lowrank_planes", _lowrank_args(dims, fs, outs), capi.stream())
+    return outs
+
+
+@lowrank_planes.register_fake
+def _(factors, ranks):
+    return [torch.empty((1, Cc, R, R), dtype=torch.float32, device=f.device, memory_format=torch.channels_last)
+            for f, (Cc, R, _) in zip(factors, _lowrank_check(factors, ranks))]
+
+
+@custom_op("nvsr::lowrank_planes_backward", mutates_args=(), device_types="cuda")
+def lowrank_planes_backward(grads: Sequence[Tensor], factors: Sequence[Tensor], ranks: Sequence[int]) -> List[Tensor]:
+    """grads: dL/d plane [1,C,R,R] per plane (channels_last memory is read in place, anything else goes through plane_to_channel_last)
+    -> dL/d factors, shaped like the factors; fixed-order sums, no atomics"""
+    dims = _lowrank_check(factors, ranks)
+    assert len(grads) == len(factors)
+    fs = [capi.f32c(f) for f in factors]
+    gs = []
+    for g, (Cc, R, _) in zip(grads, dims):
+        assert tuple(g.shape[-3:]) == (Cc, R, R), "a plane gradient is [1,C,R,R]"
+        capi.require_cuda(g)
+        g4 = g.reshape(1, Cc, R, R) if g.dim() == 3 else g
+        hwc = g4.permute(0, 2, 3, 1)[0]
+        gs.append(hwc if (g4.dtype == torch.float32 and hwc.is_contiguous()) else plane_to_channel_last(g4))
+    outs = [torch.empty(f.shape, dtype=torch.float32, device=f.device) for f in fs]
+    capi.call("nvsr_lowrank_planes_backward", _lowrank_args(dims, fs, gs, outs), capi.stream())
+    return outs
+
+
+@lowrank_planes_backward.register_fake
+def _(grads, factors, ranks):
+    _lowrank_check(factors, ranks)
+    return [f.new_empty(f.shape, dtype=torch.float32) for f in factors]
+
+
+def _lowrank_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[0])
+    ctx.ranks = list(inputs[1])
+    ctx.shapes = [tuple(o.shape) for o in output]
+
+
+def _lowrank_bwd(ctx, grads):
+    # a plane nobody sampled has no gradient: its factor gets a zero gradient (one launch serves all planes)
+    factors = list(ctx.saved_tensors)
+    gs = [torch.zeros(s, dtype=torch.float32, device=f.device, memory_format=torch.channels_last) if g is None else g
+          for g, s, f in zip(grads, ctx.shapes, factors)]
+    return torch.ops.nvsr.lowrank_planes_backward(gs, factors, ctx.ranks), None
+
+
+lowrank_planes.register_autograd(_lowrank_bwd, setup_context=_lowrank_setup)
+
+
 FORWARD_OPS = ["plane_to_channel_last", "plane_from_channel_last", "pack_decoder", "coarse_z", "importance_resample", "triplane_decode",
-               "triplane_decode_generic", "ray_points",
+               "triplane_decode_generic", "ray_points", "lowrank_planes",
                "render_pass", "render_rays", "decode_rays", "composite", "composite_rays", "edsr", "planes_sr", "cumprod_exclusive"]
 
 

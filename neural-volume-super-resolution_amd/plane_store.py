@@ -12,6 +12,7 @@ import os
 import pickle
 import re
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -127,23 +128,66 @@ def load_plane_file(path, map_location="cpu"):
     return content
 
 
+def plane_rank_dict(scene_id_plane_resolution, planes_rank_ratio, num_density_planes):
+    """models.py:541: {plane name: ceil(planes_rank_ratio * R)} for every POSITION plane of every scene (the view-direction plane is never
+    low-rank); None when planes_rank_ratio is None.  scene_id_plane_resolution: {scene id: (position resolution, view-direction resolution)}"""
+    if planes_rank_ratio is None:
+        return None
+    return dict((get_plane_name(sc, d), int(np.ceil(planes_rank_ratio * res[0])))
+                for sc, res in scene_id_plane_resolution.items() for d in range(num_density_planes))
+
+
 def save_plane_file(path, planes, coords_normalization, opt_states=None):
-    """safe_saving (nerf_helpers.py:35-48): write <path>_temp, rotate the old file to _bckp, rename, drop the backup."""
+    """safe_saving (nerf_helpers.py:35-48): write <path>_temp, rotate the old file to _bckp, rename, drop the backup.  A low-rank plane is
+    stored as its factor tensor [1,C,R,2r], as it is (the reference's files hold the parameters, never a generated plane)."""
     params = planes if isinstance(planes, nn.ParameterDict) else nn.ParameterDict({k: nn.Parameter(v.detach().cpu()) for k, v in planes.items()})
     content = {"params": params, "opt_states": opt_states if opt_states is not None else [None for _ in params],
                "coords_normalization": coords_normalization}
     safe_saving(path, content, SUFFIX)
 
 
-def load_scene(models, planes_dir, scene_id, device="cuda", best=False, model_name="coarse"):
+def check_plane_ranks(planes, plane_rank):
+    """every plane named in plane_rank (models.py:541) must be a factor tensor [1,C,R,2r]: ValueError naming the plane otherwise.  The height is
+    the plane's resolution R (planes are square: models.py:228 multiplies [R,r] by [r,R]), so a DENSE [1,C,R,R] plane under a rank r != R / 2
+    is caught by its width; R itself is only known from the file."""
+    for name, r in (plane_rank or {}).items():
+        if name not in planes:
+            continue
+        shape = tuple(planes[name].shape)
+        if len(shape) != 4 or shape[0] != 1 or int(r) < 1 or shape[3] != 2 * int(r) or shape[2] < 1:
+            raise ValueError("plane %s: plane_rank %d needs a factor tensor [1,C,R,%d] (U | V), the file holds %s" % (name, int(r), 2 * int(r), list(shape)))
+
+
+def load_scene(models, planes_dir, scene_id, device="cuda", best=False, model_name="coarse", planes_rank_ratio=None, plane_rank=None):
     """What PlanesOptimizer.load_scene does for the hot path (models.py:589-610): read the scene's planes, put them on the
-    device, assign the SAME ParameterDict and box to every model, reset the SR caches.  Returns the loaded dict."""
+    device, assign the SAME ParameterDict and box to every model, reset the SR caches.  Returns the loaded dict.
+    Low-rank planes (models.py:541-548): plane_rank = {plane name: r}, or planes_rank_ratio (r = ceil(ratio R), R read off the scene id's
+    `_PlRes<R>_<Rv>`); every model gets the dict and ONE shared, empty `generated_planes`.  Without either, the models' own settings stay."""
+    if planes_rank_ratio is not None and plane_rank is not None:
+        raise ValueError("load_scene: give planes_rank_ratio or plane_rank, not both")
     content = load_plane_file(plane_file(planes_dir, scene_id, model_name, best))
     planes = nn.ParameterDict({k: nn.Parameter(v.detach().to(device)) for k, v in content["params"].items()})
     expect = [get_plane_name(scene_id, d) for d in range(4)]
     missing = [n for n in expect if n not in planes]
     if missing:
         raise KeyError("plane file of scene %s lacks %s" % (scene_id, missing))
+    if planes_rank_ratio is not None:
+        res = re.search(r"_PlRes(\d+)_(\d+)", scene_id)
+        if res is None:
+            raise ValueError("load_scene: planes_rank_ratio needs the plane resolution in the scene id (..._PlRes<R>_<Rv>), got %r" % scene_id)
+        plane_rank = plane_rank_dict({scene_id: (int(res.group(1)), int(res.group(2)))}, planes_rank_ratio,
+                                     getattr(models[0], "num_density_planes", 3))
+    if plane_rank is not None:
+        check_plane_ranks(planes, plane_rank)
+        for name, r in plane_rank.items():
+            if name in planes and planes_rank_ratio is not None and planes[name].shape[2] != int(res.group(1)):
+                raise ValueError("plane %s: the scene id says resolution %s, the file holds %s" % (name, res.group(1), list(planes[name].shape)))
+        generated = {}
+        for m in models:
+            m.plane_rank, m.generated_planes = plane_rank, generated
+    else:
+        for m in models:
+            check_plane_ranks(planes, m.__dict__.get("plane_rank"))
     box = torch.as_tensor(content["coords_normalization"], dtype=torch.float64)
     for m in models:
         m.planes_ = planes

@@ -256,6 +256,7 @@ def _side_stream(dev):
 
 
 def _planes_need_grad(model):
+    """does a plane of the current scene train?  (asked of the stored tensor: of a low-rank plane's factors, models.gen_plane)"""
     if not torch.is_grad_enabled() or getattr(model, "planes_", None) is None:
         return False
     names = [models.get_plane_name(model.cur_id, d) for d in range(model.num_density_planes + 1)]
@@ -343,7 +344,7 @@ def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, sc
                 planes_c, _ = model_coarse.scene_args(planes=[models.to_channel_last(p.detach()) for p in leaves_c])
         else:
             names = [models.get_plane_name(scene_id, d) for d in range(4)]
-            leaves = [top.planes_[n] for n in names]
+            leaves = [top.raw_plane(n) for n in names]          # (a low-rank plane: generated once, shared by both passes; models.gen_plane)
         leaves += [model_coarse.natural_blob(differentiable=True) if dec_c_grad else None,
                    model_fine.natural_blob(differentiable=True) if dec_f_grad else None]
         leaves += leaves_c

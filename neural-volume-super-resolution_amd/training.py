@@ -620,6 +620,8 @@ class GraphedTrainStep:
                 for k in (getattr(m, "planes_", None) or {}):
                     models._PLANE_CACHE.pop(k, None)
                     models._PLANE_CACHE.pop(k + "/SR", None)
+                if hasattr(m, "_generated_dict"):
+                    m._generated_dict().clear()              # (low-rank planes: the generation kernel belongs into the graph)
                 # (the host copy of the box / projection constants stays: reading it back is a device-to-host copy, illegal in a capture)
 
         side = torch.cuda.Stream(device=dev)
