@@ -137,7 +137,14 @@ uint32_t* nvsr_get_range_flag(void);
  * that only the colour decoder of a weightless sample produces no longer reaches the pixel (the pixel is then the correct finite value; a
  * density-side overflow still gives NaN and raises the range flag -- the density pass checks acc, the colour pass rgb).
  * NVSR_RENDER_ONE_PHASE=1 in the environment (read at every launch) keeps the fused kernel; it also runs when raw outputs are requested,
- * while the stream is being captured into a graph, or when the scratch below cannot be allocated.
+ * while the stream is being captured into a graph, when S >= 2^19 (a count has to fit into a packed entry, below) or when the scratch below
+ * cannot be allocated.
+ * Ray order of the colour pass.  Between the two launches live_order_kernel rewrites the N counts in place: inside every block of 4096
+ * consecutive rays (16 workgroups) the rays are stably sorted by the bin of their count, fullest bin first -- bin = ceil(count * 32 / S): one
+ * bin for the empty rays, 32 of equal width over 1..S -- and entry j of the block becomes (count << 12) | index of that ray in the block.
+ * The lane of the colour pass that owned ray j of the block owns the ray entry j names, so a workgroup's 256 rays have similar counts and few
+ * of its steps are padding; a ray's sums do not depend on the lane that holds them: same bits.  NVSR_COLOUR_ORDER=0 (read at every launch)
+ * makes every entry name its own slot: the grouping of the density pass, for an A/B.
  * Scratch: the lists take 2 N S floats + N ints (0.98 GB for the 800 x 800 x 192 fine pass).  They are NOT part of the caller's workspace
  * (nvsr_render_workspace_floats is unchanged): the library owns one buffer per (device, stream), allocated with hipMalloc at the first
  * two-phase launch on that stream and grown (never shrunk) when a larger pass arrives -- growing waits for the device.

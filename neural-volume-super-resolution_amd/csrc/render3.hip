@@ -17,6 +17,15 @@
 
 namespace nvsr {
 
+// The colour pass's ray order (live_order_kernel below): rays are regrouped inside blocks of ORDER_RAYS consecutive rays -- 16 workgroups, the
+// 128 x 32-pixel super-block of train_utils.patch_order -- by the bin of their live count, ORDER_BINS bins of equal width over 1..S and one
+// for the empty rays.  A packed entry of live_n is (count << ORDER_SHIFT) | index of the ray in its block.
+// ORDER_BINS = 32 is measured (profiles/colour_order_ab.txt): 8 and 16 bins leave more padding, an exact sort loses more of the
+// lanes' shared texels than its fewer steps win back.
+constexpr int ORDER_SHIFT = 12, ORDER_RAYS = 1 << ORDER_SHIFT, ORDER_BINS = 32;
+constexpr int ORDER_MAX_S = 1 << (31 - ORDER_SHIFT);      // a count has to fit above the index
+static_assert(ORDER_RAYS % RAYS2 == 0, "a block of the ray order is a whole number of workgroups");
+
 // =====================================================================================================================
 // The body of both kernels below (one instantiation per LIMBS; the kernels are thin shells so that the coarse and the fine pass are two
 // symbols in a rocprofv3 kernel trace -- a second template parameter on one kernel trips hipcc's host pass over the LDS-DMA builtins).
@@ -35,6 +44,12 @@ namespace nvsr {
 //       ring); a lane evaluates its ray's k-th live sample -- today's rgb layer 0 (same K-block order), rgb layers 1..3, rgb head -- and adds
 //       w sigmoid(raw) with the operations of composite_sample.  A lane past its own count re-evaluates its last entry and KEEPS its
 //       accumulators (a select, no + 0 x: padding cannot inject a NaN).
+//       WHICH ray a lane owns comes from live_n.  The density pass writes live_n[ray] = count; live_order_kernel, launched between the two
+//       passes, rewrites every block of ORDER_RAYS consecutive rays in place: entry j = (count << ORDER_SHIFT) | index of a ray in the block,
+//       the block's rays stably sorted by the bin of their count, fullest bin first.  The lane that used to own ray j of the block (slot j)
+//       owns the ray entry j names, for the whole launch: a workgroup's 256 rays then have similar counts and trip is close to each of them.
+//       A slot >= N is invalid as before (clamped ray, count 0, nothing written).  A ray's sums and the order of its additions do not depend
+//       on the lane that holds them, so the pixels do not change.  NVSR_COLOUR_ORDER=0 (read at every launch) makes every entry name its own slot.
 // Neither chain's K-order changes and dead samples contributed +0.0 to non-negative sums, so the pixels are bit for bit the fused pass's.
 template <int LZ>
 __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const float* __restrict__ packed, long N, int S,
@@ -78,6 +93,13 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
     const bool validX = rayX < N, validY = rayY < N;
     if (!validX) rayX = N - 1;
     if (!validY) rayY = N - 1;
+    int nX = 0, nY = 0;
+    if constexpr (COLOUR) {
+        // the slot names the ray (packed entries of live_order_kernel); an invalid slot keeps the clamped ray and count 0: it cannot lengthen trip
+        const long block_base = (long)(blk / (ORDER_RAYS / RAYS2)) * ORDER_RAYS;
+        if (validX) { const int e = live_n[base]; rayX = block_base + (e & (ORDER_RAYS - 1)); nX = e >> ORDER_SHIFT; }
+        if (validY) { const int e = live_n[base + 32]; rayY = block_base + (e & (ORDER_RAYS - 1)); nY = e >> ORDER_SHIFT; }
+    }
     constexpr int RAY3_FLOATS = L::RAY_FLOATS;
     float* rcX = ldsf + L::RAYS + (rs.wave * 64 + (lane0 & 31)) * RAY3_FLOATS;
     float* rcY = rcX + 32 * RAY3_FLOATS;
@@ -116,7 +138,7 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
     const float* lzY = COLOUR ? live_z + rayY * S : nullptr;
     const float* lwX = COLOUR ? live_w + rayX * S : nullptr;
     const float* lwY = COLOUR ? live_w + rayY * S : nullptr;
-    int nX = 0, nY = 0, trip = S;
+    int trip = S;
     float wX = 0.0f, wY = 0.0f, wXn = 0.0f, wYn = 0.0f;
     // entry k of a live list, clamped to the last valid one; an empty list gives the ray's near depth and weight 0 (never composited)
     auto live_depth = [&](const float* lzp, const float* rc, int n, int k) NVSR_INL -> float {
@@ -128,7 +150,6 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
     auto live_weight = [](const float* lwp, int n, int k) NVSR_INL -> float { return n == 0 ? 0.0f : lwp[k < n ? k : n - 1]; };
     if constexpr (COLOUR) {
         __shared__ int trip_s[NW2];                   // (the colour kernels' alone: the other phases declare nothing)
-        nX = live_n[rayX]; nY = live_n[rayY];
         int m = max(nX, nY);
 #pragma unroll
         for (int o = 16; o >= 1; o >>= 1) m = max(m, __shfl_xor(m, o));
@@ -694,6 +715,66 @@ __global__ __launch_bounds__(TPB2, 1) void render_pass3_colour_z_kernel(SceneDev
 #endif
 }
 
+// ---- the colour pass's ray order: live_n[ray] = count (density pass) -> packed entries, in place ---------------------------------------
+// One workgroup per block of ORDER_RAYS consecutive rays (the last one may be ragged: M rays).  A stable counting sort by bin, fullest bin
+// first: bin = ceil(count * bins / S) -- 0 for an empty ray, `bins` equal bins over 1..S -- so rays of one bin keep their (patch) order and
+// neighbouring pixels of similar count stay neighbouring lanes.  bins = 0 puts every ray into one bin: entry j names ray j (the identity,
+// NVSR_COLOUR_ORDER=0).  Wave w holds rays 256 w .. 256 w + 255 in four rounds of 64; a ray's rank is the number of rays in fuller bins + the
+// number of rays of its bin in earlier waves + earlier rounds + lower lanes: ballots, integer sums in a fixed order, no atomics.  The whole
+// block is read before any entry is written.
+constexpr int ORDER_TPB = 1024, ORDER_WAVES = ORDER_TPB / 64, ORDER_ROUNDS = ORDER_RAYS / ORDER_TPB;
+__global__ __launch_bounds__(ORDER_TPB) void live_order_kernel(int* __restrict__ live_n, long N, int S, int bins) {
+    __shared__ int cnt_s[(ORDER_BINS + 1) * ORDER_WAVES];      // [bin][wave]: rays of the bin in the wave, then in the waves before it
+    __shared__ int tot_s[ORDER_BINS + 1], start_s[ORDER_BINS + 1];      // rays of a bin; rays of all fuller bins
+    __shared__ int out_s[ORDER_RAYS];
+    const long block_base = (long)blockIdx.x * ORDER_RAYS;
+    const int M = (int)(N - block_base < ORDER_RAYS ? N - block_base : ORDER_RAYS);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int cnt[ORDER_ROUNDS], bin[ORDER_ROUNDS];
+#pragma unroll
+    for (int r = 0; r < ORDER_ROUNDS; ++r) {
+        const int i = wave * (64 * ORDER_ROUNDS) + r * 64 + lane;
+        cnt[r] = i < M ? live_n[block_base + i] : 0;
+        const int b = (int)(((unsigned)cnt[r] * (unsigned)bins + (unsigned)(S - 1)) / (unsigned)S);      // (count <= S < 2^19, bins <= ORDER_BINS)
+        bin[r] = i < M ? (b < bins ? b : bins) : -1;
+    }
+    for (int b = 0; b <= bins; ++b) {
+        int c = 0;
+#pragma unroll
+        for (int r = 0; r < ORDER_ROUNDS; ++r) c += __popcll(__ballot(bin[r] == b));
+        if (lane == 0) cnt_s[b * ORDER_WAVES + wave] = c;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x <= bins) {
+        int run = 0;
+        for (int w = 0; w < ORDER_WAVES; ++w) { const int c = cnt_s[threadIdx.x * ORDER_WAVES + w]; cnt_s[threadIdx.x * ORDER_WAVES + w] = run; run += c; }
+        tot_s[threadIdx.x] = run;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x <= bins) {
+        int run = 0;
+        for (int b = bins; b > (int)threadIdx.x; --b) run += tot_s[b];
+        start_s[threadIdx.x] = run;
+    }
+    __syncthreads();
+    for (int b = 0; b <= bins; ++b) {
+        int at = start_s[b] + cnt_s[b * ORDER_WAVES + wave];
+#pragma unroll
+        for (int r = 0; r < ORDER_ROUNDS; ++r) {
+            const unsigned long long m = __ballot(bin[r] == b);
+            if (bin[r] == b) out_s[at + __popcll(m & below)] = (cnt[r] << ORDER_SHIFT) | (wave * (64 * ORDER_ROUNDS) + r * 64 + lane);
+            at += __popcll(m);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < ORDER_ROUNDS; ++r) {
+        const int i = threadIdx.x + r * ORDER_TPB;
+        if (i < M) live_n[block_base + i] = out_s[i];
+    }
+}
+
 // ---- natural blob -> bf16 limb fragments (the tail of the packed blob) -----------------------------------------------------------
 template <int LIMBS>
 __global__ void pack_decoder_limbs_kernel(const float* __restrict__ nat, unsigned* __restrict__ out) {
@@ -792,52 +873,89 @@ extern "C" int nvsr_pack_decoder_limbs_launch(const float* natural, float* packe
 // Contract (include/nvsr.h): one host thread at a time enqueues render launches on a given (device, stream) -- the pointer is used after
 // the table's lock is dropped; the entry of a destroyed stream keeps its buffer until nvsr_release_render_scratch.
 namespace {
-struct LiveScratch { int device; hipStream_t stream; char* p; size_t bytes; };
+struct LiveScratch { int device; hipStream_t stream; char* p; size_t bytes; int* last_n; int64_t last_N; };      // last_*: the counts of the latest launch
 std::mutex g_live_mutex;
 std::vector<LiveScratch> g_live;
 
-char* live_scratch(hipStream_t stream, size_t bytes) {
+char* live_scratch(hipStream_t stream, size_t bytes, size_t counts_at, int64_t N, bool launch) {
     int device = 0;
     if (hipGetDevice(&device) != hipSuccess) return nullptr;
     std::lock_guard<std::mutex> lock(g_live_mutex);
     LiveScratch* e = nullptr;
     for (LiveScratch& c : g_live)
         if (c.device == device && c.stream == stream) e = &c;
-    if (!e) { g_live.push_back(LiveScratch{device, stream, nullptr, 0}); e = &g_live.back(); }
+    if (!e) { g_live.push_back(LiveScratch{device, stream, nullptr, 0, nullptr, 0}); e = &g_live.back(); }
     if (e->bytes < bytes) {
         if (e->p) (void)hipFree(e->p);
-        e->p = nullptr; e->bytes = 0;
+        e->p = nullptr; e->bytes = 0; e->last_n = nullptr; e->last_N = 0;
         void* p = nullptr;
         if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
         e->p = static_cast<char*>(p); e->bytes = bytes;
     }
+    if (launch) { e->last_n = reinterpret_cast<int*>(e->p + counts_at); e->last_N = N; }      // (a reservation leaves no counts behind)
     return e->p;
 }
 
 // the two-phase route is taken unless the caller wants the raw decoder outputs, NVSR_RENDER_ONE_PHASE=1 is set (the A/B handle), the stream
-// is being captured (the scratch cannot grow inside a capture) or the scratch cannot be had -- then the fused kernel runs: same pixels
+// is being captured (the scratch cannot grow inside a capture), a count would not fit into a packed entry of the ray order (S >= 2^19) or the
+// scratch cannot be had -- then the fused kernel runs: same pixels
 struct LiveLists { float* z; float* w; int* n; };
-bool two_phase_lists(const float* raw_out, int64_t N, int S, hipStream_t stream, LiveLists& out) {
-    if (raw_out) return false;
+bool two_phase_lists(const float* raw_out, int64_t N, int S, hipStream_t stream, LiveLists& out, bool launch = true) {
+    if (raw_out || S < 1 || S >= ORDER_MAX_S) return false;
     const char* e = getenv("NVSR_RENDER_ONE_PHASE");
     if (e && e[0] == '1') return false;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return false; }
     const size_t rows = (size_t)N * (size_t)S * sizeof(float);
-    char* p = live_scratch(stream, 2 * rows + (size_t)N * sizeof(int));
+    char* p = live_scratch(stream, 2 * rows + (size_t)N * sizeof(int), 2 * rows, N, launch);
     if (!p) return false;
     out.z = reinterpret_cast<float*>(p);
     out.w = reinterpret_cast<float*>(p + rows);
     out.n = reinterpret_cast<int*>(p + 2 * rows);
     return true;
 }
+
+// the colour pass's ray order, between the density and the colour launch: ORDER_BINS bins, or the identity with NVSR_COLOUR_ORDER=0 (the A/B
+// handle, read at every launch: the colour kernel then groups its rays as the density kernel does)
+int colour_order_bins() {
+    const char* e = getenv("NVSR_COLOUR_ORDER");
+    if (e && e[0] == '0') return 0;
+    return ORDER_BINS;
+}
+void launch_live_order(int* live_n, int64_t N, int S, int bins, hipStream_t stream) {
+    hipLaunchKernelGGL(live_order_kernel, dim3((unsigned)((N + ORDER_RAYS - 1) / ORDER_RAYS)), dim3(ORDER_TPB), 0, stream, live_n, (long)N, S, bins);
+}
 }  // namespace
+
+// test hooks of the ray order.  nvsr_internal_live_order: the ordering kernel alone, with the product's bins, on a caller's array of N counts
+// (each <= S), in place.  nvsr_internal_colour_order_bins: that number of bins.  nvsr_internal_copy_live_counts: the packed entries the
+// latest two-phase launch on `stream` left in the library's scratch -> dst (N ints, device or host memory; N must be that launch's).
+extern "C" int nvsr_internal_colour_order_bins(void) { return ORDER_BINS; }
+extern "C" int nvsr_internal_live_order(int* live_n, int64_t N, int S, nvsr_stream_t stream) {
+    if (!live_n) return NVSR_ERR_NULL;
+    if (N < 1 || S < 1 || S >= ORDER_MAX_S || (N + ORDER_RAYS - 1) / ORDER_RAYS > 0x7fffffff) return NVSR_ERR_SHAPE;
+    launch_live_order(live_n, N, S, ORDER_BINS, (hipStream_t)stream);
+    return NVSR_CHECK_LAUNCH();
+}
+extern "C" int nvsr_internal_copy_live_counts(int* dst, int64_t N, nvsr_stream_t stream) {
+    if (!dst) return NVSR_ERR_NULL;
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) return NVSR_ERR_LAUNCH;
+    const int* src = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(g_live_mutex);
+        for (const LiveScratch& c : g_live)
+            if (c.device == device && c.stream == (hipStream_t)stream && c.last_n && c.last_N == N) src = c.last_n;
+    }
+    if (!src) return NVSR_ERR_SHAPE;
+    return hipMemcpyAsync(dst, src, (size_t)N * sizeof(int), hipMemcpyDefault, (hipStream_t)stream) == hipSuccess ? NVSR_OK : NVSR_ERR_LAUNCH;
+}
 
 // a frame's driver knows its largest pass before the first launch: sizing the buffer for it up front keeps the growth (a device-wide
 // wait) out of the frame -- between the coarse and the fine pass (aux.hip).  Does nothing where the two-phase route would not be taken.
 extern "C" void nvsr_internal_reserve_render_scratch(int64_t N, int S, nvsr_stream_t stream) {
     LiveLists ll;
-    (void)two_phase_lists(nullptr, N, S, (hipStream_t)stream, ll);
+    (void)two_phase_lists(nullptr, N, S, (hipStream_t)stream, ll, false);
 }
 
 extern "C" int64_t nvsr_render_scratch_bytes(void) {
@@ -871,6 +989,7 @@ extern "C" int nvsr_render_pass3_launch(int limbs, const nvsr_scene* scene, cons
 #define NVSR_LAUNCH3_2P(LIMBS_)                                                                                                            \
         hipLaunchKernelGGL(render_pass3_density_kernel<LIMBS_>, dim3((unsigned)grid), dim3(TPB2), 0, (hipStream_t)stream, to_dev(scene),   \
                            packed_decoder, (long)N, S, rays, z, noise, disp, acc, weights, depth, nvsr_get_range_flag(), ll.z, ll.w, ll.n); \
+        launch_live_order(ll.n, N, S, colour_order_bins(), (hipStream_t)stream);                                                           \
         hipLaunchKernelGGL(render_pass3_colour_kernel<LIMBS_>, dim3((unsigned)grid), dim3(TPB2), 0, (hipStream_t)stream, to_dev(scene),    \
                            packed_decoder, (long)N, S, rays, white_bkgd, rgb, acc, nvsr_get_range_flag(), ll.z, ll.w, ll.n)
         if (limbs == 3) { NVSR_LAUNCH3_2P(3); } else { NVSR_LAUNCH3_2P(2); }
@@ -900,6 +1019,7 @@ extern "C" int nvsr_render_pass3_coarse_z_launch(int limbs, const nvsr_scene* sc
 #define NVSR_LAUNCH3_2P(LIMBS_)                                                                                                            \
         hipLaunchKernelGGL(render_pass3_density_z_kernel<LIMBS_>, dim3((unsigned)grid), dim3(TPB2), 0, (hipStream_t)stream, to_dev(scene), \
                            packed_decoder, (long)N, S, rays, lindisp, noise, disp, acc, weights, depth, nvsr_get_range_flag(), ll.z, ll.w, ll.n); \
+        launch_live_order(ll.n, N, S, colour_order_bins(), (hipStream_t)stream);                                                           \
         hipLaunchKernelGGL(render_pass3_colour_z_kernel<LIMBS_>, dim3((unsigned)grid), dim3(TPB2), 0, (hipStream_t)stream, to_dev(scene),  \
                            packed_decoder, (long)N, S, rays, lindisp, white_bkgd, rgb, acc, nvsr_get_range_flag(), ll.z, ll.w, ll.n)
         if (limbs == 3) { NVSR_LAUNCH3_2P(3); } else { NVSR_LAUNCH3_2P(2); }

@@ -8,6 +8,12 @@ E[max live count] / S over a 32-ray tile, a wave's 64 rays and a workgroup's 256
 workgroup: that last figure is the share of the colour work that is left), and how many tiles / tile pairs are dead as a whole at a sample index
 (what skipping whole tiles could save).
 
+Then, per pass, what the colour pass's ray order (live_order_kernel, csrc/render3.hip) can recover: the sum over workgroups of trip /
+(workgroups x S) for (a) the grouping of the density pass (256 consecutive rays), (b) the rays stably sorted by live count, descending, inside
+each block of 4096 consecutive rays and cut into groups of 256, (c) the same with the count quantised as the kernel does it -- bin =
+ceil(count x B / S): one bin for the empty rays and B bins of equal width over 1..S -- for B = 8, 16, 32; and (d) for each of them the sum
+of trips per XCD under the kernels' mapping of workgroups to XCDs (contiguous eighths of the workgroups), as max / mean over the eight.
+
     python tools/live_sample_stats.py [--res 800] [--plane-res 800] [--seed 0] > profiles/live_sample_stats.txt
 """
 import argparse
@@ -72,6 +78,31 @@ def main():
             n = N // group * group
             dead = ~live[:n].view(-1, group, S).any(1)
             print("  %-18s with every w == 0 at a sample   %.1f %%" % (label, 100 * float(dead.float().mean())))
+        print("  colour steps left, sum of trip / (workgroups x S), and the XCDs' sums of trips as max / mean:")
+        base = None
+        for label, bins in (("(a) groups of the density pass", 0), ("(b) sorted by count in blocks of 4096", -1), ("(c) 32 bins", 32),
+                            ("(c) 16 bins", 16), ("(c)  8 bins", 8)):
+            share, xcd = grouped_trips(cnt, S, bins)
+            base = share if base is None else base
+            print("    %-40s %.3f  (%.3f of (a))   XCD max / mean %.3f" % (label, share, share / base, xcd))
+
+
+def grouped_trips(cnt, S, bins, block=4096, group=256):
+    """(sum of trip over the workgroups / (workgroups x S), max / mean of the eight XCDs' sums of trips) when the rays of every `block` are
+    stably sorted by bin, fullest first: bins = 0 one bin (the order as it is), -1 the count itself, else ceil(count x bins / S)"""
+    N = cnt.numel()
+    b = torch.zeros_like(cnt) if bins == 0 else cnt if bins < 0 else torch.clamp((cnt * bins + S - 1) // S, max=bins)
+    key = (torch.arange(N, device=cnt.device) // block) * (S + 2) + (S + 1 - b)
+    c = cnt[torch.sort(key, stable=True).indices]
+    G = (N + group - 1) // group
+    c = torch.cat([c, c.new_zeros(G * group - N)])
+    trips = c.view(G, group).max(1).values.double()
+    per, rem = G // 8, G % 8
+    sums = []
+    for x in range(8):
+        lo = x * per + min(x, rem)
+        sums.append(float(trips[lo:lo + per + (1 if x < rem else 0)].sum()))
+    return float(trips.sum()) / (G * S), max(sums) / (sum(sums) / 8)
 
 
 if __name__ == "__main__":
