@@ -156,9 +156,24 @@ uint32_t* nvsr_get_range_flag(void);
  * run: a caller, or a test, can tell that the two-phase route was taken).
  * Contract: the buffers are keyed by the stream handle and never pruned -- the entry of a destroyed stream keeps its memory (torch's
  * allocator does not see it) until nvsr_release_render_scratch; and only one host thread at a time may enqueue render launches on a given
- * (device, stream): a second thread growing that entry would free the buffer under the first one's launch. */
+ * (device, stream): a second thread growing that entry would free the buffer under the first one's launch.
+ * Order of dispatch of the colour pass.  A colour workgroup runs as many steps as its longest list, between none and S, and workgroups start
+ * in blockIdx order, workgroup b on XCD b % 8.  live_order_kernel also writes group_trip[g], the largest count among entries 256 g .. 256 g +
+ * 255 (G = ceil(N / 256) groups; a ragged last group counts what it has), and group_order_kernel (one workgroup, a stable counting sort over
+ * 0..S) writes group_slot[r] = the group that workgroup r runs: the groups heaviest first, so rank r lands on XCD r % 8.  A run of groups of
+ * equal trip is dealt in pieces, not one by one: the ranks of the run that share an XCD take consecutive groups (the contiguous-eighths formula
+ * inside the run; neighbouring groups share texels in their XCD's L2), so a frame whose trips are all equal keeps the density kernels' mapping.
+ * The density and fused kernels keep their mapping (XCD x runs the x-th contiguous eighth of the ray blocks); group_slot holds that same
+ * mapping with NVSR_COLOUR_GROUP_ORDER=0 (read at every launch, for an A/B) and beyond what the one workgroup sorts: G > 4096 or S > 511.
+ * A ray's sums do not depend on the workgroup that holds them: same bits.  The 2 G ints are kept in a buffer of their own beside the lists'
+ * (same owner, growth and release; 20 KB at the benchmark size); nvsr_render_scratch_bytes counts the lists' buffer alone. */
 int nvsr_release_render_scratch(void);
 int64_t nvsr_render_scratch_bytes(void);
+/* Internal hooks of that order (tests and tools; not part of the stable interface).  nvsr_internal_group_order: group_order_kernel alone on
+ * G trips (device memory, each 0..S) -> out[G], under the product's handle.  nvsr_internal_copy_group_order: what the latest two-phase
+ * launch on `stream` left -> dst (device or host memory), 2 G ints: group_slot[G], then group_trip[G]; G must be that launch's. */
+int nvsr_internal_group_order(const int* trips, int64_t G, int S, int* out, nvsr_stream_t stream);
+int nvsr_internal_copy_group_order(int* dst, int64_t G, nvsr_stream_t stream);
 /* The arithmetic primitive alone (test hook, one wavefront): Y[32][32] = W[32][K] X[K][32] (row-major f32, K a multiple of 16) with the
  * operands split and multiplied exactly as the kernels of `arithmetic` do it (NVSR_ARITH_F32 | _BF16X3 | _F16X2, incl. the static scales of
  * F16X2) -- lets a test put chosen mantissas / magnitudes through the products that replace models.py:381-421's nn.Linear GEMMs. */

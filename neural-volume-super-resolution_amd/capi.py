@@ -172,6 +172,8 @@ _PROTOS_OPTIONAL = {   # feature-plane super-resolution (csrc/sr.hip)
     "nvsr_render_rays_shared_arith": ([C.POINTER(Scene), _vp, _i64, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp], _i),
     "nvsr_release_render_scratch": ([], _i),
     "nvsr_render_scratch_bytes": ([], _i64),
+    "nvsr_internal_group_order": ([_vp, _i64, _i, _vp, _vp], _i),
+    "nvsr_internal_copy_group_order": ([_vp, _i64, _vp], _i),
     "nvsr_set_sr_plane_interp": ([_i], _i),
     "nvsr_get_sr_plane_interp": ([], _i),
     "nvsr_set_sr_align_corners": ([_i], _i),

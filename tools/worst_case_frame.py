@@ -1,7 +1,7 @@
 """Frame time of the render pass's worst case for the two-phase route: a scene whose every weight is positive (both density heads: weight 0,
 bias +0.05, so every live list holds all S samples and the colour pass saves nothing), benchmark size (800 x 800, 64 + 128 samples, planes
 800^2), whole frames through train_utils.eval_nerf, wall clock around a synchronised frame, no profiler.  Run from the root of the tree to be
-timed; the routes are chosen by the environment (NVSR_RENDER_ONE_PHASE, NVSR_COLOUR_ORDER).  Needs the GPU.
+timed; the routes are chosen by the environment (NVSR_RENDER_ONE_PHASE, NVSR_COLOUR_ORDER, NVSR_COLOUR_GROUP_ORDER).  Needs the GPU.
 
     python tools/worst_case_frame.py [--frames 5] [--warmup 2]
 """
