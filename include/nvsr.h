@@ -139,7 +139,7 @@ uint32_t* nvsr_get_range_flag(void);
  * NVSR_RENDER_ONE_PHASE=1 in the environment (read at every launch) keeps the fused kernel; it also runs when raw outputs are requested,
  * while the stream is being captured into a graph, when S >= 2^19 (a count has to fit into a packed entry, below) or when the scratch below
  * cannot be allocated.
- * Ray order of the colour pass.  Between the two launches live_order_kernel rewrites the N counts in place: inside every block of 4096
+ * Ray order of the colour pass (csrc/colour_order.hip, like the order of dispatch and the scratch below).  Between the two launches live_order_kernel rewrites the N counts in place: inside every block of 4096
  * consecutive rays (16 workgroups) the rays are stably sorted by the bin of their count, fullest bin first -- bin = ceil(count * 32 / S): one
  * bin for the empty rays, 32 of equal width over 1..S -- and entry j of the block becomes (count << 12) | index of that ray in the block.
  * The lane of the colour pass that owned ray j of the block owns the ray entry j names, so a workgroup's 256 rays have similar counts and few
@@ -174,6 +174,12 @@ int64_t nvsr_render_scratch_bytes(void);
  * launch on `stream` left -> dst (device or host memory), 2 G ints: group_slot[G], then group_trip[G]; G must be that launch's. */
 int nvsr_internal_group_order(const int* trips, int64_t G, int S, int* out, nvsr_stream_t stream);
 int nvsr_internal_copy_group_order(int* dst, int64_t G, nvsr_stream_t stream);
+/* Internal hooks of the ray order.  nvsr_internal_live_order: live_order_kernel alone, with the product's bins, on a caller's array of N counts
+ * (device memory, each <= S), in place.  nvsr_internal_colour_order_bins: that number of bins.  nvsr_internal_copy_live_counts: the packed
+ * entries the latest two-phase launch on `stream` left in the library's scratch -> dst (N ints, device or host memory; N must be that launch's). */
+int nvsr_internal_live_order(int* live_n, int64_t N, int S, nvsr_stream_t stream);
+int nvsr_internal_colour_order_bins(void);
+int nvsr_internal_copy_live_counts(int* dst, int64_t N, nvsr_stream_t stream);
 /* The arithmetic primitive alone (test hook, one wavefront): Y[32][32] = W[32][K] X[K][32] (row-major f32, K a multiple of 16) with the
  * operands split and multiplied exactly as the kernels of `arithmetic` do it (NVSR_ARITH_F32 | _BF16X3 | _F16X2, incl. the static scales of
  * F16X2) -- lets a test put chosen mantissas / magnitudes through the products that replace models.py:381-421's nn.Linear GEMMs. */

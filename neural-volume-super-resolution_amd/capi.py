@@ -174,6 +174,9 @@ _PROTOS_OPTIONAL = {   # feature-plane super-resolution (csrc/sr.hip)
     "nvsr_render_scratch_bytes": ([], _i64),
     "nvsr_internal_group_order": ([_vp, _i64, _i, _vp, _vp], _i),
     "nvsr_internal_copy_group_order": ([_vp, _i64, _vp], _i),
+    "nvsr_internal_live_order": ([_vp, _i64, _i, _vp], _i),
+    "nvsr_internal_colour_order_bins": ([], _i),
+    "nvsr_internal_copy_live_counts": ([_vp, _i64, _vp], _i),
     "nvsr_set_sr_plane_interp": ([_i], _i),
     "nvsr_get_sr_plane_interp": ([], _i),
     "nvsr_set_sr_align_corners": ([_i], _i),
@@ -224,6 +227,14 @@ _PROTOS_OPTIONAL = {   # feature-plane super-resolution (csrc/sr.hip)
     # low-rank feature planes (csrc/lowrank.hip)
     "nvsr_lowrank_planes": ([LowrankPlanesArgs, _vp], _i),
     "nvsr_lowrank_planes_backward": ([LowrankPlanesArgs, _vp], _i),
+}
+
+# launch symbols behind the entry points above (csrc/nvsr_internal.h) that tests and tools call directly: bound like the others, but no part
+# of include/nvsr.h and so not of exported_symbols()
+_PROTOS_LAUNCH = {
+    "nvsr_render_pass3_coarse_z_launch": ([_i, C.POINTER(Scene), _vp, _i64, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i),
+    "nvsr_decode_rays_limb_launch": ([_i, C.POINTER(Scene), _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp], _i),
+    "nvsr_decode_rays_pair_launch": ([C.POINTER(Scene), _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp], _i),
 }
 
 _lib = None
@@ -338,7 +349,7 @@ def lib():
             raise NvsrError("%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                             "(hipcc --offload-arch=gfx950); there is no CPU fallback" % LIB_PATH)
         _lib = C.CDLL(LIB_PATH)
-        for name, (args, res) in {**_PROTOS, **_PROTOS_OPTIONAL}.items():
+        for name, (args, res) in {**_PROTOS, **_PROTOS_OPTIONAL, **_PROTOS_LAUNCH}.items():
             fn = getattr(_lib, name)
             fn.argtypes, fn.restype = args, res
         for var, get in (("NVSR_DECODER_ARITHMETIC", _lib.nvsr_get_decoder_arithmetic), ("NVSR_CONV_ARITHMETIC", _lib.nvsr_get_conv_arithmetic)):

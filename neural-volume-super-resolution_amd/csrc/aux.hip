@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include "nvsr_common.h"
 #include "wave_scan.h"
+#include "nvsr_internal.h"
 
 namespace nvsr {
 
@@ -905,11 +906,8 @@ int64_t nvsr_render_workspace_floats(int64_t N, int Nc, int Nf) {
     return base + (N < NVSR_FUSED_MIN_RAYS ? 4 * N * (int64_t)(Nc + (Nf > 0 ? Nf : 0)) : 0);   // + raw [N,S,4] for the un-fused path
 }
 
-extern "C" int nvsr_internal_resolve_decoder_arith(int arithmetic);      // render.hip
-extern "C" void nvsr_internal_reserve_render_scratch(int64_t N, int S, nvsr_stream_t stream);      // render3.hip
-extern "C" int nvsr_render_pass3_coarse_z_launch(int limbs, const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays,
-                                                 int lindisp, const float* noise, int white_bkgd, float* rgb, float* disp, float* acc,
-                                                 float* weights, float* depth, float* raw_out, nvsr_stream_t stream);
+// does a render pass of this call run on the fused limb kernels (render3.hip)?  `arith`: nvsr_internal_resolve_decoder_arith's answer
+static bool fused_limb_passes(int64_t N, int arith) { return N >= NVSR_FUSED_MIN_RAYS && arith > 0 && !getenv("NVSR_RENDER_V1"); }
 
 static int render_one_pass(const nvsr_scene* scene, const float* packed, int64_t N, int S, const float* rays, const float* z,
                            const float* noise, int white, float* rgb, float* disp, float* acc, float* weights, float* raw_ws,
@@ -948,16 +946,12 @@ int nvsr_render_rays_arith(const nvsr_scene* scene, const float* packed_coarse, 
     // Inference frames (no stratified jitter) on the fused limb passes: the coarse depths are a function of (near, far, s) -- the coarse
     // pass and the resampler compute them in registers, the [N,Nc] depth tensor (164 MB at 800 x 800 x 64) is never written or read
     const int arith = nvsr_internal_resolve_decoder_arith(arithmetic);
-    const bool in_kernel_z = !t_rand && Nf > 0 && N >= NVSR_FUSED_MIN_RAYS && arith > 0 && !getenv("NVSR_RENDER_V1") && !getenv("NVSR_STORE_COARSE_Z");
+    const bool in_kernel_z = !t_rand && Nf > 0 && fused_limb_passes(N, arith) && !getenv("NVSR_STORE_COARSE_Z");
     // both passes on the fused limb kernels: the live-list scratch of the two-phase route is sized for the larger (fine) pass once
-    if (Nf > 0 && N >= NVSR_FUSED_MIN_RAYS && arith > 0 && !getenv("NVSR_RENDER_V1")) nvsr_internal_reserve_render_scratch(N, Nc + Nf, stream);
+    if (Nf > 0 && fused_limb_passes(N, arith)) nvsr_internal_reserve_render_scratch(N, Nc + Nf, stream);
     if (in_kernel_z) {
         if (!scene || !packed_coarse || !rays || !rgb_c || !disp_c || !acc_c) return NVSR_ERR_NULL;
-        for (int d = 0; d < 4; ++d) {
-            if (!scene->planes[d]) return NVSR_ERR_NULL;
-            if (!aligned16(scene->planes[d])) return NVSR_ERR_ALIGN;
-            if (scene->ph[d] < 1 || scene->pw[d] < 1 || (int64_t)scene->ph[d] * scene->pw[d] * NVSR_PLANE_CHANNELS >= (int64_t)1 << 31) return NVSR_ERR_SHAPE;
-        }
+        if ((e = check_scene(scene))) return e;
         if (!aligned16(packed_coarse)) return NVSR_ERR_ALIGN;
         e = nvsr_render_pass3_coarse_z_launch(arith, scene, packed_coarse, N, Nc, rays, lindisp, noise_coarse, white_bkgd, rgb_c, disp_c, acc_c, w_c,
                                               nullptr, nullptr, stream);
@@ -979,8 +973,8 @@ int nvsr_render_rays_arith(const nvsr_scene* scene, const float* packed_coarse, 
 // ---- one decoder for both passes (models.fine.type == 'use_same') ----------------------------------------------------------------------
 // does this call take the shared path?  (a frame without stratified jitter on the fused limb passes -- the conditions of in_kernel_z above)
 static bool shared_path(int64_t N, int Nf, const float* t_rand, int arithmetic) {
-    return !t_rand && Nf > 0 && N >= NVSR_FUSED_MIN_RAYS && nvsr_internal_resolve_decoder_arith(arithmetic) > 0 && !getenv("NVSR_RENDER_V1") &&
-           !getenv("NVSR_STORE_COARSE_Z") && !getenv("NVSR_NO_SHARED_DECODER");
+    return !t_rand && Nf > 0 && fused_limb_passes(N, nvsr_internal_resolve_decoder_arith(arithmetic)) && !getenv("NVSR_STORE_COARSE_Z") &&
+           !getenv("NVSR_NO_SHARED_DECODER");
 }
 int64_t nvsr_render_shared_workspace_floats(int64_t N, int Nc, int Nf) {
     // w_c [N,Nc], z_new [N,Nf], z_m [N,Nc+Nf], raw_c [N,Nc,4], raw_new [N,Nf,4], raw_m [N,Nc+Nf,4] -- and never less than the two-decoder path
@@ -999,11 +993,7 @@ int nvsr_render_rays_shared_arith(const nvsr_scene* scene, const float* packed, 
     if (!workspace || !scene || !packed || !rays || !rgb_c || !disp_c || !acc_c || !rgb_f || !disp_f || !acc_f) return NVSR_ERR_NULL;
     if (!aligned16(workspace) || !aligned16(packed)) return NVSR_ERR_ALIGN;
     if (Nc < 3 || Nc > 256 || Nf > 256) return NVSR_ERR_SHAPE;
-    for (int d = 0; d < 4; ++d) {
-        if (!scene->planes[d]) return NVSR_ERR_NULL;
-        if (!aligned16(scene->planes[d])) return NVSR_ERR_ALIGN;
-        if (scene->ph[d] < 1 || scene->pw[d] < 1 || (int64_t)scene->ph[d] * scene->pw[d] * NVSR_PLANE_CHANNELS >= (int64_t)1 << 31) return NVSR_ERR_SHAPE;
-    }
+    if (int e = check_scene(scene)) return e;
     const int64_t S = (int64_t)Nc + Nf;
     float* w_c = workspace;
     float* z_new = w_c + round4(N * (int64_t)Nc);

@@ -1,0 +1,27 @@
+// The two-phase route's lists and the colour pass's orders (colour_order.hip), as far as the render kernels and their launchers
+// (render3.hip) need them.  Not part of the public ABI.
+#pragma once
+#include "tile_pair.h"
+
+namespace nvsr {
+
+// The colour pass's ray order (live_order_kernel, colour_order.hip): rays are regrouped inside blocks of ORDER_RAYS consecutive rays -- 16 workgroups, the
+// 128 x 32-pixel super-block of train_utils.patch_order -- by the bin of their live count, ORDER_BINS bins of equal width over 1..S and one
+// for the empty rays.  A packed entry of live_n is (count << ORDER_SHIFT) | index of the ray in its block.
+// ORDER_BINS = 32 is measured (profiles/colour_order_ab.txt): 8 and 16 bins leave more padding, an exact sort loses more of the
+// lanes' shared texels than its fewer steps win back.
+constexpr int ORDER_SHIFT = 12, ORDER_RAYS = 1 << ORDER_SHIFT, ORDER_BINS = 32;
+constexpr int ORDER_MAX_S = 1 << (31 - ORDER_SHIFT);      // a count has to fit above the index
+static_assert(ORDER_RAYS % RAYS2 == 0, "a block of the ray order is a whole number of workgroups");
+
+// the lists of one two-phase launch, in the library's scratch: z, w [N, S] rows, n [N]; slot, trip: [G] each, G = ceil(N / RAYS2)
+struct LiveLists { float* z; float* w; int* n; int* slot; int* trip; };
+
+// The two-phase route is taken unless the caller wants the raw decoder outputs, NVSR_RENDER_ONE_PHASE=1 is set (the A/B handle), the stream
+// is being captured (the scratch cannot grow inside a capture), a count would not fit into a packed entry of the ray order (S >= 2^19) or the
+// scratch cannot be had -- then the fused kernel runs: same pixels.  launch = false sizes the scratch and leaves no launch behind.
+bool two_phase_lists(const float* raw_out, int64_t N, int S, hipStream_t stream, LiveLists& out, bool launch = true);
+// the ray order, then the order of dispatch: between the density and the colour launch
+void launch_colour_order(const LiveLists& ll, int64_t N, int S, hipStream_t stream);
+
+}  // namespace nvsr

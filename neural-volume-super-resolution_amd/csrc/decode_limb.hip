@@ -13,6 +13,7 @@
 #include <type_traits>
 
 #include "limb_core.h"
+#include "nvsr_internal.h"
 
 #ifndef L3_REC_LATE
 #define L3_REC_LATE 0   // recording forward on f16 limbs, experiment (round 6): 1 = a layer's record rows are stored inside the NEXT layer's first block, two

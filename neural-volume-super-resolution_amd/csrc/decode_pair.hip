@@ -20,6 +20,7 @@
 #include <utility>
 
 #include "pair_core.h"
+#include "nvsr_internal.h"
 
 #ifndef DP_ABLATE
 #define DP_ABLATE 0    // timing experiments (wrong results): 1 no gates, 2 no exposed view gather

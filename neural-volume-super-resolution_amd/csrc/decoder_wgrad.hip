@@ -12,6 +12,7 @@
 #include <cstdlib>
 
 #include "limb_core.h"
+#include "nvsr_internal.h"
 
 namespace nvsr {
 
@@ -336,7 +337,6 @@ __global__ __launch_bounds__(64 * HW_WAVES) void head_wgrad_kernel(const float* 
 
 using namespace nvsr;
 
-extern "C" int nvsr_internal_resolve_decoder_arith(int arithmetic);      // render.hip
 extern "C" int nvsr_decoder_weight_grad(int64_t N, int S, const float* record, float* grad_natural, nvsr_stream_t stream) {
     return nvsr_decoder_weight_grad_arith(N, S, record, grad_natural, NVSR_ARITH_INHERIT, stream);
 }

@@ -1,0 +1,46 @@
+// Every extern "C" symbol that crosses files inside the library and is not declared in include/nvsr.h, in one place: the file that defines a
+// symbol and every file that calls it include this header, so the compiler checks each definition against the prototype its callers see
+// (the symbols are extern "C": a prototype that drifted would still link and pass wrong arguments at run time).  Not part of the public ABI;
+// tests and tools that call a *_launch symbol directly take its prototype from capi.py.
+#pragma once
+#include "nvsr_common.h"
+
+extern "C" {
+// the fused render pass, second and third generation (render2.hip, render3.hip); coarse_z: the coarse pass with its depths computed in the kernel
+int nvsr_render_pass2_launch(const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays, const float* z, const float* noise, int white_bkgd,
+                             float* rgb, float* disp, float* acc, float* weights, float* depth, float* raw_out, nvsr_stream_t stream);
+int nvsr_render_pass3_launch(int limbs, const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays, const float* z, const float* noise,
+                             int white_bkgd, float* rgb, float* disp, float* acc, float* weights, float* depth, float* raw_out, nvsr_stream_t stream);
+int nvsr_render_pass3_coarse_z_launch(int limbs, const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays, int lindisp, const float* noise,
+                                      int white_bkgd, float* rgb, float* disp, float* acc, float* weights, float* depth, float* raw_out, nvsr_stream_t stream);
+// the limb fragments behind the f32 ones of the packed blobs (render3.hip, render_bwd_limb.hip)
+int nvsr_pack_decoder_limbs_launch(const float* natural, float* packed, nvsr_stream_t stream);
+int nvsr_pack_decoder_bwd_limbs_launch(const float* natural, float* packed_bwd, nvsr_stream_t stream);
+// the training forward on the limb matrix pipe (decode_limb.hip, decode_pair.hip) and its gate-driven backward (render_bwd_limb.hip)
+int nvsr_decode_rays_limb_launch(int limbs, const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays, const float* z, float* raw,
+                                 uint32_t* gates, float* record, nvsr_stream_t stream);
+int nvsr_decode_rays_pair_launch(const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays, const float* z, float* raw, uint32_t* gates,
+                                 nvsr_stream_t stream);
+int nvsr_render_pass_backward_gates_limb_launch(int limbs, const nvsr_scene* scene, const float* packed_decoder, const float* packed_bwd, int64_t N, int S, const float* rays,
+                                                const float* z, const float* g_raw, const uint32_t* gates, float* const* grad_planes, float* view_ws, float* record,
+                                                nvsr_stream_t stream);
+// render.hip: NVSR_ARITH_INHERIT -> the process default, anything that is not a mode -> -1; the mode named by an environment variable (dflt if unset)
+int nvsr_internal_resolve_decoder_arith(int arithmetic);
+int nvsr_internal_parse_arith_env(const char* name, int dflt);
+// colour_order.hip: size the two-phase route's scratch for a pass of N rays x S samples before a frame's first launch
+void nvsr_internal_reserve_render_scratch(int64_t N, int S, nvsr_stream_t stream);
+}  // extern "C"
+
+namespace nvsr {
+
+inline int check_scene(const nvsr_scene* s) {
+    if (!s) return NVSR_ERR_NULL;
+    for (int d = 0; d < 4; ++d) {
+        if (!s->planes[d]) return NVSR_ERR_NULL;
+        if (!aligned16(s->planes[d])) return NVSR_ERR_ALIGN;
+        if (s->ph[d] < 1 || s->pw[d] < 1 || (int64_t)s->ph[d] * s->pw[d] * NVSR_PLANE_CHANNELS >= (int64_t)1 << 31) return NVSR_ERR_SHAPE;
+    }
+    return NVSR_OK;
+}
+
+}  // namespace nvsr

@@ -21,6 +21,7 @@
 #include <cstring>
 
 #include "decode_core.h"
+#include "nvsr_internal.h"
 
 namespace nvsr {
 
@@ -225,18 +226,8 @@ __global__ void pack_decoder_kernel(const float* __restrict__ nat, float* __rest
 
 using namespace nvsr;
 
-extern "C" int nvsr_render_pass2_launch(const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays,
-                                        const float* z, const float* noise, int white_bkgd, float* rgb, float* disp, float* acc,
-                                        float* weights, float* depth, float* raw_out, nvsr_stream_t stream);
-extern "C" int nvsr_render_pass3_launch(int limbs, const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays,
-                                        const float* z, const float* noise, int white_bkgd, float* rgb, float* disp, float* acc,
-                                        float* weights, float* depth, float* raw_out, nvsr_stream_t stream);
-extern "C" int nvsr_pack_decoder_limbs_launch(const float* natural, float* packed, nvsr_stream_t stream);
-extern "C" int nvsr_decode_rays_limb_launch(int limbs, const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays,
-                                            const float* z, float* raw, uint32_t* gates, float* record, nvsr_stream_t stream);
-
-extern "C" int nvsr_decode_rays_pair_launch(const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays, const float* z,
-                                            float* raw, uint32_t* gates, nvsr_stream_t stream);
+// a lone render pass of this many rays runs on the two-tiles-per-wave kernels; deliberately NOT NVSR_FUSED_MIN_RAYS (where a frame stops tiling over samples)
+constexpr int64_t PER_RAY_MIN_RAYS = 16384;
 
 // arithmetic of the fused render pass (process-wide): -1 = not yet read from the environment
 static int g_decoder_arithmetic = -1;
@@ -246,7 +237,7 @@ extern "C" {
 // "f32" | "bf16x3" | "f16x2" -> the mode; unset or empty -> dflt; anything else -> NVSR_ARITH_INVALID (said once on stderr): every call that
 // inherits the process default then fails with NVSR_ERR_SHAPE instead of silently running the default (round 3 renamed bf16x2 -> f16x2:
 // a stale NVSR_DECODER_ARITHMETIC=bf16x2 must not quietly select another arithmetic)
-extern "C" int nvsr_internal_parse_arith_env(const char* name, int dflt) {
+int nvsr_internal_parse_arith_env(const char* name, int dflt) {
     const char* e = getenv(name);
     if (!e || !*e) return dflt;
     if (!strcmp(e, "f32")) return NVSR_ARITH_F32;
@@ -284,16 +275,6 @@ int nvsr_pack_decoder(const float* natural, float* packed, nvsr_stream_t stream)
     hipLaunchKernelGGL(pack_decoder_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, natural, packed);
     if (hipGetLastError() != hipSuccess) return NVSR_ERR_LAUNCH;
     return nvsr_pack_decoder_limbs_launch(natural, packed, stream);
-}
-
-static int check_scene(const nvsr_scene* s) {
-    if (!s) return NVSR_ERR_NULL;
-    for (int d = 0; d < 4; ++d) {
-        if (!s->planes[d]) return NVSR_ERR_NULL;
-        if (!aligned16(s->planes[d])) return NVSR_ERR_ALIGN;
-        if (s->ph[d] < 1 || s->pw[d] < 1 || (int64_t)s->ph[d] * s->pw[d] * NVSR_PLANE_CHANNELS >= (int64_t)1 << 31) return NVSR_ERR_SHAPE;
-    }
-    return NVSR_OK;
 }
 
 int nvsr_triplane_decode(const nvsr_scene* scene, const float* packed_decoder, int64_t P, const float* x, float* out,
@@ -383,7 +364,7 @@ int nvsr_render_pass_arith(const nvsr_scene* scene, const float* packed_decoder,
     if (!aligned16(packed_decoder) || (raw_out && !aligned16(raw_out))) return NVSR_ERR_ALIGN;
     if (N < 0 || S < 1 || S > 4096) return NVSR_ERR_SHAPE;
     if (N == 0) return NVSR_OK;
-    if (N >= 16384 && !getenv("NVSR_RENDER_V1")) {   // two-tiles-per-wave kernels; NVSR_RENDER_V1=1 selects the first-generation kernel
+    if (N >= PER_RAY_MIN_RAYS && !getenv("NVSR_RENDER_V1")) {   // two-tiles-per-wave kernels; NVSR_RENDER_V1=1 selects the first-generation kernel
         if (arith != NVSR_ARITH_F32)                 // bf16-limb matrix pipe (render3.hip)
             return nvsr_render_pass3_launch(arith, scene, packed_decoder, N, S, rays, z, noise, white_bkgd, rgb, disp, acc, weights, depth, raw_out, stream);
         return nvsr_render_pass2_launch(scene, packed_decoder, N, S, rays, z, noise, white_bkgd, rgb, disp, acc, weights, depth, raw_out, stream);

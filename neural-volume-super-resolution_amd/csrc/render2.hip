@@ -17,6 +17,7 @@
 #include <utility>
 
 #include "side_work.h"
+#include "nvsr_internal.h"
 
 #ifndef R2_STAMP
 #define R2_STAMP 0    // debug builds: raw_out[..., 0:2] of tile X = s_memtime cycles of the first hidden block pair

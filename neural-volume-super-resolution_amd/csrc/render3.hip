@@ -11,20 +11,10 @@
 // Biases are not preloaded into the accumulators: the first MFMA of a layer takes C = 0 and act = max(acc + bias, 0).
 #include "pair_core.h"
 
-#include <cstdlib>
-#include <mutex>
-#include <vector>
+#include "colour_order.h"
+#include "nvsr_internal.h"
 
 namespace nvsr {
-
-// The colour pass's ray order (live_order_kernel below): rays are regrouped inside blocks of ORDER_RAYS consecutive rays -- 16 workgroups, the
-// 128 x 32-pixel super-block of train_utils.patch_order -- by the bin of their live count, ORDER_BINS bins of equal width over 1..S and one
-// for the empty rays.  A packed entry of live_n is (count << ORDER_SHIFT) | index of the ray in its block.
-// ORDER_BINS = 32 is measured (profiles/colour_order_ab.txt): 8 and 16 bins leave more padding, an exact sort loses more of the
-// lanes' shared texels than its fewer steps win back.
-constexpr int ORDER_SHIFT = 12, ORDER_RAYS = 1 << ORDER_SHIFT, ORDER_BINS = 32;
-constexpr int ORDER_MAX_S = 1 << (31 - ORDER_SHIFT);      // a count has to fit above the index
-static_assert(ORDER_RAYS % RAYS2 == 0, "a block of the ray order is a whole number of workgroups");
 
 // =====================================================================================================================
 // The body of both kernels below (one instantiation per LIMBS; the kernels are thin shells so that the coarse and the fine pass are two
@@ -86,7 +76,7 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
     const int lane0 = rs.lane;
     // XCD-aware ray blocks: workgroup b runs on XCD b % 8 (round-robin dispatch), each XCD has its own L2.  Give XCD x the x-th contiguous
     // eighth of the ray blocks, so that the workgroups that share an L2 render neighbouring image rows (their taps share texels).
-    // Colour pass: the ray block comes from group_slot (group_order_kernel below): the blocks heaviest first, rank r -> workgroup r -> XCD
+    // Colour pass: the ray block comes from group_slot (group_order_kernel, colour_order.hip): the blocks heaviest first, rank r -> workgroup r -> XCD
     // r % 8, so that the long lists start first and are dealt round the XCDs; with NVSR_COLOUR_GROUP_ORDER=0 the table holds this formula.
     const unsigned nblk = gridDim.x, xcd = blockIdx.x & 7u, per = nblk >> 3, rem = nblk & 7u;
     unsigned blk_ = xcd * per + (xcd < rem ? xcd : rem) + (blockIdx.x >> 3);
@@ -721,158 +711,6 @@ __global__ __launch_bounds__(TPB2, 1) void render_pass3_colour_z_kernel(SceneDev
 #endif
 }
 
-// ---- the colour pass's ray order: live_n[ray] = count (density pass) -> packed entries, in place ---------------------------------------
-// One workgroup per block of ORDER_RAYS consecutive rays (the last one may be ragged: M rays).  A stable counting sort by bin, fullest bin
-// first: bin = ceil(count * bins / S) -- 0 for an empty ray, `bins` equal bins over 1..S -- so rays of one bin keep their (patch) order and
-// neighbouring pixels of similar count stay neighbouring lanes.  bins = 0 puts every ray into one bin: entry j names ray j (the identity,
-// NVSR_COLOUR_ORDER=0).  Wave w holds rays 256 w .. 256 w + 255 in four rounds of 64; a ray's rank is the number of rays in fuller bins + the
-// number of rays of its bin in earlier waves + earlier rounds + lower lanes: ballots, integer sums in a fixed order, no atomics.  The whole
-// block is read before any entry is written.
-// group_trip (may be NULL): group_trip[g] = the largest count among entries g RAYS2 .. g RAYS2 + RAYS2 - 1 of the sorted array -- the trip count
-// of the colour workgroup that runs ray block g (a ragged last group counts what it has); wave w of the block reduces its group w.
-constexpr int ORDER_TPB = 1024, ORDER_WAVES = ORDER_TPB / 64, ORDER_ROUNDS = ORDER_RAYS / ORDER_TPB;
-static_assert(ORDER_WAVES == ORDER_RAYS / RAYS2 && RAYS2 % 64 == 0, "one wave of the ordering kernel per colour workgroup of the block");
-__global__ __launch_bounds__(ORDER_TPB) void live_order_kernel(int* __restrict__ live_n, long N, int S, int bins, int* __restrict__ group_trip) {
-    __shared__ int cnt_s[(ORDER_BINS + 1) * ORDER_WAVES];      // [bin][wave]: rays of the bin in the wave, then in the waves before it
-    __shared__ int tot_s[ORDER_BINS + 1], start_s[ORDER_BINS + 1];      // rays of a bin; rays of all fuller bins
-    __shared__ int out_s[ORDER_RAYS];
-    const long block_base = (long)blockIdx.x * ORDER_RAYS;
-    const int M = (int)(N - block_base < ORDER_RAYS ? N - block_base : ORDER_RAYS);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    int cnt[ORDER_ROUNDS], bin[ORDER_ROUNDS];
-#pragma unroll
-    for (int r = 0; r < ORDER_ROUNDS; ++r) {
-        const int i = wave * (64 * ORDER_ROUNDS) + r * 64 + lane;
-        cnt[r] = i < M ? live_n[block_base + i] : 0;
-        const int b = (int)(((unsigned)cnt[r] * (unsigned)bins + (unsigned)(S - 1)) / (unsigned)S);      // (count <= S < 2^19, bins <= ORDER_BINS)
-        bin[r] = i < M ? (b < bins ? b : bins) : -1;
-    }
-    for (int b = 0; b <= bins; ++b) {
-        int c = 0;
-#pragma unroll
-        for (int r = 0; r < ORDER_ROUNDS; ++r) c += __popcll(__ballot(bin[r] == b));
-        if (lane == 0) cnt_s[b * ORDER_WAVES + wave] = c;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x <= bins) {
-        int run = 0;
-        for (int w = 0; w < ORDER_WAVES; ++w) { const int c = cnt_s[threadIdx.x * ORDER_WAVES + w]; cnt_s[threadIdx.x * ORDER_WAVES + w] = run; run += c; }
-        tot_s[threadIdx.x] = run;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x <= bins) {
-        int run = 0;
-        for (int b = bins; b > (int)threadIdx.x; --b) run += tot_s[b];
-        start_s[threadIdx.x] = run;
-    }
-    __syncthreads();
-    for (int b = 0; b <= bins; ++b) {
-        int at = start_s[b] + cnt_s[b * ORDER_WAVES + wave];
-#pragma unroll
-        for (int r = 0; r < ORDER_ROUNDS; ++r) {
-            const unsigned long long m = __ballot(bin[r] == b);
-            if (bin[r] == b) out_s[at + __popcll(m & below)] = (cnt[r] << ORDER_SHIFT) | (wave * (64 * ORDER_ROUNDS) + r * 64 + lane);
-            at += __popcll(m);
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < ORDER_ROUNDS; ++r) {
-        const int i = threadIdx.x + r * ORDER_TPB;
-        if (i < M) live_n[block_base + i] = out_s[i];
-    }
-    if (group_trip && wave * RAYS2 < M) {
-        int m = 0;
-#pragma unroll
-        for (int r = 0; r < RAYS2 / 64; ++r) {
-            const int i = wave * RAYS2 + r * 64 + lane;
-            if (i < M) m = max(m, out_s[i] >> ORDER_SHIFT);
-        }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) m = max(m, __shfl_xor(m, o));
-        if (lane == 0) group_trip[(long)blockIdx.x * ORDER_WAVES + wave] = m;
-    }
-}
-
-// ---- the colour pass's order of dispatch: group_trip[G] -> group_slot[G] ------------------------------------------------------------------
-// A colour workgroup takes trip steps, between none and S, and workgroups are dispatched in blockIdx order, b to XCD b % 8: in ray-block order
-// a heavy group may start last on its XCD, and the eighths of the image are unequal.  group_slot[r] = the ray block that workgroup r runs: the
-// G blocks sorted by trip, heaviest first, so rank r lands on XCD r % 8 -- the heavy groups start first and are dealt round the XCDs.
-// Groups of EQUAL trip are worth nothing to deal one by one, and neighbouring groups share texels in their XCD's L2 (a frame whose every
-// trip is S took 130 ms instead of 119 with its groups dealt one by one: profiles/colour_dispatch_ab.txt).  So a run of m equal trips, which
-// occupies m consecutive ranks, is dealt in pieces: the ranks of the run that share an XCD take consecutive groups, the first 1/8 of the run
-// (in group order) to the XCD of its first rank, the next to the following one -- the contiguous-eighths formula inside the run.  When every
-// trip is equal that is the density kernels' mapping itself.
-// One workgroup; a counting sort over the keys 0..S like the one above: wave w holds groups 256 w .. 256 w + 255 in four rounds of 64, a
-// group's place in its run = the groups of its trip in earlier waves + earlier rounds + lower lanes, the run's first rank = the groups of
-// larger trip (ballots, integer sums in a fixed order, no atomics).  Limits of the one workgroup: G <= GORDER_MAX_G groups (1 048 576 rays) and S <= GORDER_MAX_S; beyond either, or
-// with sorted = 0 (NVSR_COLOUR_GROUP_ORDER=0, the A/B handle), group_slot is the mapping of the density and fused kernels: XCD x runs the
-// x-th contiguous eighth of the blocks.
-constexpr int GORDER_TPB = 1024, GORDER_WAVES = GORDER_TPB / 64, GORDER_ROUNDS = 4, GORDER_MAX_G = GORDER_TPB * GORDER_ROUNDS, GORDER_MAX_S = 511;
-__global__ __launch_bounds__(GORDER_TPB) void group_order_kernel(const int* __restrict__ group_trip, int G, int S, int sorted, int* __restrict__ group_slot) {
-    if (!sorted || G > GORDER_MAX_G || S > GORDER_MAX_S) {
-        const unsigned per = (unsigned)G >> 3, rem = (unsigned)G & 7u;
-        for (unsigned r = threadIdx.x; r < (unsigned)G; r += GORDER_TPB) {
-            const unsigned xcd = r & 7u;
-            group_slot[r] = (int)(xcd * per + (xcd < rem ? xcd : rem) + (r >> 3));
-        }
-        return;
-    }
-    __shared__ int cnt_s[(GORDER_MAX_S + 1) * GORDER_WAVES];      // [trip][wave]: groups of the trip in the wave, then in the waves before it
-    __shared__ int tot_s[GORDER_MAX_S + 1], start_s[GORDER_MAX_S + 1];      // groups of a trip; groups of all larger trips
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    int key[GORDER_ROUNDS];
-#pragma unroll
-    for (int r = 0; r < GORDER_ROUNDS; ++r) {
-        const int g = wave * (64 * GORDER_ROUNDS) + r * 64 + lane;
-        const int t = g < G ? group_trip[g] : 0;
-        key[r] = g < G ? (t < 0 ? 0 : t > S ? S : t) : -1;      // (a trip is 0..S; the clamp keeps a caller's array inside the tables)
-    }
-    for (int b = 0; b <= S; ++b) {
-        int c = 0;
-#pragma unroll
-        for (int r = 0; r < GORDER_ROUNDS; ++r) c += __popcll(__ballot(key[r] == b));
-        if (lane == 0) cnt_s[b * GORDER_WAVES + wave] = c;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x <= S) {
-        int run = 0;
-        for (int w = 0; w < GORDER_WAVES; ++w) { const int c = cnt_s[threadIdx.x * GORDER_WAVES + w]; cnt_s[threadIdx.x * GORDER_WAVES + w] = run; run += c; }
-        tot_s[threadIdx.x] = run;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x <= S) {
-        int run = 0;
-        for (int b = S; b > (int)threadIdx.x; --b) run += tot_s[b];
-        start_s[threadIdx.x] = run;
-    }
-    __syncthreads();
-    if (wave * (64 * GORDER_ROUNDS) >= G) return;      // (a wave without groups; no barrier follows)
-    int place[GORDER_ROUNDS];                                     // place in the run of its trip, in group order
-#pragma unroll
-    for (int r = 0; r < GORDER_ROUNDS; ++r) place[r] = 0;
-    for (int b = 0; b <= S; ++b) {
-        int at = cnt_s[b * GORDER_WAVES + wave];
-#pragma unroll
-        for (int r = 0; r < GORDER_ROUNDS; ++r) {
-            const unsigned long long m = __ballot(key[r] == b);
-            if (key[r] == b) place[r] = at + __popcll(m & below);
-            at += __popcll(m);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < GORDER_ROUNDS; ++r) {
-        if (key[r] < 0) continue;
-        const int run = tot_s[key[r]], per = run >> 3, rem = run & 7, thr = rem * (per + 1);      // the first `rem` pieces hold per + 1 groups
-        const int j = place[r];
-        const int k = j < thr ? j / (per + 1) : rem + (j - thr) / (per ? per : 1);                // the piece, i.e. rank % 8 inside the run
-        const int i = j < thr ? j - k * (per + 1) : (j - thr) - (k - rem) * per;
-        group_slot[start_s[key[r]] + k + 8 * i] = wave * (64 * GORDER_ROUNDS) + r * 64 + lane;
-    }
-}
-
 // ---- natural blob -> bf16 limb fragments (the tail of the packed blob) -----------------------------------------------------------
 template <int LIMBS>
 __global__ void pack_decoder_limbs_kernel(const float* __restrict__ nat, unsigned* __restrict__ out) {
@@ -965,224 +803,47 @@ extern "C" int nvsr_pack_decoder_limbs_launch(const float* natural, float* packe
     return NVSR_CHECK_LAUNCH();
 }
 
-// ---- scratch of the two-phase route: the live lists, [N, S] depths + [N, S] weights + [N] counts ------------------------------------
-// Owned by the library, one buffer per (device, stream), grow-only: two launches on one stream are ordered, launches on two streams never
-// share a buffer.  Growing frees the old buffer with hipFree, which waits for the device -- no launch can still be using it.
-// Contract (include/nvsr.h): one host thread at a time enqueues render launches on a given (device, stream) -- the pointer is used after
-// the table's lock is dropped; the entry of a destroyed stream keeps its buffer until nvsr_release_render_scratch.
-// The order of dispatch (group_order_kernel) takes 2 G ints more, G = ceil(N / RAYS2): group_slot[G], then group_trip[G].  They live in a
-// small buffer of their own beside the lists (20 KB at the benchmark size), with the same owner, growth and release;
-// nvsr_render_scratch_bytes keeps counting the lists' buffer alone.
-namespace {
-struct LiveScratch { int device; hipStream_t stream; char* p; size_t bytes; int* last_n; int64_t last_N;      // last_*: the counts of the latest launch
-                     int* group; size_t group_ints; };
-std::mutex g_live_mutex;
-std::vector<LiveScratch> g_live;
-
-char* live_scratch(hipStream_t stream, size_t bytes, size_t counts_at, int64_t N, bool launch, int*& group) {
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> lock(g_live_mutex);
-    LiveScratch* e = nullptr;
-    for (LiveScratch& c : g_live)
-        if (c.device == device && c.stream == stream) e = &c;
-    if (!e) { g_live.push_back(LiveScratch{device, stream, nullptr, 0, nullptr, 0, nullptr, 0}); e = &g_live.back(); }
-    const size_t group_ints = 2 * (size_t)((N + RAYS2 - 1) / RAYS2);
-    if (e->group_ints < group_ints) {
-        if (e->group) (void)hipFree(e->group);
-        e->group = nullptr; e->group_ints = 0; e->last_n = nullptr; e->last_N = 0;      // (the new buffer holds no launch's order)
-        void* g = nullptr;
-        if (hipMalloc(&g, group_ints * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        e->group = static_cast<int*>(g); e->group_ints = group_ints;
-    }
-    group = e->group;
-    if (e->bytes < bytes) {
-        if (e->p) (void)hipFree(e->p);
-        e->p = nullptr; e->bytes = 0; e->last_n = nullptr; e->last_N = 0;
-        void* p = nullptr;
-        if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        e->p = static_cast<char*>(p); e->bytes = bytes;
-    }
-    if (launch) { e->last_n = reinterpret_cast<int*>(e->p + counts_at); e->last_N = N; }      // (a reservation leaves no counts behind)
-    return e->p;
-}
-
-// the two-phase route is taken unless the caller wants the raw decoder outputs, NVSR_RENDER_ONE_PHASE=1 is set (the A/B handle), the stream
-// is being captured (the scratch cannot grow inside a capture), a count would not fit into a packed entry of the ray order (S >= 2^19) or the
-// scratch cannot be had -- then the fused kernel runs: same pixels
-struct LiveLists { float* z; float* w; int* n; int* slot; int* trip; };      // slot, trip: [G] each, G = ceil(N / RAYS2)
-bool two_phase_lists(const float* raw_out, int64_t N, int S, hipStream_t stream, LiveLists& out, bool launch = true) {
-    if (raw_out || S < 1 || S >= ORDER_MAX_S) return false;
-    const char* e = getenv("NVSR_RENDER_ONE_PHASE");
-    if (e && e[0] == '1') return false;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return false; }
-    const size_t rows = (size_t)N * (size_t)S * sizeof(float);
-    int* group = nullptr;
-    char* p = live_scratch(stream, 2 * rows + (size_t)N * sizeof(int), 2 * rows, N, launch, group);
-    if (!p) return false;
-    out.slot = group;
-    out.trip = group + (N + RAYS2 - 1) / RAYS2;
-    out.z = reinterpret_cast<float*>(p);
-    out.w = reinterpret_cast<float*>(p + rows);
-    out.n = reinterpret_cast<int*>(p + 2 * rows);
-    return true;
-}
-
-// the colour pass's ray order, between the density and the colour launch: ORDER_BINS bins, or the identity with NVSR_COLOUR_ORDER=0 (the A/B
-// handle, read at every launch: the colour kernel then groups its rays as the density kernel does)
-int colour_order_bins() {
-    const char* e = getenv("NVSR_COLOUR_ORDER");
-    if (e && e[0] == '0') return 0;
-    return ORDER_BINS;
-}
-void launch_live_order(int* live_n, int64_t N, int S, int bins, int* group_trip, hipStream_t stream) {
-    hipLaunchKernelGGL(live_order_kernel, dim3((unsigned)((N + ORDER_RAYS - 1) / ORDER_RAYS)), dim3(ORDER_TPB), 0, stream, live_n, (long)N, S, bins, group_trip);
-}
-// the colour pass's order of dispatch, after the ray order: heaviest groups first, or the contiguous eighths with NVSR_COLOUR_GROUP_ORDER=0
-// (the A/B handle, read at every launch; same kernel, same table)
-int colour_group_sorted() {
-    const char* e = getenv("NVSR_COLOUR_GROUP_ORDER");
-    return e && e[0] == '0' ? 0 : 1;
-}
-void launch_group_order(const int* group_trip, int64_t G, int S, int* group_slot, hipStream_t stream) {
-    hipLaunchKernelGGL(group_order_kernel, dim3(1), dim3(GORDER_TPB), 0, stream, group_trip, (int)G, S, colour_group_sorted(), group_slot);
-}
-// both, between the density and the colour launch
-void launch_colour_order(const LiveLists& ll, int64_t N, int S, hipStream_t stream) {
-    launch_live_order(ll.n, N, S, colour_order_bins(), ll.trip, stream);
-    launch_group_order(ll.trip, (N + RAYS2 - 1) / RAYS2, S, ll.slot, stream);
-}
-}  // namespace
-
-// test hooks of the ray order.  nvsr_internal_live_order: the ordering kernel alone, with the product's bins, on a caller's array of N counts
-// (each <= S), in place.  nvsr_internal_colour_order_bins: that number of bins.  nvsr_internal_copy_live_counts: the packed entries the
-// latest two-phase launch on `stream` left in the library's scratch -> dst (N ints, device or host memory; N must be that launch's).
-extern "C" int nvsr_internal_colour_order_bins(void) { return ORDER_BINS; }
-extern "C" int nvsr_internal_live_order(int* live_n, int64_t N, int S, nvsr_stream_t stream) {
-    if (!live_n) return NVSR_ERR_NULL;
-    if (N < 1 || S < 1 || S >= ORDER_MAX_S || (N + ORDER_RAYS - 1) / ORDER_RAYS > 0x7fffffff) return NVSR_ERR_SHAPE;
-    launch_live_order(live_n, N, S, ORDER_BINS, nullptr, (hipStream_t)stream);
+// ---- the launches of one render pass: the two-phase route (density pass, the colour pass's orders, colour pass on the lists `ll`), or the
+// fused kernel where two_phase_lists declines (ll = NULL).  z = NULL: the coarse pass with its depths computed in the kernel from
+// (near, far, s, S, lindisp); it always writes the weights.
+template <int LIMBS>
+static int launch_pass3(const LiveLists* ll, const nvsr_scene* scene, const float* packed, int64_t N, int S, const float* rays, const float* z, int lindisp,
+                        const float* noise, int white, float* rgb, float* disp, float* acc, float* weights, float* depth, float* raw_out, hipStream_t stream) {
+    const SceneDev sc = to_dev(scene);
+    unsigned* flag = nvsr_get_range_flag();
+    auto launch = [&](auto kernel, auto... args) {      // (every kernel's arguments start alike)
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((N + RAYS2 - 1) / RAYS2)), dim3(TPB2), 0, stream, sc, packed, (long)N, S, rays, args...);
+    };
+    if (ll) {
+        if (z) launch(render_pass3_density_kernel<LIMBS>, z, noise, disp, acc, weights, depth, flag, ll->z, ll->w, ll->n);
+        else launch(render_pass3_density_z_kernel<LIMBS>, lindisp, noise, disp, acc, weights, depth, flag, ll->z, ll->w, ll->n);
+        launch_colour_order(*ll, N, S, stream);
+        if (z) launch(render_pass3_colour_kernel<LIMBS>, white, rgb, acc, flag, ll->z, ll->w, ll->n, ll->slot);
+        else launch(render_pass3_colour_z_kernel<LIMBS>, lindisp, white, rgb, acc, flag, ll->z, ll->w, ll->n, ll->slot);
+    } else if (!z) launch(render_pass3_coarse_z_kernel<LIMBS>, lindisp, noise, white, rgb, disp, acc, weights, depth, raw_out, flag);
+    else if (weights) launch(render_pass3_coarse_kernel<LIMBS>, z, noise, white, rgb, disp, acc, weights, depth, raw_out, flag);
+    else launch(render_pass3_kernel<LIMBS>, z, noise, white, rgb, disp, acc, depth, raw_out, flag);
     return NVSR_CHECK_LAUNCH();
 }
-// test hooks of the order of dispatch.  nvsr_internal_group_order: group_order_kernel alone on a caller's G trips (each 0..S) -> out[G], with
-// the product's handle (NVSR_COLOUR_GROUP_ORDER).  nvsr_internal_copy_group_order: what the latest two-phase launch on `stream` left in the
-// library's scratch -> dst, 2 G ints: group_slot[G], then group_trip[G] (G must be that launch's ceil(N / 256)).
-extern "C" int nvsr_internal_group_order(const int* trips, int64_t G, int S, int* out, nvsr_stream_t stream) {
-    if (!trips || !out) return NVSR_ERR_NULL;
-    if (G < 1 || G > 0x7fffffff || S < 1 || S >= ORDER_MAX_S) return NVSR_ERR_SHAPE;
-    launch_group_order(trips, G, S, out, (hipStream_t)stream);
-    return NVSR_CHECK_LAUNCH();
-}
-extern "C" int nvsr_internal_copy_group_order(int* dst, int64_t G, nvsr_stream_t stream) {
-    if (!dst) return NVSR_ERR_NULL;
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) return NVSR_ERR_LAUNCH;
-    const int* src = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        for (const LiveScratch& c : g_live)
-            if (c.device == device && c.stream == (hipStream_t)stream && c.last_n && (c.last_N + RAYS2 - 1) / RAYS2 == G) src = c.group;
-    }
-    if (!src) return NVSR_ERR_SHAPE;
-    return hipMemcpyAsync(dst, src, 2 * (size_t)G * sizeof(int), hipMemcpyDefault, (hipStream_t)stream) == hipSuccess ? NVSR_OK : NVSR_ERR_LAUNCH;
-}
-extern "C" int nvsr_internal_copy_live_counts(int* dst, int64_t N, nvsr_stream_t stream) {
-    if (!dst) return NVSR_ERR_NULL;
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) return NVSR_ERR_LAUNCH;
-    const int* src = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        for (const LiveScratch& c : g_live)
-            if (c.device == device && c.stream == (hipStream_t)stream && c.last_n && c.last_N == N) src = c.last_n;
-    }
-    if (!src) return NVSR_ERR_SHAPE;
-    return hipMemcpyAsync(dst, src, (size_t)N * sizeof(int), hipMemcpyDefault, (hipStream_t)stream) == hipSuccess ? NVSR_OK : NVSR_ERR_LAUNCH;
+static int launch_pass3(int limbs, const nvsr_scene* scene, const float* packed, int64_t N, int S, const float* rays, const float* z, int lindisp,
+                        const float* noise, int white, float* rgb, float* disp, float* acc, float* weights, float* depth, float* raw_out, hipStream_t stream) {
+    LiveLists lists;
+    const LiveLists* ll = two_phase_lists(raw_out, N, S, stream, lists) ? &lists : nullptr;
+    return limbs == 3 ? launch_pass3<3>(ll, scene, packed, N, S, rays, z, lindisp, noise, white, rgb, disp, acc, weights, depth, raw_out, stream)
+                      : launch_pass3<2>(ll, scene, packed, N, S, rays, z, lindisp, noise, white, rgb, disp, acc, weights, depth, raw_out, stream);
 }
 
-// a frame's driver knows its largest pass before the first launch: sizing the buffer for it up front keeps the growth (a device-wide
-// wait) out of the frame -- between the coarse and the fine pass (aux.hip).  Does nothing where the two-phase route would not be taken.
-extern "C" void nvsr_internal_reserve_render_scratch(int64_t N, int S, nvsr_stream_t stream) {
-    LiveLists ll;
-    (void)two_phase_lists(nullptr, N, S, (hipStream_t)stream, ll, false);
-}
-
-extern "C" int64_t nvsr_render_scratch_bytes(void) {
-    std::lock_guard<std::mutex> lock(g_live_mutex);
-    int64_t total = 0;
-    for (const LiveScratch& c : g_live) total += (int64_t)c.bytes;
-    return total;
-}
-
-extern "C" int nvsr_release_render_scratch(void) {
-    std::lock_guard<std::mutex> lock(g_live_mutex);
-    int prev = 0;
-    const bool have_prev = hipGetDevice(&prev) == hipSuccess;
-    int rc = NVSR_OK;
-    for (LiveScratch& c : g_live) {
-        if (!c.p) continue;
-        if (hipSetDevice(c.device) != hipSuccess || hipFree(c.p) != hipSuccess) rc = NVSR_ERR_LAUNCH;
-    }
-    for (LiveScratch& c : g_live)
-        if (c.group && (hipSetDevice(c.device) != hipSuccess || hipFree(c.group) != hipSuccess)) rc = NVSR_ERR_LAUNCH;
-    g_live.clear();
-    if (have_prev) (void)hipSetDevice(prev);
-    return rc;
-}
-
-extern "C" int nvsr_render_pass3_launch(int limbs, const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays,
-                                        const float* z, const float* noise, int white_bkgd, float* rgb, float* disp, float* acc,
-                                        float* weights, float* depth, float* raw_out, nvsr_stream_t stream) {
-    const int64_t grid = (N + RAYS2 - 1) / RAYS2;
-    if (grid > 0x7fffffff || (limbs != 2 && limbs != 3)) return NVSR_ERR_SHAPE;
-    LiveLists ll;
-    if (two_phase_lists(raw_out, N, S, (hipStream_t)stream, ll)) {
-#define NVSR_LAUNCH3_2P(LIMBS_)                                                                                                            \
-        hipLaunchKernelGGL(render_pass3_density_kernel<LIMBS_>, dim3((unsigned)grid), dim3(TPB2), 0, (hipStream_t)stream, to_dev(scene),   \
-                           packed_decoder, (long)N, S, rays, z, noise, disp, acc, weights, depth, nvsr_get_range_flag(), ll.z, ll.w, ll.n); \
-        launch_colour_order(ll, N, S, (hipStream_t)stream);                                                                                \
-        hipLaunchKernelGGL(render_pass3_colour_kernel<LIMBS_>, dim3((unsigned)grid), dim3(TPB2), 0, (hipStream_t)stream, to_dev(scene),    \
-                           packed_decoder, (long)N, S, rays, white_bkgd, rgb, acc, nvsr_get_range_flag(), ll.z, ll.w, ll.n, ll.slot)
-        if (limbs == 3) { NVSR_LAUNCH3_2P(3); } else { NVSR_LAUNCH3_2P(2); }
-#undef NVSR_LAUNCH3_2P
-        return NVSR_CHECK_LAUNCH();
-    }
-#define NVSR_LAUNCH3(LIMBS_)                                                                                                               \
-    if (weights)                                                                                                                           \
-        hipLaunchKernelGGL(render_pass3_coarse_kernel<LIMBS_>, dim3((unsigned)grid), dim3(TPB2), 0, (hipStream_t)stream, to_dev(scene),    \
-                           packed_decoder, (long)N, S, rays, z, noise, white_bkgd, rgb, disp, acc, weights, depth, raw_out, nvsr_get_range_flag());               \
-    else                                                                                                                                   \
-        hipLaunchKernelGGL(render_pass3_kernel<LIMBS_>, dim3((unsigned)grid), dim3(TPB2), 0, (hipStream_t)stream, to_dev(scene),           \
-                           packed_decoder, (long)N, S, rays, z, noise, white_bkgd, rgb, disp, acc, depth, raw_out, nvsr_get_range_flag())
-    if (limbs == 3) { NVSR_LAUNCH3(3); } else { NVSR_LAUNCH3(2); }
-#undef NVSR_LAUNCH3
-    return NVSR_CHECK_LAUNCH();
+extern "C" int nvsr_render_pass3_launch(int limbs, const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays, const float* z,
+                                        const float* noise, int white_bkgd, float* rgb, float* disp, float* acc, float* weights, float* depth, float* raw_out,
+                                        nvsr_stream_t stream) {
+    if ((N + RAYS2 - 1) / RAYS2 > 0x7fffffff || (limbs != 2 && limbs != 3)) return NVSR_ERR_SHAPE;
+    return launch_pass3(limbs, scene, packed_decoder, N, S, rays, z, 0, noise, white_bkgd, rgb, disp, acc, weights, depth, raw_out, (hipStream_t)stream);
 }
 
 // the coarse pass with its depths computed in the kernel (z = coarse_depth(near, far, s, S, lindisp)); weights are always written
-extern "C" int nvsr_render_pass3_coarse_z_launch(int limbs, const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays,
-                                                 int lindisp, const float* noise, int white_bkgd, float* rgb, float* disp, float* acc,
-                                                 float* weights, float* depth, float* raw_out, nvsr_stream_t stream) {
-    const int64_t grid = (N + RAYS2 - 1) / RAYS2;
-    if (grid > 0x7fffffff || (limbs != 2 && limbs != 3) || !weights) return NVSR_ERR_SHAPE;
-    LiveLists ll;
-    if (two_phase_lists(raw_out, N, S, (hipStream_t)stream, ll)) {
-#define NVSR_LAUNCH3_2P(LIMBS_)                                                                                                            \
-        hipLaunchKernelGGL(render_pass3_density_z_kernel<LIMBS_>, dim3((unsigned)grid), dim3(TPB2), 0, (hipStream_t)stream, to_dev(scene), \
-                           packed_decoder, (long)N, S, rays, lindisp, noise, disp, acc, weights, depth, nvsr_get_range_flag(), ll.z, ll.w, ll.n); \
-        launch_colour_order(ll, N, S, (hipStream_t)stream);                                                                                \
-        hipLaunchKernelGGL(render_pass3_colour_z_kernel<LIMBS_>, dim3((unsigned)grid), dim3(TPB2), 0, (hipStream_t)stream, to_dev(scene),  \
-                           packed_decoder, (long)N, S, rays, lindisp, white_bkgd, rgb, acc, nvsr_get_range_flag(), ll.z, ll.w, ll.n, ll.slot)
-        if (limbs == 3) { NVSR_LAUNCH3_2P(3); } else { NVSR_LAUNCH3_2P(2); }
-#undef NVSR_LAUNCH3_2P
-        return NVSR_CHECK_LAUNCH();
-    }
-    if (limbs == 3)
-        hipLaunchKernelGGL(render_pass3_coarse_z_kernel<3>, dim3((unsigned)grid), dim3(TPB2), 0, (hipStream_t)stream, to_dev(scene), packed_decoder,
-                           (long)N, S, rays, lindisp, noise, white_bkgd, rgb, disp, acc, weights, depth, raw_out, nvsr_get_range_flag());
-    else
-        hipLaunchKernelGGL(render_pass3_coarse_z_kernel<2>, dim3((unsigned)grid), dim3(TPB2), 0, (hipStream_t)stream, to_dev(scene), packed_decoder,
-                           (long)N, S, rays, lindisp, noise, white_bkgd, rgb, disp, acc, weights, depth, raw_out, nvsr_get_range_flag());
-    return NVSR_CHECK_LAUNCH();
+extern "C" int nvsr_render_pass3_coarse_z_launch(int limbs, const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays, int lindisp,
+                                                 const float* noise, int white_bkgd, float* rgb, float* disp, float* acc, float* weights, float* depth,
+                                                 float* raw_out, nvsr_stream_t stream) {
+    if ((N + RAYS2 - 1) / RAYS2 > 0x7fffffff || (limbs != 2 && limbs != 3) || !weights) return NVSR_ERR_SHAPE;
+    return launch_pass3(limbs, scene, packed_decoder, N, S, rays, nullptr, lindisp, noise, white_bkgd, rgb, disp, acc, weights, depth, raw_out, (hipStream_t)stream);
 }

@@ -14,6 +14,7 @@
 //      192 contiguous bytes, the fast shape of float atomics (one-lane-per-row scatter is ~17x slower, MI355X_MICROARCH.md).
 #include "bwd_core.h"
 #include "wave_scan.h"
+#include "nvsr_internal.h"
 
 namespace nvsr {
 
@@ -580,14 +581,6 @@ __global__ __launch_bounds__(CB_WPB * 64) void composite_backward_kernel(long N,
 }  // namespace nvsr
 
 using namespace nvsr;
-
-// render_bwd_limb.hip
-extern "C" int nvsr_pack_decoder_bwd_limbs_launch(const float* natural, float* packed_bwd, nvsr_stream_t stream);
-extern "C" int nvsr_render_pass_backward_gates_limb_launch(int limbs, const nvsr_scene* scene, const float* packed_decoder, const float* packed_bwd,
-                                                           int64_t N, int S, const float* rays, const float* z, const float* g_raw,
-                                                           const uint32_t* gates, float* const* grad_planes, float* view_ws, float* record,
-                                                           nvsr_stream_t stream);
-extern "C" int nvsr_internal_resolve_decoder_arith(int arithmetic);      // render.hip
 
 extern "C" {
 

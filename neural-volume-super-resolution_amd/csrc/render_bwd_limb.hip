@@ -37,6 +37,7 @@
 
 #include "limb_core.h"
 #include "bwd_core.h"
+#include "nvsr_internal.h"
 
 namespace nvsr {
 

@@ -19,6 +19,7 @@
 
 #include "limb_core.h"
 #include "sr_core.h"
+#include "nvsr_internal.h"
 
 namespace nvsr {
 
@@ -1001,7 +1002,6 @@ extern "C" int nvsr_get_sr_plane_interp(void) { return g_sr_bicubic ? NVSR_PLANE
 
 // arithmetic of the eligible conv layers (process-wide): -1 = not yet read from the environment
 static int g_conv_arithmetic = -1;
-extern "C" int nvsr_internal_parse_arith_env(const char* name, int dflt);      // render.hip
 extern "C" int nvsr_get_conv_arithmetic(void) {
     if (g_conv_arithmetic == -1) g_conv_arithmetic = nvsr_internal_parse_arith_env("NVSR_CONV_ARITHMETIC", NVSR_CONV_ARITH_DEFAULT);
     return g_conv_arithmetic;

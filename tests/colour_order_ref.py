@@ -1,4 +1,4 @@
-"""numpy reference of the colour pass's ray order (live_order_kernel, csrc/render3.hip) and the checks of a packed result -- shared by
+"""numpy reference of the colour pass's ray order (live_order_kernel, csrc/colour_order.hip) and the checks of a packed result -- shared by
 tests/test_colour_order.py (GPU) and tests/test_colour_order_host.py (CPU, which checks this reference against a brute-force sort).
 
 Rays are ordered inside blocks of ORDER_RAYS consecutive rays by the bin of their live count, fullest bin first, stably; entry j of a block

@@ -1,5 +1,5 @@
 """numpy reference of the colour pass's order of dispatch (group_order_kernel and the group_trip output of live_order_kernel,
-csrc/render3.hip) -- shared by tests/test_group_order.py (GPU) and tests/test_group_order_host.py (CPU, which checks this reference against a
+csrc/colour_order.hip) -- shared by tests/test_group_order.py (GPU) and tests/test_group_order_host.py (CPU, which checks this reference against a
 brute-force sort).
 
 A group is 256 consecutive entries of the ray order's packed array; its trip is the largest count among them.  group_slot[r] is the group

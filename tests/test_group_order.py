@@ -1,21 +1,17 @@
-"""GPU tests (-m gpu) of the colour pass's order of dispatch (csrc/render3.hip: group_order_kernel, the group_trip output of
-live_order_kernel, blk = group_slot[blockIdx.x] in PHASE 2 of render_pass3_body; include/nvsr.h "Order of dispatch of the colour pass").
+"""GPU tests (-m gpu) of the colour pass's order of dispatch (csrc/colour_order.hip: group_order_kernel, the group_trip output of
+live_order_kernel; csrc/render3.hip: blk = group_slot[blockIdx.x] in PHASE 2 of render_pass3_body; include/nvsr.h "Order of dispatch of the colour pass").
 
 (a) group_order_kernel alone against the numpy reference (group_order_ref.py; itself checked on the CPU by test_group_order_host.py), with a
     guard band behind the output, the handle on and off, and beyond what the one workgroup sorts;
 (b) the product route against the fused kernel (NVSR_RENDER_ONE_PHASE=1), bit for bit, on the dictated counts of test_colour_order.py with one
     group of empty rays added (N = 65536 + 4096 + 37: the last group is ragged), each handle on and off, white background off and on;
 (c) what the launch left behind: group_trip is the maxima of the packed entries' groups, group_slot is the reference's."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
-from colour_order_ref import ORDER_RAYS
 from group_order_ref import GROUP_RAYS, MAX_G, MAX_S, check_group_order, eighths, group_order_reference, group_trips
-from test_colour_order import ARITHS, N_RAYS, _env, _pass, _same, _scene
-from test_hip_parity import DEV
+from two_phase_checks import ARITHS, DEV, N_RAYS, OUTPUTS, _counts_and_noise, _env, _pass, _same, _scene
 
 pytestmark = pytest.mark.gpu
 
@@ -70,21 +66,6 @@ def test_group_order_kernel_at_and_beyond_the_limits_of_one_workgroup(hip):
 EMPTY_GROUP = 2      # rays 512..767 of the first block of the order: a group of the density pass's grouping
 
 
-def _counts_and_noise(S, seed):
-    """the construction of test_colour_order.py (half the rays empty, the rest spread over 1..S at random positions, one full ray per block
-    of the order; noise -1000 on a dead sample, 0 on a live one) with one group of 256 consecutive rays emptied: with NVSR_COLOUR_ORDER=0 that
-    group's workgroup has trip 0; with the order the blocks' last groups hold empty rays only"""
-    rng = np.random.default_rng(seed)
-    c = np.where(rng.random(N_RAYS) < 0.5, 0, rng.integers(1, S + 1, N_RAYS))
-    for b0 in range(0, N_RAYS, ORDER_RAYS):
-        c[b0 + rng.integers(0, min(ORDER_RAYS, N_RAYS - b0))] = S
-    c[EMPTY_GROUP * GROUP_RAYS:(EMPTY_GROUP + 1) * GROUP_RAYS] = 0
-    rank = np.argsort(np.argsort(rng.random((N_RAYS, S)), 1), 1)
-    live = rank < c[:, None]
-    noise = torch.from_numpy(np.where(live, 0.0, -1000.0).astype(np.float32)).to(DEV).contiguous()
-    return c, noise
-
-
 def _left_behind(hip, G):
     t = torch.full((2 * G + 64,), -7, dtype=torch.int32, device=DEV)
     assert hip.capi.lib().nvsr_internal_copy_group_order(t.data_ptr(), G, hip.capi.stream()) == 0
@@ -98,21 +79,21 @@ def _left_behind(hip, G):
 @pytest.mark.parametrize("S,read_z", [(24, False), (40, True)])
 def test_dispatch_order_keeps_the_fused_pixels_on_dictated_counts(hip, arith, S, read_z):
     """(b) and (c): S = 24 with the depths in registers, S = 40 with the depths read"""
-    mf, rays = _scene(hip, 11)
+    mc, mf, rays = _scene(hip, 11, 264, 264, n_rays=N_RAYS, sigma=0.05)
     N = N_RAYS
     G = (N + GROUP_RAYS - 1) // GROUP_RAYS
     assert N % GROUP_RAYS == 37                                             # a ragged last group
-    c, noise = _counts_and_noise(S, 100 + S)
+    c, noise = _counts_and_noise(S, 100 + S, empty_group=EMPTY_GROUP)
     g = torch.Generator(device=DEV).manual_seed(2)
     z = (2.0 + (torch.arange(S, device=DEV)[None, :] + 0.5 * torch.rand(N, 1, device=DEV, generator=g)) * (4.0 / S)).contiguous() if read_z else None
-    names = ("rgb", "disp", "acc", "depth", "weights")
+    names = OUTPUTS
     for white in (0, 1):
-        one, _ = _pass(hip, mf, rays, S, arith, z, noise, white, NVSR_RENDER_ONE_PHASE="1")
+        one, _ = _pass(hip, mf, rays, S, arith, z, noise, white, lindisp=1, release=True, NVSR_RENDER_ONE_PHASE="1")
         assert np.array_equal((one["weights"] != 0).sum(1).cpu().numpy(), c)      # the input did what the test thinks it did
         seen = {}
         for order in ("1", "0"):
             for group in ("1", "0"):
-                two, entries = _pass(hip, mf, rays, S, arith, z, noise, white, NVSR_RENDER_ONE_PHASE="0", NVSR_COLOUR_ORDER=order,
+                two, entries = _pass(hip, mf, rays, S, arith, z, noise, white, lindisp=1, release=True, NVSR_RENDER_ONE_PHASE="0", NVSR_COLOUR_ORDER=order,
                                      NVSR_COLOUR_GROUP_ORDER=group)
                 slot, trip = _left_behind(hip, G)
                 for name in names:

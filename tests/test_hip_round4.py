@@ -139,12 +139,10 @@ def test_pair_forward_matches_the_one_tile_forward(hip, N, S):
         raw = torch.full((N, S, 4), float("nan"), device=DEV)
         gates = torch.full((N, S, 32), -1, dtype=torch.int32, device=DEV)
         f = getattr(lib, fn)
-        f.restype = C.c_int
         if "limb" in fn:
-            st = f(C.c_int(2), C.byref(sc), capi.ptr(packed), C.c_int64(N), C.c_int(S), capi.ptr(rays), capi.ptr(z), capi.ptr(raw), capi.ptr(gates), None,
-                   capi.stream())
+            st = f(2, C.byref(sc), capi.ptr(packed), N, S, capi.ptr(rays), capi.ptr(z), capi.ptr(raw), capi.ptr(gates), None, capi.stream())
         else:
-            st = f(C.byref(sc), capi.ptr(packed), C.c_int64(N), C.c_int(S), capi.ptr(rays), capi.ptr(z), capi.ptr(raw), capi.ptr(gates), capi.stream())
+            st = f(C.byref(sc), capi.ptr(packed), N, S, capi.ptr(rays), capi.ptr(z), capi.ptr(raw), capi.ptr(gates), capi.stream())
         assert st == 0
         outs.append((raw, gates))
     (raw_a, gates_a), (raw_b, gates_b) = outs
@@ -155,7 +153,7 @@ def test_pair_forward_matches_the_one_tile_forward(hip, N, S):
     # without gates: the same raw, bit for bit, as with them
     raw_c = torch.empty_like(raw_b)
     f = lib.nvsr_decode_rays_pair_launch
-    assert f(C.byref(sc), capi.ptr(packed), C.c_int64(N), C.c_int(S), capi.ptr(rays), capi.ptr(z), capi.ptr(raw_c), None, capi.stream()) == 0
+    assert f(C.byref(sc), capi.ptr(packed), N, S, capi.ptr(rays), capi.ptr(z), capi.ptr(raw_c), None, capi.stream()) == 0
     assert torch.equal(raw_c, raw_b)
 
 

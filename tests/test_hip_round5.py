@@ -42,8 +42,7 @@ def test_pair_forward_against_the_oracle(hip, oracle, N, S):
     sc, keep = mf.native_scene()
     raw = torch.full((N, S, 4), float("nan"), device=DEV)
     f = lib.nvsr_decode_rays_pair_launch
-    f.restype = C.c_int
-    assert f(C.byref(sc), capi.ptr(mf.packed_decoder()), C.c_int64(N), C.c_int(S), capi.ptr(rays), capi.ptr(z), capi.ptr(raw), None, capi.stream()) == 0
+    assert f(C.byref(sc), capi.ptr(mf.packed_decoder()), N, S, capi.ptr(rays), capi.ptr(z), capi.ptr(raw), None, capi.stream()) == 0
     osc, dec = _oracle_scene_of(oracle, hip, mf, sid)
     want = oracle.render_given_z(osc, dec, N_(rays), N_(z), want_raw=True)["raw"]
     got = N_(raw)

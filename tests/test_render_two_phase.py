@@ -1,94 +1,31 @@
-"""GPU tests (-m gpu) of the two-phase render pass (csrc/render3.hip; include/nvsr.h "The two-phase render pass"): the density pass + the
+"""GPU tests (-m gpu) of the two-phase render pass (csrc/render3.hip: the kernels; csrc/colour_order.hip: the lists' scratch; include/nvsr.h "The two-phase render pass"): the density pass + the
 colour pass on the live samples against the fused kernel (NVSR_RENDER_ONE_PHASE=1), output for output, bit for bit.
 
 A sample whose weight is +0.0 added +0.0 to every sum of the fused kernel, so leaving it out changes no bit: every case asserts torch.equal
 on rgb, disp, acc, depth and the coarse weights (disp is NaN by definition on a ray with acc == 0: NaNs must sit in the same places and the
 numbers must be equal)."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch
 
-from test_hip_parity import DEV
+from colour_order_ref import order_reference
+from two_phase_checks import ARITHS, DEV, OUTPUTS, _env, _pass, _same, _scene
 
 pytestmark = pytest.mark.gpu
-
-ARITHS = ["f16x2", "bf16x3"]
-
-
-class _route:
-    """NVSR_RENDER_ONE_PHASE for the launches inside the block (the library reads it at every launch)"""
-
-    def __init__(self, one_phase):
-        self.value = "1" if one_phase else "0"
-
-    def __enter__(self):
-        self.old = os.environ.get("NVSR_RENDER_ONE_PHASE")
-        os.environ["NVSR_RENDER_ONE_PHASE"] = self.value
-
-    def __exit__(self, *exc):
-        if self.old is None:
-            os.environ.pop("NVSR_RENDER_ONE_PHASE", None)
-        else:
-            os.environ["NVSR_RENDER_ONE_PHASE"] = self.old
-
-
-def _same(a, b):
-    """torch.equal with NaNs: in the same places, and every number equal"""
-    na, nb = torch.isnan(a), torch.isnan(b)
-    return torch.equal(na, nb) and torch.equal(torch.nan_to_num(a, nan=0.0), torch.nan_to_num(b, nan=0.0))
-
-
-def _scene(hip, seed, H, W, plane_res=64):
-    from bench import make_synthetic_scene
-    mc, mf, sid, pose = make_synthetic_scene(DEV, plane_res=plane_res, view_res=16, seed=seed)
-    focal = 0.5 * W / np.tan(0.5 * 0.6911112)
-    ro, rd = hip.nerf_helpers.get_ray_bundle(H, W, focal, pose)
-    rays = hip.train_utils.pack_rays(ro, rd, 2.0, 6.0)
-    return mc, mf, rays
-
-
-def _pass(hip, model, rays, S, arith, one_phase, z=None, noise=None, white=0, lindisp=0):
-    """one render pass by the C ABI: with `z` nvsr_render_pass_arith (depths read; weights requested: the coarse kernel), without it the
-    coarse pass with its depths in registers (nvsr_render_pass3_coarse_z_launch).  Outputs start as NaN: an element a route does not write fails."""
-    capi = hip.capi
-    N = rays.shape[0]
-    assert N >= capi.fused_min_rays()
-    sc, keep = model.native_scene()
-    packed = model.packed_decoder()
-    out = dict(rgb=torch.full((N, 3), float("nan"), device=DEV), disp=torch.full((N,), float("nan"), device=DEV),
-               acc=torch.full((N,), float("nan"), device=DEV), weights=torch.full((N, S), float("nan"), device=DEV),
-               depth=torch.full((N,), float("nan"), device=DEV))
-    with _route(one_phase):
-        if z is not None:
-            capi.call("nvsr_render_pass_arith", C.byref(sc), capi.ptr(packed), N, S, capi.ptr(rays), capi.ptr(z), capi.ptr(noise), int(white),
-                      capi.ptr(out["rgb"]), capi.ptr(out["disp"]), capi.ptr(out["acc"]), capi.ptr(out["weights"]), capi.ptr(out["depth"]), None,
-                      capi.ARITHMETIC[arith], capi.stream())
-        else:
-            f = capi.lib().nvsr_render_pass3_coarse_z_launch
-            f.restype = C.c_int
-            f.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 7
-            st = f(capi.ARITHMETIC[arith], C.cast(C.byref(sc), C.c_void_p), capi.ptr(packed), N, S, capi.ptr(rays), int(lindisp), capi.ptr(noise), int(white),
-                   capi.ptr(out["rgb"]), capi.ptr(out["disp"]), capi.ptr(out["acc"]), capi.ptr(out["weights"]), capi.ptr(out["depth"]), None,
-                   capi.stream())
-            assert st == 0
-        torch.cuda.synchronize()
-    return out
-
 
 def _assert_routes_agree(hip, model, rays, S, arith, **kw):
     lib = hip.capi.lib()
     assert lib.nvsr_release_render_scratch() == 0
-    one = _pass(hip, model, rays, S, arith, True, **kw)
+    one, _ = _pass(hip, model, rays, S, arith, NVSR_RENDER_ONE_PHASE="1", **kw)
     assert lib.nvsr_render_scratch_bytes() == 0                  # the fused kernel needs no lists
-    two = _pass(hip, model, rays, S, arith, False, **kw)
+    two, _ = _pass(hip, model, rays, S, arith, NVSR_RENDER_ONE_PHASE="0", **kw)
     N = rays.shape[0]
     assert lib.nvsr_render_scratch_bytes() == 2 * 4 * N * S + 4 * N, "the two-phase route did not run"
-    for name in ("rgb", "disp", "acc", "depth", "weights"):
+    for name in OUTPUTS:
         print("two-phase vs fused, %s: %d elements differ" % (name, int((torch.nan_to_num(one[name]) != torch.nan_to_num(two[name])).sum())))
-    for name in ("rgb", "disp", "acc", "depth", "weights"):
+    for name in OUTPUTS:
         assert _same(one[name], two[name]), name
     return one, two
 
@@ -117,7 +54,7 @@ def test_frame_256x256_two_phase_equals_fused(hip, arith):
     for one_phase in (True, False):
         ws = torch.full((nws,), float("nan"), device=DEV)
         o = [torch.full(s, float("nan"), device=DEV) for s in ((N, 3), (N,), (N,), (N, 3), (N,), (N,))]
-        with _route(one_phase):
+        with _env(NVSR_RENDER_ONE_PHASE="1" if one_phase else "0"):
             capi.call("nvsr_render_rays_arith", C.byref(sc_c), capi.ptr(mc.packed_decoder()), capi.ptr(mf.packed_decoder()), N, Nc, Nf, capi.ptr(rays),
                       0, 0, None, None, None, None, *[capi.ptr(t) for t in o], capi.ptr(ws), capi.ARITHMETIC[arith], capi.stream())
             torch.cuda.synchronize()
@@ -193,12 +130,50 @@ def test_density_side_overflow_is_still_nan_and_raises_the_flag(hip):
             for one_phase in (True, False):
                 flag.reset()
                 assert hip.capi.lib().nvsr_release_render_scratch() == 0
-                outs.append(_pass(hip, mf, rays, S, "f16x2", one_phase, z=zz, white=1))
+                outs.append(_pass(hip, mf, rays, S, "f16x2", z=zz, white=1, NVSR_RENDER_ONE_PHASE="1" if one_phase else "0")[0])
                 assert (hip.capi.lib().nvsr_render_scratch_bytes() > 0) == (not one_phase)
                 words.append(int(flag.word))
             assert words == [1, 1], words
-            for name in ("rgb", "disp", "acc", "depth", "weights"):
+            for name in OUTPUTS:
                 assert _same(outs[0][name], outs[1][name]), name
             assert torch.isnan(outs[1]["rgb"]).any() and torch.isnan(outs[1]["acc"]).any()
     finally:
         flag.reset()
+
+
+def test_scratch_grows_across_launches_without_a_release(hip):
+    """The growth path of the lists' scratch (csrc/colour_order.hip), which every other test releases in front of each launch: four coarse
+    passes with their depths in registers (nvsr_render_pass3_coarse_z_launch: no minimum ray count), f16x2, one stream, no release in between
+      (a) N = 4096 + 513, S = 8       two blocks of the ray order, 19 groups, a ragged last group
+      (b) the same N, S = 24          the lists grow, the group buffer does not
+      (c) N = 2 * 4096 + 513, S = 24  both buffers grow
+      (d) (a) again                   nothing grows
+    each against the fused route bit for bit, and the scratch holds 2 * 4 N S + 4 N bytes of the LARGEST launch so far.  (e) what (d) left
+    behind is (d)'s: asking with (c)'s N is refused, (d)'s N gives the reference order of its live counts.  (f) released: nothing is held."""
+    capi = hip.capi
+    lib = capi.lib()
+    Na, Nc = 4096 + 513, 2 * 4096 + 513
+    mc, mf, rays = _scene(hip, 7, 96, 96, n_rays=Nc)
+    assert (Na + 255) // 256 == 19 and Na % 256 != 0
+    assert lib.nvsr_release_render_scratch() == 0 and lib.nvsr_render_scratch_bytes() == 0
+    largest = 0
+    for step, N, S in (("a", Na, 8), ("b", Na, 24), ("c", Nc, 24), ("d", Na, 8)):
+        r = rays[:N].contiguous()
+        one, _ = _pass(hip, mf, r, S, "f16x2", NVSR_RENDER_ONE_PHASE="1")
+        two, entries = _pass(hip, mf, r, S, "f16x2", NVSR_RENDER_ONE_PHASE="0")
+        for name in OUTPUTS:
+            assert _same(one[name], two[name]), "(%s) %s" % (step, name)
+        largest = max(largest, 2 * 4 * N * S + 4 * N)
+        assert lib.nvsr_render_scratch_bytes() == largest, step
+    # (e)
+    t = torch.full((Nc,), -1, dtype=torch.int32, device=DEV)
+    assert lib.nvsr_internal_copy_live_counts(t.data_ptr(), Nc, capi.stream()) == 1      # NVSR_ERR_SHAPE: the latest launch had Na rays
+    assert lib.nvsr_internal_copy_live_counts(t.data_ptr(), Na, capi.stream()) == 0
+    torch.cuda.synchronize()
+    c = (one["weights"] != 0).sum(1).cpu().numpy()
+    assert c.max() <= 8 and np.unique(c).size > 1                                         # the order has something to sort
+    want = order_reference(c, 8, lib.nvsr_internal_colour_order_bins())
+    assert np.array_equal(t[:Na].cpu().numpy(), want) and np.array_equal(entries, want)
+    assert bool((t[Na:] == -1).all())
+    # (f)
+    assert lib.nvsr_release_render_scratch() == 0 and lib.nvsr_render_scratch_bytes() == 0

@@ -23,9 +23,9 @@ for S in (64, 128):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
             if name == "limb":
-                st = lib.nvsr_decode_rays_limb_launch(C.c_int(2), C.byref(sc), capi.ptr(packed), C.c_int64(N), C.c_int(S), capi.ptr(rays), capi.ptr(z), capi.ptr(raw), capi.ptr(gates), None, capi.stream())
+                st = lib.nvsr_decode_rays_limb_launch(2, C.byref(sc), capi.ptr(packed), N, S, capi.ptr(rays), capi.ptr(z), capi.ptr(raw), capi.ptr(gates), None, capi.stream())
             else:
-                st = lib.nvsr_decode_rays_pair_launch(C.byref(sc), capi.ptr(packed), C.c_int64(N), C.c_int(S), capi.ptr(rays), capi.ptr(z), capi.ptr(raw), capi.ptr(gates), capi.stream())
+                st = lib.nvsr_decode_rays_pair_launch(C.byref(sc), capi.ptr(packed), N, S, capi.ptr(rays), capi.ptr(z), capi.ptr(raw), capi.ptr(gates), capi.stream())
             b.record(); torch.cuda.synchronize(); ts.append(a.elapsed_time(b))
             assert st == 0
         t = min(ts[2:])

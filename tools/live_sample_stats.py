@@ -8,7 +8,7 @@ E[max live count] / S over a 32-ray tile, a wave's 64 rays and a workgroup's 256
 workgroup: that last figure is the share of the colour work that is left), and how many tiles / tile pairs are dead as a whole at a sample index
 (what skipping whole tiles could save).
 
-Then, per pass, what the colour pass's ray order (live_order_kernel, csrc/render3.hip) can recover: the sum over workgroups of trip /
+Then, per pass, what the colour pass's ray order (live_order_kernel, csrc/colour_order.hip) can recover: the sum over workgroups of trip /
 (workgroups x S) for (a) the grouping of the density pass (256 consecutive rays), (b) the rays stably sorted by live count, descending, inside
 each block of 4096 consecutive rays and cut into groups of 256, (c) the same with the count quantised as the kernel does it -- bin =
 ceil(count x B / S): one bin for the empty rays and B bins of equal width over 1..S -- for B = 8, 16, 32; and (d) for each of them the sum

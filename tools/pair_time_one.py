@@ -21,7 +21,7 @@ for S in (64, 128):
     for i in range(10):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
-        st = lib.nvsr_decode_rays_pair_launch(C.byref(sc), capi.ptr(packed), C.c_int64(N), C.c_int(S), capi.ptr(rays), capi.ptr(z), capi.ptr(raw), capi.ptr(gates), capi.stream())
+        st = lib.nvsr_decode_rays_pair_launch(C.byref(sc), capi.ptr(packed), N, S, capi.ptr(rays), capi.ptr(z), capi.ptr(raw), capi.ptr(gates), capi.stream())
         b.record(); torch.cuda.synchronize(); ts.append(a.elapsed_time(b))
     out.append("S=%d %.3f" % (S, min(ts[2:])))
 print("  ".join(out))
