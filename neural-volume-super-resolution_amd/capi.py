@@ -232,6 +232,10 @@ _PROTOS_OPTIONAL = {   # feature-plane super-resolution (csrc/sr.hip)
 # launch symbols behind the entry points above (csrc/nvsr_internal.h) that tests and tools call directly: bound like the others, but no part
 # of include/nvsr.h and so not of exported_symbols()
 _PROTOS_LAUNCH = {
+    # the two-tile render passes behind nvsr_render_pass_arith, which sends fewer than 16 384 rays to the first-generation kernel: like the
+    # coarse_z launch they have no minimum ray count (and check no argument: the caller passes what nvsr_render_pass_arith would accept)
+    "nvsr_render_pass2_launch": ([C.POINTER(Scene), _vp, _i64, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i),
+    "nvsr_render_pass3_launch": ([_i, C.POINTER(Scene), _vp, _i64, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i),
     "nvsr_render_pass3_coarse_z_launch": ([_i, C.POINTER(Scene), _vp, _i64, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i),
     "nvsr_decode_rays_limb_launch": ([_i, C.POINTER(Scene), _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp], _i),
     "nvsr_decode_rays_pair_launch": ([C.POINTER(Scene), _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp], _i),

@@ -638,7 +638,7 @@ __global__ __launch_bounds__(WPB * 64) void composite_kernel(long N, int S, cons
             if (mip) zs = __fmul_rn(0.5f, __fadd_rn(zs, zr[s + 1]));
             float sig = rv[3];
             if (noise) sig = __fadd_rn(sig, noise[ray * S + s]);
-            sig = fmaxf(sig, 0.0f);
+            sig = sig < 0.0f ? 0.0f : sig;          // compare + select: a NaN stays a NaN (fmaxf would make it an empty sample), side_work.h
             const float alpha = __fsub_rn(1.0f, expf(-__fmul_rn(sig, dist)));
             fac = __fadd_rn(__fsub_rn(1.0f, alpha), 1e-10f);
             w = alpha;

@@ -145,7 +145,10 @@ __global__ __launch_bounds__(TPB, 1) void render_pass_kernel(SceneDev sc, const 
         // volume_render_radiance_field, one sample (volume_rendering_utils.py:18-45)
         const float nrm = reinterpret_cast<const f32x4*>(rc)[1][2];
         const float dist = __fmul_rn((s + 1 < S) ? __fsub_rn(zn, zc) : 1e10f, nrm);
-        const float sig = fmaxf(__fadd_rn(raw[3], nzs), 0.0f);
+        // relu(sigma + noise) by compare + select, as composite_sample (side_work.h): a NaN stays a NaN like torch.relu's; fmaxf returns its
+        // non-NaN operand and made a NaN density an empty sample -- a finite wrong pixel
+        const float sn = __fadd_rn(raw[3], nzs);
+        const float sig = sn < 0.0f ? 0.0f : sn;
         const float alpha = __fsub_rn(1.0f, expf(-__fmul_rn(sig, dist)));
         const float w = __fmul_rn(alpha, T);
         T = __fmul_rn(T, __fadd_rn(__fsub_rn(1.0f, alpha), 1e-10f));

@@ -529,7 +529,8 @@ __global__ __launch_bounds__(CB_WPB * 64) void composite_backward_kernel(long N,
         if (s < S) {
             const f32x4 rv = rr[s];
             const float dist = ((mip || s + 1 < S) ? (z[ray * zp + s + 1] - z[ray * zp + s]) : 1e10f) * nrm;
-            const float sig = fmaxf(rv[3] + (noise ? noise[ray * S + s] : 0.0f), 0.0f);
+            const float sn = rv[3] + (noise ? noise[ray * S + s] : 0.0f);
+            const float sig = sn < 0.0f ? 0.0f : sn;      // (the forward's relu, aux.hip composite_kernel: a NaN density stays a NaN here too)
             alpha = 1.0f - expf(-sig * dist);
             fac = (1.0f - alpha) + 1e-10f;
             gw = g0 / (1.0f + expf(-rv[0])) + g1 / (1.0f + expf(-rv[1])) + g2 / (1.0f + expf(-rv[2])) + ga;

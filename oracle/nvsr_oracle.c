@@ -269,7 +269,7 @@ static void orc_composite_ray(int S, const float* raw /*[S,4]*/, const float* z,
     for (int s = 0; s < S; ++s) {
         const float dist = ((s == S - 1) ? 1e10f : (z[s + 1] - z[s])) * nrm;
         float sig = raw[4 * s + 3] + (noise ? noise[s] : 0.0f);
-        sig = sig > 0.0f ? sig : 0.0f;
+        sig = sig < 0.0f ? 0.0f : sig; /* torch.relu: a NaN stays a NaN */
         const float alpha = 1.0f - expf(-sig * dist);
         const float w = alpha * T;
         T = T * (1.0f - alpha + 1e-10f);
@@ -307,7 +307,7 @@ ORC_EXPORT void orc_composite_mip(long N, int S, const float* raw, const float* 
         for (int s = 0; s < S; ++s) {
             const float dist = (zz[s + 1] - zz[s]) * nrm;
             float sig = rw[4 * s + 3] + (noise ? noise[(size_t)i * S + s] : 0.0f);
-            sig = sig > 0.0f ? sig : 0.0f;
+            sig = sig < 0.0f ? 0.0f : sig;
             const float alpha = 1.0f - expf(-sig * dist);
             const float w = alpha * T;
             T = T * (1.0f - alpha + 1e-10f);
