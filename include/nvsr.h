@@ -166,7 +166,21 @@ uint32_t* nvsr_get_range_flag(void);
  * The density and fused kernels keep their mapping (XCD x runs the x-th contiguous eighth of the ray blocks); group_slot holds that same
  * mapping with NVSR_COLOUR_GROUP_ORDER=0 (read at every launch, for an A/B) and beyond what the one workgroup sorts: G > 4096 or S > 511.
  * A ray's sums do not depend on the workgroup that holds them: same bits.  The 2 G ints are kept in a buffer of their own beside the lists'
- * (same owner, growth and release; 20 KB at the benchmark size); nvsr_render_scratch_bytes counts the lists' buffer alone. */
+ * (same owner, growth and release; 20 KB at the benchmark size); nvsr_render_scratch_bytes counts the lists' buffer alone.
+ * Point-major colour pass (the default).  The lockstep kernels above give a lane a ray and walk all 256 rays of a workgroup to their k-th live
+ * sample together: the k-th samples of different rays lie at unrelated depths (one gather instruction touches texels all over a plane) and
+ * the workgroup runs as many steps as its fullest ray.  Nothing in a pixel depends on the lane that evaluates a point, only on the order of a
+ * ray's additions.  So point_order_kernel (behind the two orders above, one workgroup per group) lists the live points of a group's 256 slots
+ * in the order (depth band, slot, k) -- k = the index into the ray's list; band = s * B / S of the sample index s (depths in registers), else
+ * ((z - near) * B) / (far - near) truncated and clamped, made monotone along the ray; B = S bands, one per sample (measured against 4, 8 and 16) -- cuts the sequence into steps of
+ * 256 points, sorts every step by (slot, k) so that a ray's points of a step are one run, and pads the last step.  The kernels
+ * render_pass3_points[_z]_kernel run ceil(points / 256) steps, a lane one point per step: the ray's constants come from the workgroup's ray cache
+ * by the entry's slot, its view features from a table the kernel's prologue writes (48 floats per slot), and the point's three terms
+ * w sigmoid(raw) go through LDS to the first lane of the run, which adds the run's terms in order to the ray's sums in LDS -- the operands and
+ * the order of the lockstep kernels: same bits.  Buffers, owned, grown and released like the lists' and not counted by
+ * nvsr_render_scratch_bytes: 256 G S + 2 G ints (entries (slot << 24) | k, group g's at 256 g S; step counts; offsets in steps) and 48 * 256 G
+ * floats of view features.  NVSR_COLOUR_POINTS=0 (read at every launch) selects the lockstep kernels, as does a buffer that cannot be had or
+ * G S >= 2^31; NVSR_COLOUR_ORDER, NVSR_COLOUR_GROUP_ORDER and NVSR_RENDER_ONE_PHASE keep their meaning and the order of dispatch is group_slot. */
 int nvsr_release_render_scratch(void);
 int64_t nvsr_render_scratch_bytes(void);
 /* Internal hooks of that order (tests and tools; not part of the stable interface).  nvsr_internal_group_order: group_order_kernel alone on
@@ -180,6 +194,16 @@ int nvsr_internal_copy_group_order(int* dst, int64_t G, nvsr_stream_t stream);
 int nvsr_internal_live_order(int* live_n, int64_t N, int S, nvsr_stream_t stream);
 int nvsr_internal_colour_order_bins(void);
 int nvsr_internal_copy_live_counts(int* dst, int64_t N, nvsr_stream_t stream);
+/* Internal hooks of the order of points.  nvsr_internal_point_order: point_order_kernel alone on a caller's N packed entries of the ray order
+ * and [N, S] lists (device memory) -- rays = NULL: the lists hold sample indices as int bits; else depths, and rays[ray * 11 + 6 .. 7] the
+ * ray's near and far; bands: 1..S, anything else a band per sample -> points[256 G S], steps[G], offsets[G] (in steps of 256 entries),
+ * G = ceil(N / 256); behind a group's steps[g] * 256 entries its part of `points` is not written.  nvsr_internal_point_bands: the product's
+ * number of bands (0: a band per sample).  nvsr_internal_copy_point_steps: the step counts the latest two-phase launch on `stream` left ->
+ * dst (G ints, device or host memory; G must be that launch's); NVSR_ERR_SHAPE when that launch ran the lockstep colour kernels. */
+int nvsr_internal_point_order(const int* entries, const float* lists, const float* rays, int64_t N, int S, int bands, int* points, int* steps, int* offsets,
+                              nvsr_stream_t stream);
+int nvsr_internal_point_bands(void);
+int nvsr_internal_copy_point_steps(int* dst, int64_t G, nvsr_stream_t stream);
 /* The arithmetic primitive alone (test hook, one wavefront): Y[32][32] = W[32][K] X[K][32] (row-major f32, K a multiple of 16) with the
  * operands split and multiplied exactly as the kernels of `arithmetic` do it (NVSR_ARITH_F32 | _BF16X3 | _F16X2, incl. the static scales of
  * F16X2) -- lets a test put chosen mantissas / magnitudes through the products that replace models.py:381-421's nn.Linear GEMMs. */

@@ -177,6 +177,9 @@ _PROTOS_OPTIONAL = {   # feature-plane super-resolution (csrc/sr.hip)
     "nvsr_internal_live_order": ([_vp, _i64, _i, _vp], _i),
     "nvsr_internal_colour_order_bins": ([], _i),
     "nvsr_internal_copy_live_counts": ([_vp, _i64, _vp], _i),
+    "nvsr_internal_point_bands": ([], _i),
+    "nvsr_internal_copy_point_steps": ([_vp, _i64, _vp], _i),
+    "nvsr_internal_point_order": ([_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp], _i),
     "nvsr_set_sr_plane_interp": ([_i], _i),
     "nvsr_get_sr_plane_interp": ([], _i),
     "nvsr_set_sr_align_corners": ([_i], _i),

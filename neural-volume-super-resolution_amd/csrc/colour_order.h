@@ -14,8 +14,19 @@ constexpr int ORDER_SHIFT = 12, ORDER_RAYS = 1 << ORDER_SHIFT, ORDER_BINS = 32;
 constexpr int ORDER_MAX_S = 1 << (31 - ORDER_SHIFT);      // a count has to fit above the index
 static_assert(ORDER_RAYS % RAYS2 == 0, "a block of the ray order is a whole number of workgroups");
 
+// The point-major colour pass (point_order_kernel, colour_order.hip; render3.hip PHASE 3): a group's live points in the order (band, slot, k),
+// POINT_BANDS depth bands over a ray's near..far (0: a band per sample), cut into steps of RAYS2 points; an entry is (slot << 24) | k.
+// POINT_BANDS = 0 is measured (profiles/colour_points_ab.txt): 4, 8 and 16 bands leave the fine colour kernel 1.2, 0.7 and 0.5 ms
+// slower -- the finer the bands, the closer a wave's points lie, and a band per sample also keeps the runs of a step short.
+#ifndef NVSR_POINT_BANDS
+#define NVSR_POINT_BANDS 0
+#endif
+constexpr int POINT_BANDS = NVSR_POINT_BANDS, POINT_NONE = -1, POINT_VIEW_FLOATS = 2 * HALF_C;
+static_assert(RAYS2 <= 256 && ORDER_MAX_S <= (1 << 24), "a slot and a list index share an entry");
+
 // the lists of one two-phase launch, in the library's scratch: z, w [N, S] rows, n [N]; slot, trip: [G] each, G = ceil(N / RAYS2)
-struct LiveLists { float* z; float* w; int* n; int* slot; int* trip; };
+// pts: the point-major route's entries, [G RAYS2 S]; steps [G], then offs [G]; views [G RAYS2, POINT_VIEW_FLOATS] -- all NULL: the lockstep colour kernels
+struct LiveLists { float* z; float* w; int* n; int* slot; int* trip; int* pts; int* steps; float* views; };
 
 // The two-phase route is taken unless the caller wants the raw decoder outputs, NVSR_RENDER_ONE_PHASE=1 is set (the A/B handle), the stream
 // is being captured (the scratch cannot grow inside a capture), a count would not fit into a packed entry of the ray order (S >= 2^19) or the
@@ -23,5 +34,7 @@ struct LiveLists { float* z; float* w; int* n; int* slot; int* trip; };
 bool two_phase_lists(const float* raw_out, int64_t N, int S, hipStream_t stream, LiveLists& out, bool launch = true);
 // the ray order, then the order of dispatch: between the density and the colour launch
 void launch_colour_order(const LiveLists& ll, int64_t N, int S, hipStream_t stream);
+// the order of points, behind the two orders above (ll.pts != NULL); rays_nf: the packed rays (near, far) when the lists hold depths, NULL when sample indices
+void launch_point_order(const LiveLists& ll, const float* rays_nf, int64_t N, int S, hipStream_t stream);
 
 }  // namespace nvsr

@@ -151,6 +151,84 @@ __global__ __launch_bounds__(SORT_TPB) void group_order_kernel(const int* __rest
     }
 }
 
+// ---- the point-major colour pass's order of points: packed entries + live lists -> per group, its live points in steps of 256 -------------------
+// The point-major colour kernels (render3.hip, PHASE 3) give a lane one live POINT per step, not a ray.  One workgroup per group of RAYS2 slots
+// (the rays that the packed entries name for it); thread j is slot j.  A group's points are taken in the order (band, slot, k), k = the index
+// into the ray's live list, band = a monotone function of the point's depth -- ZCOMP lists (rays_nf = NULL) hold the sample index s: band =
+// s nb / S; otherwise band = (z - near) nb / (far - near), truncated and clamped to 0..nb-1 -- made monotone along the ray by a running
+// maximum, so the order keeps every ray's sample order whatever the lists hold.  The sequence is cut into steps of 256 and every step is
+// stably sorted by (slot, k): a ray's points of a step are one contiguous run (the kernel's run heads add them to the ray's sums in order).
+// A step's points of one ray are consecutive k (the sequence holds a ray's points in k order and a step is a window of it), so the place in
+// its run is k - the smallest k of that slot in the step.  Group g's entries (slot << 24) | k start at pts[g RAYS2 S] -- a fixed offset, no
+// scan over the groups; steps[g] = ceil(total / 256), offs[g] = g S = that offset in steps; the last step is padded with POINT_NONE.
+// Deterministic: integer prefix sums in thread order; the two LDS atomics (a minimum and a count per slot) give the same result in any order.
+__global__ __launch_bounds__(RAYS2) void point_order_kernel(const int* __restrict__ live_n, const float* __restrict__ live_z, const float* __restrict__ rays_nf,
+                                                            long N, int S, int nb, int* __restrict__ pts, int* __restrict__ steps, int* __restrict__ offs) {
+    __shared__ int wsum_s[2][RAYS2 / 64], kmin_s[RAYS2], cnt_s[RAYS2], start_s[RAYS2], stage_s[RAYS2];
+    const int j = threadIdx.x, wave = j >> 6, lane = j & 63;
+    const long slot0 = (long)blockIdx.x * RAYS2;
+    int n = 0;
+    long ray = 0;
+    if (slot0 + j < N) {
+        const int e = live_n[slot0 + j];
+        n = e >> ORDER_SHIFT;
+        ray = slot0 / ORDER_RAYS * ORDER_RAYS + (e & (ORDER_RAYS - 1));
+    }
+    const float* lz = live_z + ray * S;
+    const float nr = rays_nf ? rays_nf[ray * 11 + 6] : 0.0f, fr = rays_nf ? rays_nf[ray * 11 + 7] : 0.0f;
+    auto band_of = [&](int k) -> int {
+        const float e = lz[k];
+        if (!rays_nf) {
+            const long long b = (long long)__float_as_int(e) * nb / S;
+            return b < 0 ? 0 : b < nb ? (int)b : nb - 1;
+        }
+        const float u = __fdiv_rn(__fmul_rn(__fsub_rn(e, nr), (float)nb), __fsub_rn(fr, nr));
+        return u >= 0.0f ? (u < (float)nb ? (int)u : nb - 1) : 0;      // (a NaN goes to band 0)
+    };
+    // exclusive prefix sum of c over the workgroup's threads, and the total; buffer `buf` of the wave sums (two: one barrier per call)
+    auto scan = [&](int c, int buf, int& total) -> int {
+        int incl = c;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(incl, o); if (lane >= o) incl += v; }
+        if (lane == 63) wsum_s[buf][wave] = incl;
+        __syncthreads();
+        int before = 0;
+        total = 0;
+#pragma unroll
+        for (int w = 0; w < RAYS2 / 64; ++w) { const int v = wsum_s[buf][w]; if (w < wave) before += v; total += v; }
+        return before + incl - c;
+    };
+    int* out = pts + (long)blockIdx.x * RAYS2 * S;
+    int k = 0, base = 0, nextb = n > 0 ? band_of(0) : nb;
+    for (int b = 0; b < nb; ++b) {
+        const int k0 = k;
+        while (k < n && nextb <= b) { ++k; if (k < n) nextb = max(nextb, band_of(k)); }
+        int total;
+        const int at = base + scan(k - k0, b & 1, total);
+        for (int i = k0; i < k; ++i) out[at + (i - k0)] = (j << 24) | i;
+        base += total;
+    }
+    const int nsteps = (base + RAYS2 - 1) / RAYS2;
+    if (base + j < nsteps * RAYS2) out[base + j] = POINT_NONE;      // (the padding: fewer than RAYS2 entries)
+    if (j == 0) { steps[blockIdx.x] = nsteps; offs[blockIdx.x] = (int)blockIdx.x * S; }
+    __syncthreads();                                               // the sequence, written by other threads, is read below
+    for (int t = 0; t < nsteps; ++t) {
+        const int e = out[t * RAYS2 + j];
+        const bool valid = e != POINT_NONE;
+        const int sl = (int)((unsigned)e >> 24), kk = e & 0xffffff;
+        kmin_s[j] = 0x7fffffff; cnt_s[j] = 0;
+        __syncthreads();
+        if (valid) { atomicMin(&kmin_s[sl], kk); atomicAdd(&cnt_s[sl], 1); }
+        __syncthreads();
+        int total;
+        start_s[j] = scan(cnt_s[j], 0, total);
+        __syncthreads();
+        stage_s[valid ? start_s[sl] + (kk - kmin_s[sl]) : j] = e;     // (padding follows every point of the step: it keeps its place)
+        __syncthreads();
+        out[t * RAYS2 + j] = stage_s[j];
+    }
+}
+
 // ---- scratch of the two-phase route: the live lists, [N, S] depths + [N, S] weights + [N] counts ------------------------------------
 // Owned by the library, one buffer per (device, stream), grow-only: two launches on one stream are ordered, launches on two streams never
 // share a buffer.  Growing frees the old buffer with hipFree, which waits for the device -- no launch can still be using it.
@@ -159,9 +237,11 @@ __global__ __launch_bounds__(SORT_TPB) void group_order_kernel(const int* __rest
 // The order of dispatch (group_order_kernel) takes 2 G ints more, G = ceil(N / RAYS2): group_slot[G], then group_trip[G].  They live in a
 // small buffer of their own beside the lists (20 KB at the benchmark size), with the same owner, growth and release;
 // nvsr_render_scratch_bytes keeps counting the lists' buffer alone.
+// The point-major colour pass (point_order_kernel) takes two buffers more, same owner, growth and release, not counted either: `points` --
+// G RAYS2 S ints of entries, then steps[G] and offs[G] -- and `views`, the view features of every slot, POINT_VIEW_FLOATS floats each.
 namespace {
 struct Buffer { void* p; size_t bytes; };
-struct LiveScratch { int device; hipStream_t stream; Buffer lists, group; int* last_n; int64_t last_N; };      // last_*: the counts of the latest launch
+struct LiveScratch { int device; hipStream_t stream; Buffer lists, group, points, views; int* last_n; int64_t last_N; int* last_steps; };      // last_*: the counts of the latest launch; its points' step counts
 std::mutex g_live_mutex;
 std::vector<LiveScratch> g_live;
 
@@ -176,7 +256,7 @@ bool grow(LiveScratch& e, Buffer& b, size_t bytes) {
     if (b.bytes >= bytes) return true;
     if (b.p) (void)hipFree(b.p);
     b = Buffer{nullptr, 0};
-    e.last_n = nullptr; e.last_N = 0;
+    e.last_n = nullptr; e.last_N = 0; e.last_steps = nullptr;
     void* p = nullptr;
     if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
     b = Buffer{p, bytes};
@@ -213,6 +293,10 @@ void launch_group_order(const int* group_trip, int64_t G, int S, int* group_slot
     const int sorted = !env_starts("NVSR_COLOUR_GROUP_ORDER", '0');
     hipLaunchKernelGGL(group_order_kernel, dim3(1), dim3(SORT_TPB), 0, stream, group_trip, (int)G, S, sorted, group_slot);
 }
+void launch_point_order(const int* live_n, const float* live_z, const float* rays_nf, int64_t N, int S, int nb, int* pts, int* steps, int* offs, hipStream_t stream) {
+    nb = nb < 1 || nb > S ? S : nb;      // (POINT_BANDS = 0: a band per sample)
+    hipLaunchKernelGGL(point_order_kernel, dim3((unsigned)((N + RAYS2 - 1) / RAYS2)), dim3(RAYS2), 0, stream, live_n, live_z, rays_nf, (long)N, S, nb, pts, steps, offs);
+}
 }  // namespace
 
 bool two_phase_lists(const float* raw_out, int64_t N, int S, hipStream_t stream, LiveLists& out, bool launch) {
@@ -224,7 +308,7 @@ bool two_phase_lists(const float* raw_out, int64_t N, int S, hipStream_t stream,
     const size_t rows = (size_t)N * (size_t)S * sizeof(float), G = (size_t)((N + RAYS2 - 1) / RAYS2);
     std::lock_guard<std::mutex> lock(g_live_mutex);
     LiveScratch* e = find_scratch(device, stream);
-    if (!e) { g_live.push_back(LiveScratch{device, stream, Buffer{nullptr, 0}, Buffer{nullptr, 0}, nullptr, 0}); e = &g_live.back(); }
+    if (!e) { g_live.push_back(LiveScratch{device, stream, Buffer{nullptr, 0}, Buffer{nullptr, 0}, Buffer{nullptr, 0}, Buffer{nullptr, 0}, nullptr, 0, nullptr}); e = &g_live.back(); }
     if (!grow(*e, e->group, 2 * G * sizeof(int)) || !grow(*e, e->lists, 2 * rows + (size_t)N * sizeof(int)) || !e->lists.p) return false;
     char* p = static_cast<char*>(e->lists.p);
     out.z = reinterpret_cast<float*>(p);
@@ -232,13 +316,27 @@ bool two_phase_lists(const float* raw_out, int64_t N, int S, hipStream_t stream,
     out.n = reinterpret_cast<int*>(p + 2 * rows);
     out.slot = static_cast<int*>(e->group.p);
     out.trip = out.slot + G;
-    if (launch) { e->last_n = out.n; e->last_N = N; }      // (a reservation leaves no counts behind)
+    // the point-major route's buffers (NVSR_COLOUR_POINTS=0, or a buffer that cannot be had: the lockstep colour kernels)
+    out.pts = nullptr; out.steps = nullptr; out.views = nullptr;
+    const size_t npts = G * RAYS2 * (size_t)S;
+    if (!env_starts("NVSR_COLOUR_POINTS", '0') && G * (size_t)S <= 0x7fffffffu && grow(*e, e->points, (npts + 2 * G) * sizeof(int)) &&
+        grow(*e, e->views, G * RAYS2 * POINT_VIEW_FLOATS * sizeof(float))) {
+        out.pts = static_cast<int*>(e->points.p);
+        out.steps = out.pts + npts;
+        out.views = static_cast<float*>(e->views.p);
+    }
+    if (launch) { e->last_n = out.n; e->last_N = N; e->last_steps = out.steps; }      // (a reservation leaves no counts behind)
     return true;
 }
 
 void launch_colour_order(const LiveLists& ll, int64_t N, int S, hipStream_t stream) {
     launch_live_order(ll.n, N, S, env_starts("NVSR_COLOUR_ORDER", '0') ? 0 : ORDER_BINS, ll.trip, stream);
     launch_group_order(ll.trip, (N + RAYS2 - 1) / RAYS2, S, ll.slot, stream);
+}
+
+void launch_point_order(const LiveLists& ll, const float* rays_nf, int64_t N, int S, hipStream_t stream) {
+    const int64_t G = (N + RAYS2 - 1) / RAYS2;
+    launch_point_order(ll.n, ll.z, rays_nf, N, S, POINT_BANDS, ll.pts, ll.steps, ll.steps + G, stream);
 }
 
 }  // namespace nvsr
@@ -263,6 +361,30 @@ extern "C" int nvsr_internal_group_order(const int* trips, int64_t G, int S, int
 }
 extern "C" int nvsr_internal_copy_group_order(int* dst, int64_t G, nvsr_stream_t stream) { return copy_left_behind(dst, G, true, (hipStream_t)stream); }
 
+// test hooks of the order of points (include/nvsr.h)
+extern "C" int nvsr_internal_point_bands(void) { return POINT_BANDS; }
+extern "C" int nvsr_internal_point_order(const int* entries, const float* lists, const float* rays, int64_t N, int S, int bands, int* points, int* steps, int* offsets,
+                                         nvsr_stream_t stream) {
+    if (!entries || !lists || !points || !steps || !offsets) return NVSR_ERR_NULL;
+    const int64_t G = (N + RAYS2 - 1) / RAYS2;
+    if (N < 1 || S < 1 || S >= ORDER_MAX_S || G * S > 0x7fffffff) return NVSR_ERR_SHAPE;
+    launch_point_order(entries, lists, rays, N, S, bands, points, steps, offsets, (hipStream_t)stream);
+    return NVSR_CHECK_LAUNCH();
+}
+extern "C" int nvsr_internal_copy_point_steps(int* dst, int64_t G, nvsr_stream_t stream) {
+    if (!dst) return NVSR_ERR_NULL;
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) return NVSR_ERR_LAUNCH;
+    const int* src = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(g_live_mutex);
+        const LiveScratch* c = find_scratch(device, (hipStream_t)stream);
+        if (c && c->last_n && c->last_steps && (c->last_N + RAYS2 - 1) / RAYS2 == G) src = c->last_steps;
+    }
+    if (!src) return NVSR_ERR_SHAPE;      // (also: the latest launch ran the lockstep colour kernels)
+    return hipMemcpyAsync(dst, src, (size_t)G * sizeof(int), hipMemcpyDefault, (hipStream_t)stream) == hipSuccess ? NVSR_OK : NVSR_ERR_LAUNCH;
+}
+
 // a frame's driver knows its largest pass before the first launch: sizing the buffer for it up front keeps the growth (a device-wide
 // wait) out of the frame -- between the coarse and the fine pass (aux.hip).  Does nothing where the two-phase route would not be taken.
 extern "C" void nvsr_internal_reserve_render_scratch(int64_t N, int S, nvsr_stream_t stream) {
@@ -283,7 +405,7 @@ extern "C" int nvsr_release_render_scratch(void) {
     const bool have_prev = hipGetDevice(&prev) == hipSuccess;
     int rc = NVSR_OK;
     for (const LiveScratch& c : g_live)
-        for (void* p : {c.lists.p, c.group.p})
+        for (void* p : {c.lists.p, c.group.p, c.points.p, c.views.p})
             if (p && (hipSetDevice(c.device) != hipSuccess || hipFree(p) != hipSuccess)) rc = NVSR_ERR_LAUNCH;
     g_live.clear();
     if (have_prev) (void)hipSetDevice(prev);

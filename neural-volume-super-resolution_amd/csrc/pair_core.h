@@ -75,7 +75,13 @@ struct Lds3 {
     static constexpr int FAR = LIMBS == 2 ? VTAPS + RAYS2 * TAP_FLOATS : -1;
     static constexpr int RES = VTAPS + RAYS2 * TAP_FLOATS + (LIMBS == 2 ? RAYS2 : 0);
     static constexpr int RES_KB = LIMBS == 2 ? 9 : 0;
-    static constexpr int TOTAL = RES + RES_KB * kb_words(LIMBS);
+    // the point-major colour pass's exchange (render3.hip, PHASE 3): the rays' colour sums and a step's terms, 3 RAYS2 floats each, the step's
+    // slots and the slots' rays, RAYS2 ints each -- 8 KB.  f16 limbs have under 1 KB to spare: the region is the taps' (dead after the prologue
+    // while R3_BOUNCE is off), so neither the ring nor the resident weights pay for it; 3 bf16 limbs have the room behind the ring.
+    static constexpr int PTS_WORDS = 8 * RAYS2;
+    static constexpr int PTS = LIMBS == 2 ? VTAPS : RES + RES_KB * kb_words(LIMBS);
+    static_assert(LIMBS != 2 || RAYS2 * TAP_FLOATS >= PTS_WORDS, "the points' region fits the taps'");
+    static constexpr int TOTAL = RES + RES_KB * kb_words(LIMBS) + (LIMBS == 2 ? 0 : PTS_WORDS);
 };
 static_assert(Lds3<3>::TOTAL * 4 <= 160 * 1024 && Lds3<2>::TOTAL * 4 <= 160 * 1024, "LDS budget");
 

@@ -40,6 +40,14 @@ namespace nvsr {
 //       owns the ray entry j names, for the whole launch: a workgroup's 256 rays then have similar counts and trip is close to each of them.
 //       A slot >= N is invalid as before (clamped ray, count 0, nothing written).  A ray's sums and the order of its additions do not depend
 //       on the lane that holds them, so the pixels do not change.  NVSR_COLOUR_ORDER=0 (read at every launch) makes every entry name its own slot.
+//   3 = point-major colour pass (the default; NVSR_COLOUR_POINTS=0 keeps phase 2): the same rgb chain, but a lane evaluates one live POINT per
+//       step, not its ray's k-th: point_order_kernel (colour_order.hip) lists the points of the workgroup's 256 slots in the order (depth band,
+//       slot, k), cut into steps of 256 and sorted by (slot, k) inside a step, and the loop runs the group's ceil(points / 256) steps -- no
+//       padding but in the last step, and the 64 points of a wave are a few rays x consecutive samples of one band: neighbouring texels.
+//       A lane no longer owns a ray: the ray cache is indexed by the entry's slot; the view features V, blended in the prologue as before, go to
+//       a global table (POINT_VIEW_FLOATS per slot, 48 KB per group) and each step loads its points' rows, a step ahead; every lane stores its
+//       point's three terms w sigmoid(raw) in LDS, and behind a barrier the first point of every run adds its run's terms, in order, to the
+//       ray's sums in LDS: the same operands in the same order as phase 2.  Entries are read two steps ahead, list entries one.
 // Neither chain's K-order changes and dead samples contributed +0.0 to non-negative sums, so the pixels are bit for bit the fused pass's.
 template <int LZ>
 __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const float* __restrict__ packed, long N, int S,
@@ -49,11 +57,12 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
                                                   float* __restrict__ acc, float* __restrict__ weights,
                                                   float* __restrict__ depth, float* __restrict__ raw_out, unsigned* __restrict__ flag,
                                                   float* __restrict__ live_z = nullptr, float* __restrict__ live_w = nullptr,
-                                                  int* __restrict__ live_n = nullptr, const int* __restrict__ group_slot = nullptr) {
+                                                  int* __restrict__ live_n = nullptr, const int* __restrict__ group_slot = nullptr,
+                                                  const int* __restrict__ pts = nullptr, const int* __restrict__ pt_steps = nullptr, float* views = nullptr) {
     constexpr int LIMBS = LZ & 7;
     constexpr bool ZCOMP = (LZ & 8) != 0;
     constexpr int PHASE = (LZ >> 4) & 3;
-    constexpr bool FUSED = PHASE == 0, DENSITY = PHASE == 1, COLOUR = PHASE == 2;
+    constexpr bool FUSED = PHASE == 0, DENSITY = PHASE == 1, POINTS = PHASE == 3, COLOUR = PHASE == 2 || POINTS;
     using L = Lds3<LIMBS>;
     constexpr int NP = limb_products(LIMBS);
     constexpr int NSF = 3 * 4 * NP, NSH = 4 * 4 * NP;          // slots of a feature block / of half a hidden layer
@@ -95,7 +104,8 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
         if (validY) { const int e = live_n[base + 32]; rayY = block_base + (e & (ORDER_RAYS - 1)); nY = e >> ORDER_SHIFT; }
     }
     constexpr int RAY3_FLOATS = L::RAY_FLOATS;
-    float* rcX = ldsf + L::RAYS + (rs.wave * 64 + (lane0 & 31)) * RAY3_FLOATS;
+    const int ownX = rs.wave * 64 + (lane0 & 31), ownY = ownX + 32;      // the slots whose ray the lane loads (and, but for POINTS, owns)
+    float* rcX = ldsf + L::RAYS + ownX * RAY3_FLOATS;
     float* rcY = rcX + 32 * RAY3_FLOATS;
     float* rtX = LIMBS == 2 ? ldsf + L::VTAPS + (rs.wave * 64 + (lane0 & 31)) * L::TAP_FLOATS : rcX + 8;     // view-plane taps of the ray
     float* rtY = rtX + 32 * (LIMBS == 2 ? L::TAP_FLOATS : RAY3_FLOATS);
@@ -142,7 +152,39 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
         else return e;
     };
     auto live_weight = [](const float* lwp, int n, int k) NVSR_INL -> float { return n == 0 ? 0.0f : lwp[k < n ? k : n - 1]; };
-    if constexpr (COLOUR) {
+    // point-major colour pass: the step's points.  slot: whose ray; live: not padding; e1: the entry of the step after this one
+    int slotX = ownX, slotY = ownY, slotXn = ownX, slotYn = ownY, eX1 = POINT_NONE, eY1 = POINT_NONE;
+    bool liveX = false, liveY = false, liveXn = false, liveYn = false;
+    float* const pt_sums = ldsf + L::PTS;                    // [RAYS2][3]: the rays' colour sums
+    float* const pt_exch = pt_sums + 3 * RAYS2;              // [RAYS2][3]: the step's terms
+    int* const pt_slot = reinterpret_cast<int*>(pt_exch + 3 * RAYS2);      // [RAYS2]: the slot of every point of the step (-1: padding)
+    int* const pt_ray = pt_slot + RAYS2;                     // [RAYS2]: a slot's ray, as its index in the block of the ray order
+    const long pt_block = (long)(blk / (ORDER_RAYS / RAYS2)) * ORDER_RAYS;
+    const int* const peX = POINTS ? pts + (long)blk * RAYS2 * S + ownX : nullptr;      // the lane's entries: step t at [t RAYS2] (Y: + 32)
+    // entry e -> the point's slot, whether it is one, and its list entry (depth or, ZCOMP, the depth of that sample index) and weight
+    auto point_of = [&](int e, int own, int& slot, bool& live, float& zv, float& wv) NVSR_INL {
+        live = e != POINT_NONE;
+        slot = live ? (int)((unsigned)e >> 24) : own;
+        const float* rc = ldsf + L::RAYS + slot * RAY3_FLOATS;
+        zv = rc[7]; wv = 0.0f;                               // (padding: the slot's near depth, never composited)
+        if (live) {
+            const long at = (pt_block + pt_ray[slot]) * S + (e & 0xffffff);
+            const float ze = live_z[at];
+            wv = live_w[at];
+            if constexpr (ZCOMP) zv = coarse_depth(rc[7], L::FAR >= 0 ? ldsf[L::FAR + slot] : rc[16], __float_as_int(ze), S, lindisp);
+            else zv = ze;
+        }
+    };
+    auto load_view = [&](int slot, float (&V)[HALF_C]) NVSR_INL {
+        const f32x4* vp = reinterpret_cast<const f32x4*>(views + ((long)blk * RAYS2 + slot) * POINT_VIEW_FLOATS + HALF_C * (lane0 >> 5));
+#pragma unroll
+        for (int i = 0; i < HALF_C / 4; ++i) { const f32x4 v = vp[i]; V[4 * i] = v[0]; V[4 * i + 1] = v[1]; V[4 * i + 2] = v[2]; V[4 * i + 3] = v[3]; }
+    };
+    if constexpr (POINTS) {
+        static_assert(!R3_BOUNCE, "the points' LDS region is the f16 kernels' bounce slot");
+        trip = __builtin_amdgcn_readfirstlane(pt_steps[blk]);
+        __syncthreads();                              // the ray cache, written by lanes 0..31 and read by all 64
+    } else if constexpr (COLOUR) {
         __shared__ int trip_s[NW2];                   // (the colour kernels' alone: the other phases declare nothing)
         int m = max(nX, nY);
 #pragma unroll
@@ -193,6 +235,28 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
 #pragma unroll
             for (int c = 0; c < HALF_C; ++c) gather4_blend(c, vj, rt, t.V);
         }
+        if constexpr (POINTS) {
+            // the slots' view features -> the table; the sums, the slots' rays; then the first two steps' entries and the first step's point
+#pragma unroll
+            for (int k2 = 0; k2 < 2; ++k2) {
+                const Tile3& t = k2 ? Y : X;
+                f32x4* vp = reinterpret_cast<f32x4*>(views + ((long)blk * RAYS2 + (k2 ? ownY : ownX)) * POINT_VIEW_FLOATS + HALF_C * (lane0 >> 5));
+#pragma unroll
+                for (int i = 0; i < HALF_C / 4; ++i) vp[i] = f32x4{t.V[4 * i], t.V[4 * i + 1], t.V[4 * i + 2], t.V[4 * i + 3]};
+            }
+            __syncthreads();                          // (f16 limbs: the taps, read above, lie where the sums go)
+            if (lane0 < 32) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) pt_sums[ownX * 3 + c] = pt_sums[ownY * 3 + c] = 0.0f;
+                pt_ray[ownX] = (int)(rayX - pt_block); pt_ray[ownY] = (int)(rayY - pt_block);
+            }
+            __syncthreads();                          // pt_ray and the table (global memory written by other waves of the workgroup)
+            const int eX0 = trip > 0 ? peX[0] : POINT_NONE, eY0 = trip > 0 ? peX[32] : POINT_NONE;
+            eX1 = trip > 1 ? peX[RAYS2] : POINT_NONE; eY1 = trip > 1 ? peX[RAYS2 + 32] : POINT_NONE;
+            point_of(eX0, ownX, slotX, liveX, X.zc, wX);
+            point_of(eY0, ownY, slotY, liveY, Y.zc, wY);
+            load_view(slotX, X.V); load_view(slotY, Y.V);
+        }
     } else {
         // density pass: D of sample 0 (every later sample's is gathered during the sample before it) -- the operations of the rolling gather
 #pragma unroll
@@ -233,12 +297,15 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
     for (int s = 0; s < steps; ++s) {
         asm volatile("" : "+v"(rs.voff), "+v"(rs.lane));
 #if R3_NO_VIEW_HOIST
+        if constexpr (!POINTS) {
         // The view features are loop-invariant and so are their limbs: hipcc hoists the two split_feat(V) of a step out of the sample loop
         // (72 registers of limbs), runs out of registers and spills 8 of them plus the two depth-row pointers -- 4 scratch reloads per
         // sample, each behind an s_waitcnt vmcnt(0) that also waits for every gather and weight copy in flight.  Opaque per iteration.
 #pragma unroll
         for (int c = 0; c < HALF_C; ++c) asm volatile("" : "+v"(X.V[c]), "+v"(Y.V[c]));
+        }
 #endif
+        if constexpr (POINTS) { rcX = ldsf + L::RAYS + slotX * RAY3_FLOATS; rcY = ldsf + L::RAYS + slotY * RAY3_FLOATS; }
         const int lane = rs.lane, h = lane >> 5;
         const bool last = (s + 1 == S);
         if constexpr (!COLOUR) {
@@ -272,7 +339,13 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
         GatherJob ja, jb;
         R3_MARK(0)      // loop top
         ring3_sync<(ZCOMP || COLOUR) ? 0 : 2>();                 // the step's first ring chunk (issued during the previous sample) -- younger: the two z loads above
-        if constexpr (COLOUR) {
+        int eX2 = POINT_NONE, eY2 = POINT_NONE;
+        if constexpr (POINTS) {
+            // the entries of the step after the next, and the next step's point: both a whole step ahead of their use
+            if (s + 2 < steps) { eX2 = peX[(s + 2) * RAYS2]; eY2 = peX[(s + 2) * RAYS2 + 32]; }
+            point_of(eX1, ownX, slotXn, liveXn, X.zn, wXn);
+            point_of(eY1, ownY, slotYn, liveYn, Y.zn, wYn);
+        } else if constexpr (COLOUR) {
             // the next live entry, a whole step ahead of its use (issued behind the wait: no ring wait has to count these loads)
             X.zn = live_depth(lzX, rcX, nX, s + 1); Y.zn = live_depth(lzY, rcY, nY, s + 1);
             wXn = live_weight(lwX, nX, s + 1); wYn = live_weight(lwY, nY, s + 1);
@@ -294,11 +367,13 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
         if constexpr (RESIDENT) limb_block<LIMBS, 3, true, true>(w_view, lane, X.acc, cur, fa, feat(X.V), NVSR_ROLL(X, ja, Y, jb, true, false), NoTail{});
         else limb_block<LIMBS, 3, true, true>(cw, lane, X.acc, cur, fa, feat(X.V), NVSR_ROLL_DMA(X, ja, Y, jb, true, false, 3, KB_RGB0 + 3), NoTail{});
         R3_MARKB(0)
+        if constexpr (POINTS) load_view(slotXn, X.V);           // (X.V is dead from here: the next step's, a step ahead)
         // Y view | blends X plane 0, loads Y plane 0
         jb.plane = sc.plane[0]; jb.t = pos_taps2(sc, 0, yn0, yn1, yn2); scale_taps(jb.t);
         split_feat(Y.V);
         limb_block<LIMBS, 3, true, false>(w_view, lane, Y.acc, cur, fa, feat(Y.V), NVSR_ROLL(Y, jb, X, ja, true, true), NoTail{});
         R3_MARKB(1)
+        if constexpr (POINTS) load_view(slotYn, Y.V);
         const unsigned* w_p0 = res + 3 * kb_words(LIMBS);
         if constexpr (!RESIDENT) {
             cw = nw;
@@ -586,8 +661,30 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
 #pragma unroll
             for (int c = 0; c < 3; ++c) Y.raw[c] = hd[c] + small[S_HEAD_B + 1 + c];
         }
-        composite_colour(X, wX, s < nX);
-        composite_colour(Y, wY, s < nY);
+        if constexpr (POINTS) {
+            // the step's terms and slots -> LDS; the first point of every run (position p: lane p of the workgroup) adds its run to the ray's sums
+            if (lane < 32) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) { pt_exch[ownX * 3 + c] = colour_term(wX, X.raw[c]); pt_exch[ownY * 3 + c] = colour_term(wY, Y.raw[c]); }
+                pt_slot[ownX] = liveX ? slotX : -1; pt_slot[ownY] = liveY ? slotY : -1;
+            }
+            __syncthreads();
+            const int p = rs.wave * 64 + lane, sl = pt_slot[p];
+            if (sl >= 0 && (p == 0 || pt_slot[p - 1] != sl)) {
+                float a0 = pt_sums[sl * 3], a1 = pt_sums[sl * 3 + 1], a2 = pt_sums[sl * 3 + 2];
+                int q = p;
+                do {
+                    a0 = __fadd_rn(a0, pt_exch[q * 3]); a1 = __fadd_rn(a1, pt_exch[q * 3 + 1]); a2 = __fadd_rn(a2, pt_exch[q * 3 + 2]);
+                    ++q;
+                } while (q < RAYS2 && pt_slot[q] == sl);
+                pt_sums[sl * 3] = a0; pt_sums[sl * 3 + 1] = a1; pt_sums[sl * 3 + 2] = a2;
+            }
+            __syncthreads();                          // the next step's terms go where these were read; after the last step: the sums
+            slotX = slotXn; slotY = slotYn; liveX = liveXn; liveY = liveYn; eX1 = eX2; eY1 = eY2;
+        } else {
+            composite_colour(X, wX, s < nX);
+            composite_colour(Y, wY, s < nY);
+        }
         wX = wXn; wY = wYn;
         }
 #undef NVSR_HIDDEN_LAYER
@@ -605,6 +702,12 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
 #endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the copy issued for a sample after the last one must land before the wave ends
 
+    if constexpr (POINTS) {
+        if (rs.lane < 32) {
+            X.cr = pt_sums[ownX * 3]; X.cg = pt_sums[ownX * 3 + 1]; X.cb = pt_sums[ownX * 3 + 2];
+            Y.cr = pt_sums[ownY * 3]; Y.cg = pt_sums[ownY * 3 + 1]; Y.cb = pt_sums[ownY * 3 + 2];
+        }
+    }
     if (rs.lane < 32) {
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
@@ -708,6 +811,32 @@ __global__ __launch_bounds__(TPB2, 1) void render_pass3_colour_z_kernel(SceneDev
                                                                        const int* __restrict__ group_slot) {
 #if defined(__HIP_DEVICE_COMPILE__)
     render_pass3_body<LIMBS + 8 + 32>(sc, packed, N, S, rays, nullptr, lindisp, nullptr, white, rgb, nullptr, acc, nullptr, nullptr, nullptr, flag, live_z, live_w, live_n, group_slot);
+#endif
+}
+
+// the point-major colour pass (PHASE 3): pts, pt_steps: point_order_kernel's entries and step counts; views: the slots' view features
+template <int LIMBS>
+__global__ __launch_bounds__(TPB2, 1) void render_pass3_points_kernel(SceneDev sc, const float* __restrict__ packed, long N, int S,
+                                                                     const float* __restrict__ rays, int white, float* __restrict__ rgb,
+                                                                     float* __restrict__ acc, unsigned* __restrict__ flag,
+                                                                     float* __restrict__ live_z, float* __restrict__ live_w, int* __restrict__ live_n,
+                                                                     const int* __restrict__ group_slot, const int* __restrict__ pts,
+                                                                     const int* __restrict__ pt_steps, float* views) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    render_pass3_body<LIMBS + 48>(sc, packed, N, S, rays, nullptr, 0, nullptr, white, rgb, nullptr, acc, nullptr, nullptr, nullptr, flag, live_z, live_w, live_n, group_slot,
+                                  pts, pt_steps, views);
+#endif
+}
+template <int LIMBS>
+__global__ __launch_bounds__(TPB2, 1) void render_pass3_points_z_kernel(SceneDev sc, const float* __restrict__ packed, long N, int S,
+                                                                       const float* __restrict__ rays, int lindisp, int white,
+                                                                       float* __restrict__ rgb, float* __restrict__ acc, unsigned* __restrict__ flag,
+                                                                       float* __restrict__ live_z, float* __restrict__ live_w, int* __restrict__ live_n,
+                                                                       const int* __restrict__ group_slot, const int* __restrict__ pts,
+                                                                       const int* __restrict__ pt_steps, float* views) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    render_pass3_body<LIMBS + 8 + 48>(sc, packed, N, S, rays, nullptr, lindisp, nullptr, white, rgb, nullptr, acc, nullptr, nullptr, nullptr, flag, live_z, live_w, live_n,
+                                      group_slot, pts, pt_steps, views);
 #endif
 }
 
@@ -818,7 +947,11 @@ static int launch_pass3(const LiveLists* ll, const nvsr_scene* scene, const floa
         if (z) launch(render_pass3_density_kernel<LIMBS>, z, noise, disp, acc, weights, depth, flag, ll->z, ll->w, ll->n);
         else launch(render_pass3_density_z_kernel<LIMBS>, lindisp, noise, disp, acc, weights, depth, flag, ll->z, ll->w, ll->n);
         launch_colour_order(*ll, N, S, stream);
-        if (z) launch(render_pass3_colour_kernel<LIMBS>, white, rgb, acc, flag, ll->z, ll->w, ll->n, ll->slot);
+        if (ll->pts) {
+            launch_point_order(*ll, z ? rays : nullptr, N, S, stream);
+            if (z) launch(render_pass3_points_kernel<LIMBS>, white, rgb, acc, flag, ll->z, ll->w, ll->n, ll->slot, ll->pts, ll->steps, ll->views);
+            else launch(render_pass3_points_z_kernel<LIMBS>, lindisp, white, rgb, acc, flag, ll->z, ll->w, ll->n, ll->slot, ll->pts, ll->steps, ll->views);
+        } else if (z) launch(render_pass3_colour_kernel<LIMBS>, white, rgb, acc, flag, ll->z, ll->w, ll->n, ll->slot);
         else launch(render_pass3_colour_z_kernel<LIMBS>, lindisp, white, rgb, acc, flag, ll->z, ll->w, ll->n, ll->slot);
     } else if (!z) launch(render_pass3_coarse_z_kernel<LIMBS>, lindisp, noise, white, rgb, disp, acc, weights, depth, raw_out, flag);
     else if (weights) launch(render_pass3_coarse_kernel<LIMBS>, z, noise, white, rgb, disp, acc, weights, depth, raw_out, flag);

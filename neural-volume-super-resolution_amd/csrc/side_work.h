@@ -97,12 +97,14 @@ __device__ __forceinline__ void composite_weight(TileT& t, float nrm, float nois
     t.ac = __fadd_rn(t.ac, w);
     t.raw[3] = w;
 }
+// a point's term of a colour sum, w sigmoid(raw): what composite_colour adds (the point-major colour pass adds it through LDS)
+__device__ __forceinline__ float colour_term(float w, float raw) { return __fmul_rn(w, 1.0f / (1.0f + expf(-raw))); }
 // Colour pass: c += w sigmoid(raw) for a live entry; a lane past its ray's list keeps its sums (a select, never + 0 x)
 template <class TileT>
 __device__ __forceinline__ void composite_colour(TileT& t, float w, bool live) {
-    const float cr = __fadd_rn(t.cr, __fmul_rn(w, 1.0f / (1.0f + expf(-t.raw[0]))));
-    const float cg = __fadd_rn(t.cg, __fmul_rn(w, 1.0f / (1.0f + expf(-t.raw[1]))));
-    const float cb = __fadd_rn(t.cb, __fmul_rn(w, 1.0f / (1.0f + expf(-t.raw[2]))));
+    const float cr = __fadd_rn(t.cr, colour_term(w, t.raw[0]));
+    const float cg = __fadd_rn(t.cg, colour_term(w, t.raw[1]));
+    const float cb = __fadd_rn(t.cb, colour_term(w, t.raw[2]));
     t.cr = live ? cr : t.cr; t.cg = live ? cg : t.cg; t.cb = live ? cb : t.cb;
 }
 
