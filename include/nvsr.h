@@ -672,6 +672,14 @@ int nvsr_render_rays_shared_arith(const nvsr_scene* scene, const float* packed_d
                                   int white_bkgd, const float* t_rand, const float* u, const float* noise_coarse, const float* noise_fine,
                                   float* rgb_c, float* disp_c, float* acc_c, float* rgb_f, float* disp_f, float* acc_f, float* workspace,
                                   int arithmetic, nvsr_stream_t stream);
+/* The merge of that route alone: the Nc un-jittered coarse depths of a ray (recomputed from near / far of the packed rays [N,11] -- what
+ * nvsr_coarse_z writes, bit for bit) and its Nf new samples z_new [N,Nf] -> z_merged [N,Nc+Nf], and the decoder outputs raw_coarse [N,Nc,4],
+ * raw_new [N,Nf,4] gathered into the same order -> raw_merged [N,Nc+Nf,4] (verbatim 16-byte copies).  The order is the stable sort of
+ * [coarse | new]: a coarse depth stands behind the samples that are smaller, a sample behind the coarse depths that are smaller or equal, ties
+ * inside a list go by index, NaNs go last (coarse before samples, by index) like torch.sort's.  The samples need not be sorted.
+ * 3 <= Nc <= 256, 1 <= Nf <= 256; the three raw pointers 16-byte aligned. */
+int nvsr_shared_merge(int64_t N, int Nc, int Nf, const float* rays, int lindisp, const float* z_new, const float* raw_coarse, const float* raw_new,
+                      float* z_merged, float* raw_merged, nvsr_stream_t stream);
 int nvsr_render_pass_backward_gates_arith(const nvsr_scene* scene, const float* packed_decoder, const float* packed_bwd, int64_t N, int S,
                                           const float* rays, const float* z, const float* g_raw, const uint32_t* gates,
                                           float* const* grad_planes, float* view_ws, float* record, int arithmetic, nvsr_stream_t stream);

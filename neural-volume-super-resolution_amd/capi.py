@@ -170,6 +170,7 @@ _PROTOS_OPTIONAL = {   # feature-plane super-resolution (csrc/sr.hip)
     "nvsr_ray_points": ([_i64, _i, _vp, _vp, _vp, _vp], _i),
     "nvsr_render_shared_workspace_floats": ([_i64, _i, _i], _i64),
     "nvsr_render_rays_shared_arith": ([C.POINTER(Scene), _vp, _i64, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp], _i),
+    "nvsr_shared_merge": ([_i64, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp], _i),
     "nvsr_release_render_scratch": ([], _i),
     "nvsr_render_scratch_bytes": ([], _i64),
     "nvsr_internal_group_order": ([_vp, _i64, _i, _vp, _vp], _i),

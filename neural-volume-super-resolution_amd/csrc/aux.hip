@@ -554,7 +554,11 @@ __global__ __launch_bounds__(WPB * 64) void importance_resample_kernel(long N, i
 // same points -- in the coarse pass.  The decoder runs on the new samples only; this kernel merges the two sorted depth lists of a ray and
 // gathers the two lists of decoder outputs into the merged order, which is then composited.  Positions: a coarse depth goes behind the new
 // samples that are smaller, a new sample behind the coarse depths that are smaller or equal (at equal depths the two points are the same
-// point and their outputs the same numbers).  Unsorted input (NaN weights) falls back to counting.  One wave per ray.
+// point and their outputs the same numbers), ties inside a list go by index: the stable sort of [a | b].  Two sorted NaN-free lists take two
+// binary searches per element.  Anything else (NaN weights make every sample NaN, a NaN near every coarse depth) is ranked by counting over
+// [a | b] with the predicate of rank_sort_wave: NaNs last, coarse before samples, by index -- the order merge_sort_wave gives the two-decoder
+// route.  (Counting with plain < / <= / == gave every NaN position 0: the ray's NaN elements raced for one slot and as many slots of z_m and
+// raw_m -- workspace, holding an earlier frame's numbers -- stayed unwritten.)  One wave per ray.
 __global__ __launch_bounds__(WPB * 64) void shared_merge_kernel(long N, int Nc, int Nf, const float* __restrict__ rays, int lindisp,
                                                                const float* __restrict__ z_new, const float* __restrict__ raw_c,
                                                                const float* __restrict__ raw_new, float* __restrict__ z_m, float* __restrict__ raw_m) {
@@ -569,14 +573,19 @@ __global__ __launch_bounds__(WPB * 64) void shared_merge_kernel(long N, int Nc, 
     for (int j = lane; j < Nf; j += 64) b[j] = z_new[ray * Nf + j];
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_s_waitcnt(0xc07f);
-    bool sorted = true;
+    bool sorted = true;                                                  // (and NaN-free: a lone NaN sample, Nf == 1, has no neighbour to fail against)
     for (int i = lane; i + 1 < Nc; i += 64) sorted = sorted && (a[i] <= a[i + 1]);
-    for (int j = lane; j + 1 < Nf; j += 64) sorted = sorted && (b[j] <= b[j + 1]);
+    for (int j = lane; j < Nf; j += 64) sorted = sorted && (b[j] == b[j]) && (j + 1 >= Nf || b[j] <= b[j + 1]);
     const bool fast = __builtin_amdgcn_ballot_w64(!sorted) == 0;
     float* zo = z_m + ray * (Nc + Nf);
     f32x4* ro = reinterpret_cast<f32x4*>(raw_m) + ray * (Nc + Nf);
     const f32x4* rc = reinterpret_cast<const f32x4*>(raw_c) + ray * Nc;
     const f32x4* rn = reinterpret_cast<const f32x4*>(raw_new) + ray * Nf;
+    // does o stand before v?  (`first`: o's place in [a | b] is before v's)
+    auto before = [](float o, float v, bool first) {
+        const bool onan = o != o, vnan = v != v;
+        return (o < v) || (!onan && vnan) || ((o == v || (onan && vnan)) && first);
+    };
     for (int i = lane; i < Nc; i += 64) {
         const float v = a[i];
         int cnt = 0, rank = i;
@@ -585,9 +594,9 @@ __global__ __launch_bounds__(WPB * 64) void shared_merge_kernel(long N, int Nc, 
             while (lo < hi) { const int mid = (lo + hi) >> 1; if (b[mid] < v) lo = mid + 1; else hi = mid; }
             cnt = lo;
         } else {
-            for (int j = 0; j < Nf; ++j) cnt += b[j] < v ? 1 : 0;
+            for (int j = 0; j < Nf; ++j) cnt += before(b[j], v, false) ? 1 : 0;
             rank = 0;
-            for (int k = 0; k < Nc; ++k) rank += (a[k] < v || (a[k] == v && k < i)) ? 1 : 0;
+            for (int k = 0; k < Nc; ++k) rank += before(a[k], v, k < i) ? 1 : 0;
         }
         const int pos = min(rank + cnt, Nc + Nf - 1);
         zo[pos] = v;
@@ -601,9 +610,9 @@ __global__ __launch_bounds__(WPB * 64) void shared_merge_kernel(long N, int Nc, 
             while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] <= v) lo = mid + 1; else hi = mid; }
             cnt = lo;
         } else {
-            for (int i = 0; i < Nc; ++i) cnt += a[i] <= v ? 1 : 0;
+            for (int i = 0; i < Nc; ++i) cnt += before(a[i], v, true) ? 1 : 0;
             rank = 0;
-            for (int k = 0; k < Nf; ++k) rank += (b[k] < v || (b[k] == v && k < j)) ? 1 : 0;
+            for (int k = 0; k < Nf; ++k) rank += before(b[k], v, k < j) ? 1 : 0;
         }
         const int pos = min(rank + cnt, Nc + Nf - 1);
         zo[pos] = v;
@@ -865,6 +874,17 @@ int nvsr_importance_resample_rays(int64_t N, int Nc, int Nf, const float* rays, 
     return importance_resample_rays_impl(N, Nc, Nf, rays, lindisp, weights, u, z_fine, nullptr, stream);
 }
 
+int nvsr_shared_merge(int64_t N, int Nc, int Nf, const float* rays, int lindisp, const float* z_new, const float* raw_coarse, const float* raw_new,
+                      float* z_merged, float* raw_merged, nvsr_stream_t stream) {
+    if (!rays || !z_new || !raw_coarse || !raw_new || !z_merged || !raw_merged) return NVSR_ERR_NULL;
+    if (!aligned16(raw_coarse) || !aligned16(raw_new) || !aligned16(raw_merged)) return NVSR_ERR_ALIGN;
+    if (N < 0 || Nc < 3 || Nc > 256 || Nf < 1 || Nf > 256) return NVSR_ERR_SHAPE;
+    if (N == 0) return NVSR_OK;
+    hipLaunchKernelGGL(shared_merge_kernel, dim3(blocks_for(N, WPB)), dim3(WPB * 64), 0, (hipStream_t)stream, (long)N, Nc, Nf, rays, lindisp, z_new,
+                       raw_coarse, raw_new, z_merged, raw_merged);
+    return NVSR_CHECK_LAUNCH();
+}
+
 int nvsr_composite(int64_t N, int S, const float* raw, const float* z, const float* rd, const float* noise, int white_bkgd, float* rgb,
                    float* disp, float* acc, float* weights, float* depth, nvsr_stream_t stream) {
     if (!raw || !z || !rd || !rgb || !disp || !acc) return NVSR_ERR_NULL;
@@ -1009,9 +1029,7 @@ int nvsr_render_rays_shared_arith(const nvsr_scene* scene, const float* packed, 
     // the decoder on the new samples only (its own compositing lands in the fine outputs and is overwritten below)
     if ((e = nvsr_render_pass_arith(scene, packed, N, Nf, rays, z_new, nullptr, white_bkgd, rgb_f, disp_f, acc_f, nullptr, nullptr, raw_new, arithmetic, stream)))
         return e;
-    hipLaunchKernelGGL(shared_merge_kernel, dim3(blocks_for(N, WPB)), dim3(WPB * 64), 0, (hipStream_t)stream, (long)N, Nc, Nf, rays, lindisp, z_new,
-                       raw_c, raw_new, z_m, raw_m);
-    if ((e = NVSR_CHECK_LAUNCH())) return e;
+    if ((e = nvsr_shared_merge(N, Nc, Nf, rays, lindisp, z_new, raw_c, raw_new, z_m, raw_m, stream))) return e;
     return nvsr_composite_rays(N, (int)S, raw_m, z_m, rays, noise_fine, white_bkgd, rgb_f, disp_f, acc_f, nullptr, nullptr, stream);
 }
 
