@@ -204,6 +204,61 @@ int nvsr_internal_point_order(const int* entries, const float* lists, const floa
                               nvsr_stream_t stream);
 int nvsr_internal_point_bands(void);
 int nvsr_internal_copy_point_steps(int* dst, int64_t G, nvsr_stream_t stream);
+/* Occupancy grid (csrc/occupancy.hip; opt-in: a caller who builds no grid gets the launches and the bits described above).  A grid belongs to one
+ * (scene planes, decoder) pair: G^3 bits over the scene's normalised box, 1 <= G <= 512.  Cell (ix, iy, iz) is bit i & 31 of 32-bit word
+ * i >> 5, i = (iz G + iy) G + ix; nvsr_occupancy_words(G) = ceil(G^3 / 32) words, the unused bits of the last word 0.
+ * Cell of a sample, per axis: c = clamp((int)floorf(((n + 1.0f) * 0.5f) * (float)G), 0, G - 1), n the normalised coordinate exactly as the
+ * render kernels form it (2 ((o + d z) - lo) / range - 1), every step one correctly rounded f32 operation; the clamp matches
+ * padding_mode='border' (a point outside the box has the border's features).  A sample with a NaN coordinate is KEPT.
+ * A CULLED sample (cell bit 0) behaves exactly as if the density decoder had answered sigma + noise <= 0: alpha = 0, w = +0.0, T unchanged
+ * (T (1 - 0 + 1e-10f) is T in f32), +0.0 added to depth, acc and the colour sums, weight +0.0 in the [N, S] weights, absent from the live list.
+ * A KEPT sample is evaluated with the arithmetic of the two-phase pass; its dist comes from its own successor in the full depth row,
+ * z[s + 1] - z[s] (1e10 for s = S - 1), not from the next kept sample.  So an occupancy pass equals, bit for bit in rgb, disp, acc, depth,
+ * weights and the live entries, the two-phase pass run with noise = 0 on kept samples and noise = -1e30 on culled ones (as long as T stays
+ * a number: behind a NaN transmittance the noise route's culled samples carry NaN weights, this route's +0.0).  One difference is
+ * documented: a NaN sigma inside a culled cell no longer reaches the pixel (the pixel is then the finite value of the other samples).
+ * The grid is APPROXIMATE by nature: no finite set of probes bounds an MLP over a cell, so a built grid may cull a sample of small positive
+ * density.  nvsr_occupancy_build probes every cell at K^3 points, K in 1..4 -- along each axis probe j of cell i at u = ((float)(i K + j) +
+ * 0.5f) / (float)(G K) of the box, world coordinate lo + u range, view direction (1, 0, 0): sigma does not depend on it -- with
+ * nvsr_triplane_decode_arith in `arithmetic`, sets a cell's bit iff any of its probes has sigma_raw > threshold or a NaN sigma_raw, then
+ * applies `dilate` rounds of a 3 x 3 x 3 OR (two buffers, no atomics: deterministic).  It works through the grid in slabs of whole words;
+ * workspace: nvsr_occupancy_workspace_floats(G, K) floats (at most 80 MB), 16-byte aligned.  K, threshold and dilate are the caller's knobs.
+ * nvsr_render_pass_occupancy_arith is nvsr_render_pass_arith without noise and raw outputs, for the limb arithmetics only and without a
+ * minimum ray count (like the kernels behind it): occupancy_cull_kernel (one wave per ray, 64 samples per trip) lists every ray's kept
+ * sample indices in sample order, live_order_kernel and group_order_kernel order rays and dispatch on the kept counts as they do for the
+ * colour pass, and render_pass3_density_kept[_z]_kernel runs the density decoder over the kept lists -- as many steps as the longest list
+ * among a workgroup's 256 rays -- and leaves disp, acc, depth, the weights (zero-filled, then written at the kept samples), the range flag and
+ * the live lists; the colour pass and its orders follow unchanged.  z == NULL: the depths are those of nvsr_coarse_z without jitter, formed
+ * in registers from the rays' near / far (lindisp as there), and `weights` is required; with z, lindisp is ignored.
+ * The route DECLINES and runs the plain route -- always legal: the plain route is what the grid approximates -- where the two-phase pass
+ * declines (NVSR_RENDER_ONE_PHASE=1, a stream being captured, S >= 2^19, no scratch) or its own scratch cannot be had.  Scratch: N S + N ints
+ * and 2 G ints of group table, owned by the library per (device, stream) beside the live lists, grown and released like them
+ * (nvsr_release_render_scratch) and NOT counted by nvsr_render_scratch_bytes, whose value a non-occupancy launch leaves as it was.
+ * NVSR_ERR_SHAPE with nothing launched: G outside 1..512, K outside 1..4, dilate < 0, an arithmetic that is not a limb mode on the pass entry. */
+int64_t nvsr_occupancy_words(int G);
+int64_t nvsr_occupancy_workspace_floats(int G, int K);
+int nvsr_occupancy_build(const nvsr_scene* scene, const float* packed_decoder, int G, int K, float threshold, int dilate, int arithmetic, uint32_t* grid,
+                         float* workspace, nvsr_stream_t stream);
+int nvsr_render_pass_occupancy_arith(const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays, const float* z, int lindisp,
+                                     int white_bkgd, float* rgb, float* disp, float* acc, float* weights, float* depth, const uint32_t* grid, int G, int arithmetic,
+                                     nvsr_stream_t stream);
+/* The frame (nvsr_render_rays_arith without the two noise arguments) with a grid per pass: a pass with a grid goes through
+ * nvsr_render_pass_occupancy_arith, a pass whose grid is NULL runs the plain route.  Below nvsr_fused_min_rays() rays, in the f32 arithmetic
+ * and with both grids NULL the call is nvsr_render_rays_arith's with noise = NULL: the un-fused path runs and the grids are ignored. */
+int nvsr_render_rays_occupancy_arith(const nvsr_scene* scene, const float* packed_coarse, const float* packed_fine, int64_t N, int Nc, int Nf,
+                                     const float* rays, int lindisp, int white_bkgd, const float* t_rand, const float* u, float* rgb_c, float* disp_c,
+                                     float* acc_c, float* rgb_f, float* disp_f, float* acc_f, float* workspace, const uint32_t* grid_coarse, int G_coarse,
+                                     const uint32_t* grid_fine, int G_fine, int arithmetic, nvsr_stream_t stream);
+/* Internal hooks of the occupancy route (tests and tools; not part of the stable interface).  nvsr_internal_occupancy_probes: the probe
+ * kernel alone over the whole grid -> x [G^3 K^3, 6], probe (jz K + jy) K + jx of cell i at row i K^3 + it.  nvsr_internal_occupancy_cull:
+ * the cull kernel alone -> kept [N, S] (a row's first kept_n[ray] entries are the kept sample indices, the others -1), kept_n [N].
+ * nvsr_internal_copy_kept_counts: the kept counts the latest occupancy launch on `stream` left -> dst (N ints, device or host memory; N must
+ * be that launch's), as packed entries of the ray order, (count << 12) | index of the ray in its block of 4096; NVSR_ERR_SHAPE when none ran or
+ * the latest one declined. */
+int nvsr_internal_occupancy_probes(const nvsr_scene* scene, int G, int K, float* x, nvsr_stream_t stream);
+int nvsr_internal_occupancy_cull(const nvsr_scene* scene, int64_t N, int S, const float* rays, const float* z, int lindisp, const uint32_t* grid, int G, int* kept,
+                                 int* kept_n, nvsr_stream_t stream);
+int nvsr_internal_copy_kept_counts(int* dst, int64_t N, nvsr_stream_t stream);
 /* The arithmetic primitive alone (test hook, one wavefront): Y[32][32] = W[32][K] X[K][32] (row-major f32, K a multiple of 16) with the
  * operands split and multiplied exactly as the kernels of `arithmetic` do it (NVSR_ARITH_F32 | _BF16X3 | _F16X2, incl. the static scales of
  * F16X2) -- lets a test put chosen mantissas / magnitudes through the products that replace models.py:381-421's nn.Linear GEMMs. */

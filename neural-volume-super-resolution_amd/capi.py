@@ -181,6 +181,16 @@ _PROTOS_OPTIONAL = {   # feature-plane super-resolution (csrc/sr.hip)
     "nvsr_internal_point_bands": ([], _i),
     "nvsr_internal_copy_point_steps": ([_vp, _i64, _vp], _i),
     "nvsr_internal_point_order": ([_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp], _i),
+    # occupancy grid (csrc/occupancy.hip; include/nvsr.h, "Occupancy grid")
+    "nvsr_occupancy_words": ([_i], _i64),
+    "nvsr_occupancy_workspace_floats": ([_i, _i], _i64),
+    "nvsr_occupancy_build": ([C.POINTER(Scene), _vp, _i, _i, C.c_float, _i, _i, _vp, _vp, _vp], _i),
+    "nvsr_render_pass_occupancy_arith": ([C.POINTER(Scene), _vp, _i64, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp], _i),
+    "nvsr_render_rays_occupancy_arith": ([C.POINTER(Scene), _vp, _vp, _i64, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i,
+                                          _i, _vp], _i),
+    "nvsr_internal_occupancy_probes": ([C.POINTER(Scene), _i, _i, _vp, _vp], _i),
+    "nvsr_internal_occupancy_cull": ([C.POINTER(Scene), _i64, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp], _i),
+    "nvsr_internal_copy_kept_counts": ([_vp, _i64, _vp], _i),
     "nvsr_set_sr_plane_interp": ([_i], _i),
     "nvsr_get_sr_plane_interp": ([], _i),
     "nvsr_set_sr_align_corners": ([_i], _i),

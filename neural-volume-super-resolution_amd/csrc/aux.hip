@@ -990,6 +990,46 @@ int nvsr_render_rays_arith(const nvsr_scene* scene, const float* packed_coarse, 
     return render_one_pass(scene, packed_fine, N, Nc + Nf, rays, z_f, noise_fine, white_bkgd, rgb_f, disp_f, acc_f, nullptr, raw_ws, arithmetic, stream);
 }
 
+// The frame with occupancy grids (include/nvsr.h, "Occupancy grid"): nvsr_render_rays_arith without noise, each pass through
+// nvsr_render_pass_occupancy_arith where it has a grid.  Without a grid, below NVSR_FUSED_MIN_RAYS or in the f32 arithmetic: the plain frame.
+int nvsr_render_rays_occupancy_arith(const nvsr_scene* scene, const float* packed_coarse, const float* packed_fine, int64_t N, int Nc, int Nf,
+                                     const float* rays, int lindisp, int white_bkgd, const float* t_rand, const float* u, float* rgb_c, float* disp_c,
+                                     float* acc_c, float* rgb_f, float* disp_f, float* acc_f, float* workspace, const uint32_t* grid_coarse, int G_coarse,
+                                     const uint32_t* grid_fine, int G_fine, int arithmetic, nvsr_stream_t stream) {
+    if ((grid_coarse && (G_coarse < 1 || G_coarse > 512)) || (grid_fine && (G_fine < 1 || G_fine > 512))) return NVSR_ERR_SHAPE;
+    const int arith = nvsr_internal_resolve_decoder_arith(arithmetic);
+    if (Nf <= 0) grid_fine = nullptr;
+    if (!fused_limb_passes(N, arith) || (!grid_coarse && !grid_fine))
+        return nvsr_render_rays_arith(scene, packed_coarse, packed_fine, N, Nc, Nf, rays, lindisp, white_bkgd, t_rand, u, nullptr, nullptr, rgb_c, disp_c, acc_c,
+                                      rgb_f, disp_f, acc_f, workspace, arithmetic, stream);
+    if (!workspace || !scene || !packed_coarse || !rays || !rgb_c || !disp_c || !acc_c) return NVSR_ERR_NULL;
+    if (!aligned16(workspace) || !aligned16(packed_coarse)) return NVSR_ERR_ALIGN;
+    if (Nc < 1 || Nf < 0 || (Nf > 0 && (Nc < 3 || Nc > 256 || Nf > 256))) return NVSR_ERR_SHAPE;
+    if (Nf > 0 && (!packed_fine || !rgb_f || !disp_f || !acc_f)) return NVSR_ERR_NULL;
+    int e;
+    if ((e = check_scene(scene))) return e;
+    float* z_c = workspace;
+    float* w_c = z_c + round4(N * (int64_t)Nc);
+    float* z_f = w_c + round4(N * (int64_t)Nc);
+    const bool in_kernel_z = !t_rand && Nf > 0 && !getenv("NVSR_STORE_COARSE_Z");      // (as nvsr_render_rays_arith: the coarse depths in registers)
+    if (Nf > 0) nvsr_internal_reserve_render_scratch(N, Nc + Nf, stream);
+    if (!in_kernel_z && (e = nvsr_coarse_z(N, Nc, rays, lindisp, t_rand, z_c, stream))) return e;
+    const float* zc = in_kernel_z ? nullptr : z_c;
+    float* wc = Nf > 0 ? w_c : nullptr;
+    if (grid_coarse) e = nvsr_render_pass_occupancy_arith(scene, packed_coarse, N, Nc, rays, zc, lindisp, white_bkgd, rgb_c, disp_c, acc_c, wc, nullptr, grid_coarse,
+                                                          G_coarse, arith, stream);
+    else if (in_kernel_z) e = nvsr_render_pass3_coarse_z_launch(arith, scene, packed_coarse, N, Nc, rays, lindisp, nullptr, white_bkgd, rgb_c, disp_c, acc_c, w_c,
+                                                                nullptr, nullptr, stream);
+    else e = nvsr_render_pass_arith(scene, packed_coarse, N, Nc, rays, z_c, nullptr, white_bkgd, rgb_c, disp_c, acc_c, wc, nullptr, nullptr, arith, stream);
+    if (e || Nf <= 0) return e;
+    e = in_kernel_z ? nvsr_importance_resample_rays(N, Nc, Nf, rays, lindisp, w_c, u, z_f, stream) : nvsr_importance_resample(N, Nc, Nf, z_c, w_c, u, z_f, stream);
+    if (e) return e;
+    if (grid_fine)
+        return nvsr_render_pass_occupancy_arith(scene, packed_fine, N, Nc + Nf, rays, z_f, 0, white_bkgd, rgb_f, disp_f, acc_f, nullptr, nullptr, grid_fine, G_fine,
+                                                arith, stream);
+    return nvsr_render_pass_arith(scene, packed_fine, N, Nc + Nf, rays, z_f, nullptr, white_bkgd, rgb_f, disp_f, acc_f, nullptr, nullptr, nullptr, arith, stream);
+}
+
 // ---- one decoder for both passes (models.fine.type == 'use_same') ----------------------------------------------------------------------
 // does this call take the shared path?  (a frame without stratified jitter on the fused limb passes -- the conditions of in_kernel_z above)
 static bool shared_path(int64_t N, int Nf, const float* t_rand, int arithmetic) {

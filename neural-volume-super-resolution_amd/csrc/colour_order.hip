@@ -2,6 +2,7 @@
 // ray a colour lane owns (live_order_kernel), WHICH ray block a colour workgroup runs (group_order_kernel), and the library's scratch that
 // holds the live lists and both orders between the launches.  include/nvsr.h, "The two-phase render pass", is the contract.
 #include "colour_order.h"
+#include "occupancy.h"
 #include "nvsr_internal.h"
 
 #include <cstdlib>
@@ -241,7 +242,10 @@ __global__ __launch_bounds__(RAYS2) void point_order_kernel(const int* __restric
 // G RAYS2 S ints of entries, then steps[G] and offs[G] -- and `views`, the view features of every slot, POINT_VIEW_FLOATS floats each.
 namespace {
 struct Buffer { void* p; size_t bytes; };
-struct LiveScratch { int device; hipStream_t stream; Buffer lists, group, points, views; int* last_n; int64_t last_N; int* last_steps; };      // last_*: the counts of the latest launch; its points' step counts
+struct LiveScratch {
+    int device; hipStream_t stream; Buffer lists, group, points, views; int* last_n; int64_t last_N; int* last_steps;      // last_*: the counts of the latest launch; its points' step counts
+    Buffer kept, kgroup; int* last_kept; int64_t last_kept_N;      // the occupancy route's kept lists and their group table; the packed kept counts of its latest launch
+};
 std::mutex g_live_mutex;
 std::vector<LiveScratch> g_live;
 
@@ -256,7 +260,7 @@ bool grow(LiveScratch& e, Buffer& b, size_t bytes) {
     if (b.bytes >= bytes) return true;
     if (b.p) (void)hipFree(b.p);
     b = Buffer{nullptr, 0};
-    e.last_n = nullptr; e.last_N = 0; e.last_steps = nullptr;
+    e.last_n = nullptr; e.last_N = 0; e.last_steps = nullptr; e.last_kept = nullptr; e.last_kept_N = 0;
     void* p = nullptr;
     if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
     b = Buffer{p, bytes};
@@ -329,10 +333,34 @@ bool two_phase_lists(const float* raw_out, int64_t N, int S, hipStream_t stream,
     return true;
 }
 
-void launch_colour_order(const LiveLists& ll, int64_t N, int S, hipStream_t stream) {
-    launch_live_order(ll.n, N, S, env_starts("NVSR_COLOUR_ORDER", '0') ? 0 : ORDER_BINS, ll.trip, stream);
-    launch_group_order(ll.trip, (N + RAYS2 - 1) / RAYS2, S, ll.slot, stream);
+// the occupancy route's scratch: the two-phase route's, then the kept lists
+bool occupancy_lists(int64_t N, int S, hipStream_t stream, LiveLists& live, KeptLists& kept) {
+    const bool lists = two_phase_lists(nullptr, N, S, stream, live);
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) return false;
+    const size_t rows = (size_t)N * (size_t)S, G = (size_t)((N + RAYS2 - 1) / RAYS2);
+    std::lock_guard<std::mutex> lock(g_live_mutex);
+    LiveScratch* e = find_scratch(device, stream);
+    if (!e) return false;                             // (two_phase_lists declined before it made the entry)
+    e->last_kept = nullptr; e->last_kept_N = 0;
+    if (!lists || !grow(*e, e->kgroup, 2 * G * sizeof(int)) || !grow(*e, e->kept, (rows + (size_t)N) * sizeof(int))) return false;
+    kept.idx = static_cast<int*>(e->kept.p);
+    kept.n = kept.idx + rows;
+    kept.slot = static_cast<int*>(e->kgroup.p);
+    kept.trip = kept.slot + G;
+    // (growing the kept lists forgot the launch that two_phase_lists has just recorded: the buffers of that launch are the same ones)
+    e->last_n = live.n; e->last_N = N; e->last_steps = live.steps;
+    e->last_kept = kept.n; e->last_kept_N = N;
+    return true;
 }
+
+// the ray order on the counts n (in place), then the order of dispatch on the trips it leaves
+static void launch_orders(int* n, int* trip, int* slot, int64_t N, int S, hipStream_t stream) {
+    launch_live_order(n, N, S, env_starts("NVSR_COLOUR_ORDER", '0') ? 0 : ORDER_BINS, trip, stream);
+    launch_group_order(trip, (N + RAYS2 - 1) / RAYS2, S, slot, stream);
+}
+void launch_kept_order(const KeptLists& kl, int64_t N, int S, hipStream_t stream) { launch_orders(kl.n, kl.trip, kl.slot, N, S, stream); }
+void launch_colour_order(const LiveLists& ll, int64_t N, int S, hipStream_t stream) { launch_orders(ll.n, ll.trip, ll.slot, N, S, stream); }
 
 void launch_point_order(const LiveLists& ll, const float* rays_nf, int64_t N, int S, hipStream_t stream) {
     const int64_t G = (N + RAYS2 - 1) / RAYS2;
@@ -385,6 +413,21 @@ extern "C" int nvsr_internal_copy_point_steps(int* dst, int64_t G, nvsr_stream_t
     return hipMemcpyAsync(dst, src, (size_t)G * sizeof(int), hipMemcpyDefault, (hipStream_t)stream) == hipSuccess ? NVSR_OK : NVSR_ERR_LAUNCH;
 }
 
+// hook of the occupancy route (include/nvsr.h): the packed kept counts of the latest occupancy launch on `stream`; none ran (or it declined): an error
+extern "C" int nvsr_internal_copy_kept_counts(int* dst, int64_t N, nvsr_stream_t stream) {
+    if (!dst) return NVSR_ERR_NULL;
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) return NVSR_ERR_LAUNCH;
+    const int* src = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(g_live_mutex);
+        const LiveScratch* c = find_scratch(device, (hipStream_t)stream);
+        if (c && c->last_kept && c->last_kept_N == N) src = c->last_kept;
+    }
+    if (!src) return NVSR_ERR_SHAPE;
+    return hipMemcpyAsync(dst, src, (size_t)N * sizeof(int), hipMemcpyDefault, (hipStream_t)stream) == hipSuccess ? NVSR_OK : NVSR_ERR_LAUNCH;
+}
+
 // a frame's driver knows its largest pass before the first launch: sizing the buffer for it up front keeps the growth (a device-wide
 // wait) out of the frame -- between the coarse and the fine pass (aux.hip).  Does nothing where the two-phase route would not be taken.
 extern "C" void nvsr_internal_reserve_render_scratch(int64_t N, int S, nvsr_stream_t stream) {
@@ -405,7 +448,7 @@ extern "C" int nvsr_release_render_scratch(void) {
     const bool have_prev = hipGetDevice(&prev) == hipSuccess;
     int rc = NVSR_OK;
     for (const LiveScratch& c : g_live)
-        for (void* p : {c.lists.p, c.group.p, c.points.p, c.views.p})
+        for (void* p : {c.lists.p, c.group.p, c.points.p, c.views.p, c.kept.p, c.kgroup.p})
             if (p && (hipSetDevice(c.device) != hipSuccess || hipFree(p) != hipSuccess)) rc = NVSR_ERR_LAUNCH;
     g_live.clear();
     if (have_prev) (void)hipSetDevice(prev);

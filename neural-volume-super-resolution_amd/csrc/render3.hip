@@ -12,6 +12,7 @@
 #include "pair_core.h"
 
 #include "colour_order.h"
+#include "occupancy.h"
 #include "nvsr_internal.h"
 
 namespace nvsr {
@@ -21,7 +22,7 @@ namespace nvsr {
 // symbols in a rocprofv3 kernel trace -- a second template parameter on one kernel trips hipcc's host pass over the LDS-DMA builtins).
 // ZCOMP: the depths are the un-jittered coarse ones (train_utils.py:95-100) and are computed from the ray's near / far in registers
 // (coarse_depth, bit for bit what nvsr_coarse_z writes) instead of being read: `z` is NULL and `lindisp` selects the spacing
-// (ONE template parameter, LZ = LIMBS + 8 * ZCOMP + 16 * PHASE: with a second one hipcc's host pass fails to resolve the LDS-DMA helpers inside the body)
+// (ONE template parameter, LZ = LIMBS + 8 * ZCOMP + 16 * PHASE, PHASE three bits wide: with a second one hipcc's host pass fails to resolve the LDS-DMA helpers inside the body)
 //
 // PHASE: 0 = the fused pass (both decoders on every sample: the path of raw_out != NULL and of NVSR_RENDER_ONE_PHASE=1).
 // The two-phase route runs the colour decoder only where it can reach the pixel -- w = alpha T is +0.0 exactly wherever sigma + noise <= 0,
@@ -48,6 +49,15 @@ namespace nvsr {
 //       a global table (POINT_VIEW_FLOATS per slot, 48 KB per group) and each step loads its points' rows, a step ahead; every lane stores its
 //       point's three terms w sigmoid(raw) in LDS, and behind a barrier the first point of every run adds its run's terms, in order, to the
 //       ray's sums in LDS: the same operands in the same order as phase 2.  Entries are read two steps ahead, list entries one.
+//   4 = density pass over the kept lists of the occupancy route (occupancy.hip; include/nvsr.h, "Occupancy grid"): phase 1's decoder, gathers and
+//       compositing, but the loop runs over k < trip = max kept count of the workgroup's 256 rays, as phase 2's does: a lane evaluates its ray's
+//       k-th KEPT sample idx = kept[ray][k] -- zc = depth(idx); dist from the sample's own successor in the full row, depth(idx + 1) - zc, or
+//       1e10 for idx = S - 1 -- and a lane past its own count re-evaluates its last entry and keeps T, depth, acc and its list cursor by selects.
+//       A culled sample is never seen: it would have had alpha = 0, w = +0.0 and left T as it was.  The next step's gathers roll through the
+//       current one as in phase 1; the kept entries are read in the epilogue, up to two steps ahead, so that (depths read) the next step's depth
+//       can be loaded a step ahead; an invalid slot (ray >= N) reads the clamped ray's row but is never active.
+//       Which ray a lane owns and which block a workgroup runs come from live_order_kernel / group_order_kernel on the kept counts (kept_n:
+//       packed entries, an array of its own); the pass writes live_n[ray] and the live lists as phase 1 does, and weights at [ray][idx] only.
 // Neither chain's K-order changes and dead samples contributed +0.0 to non-negative sums, so the pixels are bit for bit the fused pass's.
 template <int LZ>
 __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const float* __restrict__ packed, long N, int S,
@@ -58,11 +68,12 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
                                                   float* __restrict__ depth, float* __restrict__ raw_out, unsigned* __restrict__ flag,
                                                   float* __restrict__ live_z = nullptr, float* __restrict__ live_w = nullptr,
                                                   int* __restrict__ live_n = nullptr, const int* __restrict__ group_slot = nullptr,
-                                                  const int* __restrict__ pts = nullptr, const int* __restrict__ pt_steps = nullptr, float* views = nullptr) {
+                                                  const int* __restrict__ pts = nullptr, const int* __restrict__ pt_steps = nullptr, float* views = nullptr,
+                                                  const int* __restrict__ kept = nullptr, const int* __restrict__ kept_n = nullptr) {
     constexpr int LIMBS = LZ & 7;
     constexpr bool ZCOMP = (LZ & 8) != 0;
-    constexpr int PHASE = (LZ >> 4) & 3;
-    constexpr bool FUSED = PHASE == 0, DENSITY = PHASE == 1, POINTS = PHASE == 3, COLOUR = PHASE == 2 || POINTS;
+    constexpr int PHASE = (LZ >> 4) & 7;
+    constexpr bool FUSED = PHASE == 0, KEPT = PHASE == 4, DENSITY = PHASE == 1 || KEPT, POINTS = PHASE == 3, COLOUR = PHASE == 2 || POINTS;
     using L = Lds3<LIMBS>;
     constexpr int NP = limb_products(LIMBS);
     constexpr int NSF = 3 * 4 * NP, NSH = 4 * 4 * NP;          // slots of a feature block / of half a hidden layer
@@ -89,7 +100,7 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
     // r % 8, so that the long lists start first and are dealt round the XCDs; with NVSR_COLOUR_GROUP_ORDER=0 the table holds this formula.
     const unsigned nblk = gridDim.x, xcd = blockIdx.x & 7u, per = nblk >> 3, rem = nblk & 7u;
     unsigned blk_ = xcd * per + (xcd < rem ? xcd : rem) + (blockIdx.x >> 3);
-    if constexpr (COLOUR) blk_ = (unsigned)__builtin_amdgcn_readfirstlane(group_slot[blockIdx.x]);
+    if constexpr (COLOUR || KEPT) blk_ = (unsigned)__builtin_amdgcn_readfirstlane(group_slot[blockIdx.x]);
     const unsigned blk = blk_;
     const long base = (long)blk * RAYS2 + rs.wave * 64 + (lane0 & 31);
     long rayX = base, rayY = base + 32;
@@ -97,11 +108,12 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
     if (!validX) rayX = N - 1;
     if (!validY) rayY = N - 1;
     int nX = 0, nY = 0;
-    if constexpr (COLOUR) {
+    if constexpr (COLOUR || KEPT) {
         // the slot names the ray (packed entries of live_order_kernel); an invalid slot keeps the clamped ray and count 0: it cannot lengthen trip
+        const int* const order = KEPT ? kept_n : live_n;
         const long block_base = (long)(blk / (ORDER_RAYS / RAYS2)) * ORDER_RAYS;
-        if (validX) { const int e = live_n[base]; rayX = block_base + (e & (ORDER_RAYS - 1)); nX = e >> ORDER_SHIFT; }
-        if (validY) { const int e = live_n[base + 32]; rayY = block_base + (e & (ORDER_RAYS - 1)); nY = e >> ORDER_SHIFT; }
+        if (validX) { const int e = order[base]; rayX = block_base + (e & (ORDER_RAYS - 1)); nX = e >> ORDER_SHIFT; }
+        if (validY) { const int e = order[base + 32]; rayY = block_base + (e & (ORDER_RAYS - 1)); nY = e >> ORDER_SHIFT; }
     }
     constexpr int RAY3_FLOATS = L::RAY_FLOATS;
     const int ownX = rs.wave * 64 + (lane0 & 31), ownY = ownX + 32;      // the slots whose ray the lane loads (and, but for POINTS, owns)
@@ -126,8 +138,9 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
             reinterpret_cast<f32x4*>(rtp)[1] = f32x4{vt.nw, vt.ne, vt.sw, vt.se};
         }
     }
-    const float* zX = ZCOMP || COLOUR ? nullptr : z + rayX * S;
-    const float* zY = ZCOMP || COLOUR ? nullptr : z + rayY * S;
+    // (kept lists: the depth rows' pointers, like the kept rows', are formed where they are used: z_row)
+    const float* zX = ZCOMP || COLOUR || KEPT ? nullptr : z + rayX * S;
+    const float* zY = ZCOMP || COLOUR || KEPT ? nullptr : z + rayY * S;
     auto depth_of = [&](const float* zp, const float* rc, int k) NVSR_INL {
         if constexpr (ZCOMP) return coarse_depth(rc[7], L::FAR >= 0 ? ldsf[L::FAR + rs.wave * 64 + (rs.lane & 31) + (rc == rcX ? 0 : 32)] : rc[16], k, S, lindisp);
         else return zp[k];
@@ -144,6 +157,23 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
     const float* lwY = COLOUR ? live_w + rayY * S : nullptr;
     int trip = S;
     float wX = 0.0f, wY = 0.0f, wXn = 0.0f, wYn = 0.0f;
+    // density pass over the kept lists: the rays' lists (rows of S sample indices; nX, nY are valid), the entries of this step, the next and the
+    // one after it, the depth of this sample's successor in the full row, and the cursors of the live lists (phase 1 too)
+    // (a row of `kept` starts rayX * S words into it: the row pointers are formed where they are used, not held over the decoder's blocks)
+    auto kept_row = [&](long ray) NVSR_INL -> const int* {
+        asm volatile("" : "+v"(ray));
+        return kept + ray * S;
+    };
+    auto z_row = [&](long ray) NVSR_INL -> const float* {
+        if constexpr (ZCOMP) return nullptr;
+        asm volatile("" : "+v"(ray));
+        return z + ray * S;
+    };
+    int idxX = 0, idxY = 0, idxXn = 0, idxYn = 0, cX = 0, cY = 0;
+    bool actX = false, actY = false;                 // does the lane's list reach this step?  (past it the lane keeps what it has)
+    // entry k of a kept list; behind the list's end (the cull kernel wrote -1 there) the entry before it, so the index stops advancing: a
+    // step is the list's own iff its index differs from the previous step's.  An empty list gives sample 0 (evaluated, never composited).
+    auto kept_at = [&](const int* kp, int k, int prev) NVSR_INL -> int { const int e = kp[k < S ? k : S - 1]; return e < 0 ? prev : e; };
     // entry k of a live list, clamped to the last valid one; an empty list gives the ray's near depth and weight 0 (never composited)
     auto live_depth = [&](const float* lzp, const float* rc, int n, int k) NVSR_INL -> float {
         if (n == 0) return rc[7];
@@ -184,16 +214,25 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
         static_assert(!R3_BOUNCE, "the points' LDS region is the f16 kernels' bounce slot");
         trip = __builtin_amdgcn_readfirstlane(pt_steps[blk]);
         __syncthreads();                              // the ray cache, written by lanes 0..31 and read by all 64
-    } else if constexpr (COLOUR) {
-        __shared__ int trip_s[NW2];                   // (the colour kernels' alone: the other phases declare nothing)
+    } else if constexpr (COLOUR || KEPT) {
+        __shared__ int trip_s[NW2];                   // (the colour kernels' and the kept density kernels' alone: the other phases declare nothing)
         int m = max(nX, nY);
 #pragma unroll
         for (int o = 16; o >= 1; o >>= 1) m = max(m, __shfl_xor(m, o));
         if (lane0 == 0) trip_s[rs.wave] = m;
         __syncthreads();                              // the wave maxima; also the ray cache, written by lanes 0..31 and read by all 64
         trip = __builtin_amdgcn_readfirstlane(max(max(trip_s[0], trip_s[1]), max(trip_s[2], trip_s[3])));
-        X.zc = live_depth(lzX, rcX, nX, 0); Y.zc = live_depth(lzY, rcY, nY, 0);
-        wX = live_weight(lwX, nX, 0); wY = live_weight(lwY, nY, 0);
+        if constexpr (KEPT) {
+            const int* kX = kept_row(rayX);
+            const int* kY = kept_row(rayY);
+            actX = nX > 0; actY = nY > 0;
+            idxX = kept_at(kX, 0, 0); idxY = kept_at(kY, 0, 0);
+            idxXn = kept_at(kX, 1, idxX); idxYn = kept_at(kY, 1, idxY);
+            X.zc = depth_of(z_row(rayX), rcX, idxX); Y.zc = depth_of(z_row(rayY), rcY, idxY);
+        } else {
+            X.zc = live_depth(lzX, rcX, nX, 0); Y.zc = live_depth(lzY, rcY, nY, 0);
+            wX = live_weight(lwX, nX, 0); wY = live_weight(lwY, nY, 0);
+        }
     } else {
         if constexpr (ZCOMP) __syncthreads();         // (the ray cache is written by lanes 0..31 and read by all 64, see below)
         X.zc = depth_of(zX, rcX, 0); Y.zc = depth_of(zY, rcY, 0);
@@ -293,7 +332,7 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
     unsigned* const res = lds + L::RES;
     if constexpr (RESIDENT) ring3_load_resident<LIMBS, L::RES_KB>(rs, res, KB_RGB0);
     unsigned* cw = const_cast<unsigned*>(ring3_issue<LIMBS, 3>(rs, KB_FIRST));     // first ring chunk of sample 0; every later one is issued during the previous sample
-    const int steps = COLOUR ? trip : S;
+    const int steps = COLOUR || KEPT ? trip : S;
     for (int s = 0; s < steps; ++s) {
         asm volatile("" : "+v"(rs.voff), "+v"(rs.lane));
 #if R3_NO_VIEW_HOIST
@@ -308,7 +347,7 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
         if constexpr (POINTS) { rcX = ldsf + L::RAYS + slotX * RAY3_FLOATS; rcY = ldsf + L::RAYS + slotY * RAY3_FLOATS; }
         const int lane = rs.lane, h = lane >> 5;
         const bool last = (s + 1 == S);
-        if constexpr (!COLOUR) {
+        if constexpr (!COLOUR && !KEPT) {
             X.zn = depth_of(zX, rcX, last ? s : s + 1);        // (unconditional loads unless ZCOMP: ring3_sync<2> below counts them)
             Y.zn = depth_of(zY, rcY, last ? s : s + 1);
         }
@@ -316,8 +355,10 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
         const float nzY = !COLOUR && noise ? noise[rayY * S + s] : 0.0f;
         float xn0, xn1, xn2, yn0, yn1, yn2;
         // (density pass: the planes gathered during this step are the NEXT sample's; after the last sample they are gathered again and dropped)
-        point_norm(rcX, DENSITY ? X.zn : X.zc, xn0, xn1, xn2);
-        point_norm(rcY, DENSITY ? Y.zn : Y.zc, yn0, yn1, yn2);
+        if constexpr (!KEPT) {
+            point_norm(rcX, DENSITY ? X.zn : X.zc, xn0, xn1, xn2);
+            point_norm(rcY, DENSITY ? Y.zn : Y.zc, yn0, yn1, yn2);
+        }
         BiasPend4 bp;
         bp.slot = bounce_slot(ldsf + L::VTAPS + rs.wave * 64 * L::TAP_FLOATS + lane * 4);     // (f16 limbs: the wave's tap region, dead since the prologue)
         HeadPend<3> hp3;
@@ -338,7 +379,7 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
         // multiplies plane p - 1 of a tile loads plane p of the same tile, the next block blends it.
         GatherJob ja, jb;
         R3_MARK(0)      // loop top
-        ring3_sync<(ZCOMP || COLOUR) ? 0 : 2>();                 // the step's first ring chunk (issued during the previous sample) -- younger: the two z loads above
+        ring3_sync<(ZCOMP || COLOUR || KEPT) ? 0 : 2>();         // the step's first ring chunk (issued during the previous sample) -- younger: the two z loads above
         int eX2 = POINT_NONE, eY2 = POINT_NONE;
         if constexpr (POINTS) {
             // the entries of the step after the next, and the next step's point: both a whole step ahead of their use
@@ -349,6 +390,11 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
             // the next live entry, a whole step ahead of its use (issued behind the wait: no ring wait has to count these loads)
             X.zn = live_depth(lzX, rcX, nX, s + 1); Y.zn = live_depth(lzY, rcY, nY, s + 1);
             wXn = live_weight(lwX, nX, s + 1); wYn = live_weight(lwY, nY, s + 1);
+        } else if constexpr (KEPT) {
+            // behind the wait, like the colour pass's: the next sample's depth (its gathers roll through this step)
+            X.zn = depth_of(z_row(rayX), rcX, idxXn); Y.zn = depth_of(z_row(rayY), rcY, idxYn);
+            point_norm(rcX, X.zn, xn0, xn1, xn2);
+            point_norm(rcY, Y.zn, yn0, yn1, yn2);
         }
         // RESIDENT (f16 limbs): view plane, planes 0 and 1 multiply out of the resident region; the ring chunk that has just landed is plane 2's,
         // and the blocks that issue gathers (B0 .. B5) issue no weight copy and need no ring wait
@@ -618,6 +664,17 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
         if constexpr (!COLOUR) {
 
         // ---- epilogue (exposed): Y's last activation + sigma head, both tiles' compositing -----------------------------------------
+        // kept lists: the depth of this sample's successor in the full row (its dist) and the raw entries of the next step and of the one after
+        // it -- two steps ahead, so that the next step can load its depth a step ahead (waited for at the loop's top) -- are fetched here, in
+        // front of Y's head, and held over the compositing only: the decoder's blocks carry the current entry alone
+        float zsX = 0.0f, zsY = 0.0f;
+        int e1X = 0, e1Y = 0, e2X = 0, e2Y = 0;
+        const bool lastX = KEPT ? idxX + 1 == S : last, lastY = KEPT ? idxY + 1 == S : last;
+        if constexpr (KEPT) {
+            zsX = depth_of(z_row(rayX), rcX, lastX ? idxX : idxX + 1); zsY = depth_of(z_row(rayY), rcY, lastY ? idxY : idxY + 1);
+            { const int* kX = kept_row(rayX); e1X = kX[s + 1 < S ? s + 1 : S - 1]; e2X = kX[s + 2 < S ? s + 2 : S - 1]; }
+            { const int* kY = kept_row(rayY); e1Y = kY[s + 1 < S ? s + 1 : S - 1]; e2Y = kY[s + 2 < S ? s + 2 : S - 1]; }
+        }
 #pragma unroll
         for (int k = 0; k < RELU_STEPS; ++k) relu_bias_step<LIMBS>(k, small + S_BIAS + 3 * HID, h, Y.acc, Y.act, bp, nsc);
         {
@@ -629,7 +686,22 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
             if (validX) *reinterpret_cast<f32x4*>(raw_out + (rayX * S + s) * 4) = f32x4{X.raw[0], X.raw[1], X.raw[2], X.raw[3]};
             if (validY) *reinterpret_cast<f32x4*>(raw_out + (rayY * S + s) * 4) = f32x4{Y.raw[0], Y.raw[1], Y.raw[2], Y.raw[3]};
         }
-        if constexpr (DENSITY) {
+        if constexpr (!KEPT) actX = actY = true;
+        if constexpr (KEPT) {
+            // one tile at a time: the successor's depth stands in for zn during the compositing; a lane past its list keeps what it had
+            {
+                const float t0 = X.T, d0 = X.dep, a0 = X.ac, g0 = X.zn;
+                X.zn = zsX;
+                composite_weight(X, reinterpret_cast<const f32x4*>(rcX)[1][2], 0.0f, lastX);
+                X.zn = g0; X.T = actX ? X.T : t0; X.dep = actX ? X.dep : d0; X.ac = actX ? X.ac : a0;
+            }
+            {
+                const float t0 = Y.T, d0 = Y.dep, a0 = Y.ac, g0 = Y.zn;
+                Y.zn = zsY;
+                composite_weight(Y, reinterpret_cast<const f32x4*>(rcY)[1][2], 0.0f, lastY);
+                Y.zn = g0; Y.T = actY ? Y.T : t0; Y.dep = actY ? Y.dep : d0; Y.ac = actY ? Y.ac : a0;
+            }
+        } else if constexpr (DENSITY) {
             composite_weight(X, reinterpret_cast<const f32x4*>(rcX)[1][2], nzX, last);
             composite_weight(Y, reinterpret_cast<const f32x4*>(rcY)[1][2], nzY, last);
         } else {
@@ -637,17 +709,23 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
             composite_sample(Y, reinterpret_cast<const f32x4*>(rcY)[1][2], nzY, last);
         }
         if (weights && lane < 32) {
-            if (validX) weights[rayX * S + s] = X.raw[3];
-            if (validY) weights[rayY * S + s] = Y.raw[3];
+            if (validX && actX) weights[rayX * S + (KEPT ? idxX : s)] = X.raw[3];
+            if (validY && actY) weights[rayY * S + (KEPT ? idxY : s)] = Y.raw[3];
         }
         if constexpr (DENSITY) {
             // the live list: every sample whose weight is not zero (a NaN weight is live), in sample order
-            const bool liveX = !(X.raw[3] == 0.0f), liveY = !(Y.raw[3] == 0.0f);
+            const bool liveX = actX && !(X.raw[3] == 0.0f), liveY = actY && !(Y.raw[3] == 0.0f);
             if (lane < 32) {
-                if (validX && liveX) { live_z[rayX * S + nX] = ZCOMP ? __int_as_float(s) : X.zc; live_w[rayX * S + nX] = X.raw[3]; }
-                if (validY && liveY) { live_z[rayY * S + nY] = ZCOMP ? __int_as_float(s) : Y.zc; live_w[rayY * S + nY] = Y.raw[3]; }
+                if (validX && liveX) { live_z[rayX * S + cX] = ZCOMP ? __int_as_float(KEPT ? idxX : s) : X.zc; live_w[rayX * S + cX] = X.raw[3]; }
+                if (validY && liveY) { live_z[rayY * S + cY] = ZCOMP ? __int_as_float(KEPT ? idxY : s) : Y.zc; live_w[rayY * S + cY] = Y.raw[3]; }
             }
-            nX += liveX; nY += liveY;
+            cX += liveX; cY += liveY;
+            if constexpr (KEPT) {
+                // the next step is the list's own iff its entry exists; behind the list's end the index stops advancing (kept_at)
+                actX = validX && s + 1 < S && e1X >= 0; actY = validY && s + 1 < S && e1Y >= 0;      // (an invalid slot reads the clamped ray's row: never active)
+                idxX = e1X < 0 ? idxX : e1X; idxY = e1Y < 0 ? idxY : e1Y;
+                idxXn = e2X < 0 ? idxX : e2X; idxYn = e2Y < 0 ? idxY : e2Y;
+            }
         }
         } else {
         // ---- colour pass epilogue (exposed): X's raw colours, Y's last activation + rgb heads, both tiles' w sigmoid(raw) ------------
@@ -723,7 +801,7 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
                 if (depth) depth[ray] = t.dep;
             }
             if constexpr (DENSITY) {
-                live_n[ray] = k ? nY : nX;
+                live_n[ray] = k ? cY : cX;
                 cr = cg = cb = 0.0f;                            // (the range flag below then looks at acc alone; the colour pass looks at rgb)
             } else {
                 if (white) { const float bg = 1.0f - ac; cr += bg; cg += bg; cb += bg; }
@@ -811,6 +889,35 @@ __global__ __launch_bounds__(TPB2, 1) void render_pass3_colour_z_kernel(SceneDev
                                                                        const int* __restrict__ group_slot) {
 #if defined(__HIP_DEVICE_COMPILE__)
     render_pass3_body<LIMBS + 8 + 32>(sc, packed, N, S, rays, nullptr, lindisp, nullptr, white, rgb, nullptr, acc, nullptr, nullptr, nullptr, flag, live_z, live_w, live_n, group_slot);
+#endif
+}
+
+// the density pass over the kept lists of the occupancy route (PHASE 4): kept [N, S] sample indices, kept_n [N] packed entries of the ray order
+// on the kept counts, group_slot: the order of dispatch on them.  No noise: the route serves evaluation.
+template <int LIMBS>
+__global__ __launch_bounds__(TPB2, 1) void render_pass3_density_kept_kernel(SceneDev sc, const float* __restrict__ packed, long N, int S,
+                                                                           const float* __restrict__ rays, const float* __restrict__ z,
+                                                                           float* __restrict__ disp, float* __restrict__ acc, float* __restrict__ weights,
+                                                                           float* __restrict__ depth, unsigned* __restrict__ flag,
+                                                                           float* __restrict__ live_z, float* __restrict__ live_w, int* __restrict__ live_n,
+                                                                           const int* __restrict__ group_slot, const int* __restrict__ kept,
+                                                                           const int* __restrict__ kept_n) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    render_pass3_body<LIMBS + 64>(sc, packed, N, S, rays, z, 0, nullptr, 0, nullptr, disp, acc, weights, depth, nullptr, flag, live_z, live_w, live_n, group_slot,
+                                  nullptr, nullptr, nullptr, kept, kept_n);
+#endif
+}
+template <int LIMBS>
+__global__ __launch_bounds__(TPB2, 1) void render_pass3_density_kept_z_kernel(SceneDev sc, const float* __restrict__ packed, long N, int S,
+                                                                             const float* __restrict__ rays, int lindisp,
+                                                                             float* __restrict__ disp, float* __restrict__ acc, float* __restrict__ weights,
+                                                                             float* __restrict__ depth, unsigned* __restrict__ flag,
+                                                                             float* __restrict__ live_z, float* __restrict__ live_w, int* __restrict__ live_n,
+                                                                             const int* __restrict__ group_slot, const int* __restrict__ kept,
+                                                                             const int* __restrict__ kept_n) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    render_pass3_body<LIMBS + 8 + 64>(sc, packed, N, S, rays, nullptr, lindisp, nullptr, 0, nullptr, disp, acc, weights, depth, nullptr, flag, live_z, live_w, live_n,
+                                      group_slot, nullptr, nullptr, nullptr, kept, kept_n);
 #endif
 }
 
@@ -935,16 +1042,27 @@ extern "C" int nvsr_pack_decoder_limbs_launch(const float* natural, float* packe
 // ---- the launches of one render pass: the two-phase route (density pass, the colour pass's orders, colour pass on the lists `ll`), or the
 // fused kernel where two_phase_lists declines (ll = NULL).  z = NULL: the coarse pass with its depths computed in the kernel from
 // (near, far, s, S, lindisp); it always writes the weights.
+// occ (with ll): the occupancy route -- the cull kernel and the orders on its counts in front, the density pass over the kept lists.
+struct OccLaunch { const uint32_t* grid; int G; KeptLists kept; };
 template <int LIMBS>
 static int launch_pass3(const LiveLists* ll, const nvsr_scene* scene, const float* packed, int64_t N, int S, const float* rays, const float* z, int lindisp,
-                        const float* noise, int white, float* rgb, float* disp, float* acc, float* weights, float* depth, float* raw_out, hipStream_t stream) {
+                        const float* noise, int white, float* rgb, float* disp, float* acc, float* weights, float* depth, float* raw_out, hipStream_t stream,
+                        const OccLaunch* occ = nullptr) {
     const SceneDev sc = to_dev(scene);
     unsigned* flag = nvsr_get_range_flag();
     auto launch = [&](auto kernel, auto... args) {      // (every kernel's arguments start alike)
         hipLaunchKernelGGL(kernel, dim3((unsigned)((N + RAYS2 - 1) / RAYS2)), dim3(TPB2), 0, stream, sc, packed, (long)N, S, rays, args...);
     };
     if (ll) {
-        if (z) launch(render_pass3_density_kernel<LIMBS>, z, noise, disp, acc, weights, depth, flag, ll->z, ll->w, ll->n);
+        if (occ) {
+            const KeptLists& kl = occ->kept;
+            launch_occupancy_cull(sc, N, S, rays, z, lindisp, occ->grid, occ->G, kl.idx, kl.n, stream);
+            launch_kept_order(kl, N, S, stream);
+            // a culled sample has weight +0.0: the pass writes the kept samples' weights only
+            if (weights && hipMemsetAsync(weights, 0, (size_t)N * (size_t)S * sizeof(float), stream) != hipSuccess) return NVSR_ERR_LAUNCH;
+            if (z) launch(render_pass3_density_kept_kernel<LIMBS>, z, disp, acc, weights, depth, flag, ll->z, ll->w, ll->n, kl.slot, kl.idx, kl.n);
+            else launch(render_pass3_density_kept_z_kernel<LIMBS>, lindisp, disp, acc, weights, depth, flag, ll->z, ll->w, ll->n, kl.slot, kl.idx, kl.n);
+        } else if (z) launch(render_pass3_density_kernel<LIMBS>, z, noise, disp, acc, weights, depth, flag, ll->z, ll->w, ll->n);
         else launch(render_pass3_density_z_kernel<LIMBS>, lindisp, noise, disp, acc, weights, depth, flag, ll->z, ll->w, ll->n);
         launch_colour_order(*ll, N, S, stream);
         if (ll->pts) {
@@ -979,4 +1097,28 @@ extern "C" int nvsr_render_pass3_coarse_z_launch(int limbs, const nvsr_scene* sc
                                                  float* raw_out, nvsr_stream_t stream) {
     if ((N + RAYS2 - 1) / RAYS2 > 0x7fffffff || (limbs != 2 && limbs != 3) || !weights) return NVSR_ERR_SHAPE;
     return launch_pass3(limbs, scene, packed_decoder, N, S, rays, nullptr, lindisp, noise, white_bkgd, rgb, disp, acc, weights, depth, raw_out, (hipStream_t)stream);
+}
+
+// The occupancy route (include/nvsr.h, "Occupancy grid"): the pass above with the density decoder run on the samples of set cells only.  Declines -- and
+// runs the plain route, which is what the grid approximates -- where the two-phase route declines or the kept lists cannot be had.
+// z == NULL: the depths of coarse_depth in registers (lindisp); weights are then required, as by the coarse_z launch.
+extern "C" int nvsr_render_pass_occupancy_arith(const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays, const float* z, int lindisp,
+                                                int white_bkgd, float* rgb, float* disp, float* acc, float* weights, float* depth, const uint32_t* grid, int G,
+                                                int arithmetic, nvsr_stream_t stream) {
+    const int arith = nvsr_internal_resolve_decoder_arith(arithmetic);
+    if ((arith != NVSR_ARITH_F16X2 && arith != NVSR_ARITH_BF16X3) || G < 1 || G > OCC_MAX_G) return NVSR_ERR_SHAPE;
+    if (int e = check_scene(scene)) return e;
+    if (!packed_decoder || !rays || !rgb || !disp || !acc || !grid || (!z && !weights)) return NVSR_ERR_NULL;
+    if (!aligned16(packed_decoder)) return NVSR_ERR_ALIGN;
+    if (N < 0 || S < 1 || S > 4096 || (N + RAYS2 - 1) / RAYS2 > 0x7fffffff) return NVSR_ERR_SHAPE;
+    if (N == 0) return NVSR_OK;
+    const int limbs = arith == NVSR_ARITH_F16X2 ? 2 : 3;
+    LiveLists lists;
+    OccLaunch occ{grid, G, {}};
+    if (!occupancy_lists(N, S, (hipStream_t)stream, lists, occ.kept))
+        return launch_pass3(limbs, scene, packed_decoder, N, S, rays, z, lindisp, nullptr, white_bkgd, rgb, disp, acc, weights, depth, nullptr, (hipStream_t)stream);
+    return limbs == 3 ? launch_pass3<3>(&lists, scene, packed_decoder, N, S, rays, z, lindisp, nullptr, white_bkgd, rgb, disp, acc, weights, depth, nullptr,
+                                        (hipStream_t)stream, &occ)
+                      : launch_pass3<2>(&lists, scene, packed_decoder, N, S, rays, z, lindisp, nullptr, white_bkgd, rgb, disp, acc, weights, depth, nullptr,
+                                        (hipStream_t)stream, &occ);
 }

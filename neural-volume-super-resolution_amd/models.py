@@ -311,6 +311,66 @@ class TwoDimPlanesModel(nn.Module):
                 _PLANE_CACHE.pop(k, None)
                 _PLANE_CACHE.pop(k + "/SR", None)
         self._generated_dict().clear()           # (a `.data` write leaves the factor's version where it was)
+        self.__dict__.pop("_occupancy", None)    # (occupancy grids are derived from the planes and the decoder)
+
+    # ---- occupancy grid (csrc/occupancy.hip; include/nvsr.h, "Occupancy grid"): opt-in, evaluation only ------------------------------------
+    def _occupancy_key(self):
+        """(data_ptr, _version) of everything a grid of the current scene was probed from: the planes scene_args() returns now, through their
+        sources -- the raw or generated planes; for a super-resolved plane what it is made from, the SR network's parameters and its LR
+        planes, not the SR output itself: that tensor is remade (the f16 range re-render in 'bf16x3' drops it) without the scene changing --
+        and the decoder"""
+        self.scene_args()                          # (super-resolves / generates what is missing, so that the sources below are the cached ones)
+        srcs = [self._plane_source(d) for d in range(self.num_density_planes + 1)]
+        ts = [t for name, t in srcs if not name.endswith("/SR")] + list(self.decoder_parameters())
+        if hasattr(self, "SR_model") and not self.skip_SR_:
+            ts += list(self.SR_model.inner_model.parameters()) + list(getattr(self.SR_model, "LR_planes", {}).values())
+        for name, t in srcs:                                # a generated low-rank plane: also the factor it was made from, at that version
+            meta = getattr(t, "_nvsr_generated", None)
+            src = meta.src() if meta is not None else None
+            if src is not None:
+                ts = ts + [src]
+        return tuple((t.data_ptr(), t._version) for t in ts)
+
+    def build_occupancy(self, scene_id, resolution=128, probes=2, threshold=0.0, dilate=1):
+        """Build and keep the occupancy grid of `scene_id` for THIS model's decoder (the coarse and the fine model each have their own):
+        resolution^3 cells over the scene's box, each probed at probes^3 points with the density decoder; a cell is occupied iff a probe
+        has sigma_raw > threshold (or NaN), then `dilate` rounds of a 3x3x3 OR.  Evaluation renders of this scene (no noise, native geometry,
+        a limb arithmetic) then skip the density decoder in empty cells.  The grid is APPROXIMATE by nature -- no finite set of probes bounds
+        an MLP over a cell -- and resolution, probes, threshold and dilate are the caller's knobs.  It is built from what scene_args()
+        returns now (super-resolved planes where the model super-resolves, generated planes of low-rank scenes) and is dropped, never
+        used, once a plane or a decoder parameter has changed (occupancy()).  -> the grid, int32 [ceil(resolution^3 / 32)]"""
+        self._check_native_geometry()
+        self.set_cur_scene_id(scene_id)
+        with torch.no_grad():
+            planes, consts = self.scene_args()
+            grid = torch.ops.nvsr.occupancy_build(planes, consts, self.packed_decoder(), int(resolution), int(probes), float(threshold), int(dilate),
+                                                  self.arith())
+        self.__dict__.setdefault("_occupancy", {})[scene_id] = (self._occupancy_key(), grid, int(resolution))
+        return grid
+
+    def clear_occupancy(self, scene_id=None):
+        """drop the grid of one scene, or of every scene"""
+        if scene_id is None:
+            self.__dict__.pop("_occupancy", None)
+        else:
+            self.__dict__.get("_occupancy", {}).pop(scene_id, None)
+
+    def occupancy_entry(self, scene_id):
+        """(grid, resolution) of `scene_id`, or None if there is none or it is stale -- a stale grid is dropped, never used.  Makes `scene_id`
+        the current scene."""
+        hit = self.__dict__.get("_occupancy", {}).get(scene_id)
+        if hit is None:
+            return None
+        self.set_cur_scene_id(scene_id)
+        if hit[0] != self._occupancy_key():
+            self.clear_occupancy(scene_id)
+            return None
+        return hit[1], hit[2]
+
+    def occupancy(self, scene_id):
+        """the grid of `scene_id` (build_occupancy), or None if there is none or if it is stale"""
+        hit = self.occupancy_entry(scene_id)
+        return None if hit is None else hit[0]
 
     def train(self, mode=True):
         """nn.Module.train, and on a CHANGE of mode the derived copies are dropped: a training loop may have updated the parameters through

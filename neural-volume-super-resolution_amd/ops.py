@@ -362,6 +362,94 @@ def _(planes, consts, packed_coarse, packed_fine, rays, Nc, Nf, lindisp, white, 
     return e((N, 3)), e((N,)), e((N,)), e((M, 3)), e((M,)), e((M,))
 
 
+# ---- occupancy grid (csrc/occupancy.hip; include/nvsr.h, "Occupancy grid"): opt-in, evaluation only -------------------------------------
+def _grid(grid, G):
+    """a grid tensor of an operator: int32 [ceil(G^3 / 32)] on the GPU, or None"""
+    if grid is None:
+        return None
+    capi.require_cuda(grid)
+    assert grid.dtype == torch.int32 and grid.is_contiguous() and grid.numel() == (G ** 3 + 31) // 32, "grid: int32 [ceil(G^3 / 32)]"
+    return grid
+
+
+@custom_op("nvsr::occupancy_build", mutates_args=(), device_types="cuda")
+def occupancy_build(planes: Sequence[Tensor], consts: Sequence[float], packed: Tensor, G: int, K: int, threshold: float, dilate: int,
+                    arith: int = -1) -> Tensor:
+    """The occupancy grid of (planes, decoder): G^3 bits over the scene's box, cell (ix, iy, iz) = bit i & 31 of word i >> 5, i = (iz G + iy) G + ix.
+    A bit is set iff one of the cell's K^3 probes has sigma_raw > threshold (or NaN), then `dilate` rounds of a 3x3x3 OR.  Approximate by
+    nature: K, threshold and dilate are the caller's knobs.  -> int32 [ceil(G^3 / 32)]"""
+    sc = _scene(planes, consts)
+    words = capi.lib().nvsr_occupancy_words(int(G))
+    if words <= 0:
+        raise capi.NvsrError("nvsr_occupancy_build failed: %s" % capi._STATUS[1])
+    grid = torch.empty(words, dtype=torch.int32, device=packed.device)
+    ws = _f(max(int(capi.lib().nvsr_occupancy_workspace_floats(int(G), int(K))), 4), like=packed)
+    capi.call("nvsr_occupancy_build", C.byref(sc), capi.ptr(packed), int(G), int(K), float(threshold), int(dilate), int(arith), capi.ptr(grid), capi.ptr(ws),
+              capi.stream())
+    return grid
+
+
+@occupancy_build.register_fake
+def _(planes, consts, packed, G, K, threshold, dilate, arith=-1):
+    return packed.new_empty(((G ** 3 + 31) // 32,), dtype=torch.int32)
+
+
+@custom_op("nvsr::render_pass_occupancy", mutates_args=(), device_types="cuda")
+def render_pass_occupancy(planes: Sequence[Tensor], consts: Sequence[float], packed: Tensor, rays: Tensor, z: Optional[Tensor], S: int, lindisp: bool,
+                          white: bool, want_weights: bool, grid: Tensor, G: int, arithmetic: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """render_pass with the density decoder run only on the samples whose cell of `grid` is set (limb arithmetics, no noise).  z [N,S], or
+    None: the S un-jittered coarse depths, formed in the kernel (lindisp; the weights are then always written)
+    -> rgb [N,3], disp [N], acc [N], weights [N,S] (empty unless want_weights)"""
+    rays, z = _c(rays), _c(z)
+    sc = _scene(planes, consts)
+    N = rays.shape[0]
+    assert z is None or tuple(z.shape) == (N, S)
+    want_weights = bool(want_weights) or z is None
+    rgb, disp, acc = _f(N, 3, like=rays), _f(N, like=rays), _f(N, like=rays)
+    w = _f(N, S, like=rays) if want_weights else _f(0, like=rays)
+    if N:
+        capi.call("nvsr_render_pass_occupancy_arith", C.byref(sc), capi.ptr(packed), N, int(S), capi.ptr(rays), capi.ptr(z), int(lindisp), int(white),
+                  capi.ptr(rgb), capi.ptr(disp), capi.ptr(acc), capi.ptr(w) if want_weights else None, None, capi.ptr(_grid(grid, G)), int(G), arithmetic,
+                  capi.stream())
+    return rgb, disp, acc, w
+
+
+@render_pass_occupancy.register_fake
+def _(planes, consts, packed, rays, z, S, lindisp, white, want_weights, grid, G, arithmetic):
+    N = rays.shape[0]
+    return rays.new_empty((N, 3)), rays.new_empty((N,)), rays.new_empty((N,)), rays.new_empty((N, S) if (want_weights or z is None) else (0,))
+
+
+@custom_op("nvsr::render_rays_occupancy", mutates_args=(), device_types="cuda")
+def render_rays_occupancy(planes: Sequence[Tensor], consts: Sequence[float], packed_coarse: Tensor, packed_fine: Optional[Tensor], rays: Tensor,
+                          Nc: int, Nf: int, lindisp: bool, white: bool, t_rand: Optional[Tensor], u: Optional[Tensor], grid_coarse: Optional[Tensor],
+                          G_coarse: int, grid_fine: Optional[Tensor], G_fine: int,
+                          arithmetic: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """render_rays (without noise) with an occupancy grid per pass; a pass whose grid is None runs the plain route, and below
+    capi.fused_min_rays() rays the grids are ignored.  Two decoders always: the shared-decoder frame has no occupancy route."""
+    rays, t_rand, u = _c(rays), _c(t_rand), _c(u)
+    sc = _scene(planes, consts)
+    N = rays.shape[0]
+    rgb_c, disp_c, acc_c = _f(N, 3, like=rays), _f(N, like=rays), _f(N, like=rays)
+    M = N if Nf > 0 else 0
+    rgb_f, disp_f, acc_f = _f(M, 3, like=rays), _f(M, like=rays), _f(M, like=rays)
+    if N:
+        ws = _f(capi.lib().nvsr_render_workspace_floats(N, Nc, Nf), like=rays)
+        capi.call("nvsr_render_rays_occupancy_arith", C.byref(sc), capi.ptr(packed_coarse), capi.ptr(packed_fine), N, Nc, Nf, capi.ptr(rays), int(lindisp),
+                  int(white), capi.ptr(t_rand), capi.ptr(u), capi.ptr(rgb_c), capi.ptr(disp_c), capi.ptr(acc_c), capi.ptr(rgb_f) if Nf > 0 else None,
+                  capi.ptr(disp_f) if Nf > 0 else None, capi.ptr(acc_f) if Nf > 0 else None, capi.ptr(ws), capi.ptr(_grid(grid_coarse, G_coarse)),
+                  int(G_coarse), capi.ptr(_grid(grid_fine, G_fine)), int(G_fine), arithmetic, capi.stream())
+    return rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f
+
+
+@render_rays_occupancy.register_fake
+def _(planes, consts, packed_coarse, packed_fine, rays, Nc, Nf, lindisp, white, t_rand, u, grid_coarse, G_coarse, grid_fine, G_fine, arithmetic):
+    N = rays.shape[0]
+    M = N if Nf > 0 else 0
+    e = rays.new_empty
+    return e((N, 3)), e((N,)), e((N,)), e((M, 3)), e((M,)), e((M,))
+
+
 @custom_op("nvsr::decode_rays", mutates_args=(), device_types="cuda")
 def decode_rays(planes: Sequence[Tensor], consts: Sequence[float], packed: Tensor, rays: Tensor, z: Tensor, want_gates: bool,
                 want_record: bool, arithmetic: int) -> Tuple[Tensor, Tensor, Tensor]:

@@ -367,27 +367,41 @@ def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, sc
     if N == 0:
         e = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
         return (e(0, 3), e(0), e(0)) + ((e(0, 3), e(0), e(0)) if Nf > 0 else (None, None, None)) + (None, None, None)
+    # occupancy grids (models.build_occupancy): evaluation without noise only, each model its own grid; (grid, resolution) or None.  The frame
+    # of one shared decoder has no occupancy route and keeps the plain one.
+    occ_c = occ_f = None
+    limb = (capi.ARITHMETIC["f16x2"], capi.ARITHMETIC["bf16x3"])
+    if mode != "train" and std == 0.0 and n_c is None and n_f is None and not (Nf > 0 and packed_f.data_ptr() == packed_c.data_ptr()):
+        occ_c = model_coarse.occupancy_entry(scene_id) if arith_c in limb else None
+        occ_f = model_fine.occupancy_entry(scene_id) if Nf > 0 and arith_f in limb else None
     if same and arith_c == arith_f:
-        rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f = nv.render_rays(planes_c, consts, packed_c, packed_f, rays, Nc, Nf, lindisp, white, t_rand, u,
-                                                                   n_c, n_f, arith_c)
+        if occ_c is not None or occ_f is not None:
+            (g_c, G_c), (g_f, G_f) = occ_c or (None, 1), occ_f or (None, 1)
+            rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f = nv.render_rays_occupancy(planes_c, consts, packed_c, packed_f, rays, Nc, Nf, lindisp, white, t_rand,
+                                                                                 u, g_c, G_c, g_f, G_f, arith_c)
+        else:
+            rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f = nv.render_rays(planes_c, consts, packed_c, packed_f, rays, Nc, Nf, lindisp, white, t_rand, u,
+                                                                       n_c, n_f, arith_c)
         if Nf <= 0:
             rgb_f = disp_f = acc_f = None
     else:
         # the two passes sample different planes (only the fine model super-resolves) or run in different arithmetic: pass by pass
         fused = N >= capi.fused_min_rays()     # below it the sample-parallel decoder + the wave-per-ray compositor fill the chip
 
-        def one_pass(planes, packed, z, noise, want_w, arith):
+        def one_pass(planes, packed, z, noise, want_w, arith, occ=None):
+            if fused and occ is not None:
+                return nv.render_pass_occupancy(planes, consts, packed, rays, z, z.shape[1], lindisp, white, want_w, occ[0], occ[1], arith)
             if fused:
                 return nv.render_pass(planes, consts, packed, rays, z, noise, white, want_w, arith)
             raw, _, _ = nv.decode_rays(planes, consts, packed, rays, z, False, False, arith)
             return nv.composite_rays(raw, z, rays, noise, white, want_w)
 
         z_c = nv.coarse_z(rays, Nc, lindisp, t_rand)
-        rgb_c, disp_c, acc_c, w_c = one_pass(planes_c, packed_c, z_c, n_c, Nf > 0, arith_c)
+        rgb_c, disp_c, acc_c, w_c = one_pass(planes_c, packed_c, z_c, n_c, Nf > 0, arith_c, occ_c)
         rgb_f = disp_f = acc_f = None
         if Nf > 0:
             z_f = nv.importance_resample(z_c, w_c, Nf, u)
-            rgb_f, disp_f, acc_f, _ = one_pass(planes_f, packed_f, z_f, n_f, False, arith_f)
+            rgb_f, disp_f, acc_f, _ = one_pass(planes_f, packed_f, z_f, n_f, False, arith_f, occ_f)
     return rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f, None, None, None
 
 

@@ -1,5 +1,5 @@
 // Host-side bookkeeping of the two-phase route's scratch (csrc/colour_order.hip: the lists, the group table, the point-major pass's points and
-// views -- grow-only buffers per (device, stream), released together) as a stand-alone CPU program for the sanitizers.  The HIP allocation and
+// views, the occupancy route's kept lists and their group table -- grow-only buffers per (device, stream), released together) as a stand-alone CPU program for the sanitizers.  The HIP allocation and
 // device calls the bookkeeping makes are defined HERE on the host heap (the executable's definitions win over the runtime library's), so the
 // program needs no GPU, launches no kernel, and AddressSanitizer sees every buffer the bookkeeping allocates, frees or forgets:
 //
@@ -10,9 +10,11 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <set>
 
 #include "../neural-volume-super-resolution_amd/csrc/colour_order.h"
+#include "../neural-volume-super-resolution_amd/csrc/occupancy.h"
 #include "../neural-volume-super-resolution_amd/csrc/nvsr_internal.h"
 
 static std::set<void*> g_live_allocs;
@@ -35,6 +37,7 @@ hipError_t hipFree(void* p) {
 hipError_t hipGetDevice(int* d) { *d = g_device; return hipSuccess; }
 hipError_t hipSetDevice(int d) { g_device = d; return hipSuccess; }
 hipError_t hipGetLastError(void) { return hipSuccess; }
+hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind, hipStream_t) { memcpy(dst, src, bytes); return hipSuccess; }
 hipError_t hipStreamIsCapturing(hipStream_t, hipStreamCaptureStatus* s) { *s = hipStreamCaptureStatusNone; return hipSuccess; }
 }
 
@@ -82,6 +85,36 @@ int main() {
     setenv("NVSR_RENDER_ONE_PHASE", "1", 1);
     CHECK(!two_phase_lists(nullptr, 1000, 8, s0, ll));
     unsetenv("NVSR_RENDER_ONE_PHASE");
+    // the occupancy route: the kept lists (N S + N ints) and their group table, beside the others and not counted; a plain launch leaves them alone
+    {
+        KeptLists kl;
+        const hipStream_t s2 = reinterpret_cast<hipStream_t>(0x20);
+        CHECK(nvsr_internal_copy_kept_counts(dst, 300, (nvsr_stream_t)s2) == NVSR_ERR_SHAPE);       // none ran
+        const size_t before = g_live_allocs.size();
+        const int64_t counted = nvsr_render_scratch_bytes();
+        CHECK(occupancy_lists(300, 4, s2, ll, kl) && g_live_allocs.size() == before + 6 && nvsr_render_scratch_bytes() == counted + lists_bytes(300, 4));
+        CHECK(kl.n == kl.idx + 300 * 4 && kl.trip == kl.slot + 2 && ll.z && ll.pts);
+        reinterpret_cast<char*>(kl.n + 300)[-1] = 1;                                                // the last byte of each buffer is the buffer's
+        reinterpret_cast<char*>(kl.trip + 2)[-1] = 1;
+        for (int i = 0; i < 300; ++i) kl.n[i] = i;
+        int got[300];
+        CHECK(nvsr_internal_copy_kept_counts(got, 300, (nvsr_stream_t)s2) == NVSR_OK && got[299] == 299);
+        CHECK(nvsr_internal_copy_kept_counts(got, 301, (nvsr_stream_t)s2) == NVSR_ERR_SHAPE);       // asked for with the launch's own N
+        CHECK(nvsr_internal_copy_live_counts(got, 300, (nvsr_stream_t)s2) == NVSR_OK);              // the two-phase launch it is part of
+        // growth forgets the latest launch's counts until the launch that grew it is recorded; a smaller launch grows nothing
+        CHECK(occupancy_lists(900, 8, s2, ll, kl) && g_live_allocs.size() == before + 6);
+        CHECK(nvsr_internal_copy_kept_counts(got, 300, (nvsr_stream_t)s2) == NVSR_ERR_SHAPE);
+        const size_t allocs2 = g_allocs;
+        CHECK(occupancy_lists(300, 4, s2, ll, kl) && g_allocs == allocs2);
+        // a plain two-phase launch keeps the kept lists of the latest occupancy launch; a declining occupancy launch forgets them
+        CHECK(two_phase_lists(nullptr, 300, 4, s2, ll) && nvsr_internal_copy_kept_counts(got, 300, (nvsr_stream_t)s2) == NVSR_OK);
+        CHECK(!occupancy_lists(300, ORDER_MAX_S, s2, ll, kl) && nvsr_internal_copy_kept_counts(got, 300, (nvsr_stream_t)s2) == NVSR_ERR_SHAPE);
+        // kept lists that cannot be had (the first allocation of a larger launch's kept buffers: the group table): the route declines, the plain lists stay
+        CHECK(two_phase_lists(nullptr, 5000, 8, s2, ll));
+        g_fail_in = 1;
+        CHECK(!occupancy_lists(5000, 8, s2, ll, kl) && g_fail_in == 0 && nvsr_internal_copy_live_counts(got, 5000, (nvsr_stream_t)s2) == NVSR_ERR_SHAPE);
+        CHECK(occupancy_lists(5000, 8, s2, ll, kl));
+    }
     // release: everything, on every stream; later launches allocate anew
     CHECK(nvsr_release_render_scratch() == NVSR_OK && g_live_allocs.empty() && nvsr_render_scratch_bytes() == 0);
     CHECK(two_phase_lists(nullptr, 300, 4, s0, ll) && g_live_allocs.size() == 4);
