@@ -244,7 +244,8 @@ int nvsr_render_pass_occupancy_arith(const nvsr_scene* scene, const float* packe
                                      nvsr_stream_t stream);
 /* The frame (nvsr_render_rays_arith without the two noise arguments) with a grid per pass: a pass with a grid goes through
  * nvsr_render_pass_occupancy_arith, a pass whose grid is NULL runs the plain route.  Below nvsr_fused_min_rays() rays, in the f32 arithmetic
- * and with both grids NULL the call is nvsr_render_rays_arith's with noise = NULL: the un-fused path runs and the grids are ignored. */
+ * and with both grids NULL the call is nvsr_render_rays_arith's with noise = NULL: the un-fused path runs and the grids are ignored.
+ * (One driver serves both entry points -- render_frame, csrc/aux.hip: this one checks its G arguments and calls it without noise.) */
 int nvsr_render_rays_occupancy_arith(const nvsr_scene* scene, const float* packed_coarse, const float* packed_fine, int64_t N, int Nc, int Nf,
                                      const float* rays, int lindisp, int white_bkgd, const float* t_rand, const float* u, float* rgb_c, float* disp_c,
                                      float* acc_c, float* rgb_f, float* disp_f, float* acc_f, float* workspace, const uint32_t* grid_coarse, int G_coarse,

@@ -948,10 +948,16 @@ int nvsr_render_rays(const nvsr_scene* scene, const float* packed_coarse, const 
                                   rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f, workspace, NVSR_ARITH_INHERIT, stream);
 }
 
-int nvsr_render_rays_arith(const nvsr_scene* scene, const float* packed_coarse, const float* packed_fine, int64_t N, int Nc, int Nf,
-                           const float* rays, int lindisp, int white_bkgd, const float* t_rand, const float* u, const float* noise_coarse,
-                           const float* noise_fine, float* rgb_c, float* disp_c, float* acc_c, float* rgb_f, float* disp_f, float* acc_f,
-                           float* workspace, int arithmetic, nvsr_stream_t stream) {
+// ---- the frame: coarse pass -> importance resampling -> fine pass -----------------------------------------------------------------------
+// One driver for every frame of two decoders.  A pass that has an occupancy grid (include/nvsr.h, "Occupancy grid") goes through
+// nvsr_render_pass_occupancy_arith, which takes no noise; grids count on the fused limb passes only -- below NVSR_FUSED_MIN_RAYS, in the f32
+// arithmetic or under NVSR_RENDER_V1 the frame is the plain one -- and the fine grid only where there is a fine pass.
+struct FrameGrids { const uint32_t* coarse; int G_coarse; const uint32_t* fine; int G_fine; };      // (NULL: that pass has no grid)
+
+static int render_frame(const nvsr_scene* scene, const float* packed_coarse, const float* packed_fine, int64_t N, int Nc, int Nf, const float* rays,
+                        int lindisp, int white_bkgd, const float* t_rand, const float* u, const float* noise_coarse, const float* noise_fine,
+                        float* rgb_c, float* disp_c, float* acc_c, float* rgb_f, float* disp_f, float* acc_f, float* workspace, int arithmetic,
+                        nvsr_stream_t stream, FrameGrids grids) {
     if (!workspace) return NVSR_ERR_NULL;
     if (!aligned16(workspace)) return NVSR_ERR_ALIGN;
     if (N < 0 || Nc < 1 || Nf < 0) return NVSR_ERR_SHAPE;
@@ -962,72 +968,51 @@ int nvsr_render_rays_arith(const nvsr_scene* scene, const float* packed_coarse, 
     float* w_c = z_c + round4(N * (int64_t)Nc);
     float* z_f = w_c + round4(N * (int64_t)Nc);
     float* raw_ws = z_f + (Nf > 0 ? round4(N * (int64_t)(Nc + Nf)) : 0);
-    int e;
+    const int arith = nvsr_internal_resolve_decoder_arith(arithmetic);
+    const bool fused = fused_limb_passes(N, arith);
+    if (!fused) grids.coarse = nullptr;
+    if (!fused || Nf <= 0) grids.fine = nullptr;
     // Inference frames (no stratified jitter) on the fused limb passes: the coarse depths are a function of (near, far, s) -- the coarse
     // pass and the resampler compute them in registers, the [N,Nc] depth tensor (164 MB at 800 x 800 x 64) is never written or read
-    const int arith = nvsr_internal_resolve_decoder_arith(arithmetic);
-    const bool in_kernel_z = !t_rand && Nf > 0 && fused_limb_passes(N, arith) && !getenv("NVSR_STORE_COARSE_Z");
+    const bool in_kernel_z = !t_rand && Nf > 0 && fused && !getenv("NVSR_STORE_COARSE_Z");
     // both passes on the fused limb kernels: the live-list scratch of the two-phase route is sized for the larger (fine) pass once
-    if (Nf > 0 && fused_limb_passes(N, arith)) nvsr_internal_reserve_render_scratch(N, Nc + Nf, stream);
+    if (Nf > 0 && fused) nvsr_internal_reserve_render_scratch(N, Nc + Nf, stream);
+    // one pass of the frame; z = NULL: the coarse pass with its depths in registers (its launcher checks nothing: the checks below)
+    auto pass = [&](const float* packed, int S, const float* z, int z_lindisp, const float* noise, float* rgb, float* disp, float* acc, float* weights,
+                    const uint32_t* grid, int G) {
+        if (grid) return nvsr_render_pass_occupancy_arith(scene, packed, N, S, rays, z, z_lindisp, white_bkgd, rgb, disp, acc, weights, nullptr, grid, G, arith, stream);
+        if (!z) return nvsr_render_pass3_coarse_z_launch(arith, scene, packed, N, S, rays, z_lindisp, noise, white_bkgd, rgb, disp, acc, weights, nullptr, nullptr, stream);
+        return render_one_pass(scene, packed, N, S, rays, z, noise, white_bkgd, rgb, disp, acc, weights, raw_ws, arithmetic, stream);
+    };
+    int e;
     if (in_kernel_z) {
         if (!scene || !packed_coarse || !rays || !rgb_c || !disp_c || !acc_c) return NVSR_ERR_NULL;
         if ((e = check_scene(scene))) return e;
         if (!aligned16(packed_coarse)) return NVSR_ERR_ALIGN;
-        e = nvsr_render_pass3_coarse_z_launch(arith, scene, packed_coarse, N, Nc, rays, lindisp, noise_coarse, white_bkgd, rgb_c, disp_c, acc_c, w_c,
-                                              nullptr, nullptr, stream);
-        if (e) return e;
-        e = nvsr_importance_resample_rays(N, Nc, Nf, rays, lindisp, w_c, u, z_f, stream);
-        if (e) return e;
-        return render_one_pass(scene, packed_fine, N, Nc + Nf, rays, z_f, noise_fine, white_bkgd, rgb_f, disp_f, acc_f, nullptr, raw_ws, arithmetic, stream);
-    }
-    e = nvsr_coarse_z(N, Nc, rays, lindisp, t_rand, z_c, stream);
-    if (e) return e;
-    e = render_one_pass(scene, packed_coarse, N, Nc, rays, z_c, noise_coarse, white_bkgd, rgb_c, disp_c, acc_c, Nf > 0 ? w_c : nullptr,
-                        raw_ws, arithmetic, stream);
+    } else if ((e = nvsr_coarse_z(N, Nc, rays, lindisp, t_rand, z_c, stream))) return e;
+    e = pass(packed_coarse, Nc, in_kernel_z ? nullptr : z_c, lindisp, noise_coarse, rgb_c, disp_c, acc_c, Nf > 0 ? w_c : nullptr, grids.coarse, grids.G_coarse);
     if (e || Nf <= 0) return e;
-    e = nvsr_importance_resample(N, Nc, Nf, z_c, w_c, u, z_f, stream);
+    e = in_kernel_z ? nvsr_importance_resample_rays(N, Nc, Nf, rays, lindisp, w_c, u, z_f, stream) : nvsr_importance_resample(N, Nc, Nf, z_c, w_c, u, z_f, stream);
     if (e) return e;
-    return render_one_pass(scene, packed_fine, N, Nc + Nf, rays, z_f, noise_fine, white_bkgd, rgb_f, disp_f, acc_f, nullptr, raw_ws, arithmetic, stream);
+    return pass(packed_fine, Nc + Nf, z_f, 0, noise_fine, rgb_f, disp_f, acc_f, nullptr, grids.fine, grids.G_fine);
 }
 
-// The frame with occupancy grids (include/nvsr.h, "Occupancy grid"): nvsr_render_rays_arith without noise, each pass through
-// nvsr_render_pass_occupancy_arith where it has a grid.  Without a grid, below NVSR_FUSED_MIN_RAYS or in the f32 arithmetic: the plain frame.
+int nvsr_render_rays_arith(const nvsr_scene* scene, const float* packed_coarse, const float* packed_fine, int64_t N, int Nc, int Nf,
+                           const float* rays, int lindisp, int white_bkgd, const float* t_rand, const float* u, const float* noise_coarse,
+                           const float* noise_fine, float* rgb_c, float* disp_c, float* acc_c, float* rgb_f, float* disp_f, float* acc_f,
+                           float* workspace, int arithmetic, nvsr_stream_t stream) {
+    return render_frame(scene, packed_coarse, packed_fine, N, Nc, Nf, rays, lindisp, white_bkgd, t_rand, u, noise_coarse, noise_fine, rgb_c, disp_c, acc_c, rgb_f,
+                        disp_f, acc_f, workspace, arithmetic, stream, FrameGrids{});
+}
+
+// The frame with occupancy grids: its own check of the grids' sizes, then the frame above without noise.
 int nvsr_render_rays_occupancy_arith(const nvsr_scene* scene, const float* packed_coarse, const float* packed_fine, int64_t N, int Nc, int Nf,
                                      const float* rays, int lindisp, int white_bkgd, const float* t_rand, const float* u, float* rgb_c, float* disp_c,
                                      float* acc_c, float* rgb_f, float* disp_f, float* acc_f, float* workspace, const uint32_t* grid_coarse, int G_coarse,
                                      const uint32_t* grid_fine, int G_fine, int arithmetic, nvsr_stream_t stream) {
     if ((grid_coarse && (G_coarse < 1 || G_coarse > 512)) || (grid_fine && (G_fine < 1 || G_fine > 512))) return NVSR_ERR_SHAPE;
-    const int arith = nvsr_internal_resolve_decoder_arith(arithmetic);
-    if (Nf <= 0) grid_fine = nullptr;
-    if (!fused_limb_passes(N, arith) || (!grid_coarse && !grid_fine))
-        return nvsr_render_rays_arith(scene, packed_coarse, packed_fine, N, Nc, Nf, rays, lindisp, white_bkgd, t_rand, u, nullptr, nullptr, rgb_c, disp_c, acc_c,
-                                      rgb_f, disp_f, acc_f, workspace, arithmetic, stream);
-    if (!workspace || !scene || !packed_coarse || !rays || !rgb_c || !disp_c || !acc_c) return NVSR_ERR_NULL;
-    if (!aligned16(workspace) || !aligned16(packed_coarse)) return NVSR_ERR_ALIGN;
-    if (Nc < 1 || Nf < 0 || (Nf > 0 && (Nc < 3 || Nc > 256 || Nf > 256))) return NVSR_ERR_SHAPE;
-    if (Nf > 0 && (!packed_fine || !rgb_f || !disp_f || !acc_f)) return NVSR_ERR_NULL;
-    int e;
-    if ((e = check_scene(scene))) return e;
-    float* z_c = workspace;
-    float* w_c = z_c + round4(N * (int64_t)Nc);
-    float* z_f = w_c + round4(N * (int64_t)Nc);
-    const bool in_kernel_z = !t_rand && Nf > 0 && !getenv("NVSR_STORE_COARSE_Z");      // (as nvsr_render_rays_arith: the coarse depths in registers)
-    if (Nf > 0) nvsr_internal_reserve_render_scratch(N, Nc + Nf, stream);
-    if (!in_kernel_z && (e = nvsr_coarse_z(N, Nc, rays, lindisp, t_rand, z_c, stream))) return e;
-    const float* zc = in_kernel_z ? nullptr : z_c;
-    float* wc = Nf > 0 ? w_c : nullptr;
-    if (grid_coarse) e = nvsr_render_pass_occupancy_arith(scene, packed_coarse, N, Nc, rays, zc, lindisp, white_bkgd, rgb_c, disp_c, acc_c, wc, nullptr, grid_coarse,
-                                                          G_coarse, arith, stream);
-    else if (in_kernel_z) e = nvsr_render_pass3_coarse_z_launch(arith, scene, packed_coarse, N, Nc, rays, lindisp, nullptr, white_bkgd, rgb_c, disp_c, acc_c, w_c,
-                                                                nullptr, nullptr, stream);
-    else e = nvsr_render_pass_arith(scene, packed_coarse, N, Nc, rays, z_c, nullptr, white_bkgd, rgb_c, disp_c, acc_c, wc, nullptr, nullptr, arith, stream);
-    if (e || Nf <= 0) return e;
-    e = in_kernel_z ? nvsr_importance_resample_rays(N, Nc, Nf, rays, lindisp, w_c, u, z_f, stream) : nvsr_importance_resample(N, Nc, Nf, z_c, w_c, u, z_f, stream);
-    if (e) return e;
-    if (grid_fine)
-        return nvsr_render_pass_occupancy_arith(scene, packed_fine, N, Nc + Nf, rays, z_f, 0, white_bkgd, rgb_f, disp_f, acc_f, nullptr, nullptr, grid_fine, G_fine,
-                                                arith, stream);
-    return nvsr_render_pass_arith(scene, packed_fine, N, Nc + Nf, rays, z_f, nullptr, white_bkgd, rgb_f, disp_f, acc_f, nullptr, nullptr, nullptr, arith, stream);
+    return render_frame(scene, packed_coarse, packed_fine, N, Nc, Nf, rays, lindisp, white_bkgd, t_rand, u, nullptr, nullptr, rgb_c, disp_c, acc_c, rgb_f, disp_f,
+                        acc_f, workspace, arithmetic, stream, FrameGrids{grid_coarse, G_coarse, grid_fine, G_fine});
 }
 
 // ---- one decoder for both passes (models.fine.type == 'use_same') ----------------------------------------------------------------------

@@ -28,12 +28,25 @@ static_assert(RAYS2 <= 256 && ORDER_MAX_S <= (1 << 24), "a slot and a list index
 // pts: the point-major route's entries, [G RAYS2 S]; steps [G], then offs [G]; views [G RAYS2, POINT_VIEW_FLOATS] -- all NULL: the lockstep colour kernels
 struct LiveLists { float* z; float* w; int* n; int* slot; int* trip; int* pts; int* steps; float* views; };
 
-// The two-phase route is taken unless the caller wants the raw decoder outputs, NVSR_RENDER_ONE_PHASE=1 is set (the A/B handle), the stream
-// is being captured (the scratch cannot grow inside a capture), a count would not fit into a packed entry of the ray order (S >= 2^19) or the
-// scratch cannot be had -- then the fused kernel runs: same pixels.  launch = false sizes the scratch and leaves no launch behind.
-bool two_phase_lists(const float* raw_out, int64_t N, int S, hipStream_t stream, LiveLists& out, bool launch = true);
+// the kept lists of one occupancy launch (include/nvsr.h, "Occupancy grid"), in the library's scratch: idx [N, S] rows of sample indices in
+// sample order (the first count entries are valid, the others -1), n [N] counts -- rewritten by live_order_kernel into packed entries like
+// the live counts --, and the order of dispatch of the density pass over them: slot [G], trip [G]
+struct KeptLists { int* idx; int* n; int* slot; int* trip; };
+
+// The scratch of one render pass, asked for once per pass (colour_order.hip owns it, per (device, stream)); the answer is the pass's route:
+//   Fused      the fused kernel, no lists: the caller wants the raw decoder outputs, NVSR_RENDER_ONE_PHASE=1 is set (the A/B handle), the stream
+//              is being captured (the scratch cannot grow inside a capture), a count would not fit into a packed entry of the ray order
+//              (S >= 2^19) or the lists cannot be had -- same pixels
+//   TwoPhase   `live` is filled.  Also the answer to want_kept where the kept lists cannot be had: the pass runs the plain route
+//   Occupancy  want_kept only: `live` and `kept` are filled
+// An occupancy pass that is not answered Occupancy forgets the kept counts of the stream's latest occupancy launch
+// (nvsr_internal_copy_kept_counts returns an error).  launch = false sizes the scratch and leaves no launch behind.
+enum class PassRoute { Fused, TwoPhase, Occupancy };
+PassRoute acquire_pass_scratch(int64_t N, int S, hipStream_t stream, bool raw_out, bool want_kept, bool launch, LiveLists& live, KeptLists& kept);
 // the ray order, then the order of dispatch: between the density and the colour launch
 void launch_colour_order(const LiveLists& ll, int64_t N, int S, hipStream_t stream);
+// the same two orders for the density pass over the kept lists (live_order_kernel and group_order_kernel on the kept counts)
+void launch_kept_order(const KeptLists& kl, int64_t N, int S, hipStream_t stream);
 // the order of points, behind the two orders above (ll.pts != NULL); rays_nf: the packed rays (near, far) when the lists hold depths, NULL when sample indices
 void launch_point_order(const LiveLists& ll, const float* rays_nf, int64_t N, int S, hipStream_t stream);
 

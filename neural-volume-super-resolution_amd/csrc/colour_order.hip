@@ -6,7 +6,6 @@
 #include "nvsr_internal.h"
 
 #include <cstdlib>
-#include <initializer_list>
 #include <mutex>
 #include <vector>
 
@@ -231,61 +230,69 @@ __global__ __launch_bounds__(RAYS2) void point_order_kernel(const int* __restric
 }
 
 // ---- scratch of the two-phase route: the live lists, [N, S] depths + [N, S] weights + [N] counts ------------------------------------
-// Owned by the library, one buffer per (device, stream), grow-only: two launches on one stream are ordered, launches on two streams never
+// Owned by the library, one entry per (device, stream), grow-only: two launches on one stream are ordered, launches on two streams never
 // share a buffer.  Growing frees the old buffer with hipFree, which waits for the device -- no launch can still be using it.
-// Contract (include/nvsr.h): one host thread at a time enqueues render launches on a given (device, stream) -- the pointer is used after
-// the table's lock is dropped; the entry of a destroyed stream keeps its buffer until nvsr_release_render_scratch.
-// The order of dispatch (group_order_kernel) takes 2 G ints more, G = ceil(N / RAYS2): group_slot[G], then group_trip[G].  They live in a
-// small buffer of their own beside the lists (20 KB at the benchmark size), with the same owner, growth and release;
-// nvsr_render_scratch_bytes keeps counting the lists' buffer alone.
-// The point-major colour pass (point_order_kernel) takes two buffers more, same owner, growth and release, not counted either: `points` --
-// G RAYS2 S ints of entries, then steps[G] and offs[G] -- and `views`, the view features of every slot, POINT_VIEW_FLOATS floats each.
+// Contract (include/nvsr.h): one host thread at a time enqueues render launches on a given (device, stream) -- the pointers are used after
+// the table's lock is dropped; the entry of a destroyed stream keeps its buffers until nvsr_release_render_scratch.
+// An entry's buffers, in the order in which a pass allocates them (GROUP, LISTS, POINTS, VIEWS, KEPT_GROUP, KEPT), G = ceil(N / RAYS2):
+//   LISTS       z [N, S], w [N, S], n [N] -- the only buffer that nvsr_render_scratch_bytes counts
+//   GROUP       the order of dispatch (group_order_kernel): group_slot [G], then group_trip [G] (20 KB at the benchmark size)
+//   POINTS      the point-major colour pass (point_order_kernel): G RAYS2 S ints of entries, then steps [G] and offs [G]
+//   VIEWS       the view features of every slot of that pass, POINT_VIEW_FLOATS floats each
+//   KEPT        the occupancy route's kept lists: idx [N, S], then n [N]
+//   KEPT_GROUP  the order of dispatch of the density pass over the kept lists: slot [G], then trip [G]
 namespace {
+enum { LISTS, GROUP, POINTS, VIEWS, KEPT, KEPT_GROUP, N_BUFFERS };
 struct Buffer { void* p; size_t bytes; };
-struct LiveScratch {
-    int device; hipStream_t stream; Buffer lists, group, points, views; int* last_n; int64_t last_N; int* last_steps;      // last_*: the counts of the latest launch; its points' step counts
-    Buffer kept, kgroup; int* last_kept; int64_t last_kept_N;      // the occupancy route's kept lists and their group table; the packed kept counts of its latest launch
-};
+// What the latest launch of an entry left behind, for the nvsr_internal_copy_* hooks: its N, its packed counts, its points' step counts
+// (NULL: it ran the lockstep colour kernels) and the packed kept counts of the latest OCCUPANCY launch with that launch's N (NULL: none).
+// Lifetime: any growth of any buffer forgets all of it (a new buffer holds no launch's lists or order); a pass that takes the two-phase
+// route assigns all of it -- a plain pass carries the kept counts over, an occupancy pass replaces them; an occupancy pass that declines
+// forgets the kept counts and leaves the rest to the route it falls back to; a reservation assigns nothing.
+struct Launch { int64_t N; int* n; int* steps; int64_t kept_N; int* kept; };
+struct Scratch { int device; hipStream_t stream; Buffer buf[N_BUFFERS]; Launch last; };
 std::mutex g_live_mutex;
-std::vector<LiveScratch> g_live;
+std::vector<Scratch> g_live;
 
-LiveScratch* find_scratch(int device, hipStream_t stream) {      // (under the lock)
-    for (LiveScratch& c : g_live)
+Scratch* find_scratch(int device, hipStream_t stream) {      // (under the lock)
+    for (Scratch& c : g_live)
         if (c.device == device && c.stream == stream) return &c;
     return nullptr;
 }
 
-// grow-only: free, forget the last launch (the new buffer holds no launch's lists or order), allocate
-bool grow(LiveScratch& e, Buffer& b, size_t bytes) {
+// grow-only: free, forget the latest launch, allocate
+bool grow(Scratch& e, int which, size_t bytes) {
+    Buffer& b = e.buf[which];
     if (b.bytes >= bytes) return true;
     if (b.p) (void)hipFree(b.p);
-    b = Buffer{nullptr, 0};
-    e.last_n = nullptr; e.last_N = 0; e.last_steps = nullptr; e.last_kept = nullptr; e.last_kept_N = 0;
+    b = Buffer{};
+    e.last = Launch{};
     void* p = nullptr;
     if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
     b = Buffer{p, bytes};
     return true;
 }
 
-// what the latest two-phase launch on (the current device, stream) left behind -> dst (device or host memory): its N packed entries, or
-// (groups) its group_slot[G] + group_trip[G]; `count` must be that launch's N, or its G
-int copy_left_behind(int* dst, int64_t count, bool groups, hipStream_t stream) {
+int64_t groups_of(int64_t N) { return (N + RAYS2 - 1) / RAYS2; }
+
+// behind the nvsr_internal_copy_* hooks: `ints` ints of what the latest launch on (the current device, stream) left behind -> dst (device
+// or host memory).  pick(entry) names them, or answers NULL where the caller's count is not that launch's or the launch left none.
+template <class Pick>
+int copy_left_behind(int* dst, int64_t ints, nvsr_stream_t stream, Pick pick) {
     if (!dst) return NVSR_ERR_NULL;
     int device = 0;
     if (hipGetDevice(&device) != hipSuccess) return NVSR_ERR_LAUNCH;
     const int* src = nullptr;
     {
         std::lock_guard<std::mutex> lock(g_live_mutex);
-        const LiveScratch* c = find_scratch(device, stream);
-        if (c && c->last_n && (groups ? (c->last_N + RAYS2 - 1) / RAYS2 : c->last_N) == count) src = groups ? static_cast<const int*>(c->group.p) : c->last_n;
+        const Scratch* c = find_scratch(device, (hipStream_t)stream);
+        if (c) src = pick(*c);
     }
     if (!src) return NVSR_ERR_SHAPE;
-    return hipMemcpyAsync(dst, src, (groups ? 2 : 1) * (size_t)count * sizeof(int), hipMemcpyDefault, stream) == hipSuccess ? NVSR_OK : NVSR_ERR_LAUNCH;
+    return hipMemcpyAsync(dst, src, (size_t)ints * sizeof(int), hipMemcpyDefault, (hipStream_t)stream) == hipSuccess ? NVSR_OK : NVSR_ERR_LAUNCH;
 }
 
-// The three environment handles of the route, each read at every launch, for A/Bs: NVSR_RENDER_ONE_PHASE=1 keeps the fused kernel;
-// NVSR_COLOUR_ORDER=0 makes the ray order the identity (bins = 0: the colour kernel groups its rays as the density kernel does);
-// NVSR_COLOUR_GROUP_ORDER=0 makes the order of dispatch the contiguous eighths (same kernel, same table).
+// The four environment handles of the route, for A/Bs, each read at every launch by the function that acts on it (named there).
 bool env_starts(const char* name, char c) {
     const char* e = getenv(name);
     return e && e[0] == c;
@@ -294,77 +301,74 @@ void launch_live_order(int* live_n, int64_t N, int S, int bins, int* group_trip,
     hipLaunchKernelGGL(live_order_kernel, dim3((unsigned)((N + ORDER_RAYS - 1) / ORDER_RAYS)), dim3(SORT_TPB), 0, stream, live_n, (long)N, S, bins, group_trip);
 }
 void launch_group_order(const int* group_trip, int64_t G, int S, int* group_slot, hipStream_t stream) {
-    const int sorted = !env_starts("NVSR_COLOUR_GROUP_ORDER", '0');
+    const int sorted = !env_starts("NVSR_COLOUR_GROUP_ORDER", '0');      // =0: the order of dispatch is the contiguous eighths (same kernel, same table)
     hipLaunchKernelGGL(group_order_kernel, dim3(1), dim3(SORT_TPB), 0, stream, group_trip, (int)G, S, sorted, group_slot);
 }
 void launch_point_order(const int* live_n, const float* live_z, const float* rays_nf, int64_t N, int S, int nb, int* pts, int* steps, int* offs, hipStream_t stream) {
     nb = nb < 1 || nb > S ? S : nb;      // (POINT_BANDS = 0: a band per sample)
-    hipLaunchKernelGGL(point_order_kernel, dim3((unsigned)((N + RAYS2 - 1) / RAYS2)), dim3(RAYS2), 0, stream, live_n, live_z, rays_nf, (long)N, S, nb, pts, steps, offs);
+    hipLaunchKernelGGL(point_order_kernel, dim3((unsigned)groups_of(N)), dim3(RAYS2), 0, stream, live_n, live_z, rays_nf, (long)N, S, nb, pts, steps, offs);
 }
 }  // namespace
 
-bool two_phase_lists(const float* raw_out, int64_t N, int S, hipStream_t stream, LiveLists& out, bool launch) {
-    if (raw_out || S < 1 || S >= ORDER_MAX_S || env_starts("NVSR_RENDER_ONE_PHASE", '1')) return false;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return false; }
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) return false;
-    const size_t rows = (size_t)N * (size_t)S * sizeof(float), G = (size_t)((N + RAYS2 - 1) / RAYS2);
-    std::lock_guard<std::mutex> lock(g_live_mutex);
-    LiveScratch* e = find_scratch(device, stream);
-    if (!e) { g_live.push_back(LiveScratch{device, stream, Buffer{nullptr, 0}, Buffer{nullptr, 0}, Buffer{nullptr, 0}, Buffer{nullptr, 0}, nullptr, 0, nullptr}); e = &g_live.back(); }
-    if (!grow(*e, e->group, 2 * G * sizeof(int)) || !grow(*e, e->lists, 2 * rows + (size_t)N * sizeof(int)) || !e->lists.p) return false;
-    char* p = static_cast<char*>(e->lists.p);
-    out.z = reinterpret_cast<float*>(p);
-    out.w = reinterpret_cast<float*>(p + rows);
-    out.n = reinterpret_cast<int*>(p + 2 * rows);
-    out.slot = static_cast<int*>(e->group.p);
-    out.trip = out.slot + G;
-    // the point-major route's buffers (NVSR_COLOUR_POINTS=0, or a buffer that cannot be had: the lockstep colour kernels)
-    out.pts = nullptr; out.steps = nullptr; out.views = nullptr;
-    const size_t npts = G * RAYS2 * (size_t)S;
-    if (!env_starts("NVSR_COLOUR_POINTS", '0') && G * (size_t)S <= 0x7fffffffu && grow(*e, e->points, (npts + 2 * G) * sizeof(int)) &&
-        grow(*e, e->views, G * RAYS2 * POINT_VIEW_FLOATS * sizeof(float))) {
-        out.pts = static_cast<int*>(e->points.p);
-        out.steps = out.pts + npts;
-        out.views = static_cast<float*>(e->views.p);
+PassRoute acquire_pass_scratch(int64_t N, int S, hipStream_t stream, bool raw_out, bool want_kept, bool launch, LiveLists& live, KeptLists& kept) {
+    // NVSR_RENDER_ONE_PHASE=1 keeps the fused kernel
+    bool declines = raw_out || S < 1 || S >= ORDER_MAX_S || env_starts("NVSR_RENDER_ONE_PHASE", '1');
+    if (!declines) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) { (void)hipGetLastError(); declines = true; }
     }
-    if (launch) { e->last_n = out.n; e->last_N = N; e->last_steps = out.steps; }      // (a reservation leaves no counts behind)
-    return true;
-}
-
-// the occupancy route's scratch: the two-phase route's, then the kept lists
-bool occupancy_lists(int64_t N, int S, hipStream_t stream, LiveLists& live, KeptLists& kept) {
-    const bool lists = two_phase_lists(nullptr, N, S, stream, live);
+    if (declines && !want_kept) return PassRoute::Fused;      // (nothing to forget: the table is not looked at)
     int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) return false;
-    const size_t rows = (size_t)N * (size_t)S, G = (size_t)((N + RAYS2 - 1) / RAYS2);
+    if (hipGetDevice(&device) != hipSuccess) return PassRoute::Fused;
+    const size_t rows = (size_t)N * (size_t)S, G = (size_t)groups_of(N);
     std::lock_guard<std::mutex> lock(g_live_mutex);
-    LiveScratch* e = find_scratch(device, stream);
-    if (!e) return false;                             // (two_phase_lists declined before it made the entry)
-    e->last_kept = nullptr; e->last_kept_N = 0;
-    if (!lists || !grow(*e, e->kgroup, 2 * G * sizeof(int)) || !grow(*e, e->kept, (rows + (size_t)N) * sizeof(int))) return false;
-    kept.idx = static_cast<int*>(e->kept.p);
-    kept.n = kept.idx + rows;
-    kept.slot = static_cast<int*>(e->kgroup.p);
-    kept.trip = kept.slot + G;
-    // (growing the kept lists forgot the launch that two_phase_lists has just recorded: the buffers of that launch are the same ones)
-    e->last_n = live.n; e->last_N = N; e->last_steps = live.steps;
-    e->last_kept = kept.n; e->last_kept_N = N;
-    return true;
+    Scratch* e = find_scratch(device, stream);
+    if (e && want_kept) { e->last.kept_N = 0; e->last.kept = nullptr; }      // (an occupancy pass: its own kept counts below, or none)
+    if (declines) return PassRoute::Fused;
+    if (!e) {
+        g_live.emplace_back();
+        e = &g_live.back();
+        e->device = device; e->stream = stream;
+    }
+    if (!grow(*e, GROUP, 2 * G * sizeof(int)) || !grow(*e, LISTS, (2 * rows + (size_t)N) * sizeof(float)) || !e->buf[LISTS].p) return PassRoute::Fused;
+    live = LiveLists{};
+    live.z = static_cast<float*>(e->buf[LISTS].p);
+    live.w = live.z + rows;
+    live.n = reinterpret_cast<int*>(live.w + rows);
+    live.slot = static_cast<int*>(e->buf[GROUP].p);
+    live.trip = live.slot + G;
+    // the point-major colour pass's buffers; NVSR_COLOUR_POINTS=0, G S >= 2^31 or a buffer that cannot be had: the lockstep colour kernels
+    const size_t npts = G * RAYS2 * (size_t)S;
+    if (!env_starts("NVSR_COLOUR_POINTS", '0') && G * (size_t)S <= 0x7fffffffu && grow(*e, POINTS, (npts + 2 * G) * sizeof(int)) &&
+        grow(*e, VIEWS, G * RAYS2 * POINT_VIEW_FLOATS * sizeof(float))) {
+        live.pts = static_cast<int*>(e->buf[POINTS].p);
+        live.steps = live.pts + npts;
+        live.views = static_cast<float*>(e->buf[VIEWS].p);
+    }
+    // the occupancy route's kept lists; where they cannot be had the pass runs the plain two-phase route on the lists above
+    PassRoute route = PassRoute::TwoPhase;
+    if (want_kept && grow(*e, KEPT_GROUP, 2 * G * sizeof(int)) && grow(*e, KEPT, (rows + (size_t)N) * sizeof(int))) {
+        kept.idx = static_cast<int*>(e->buf[KEPT].p);
+        kept.n = kept.idx + rows;
+        kept.slot = static_cast<int*>(e->buf[KEPT_GROUP].p);
+        kept.trip = kept.slot + G;
+        route = PassRoute::Occupancy;
+    }
+    if (launch) e->last = route == PassRoute::Occupancy ? Launch{N, live.n, live.steps, N, kept.n} : Launch{N, live.n, live.steps, e->last.kept_N, e->last.kept};
+    return route;
 }
 
 // the ray order on the counts n (in place), then the order of dispatch on the trips it leaves
 static void launch_orders(int* n, int* trip, int* slot, int64_t N, int S, hipStream_t stream) {
+    // NVSR_COLOUR_ORDER=0 makes the ray order the identity (bins = 0: the colour kernel groups its rays as the density kernel does)
     launch_live_order(n, N, S, env_starts("NVSR_COLOUR_ORDER", '0') ? 0 : ORDER_BINS, trip, stream);
-    launch_group_order(trip, (N + RAYS2 - 1) / RAYS2, S, slot, stream);
+    launch_group_order(trip, groups_of(N), S, slot, stream);
 }
 void launch_kept_order(const KeptLists& kl, int64_t N, int S, hipStream_t stream) { launch_orders(kl.n, kl.trip, kl.slot, N, S, stream); }
 void launch_colour_order(const LiveLists& ll, int64_t N, int S, hipStream_t stream) { launch_orders(ll.n, ll.trip, ll.slot, N, S, stream); }
 
 void launch_point_order(const LiveLists& ll, const float* rays_nf, int64_t N, int S, hipStream_t stream) {
-    const int64_t G = (N + RAYS2 - 1) / RAYS2;
-    launch_point_order(ll.n, ll.z, rays_nf, N, S, POINT_BANDS, ll.pts, ll.steps, ll.steps + G, stream);
+    launch_point_order(ll.n, ll.z, rays_nf, N, S, POINT_BANDS, ll.pts, ll.steps, ll.steps + groups_of(N), stream);
 }
 
 }  // namespace nvsr
@@ -379,7 +383,9 @@ extern "C" int nvsr_internal_live_order(int* live_n, int64_t N, int S, nvsr_stre
     launch_live_order(live_n, N, S, ORDER_BINS, nullptr, (hipStream_t)stream);
     return NVSR_CHECK_LAUNCH();
 }
-extern "C" int nvsr_internal_copy_live_counts(int* dst, int64_t N, nvsr_stream_t stream) { return copy_left_behind(dst, N, false, (hipStream_t)stream); }
+extern "C" int nvsr_internal_copy_live_counts(int* dst, int64_t N, nvsr_stream_t stream) {
+    return copy_left_behind(dst, N, stream, [N](const Scratch& c) { return c.last.N == N ? c.last.n : nullptr; });
+}
 // test hooks of the order of dispatch (include/nvsr.h)
 extern "C" int nvsr_internal_group_order(const int* trips, int64_t G, int S, int* out, nvsr_stream_t stream) {
     if (!trips || !out) return NVSR_ERR_NULL;
@@ -387,7 +393,9 @@ extern "C" int nvsr_internal_group_order(const int* trips, int64_t G, int S, int
     launch_group_order(trips, G, S, out, (hipStream_t)stream);
     return NVSR_CHECK_LAUNCH();
 }
-extern "C" int nvsr_internal_copy_group_order(int* dst, int64_t G, nvsr_stream_t stream) { return copy_left_behind(dst, G, true, (hipStream_t)stream); }
+extern "C" int nvsr_internal_copy_group_order(int* dst, int64_t G, nvsr_stream_t stream) {      // (group_slot [G], then group_trip [G])
+    return copy_left_behind(dst, 2 * G, stream, [G](const Scratch& c) { return c.last.n && groups_of(c.last.N) == G ? static_cast<int*>(c.buf[GROUP].p) : nullptr; });
+}
 
 // test hooks of the order of points (include/nvsr.h)
 extern "C" int nvsr_internal_point_bands(void) { return POINT_BANDS; }
@@ -399,46 +407,27 @@ extern "C" int nvsr_internal_point_order(const int* entries, const float* lists,
     launch_point_order(entries, lists, rays, N, S, bands, points, steps, offsets, (hipStream_t)stream);
     return NVSR_CHECK_LAUNCH();
 }
-extern "C" int nvsr_internal_copy_point_steps(int* dst, int64_t G, nvsr_stream_t stream) {
-    if (!dst) return NVSR_ERR_NULL;
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) return NVSR_ERR_LAUNCH;
-    const int* src = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        const LiveScratch* c = find_scratch(device, (hipStream_t)stream);
-        if (c && c->last_n && c->last_steps && (c->last_N + RAYS2 - 1) / RAYS2 == G) src = c->last_steps;
-    }
-    if (!src) return NVSR_ERR_SHAPE;      // (also: the latest launch ran the lockstep colour kernels)
-    return hipMemcpyAsync(dst, src, (size_t)G * sizeof(int), hipMemcpyDefault, (hipStream_t)stream) == hipSuccess ? NVSR_OK : NVSR_ERR_LAUNCH;
+extern "C" int nvsr_internal_copy_point_steps(int* dst, int64_t G, nvsr_stream_t stream) {      // (no steps: the latest launch ran the lockstep colour kernels)
+    return copy_left_behind(dst, G, stream, [G](const Scratch& c) { return c.last.n && groups_of(c.last.N) == G ? c.last.steps : nullptr; });
 }
 
 // hook of the occupancy route (include/nvsr.h): the packed kept counts of the latest occupancy launch on `stream`; none ran (or it declined): an error
 extern "C" int nvsr_internal_copy_kept_counts(int* dst, int64_t N, nvsr_stream_t stream) {
-    if (!dst) return NVSR_ERR_NULL;
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) return NVSR_ERR_LAUNCH;
-    const int* src = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(g_live_mutex);
-        const LiveScratch* c = find_scratch(device, (hipStream_t)stream);
-        if (c && c->last_kept && c->last_kept_N == N) src = c->last_kept;
-    }
-    if (!src) return NVSR_ERR_SHAPE;
-    return hipMemcpyAsync(dst, src, (size_t)N * sizeof(int), hipMemcpyDefault, (hipStream_t)stream) == hipSuccess ? NVSR_OK : NVSR_ERR_LAUNCH;
+    return copy_left_behind(dst, N, stream, [N](const Scratch& c) { return c.last.kept_N == N ? c.last.kept : nullptr; });
 }
 
 // a frame's driver knows its largest pass before the first launch: sizing the buffer for it up front keeps the growth (a device-wide
 // wait) out of the frame -- between the coarse and the fine pass (aux.hip).  Does nothing where the two-phase route would not be taken.
 extern "C" void nvsr_internal_reserve_render_scratch(int64_t N, int S, nvsr_stream_t stream) {
-    LiveLists ll;
-    (void)two_phase_lists(nullptr, N, S, (hipStream_t)stream, ll, false);
+    LiveLists live;
+    KeptLists kept;
+    (void)acquire_pass_scratch(N, S, (hipStream_t)stream, /*raw_out*/ false, /*want_kept*/ false, /*launch*/ false, live, kept);
 }
 
 extern "C" int64_t nvsr_render_scratch_bytes(void) {
     std::lock_guard<std::mutex> lock(g_live_mutex);
     int64_t total = 0;
-    for (const LiveScratch& c : g_live) total += (int64_t)c.lists.bytes;
+    for (const Scratch& c : g_live) total += (int64_t)c.buf[LISTS].bytes;
     return total;
 }
 
@@ -447,9 +436,9 @@ extern "C" int nvsr_release_render_scratch(void) {
     int prev = 0;
     const bool have_prev = hipGetDevice(&prev) == hipSuccess;
     int rc = NVSR_OK;
-    for (const LiveScratch& c : g_live)
-        for (void* p : {c.lists.p, c.group.p, c.points.p, c.views.p, c.kept.p, c.kgroup.p})
-            if (p && (hipSetDevice(c.device) != hipSuccess || hipFree(p) != hipSuccess)) rc = NVSR_ERR_LAUNCH;
+    for (const Scratch& c : g_live)
+        for (const Buffer& b : c.buf)
+            if (b.p && (hipSetDevice(c.device) != hipSuccess || hipFree(b.p) != hipSuccess)) rc = NVSR_ERR_LAUNCH;
     g_live.clear();
     if (have_prev) (void)hipSetDevice(prev);
     return rc;

@@ -27,7 +27,8 @@ int nvsr_render_pass_backward_gates_limb_launch(int limbs, const nvsr_scene* sce
 // render.hip: NVSR_ARITH_INHERIT -> the process default, anything that is not a mode -> -1; the mode named by an environment variable (dflt if unset)
 int nvsr_internal_resolve_decoder_arith(int arithmetic);
 int nvsr_internal_parse_arith_env(const char* name, int dflt);
-// colour_order.hip: size the two-phase route's scratch for a pass of N rays x S samples before a frame's first launch
+// colour_order.hip: size the two-phase route's scratch for a pass of N rays x S samples before a frame's first launch (acquire_pass_scratch
+// of colour_order.h as a reservation: it leaves no launch behind)
 void nvsr_internal_reserve_render_scratch(int64_t N, int S, nvsr_stream_t stream);
 }  // extern "C"
 

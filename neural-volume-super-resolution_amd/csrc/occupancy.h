@@ -1,5 +1,5 @@
-// The occupancy route of the render pass (include/nvsr.h, "Occupancy grid"): what occupancy.hip (the grid's build and the cull kernel),
-// colour_order.hip (the scratch of the kept lists) and render3.hip (the density pass over the kept lists) share.  Not part of the public ABI.
+// The occupancy route of the render pass (include/nvsr.h, "Occupancy grid"): what occupancy.hip (the grid's build and the cull kernel)
+// and render3.hip (the density pass over the kept lists) share; the kept lists and their scratch: colour_order.h.  Not part of the public ABI.
 #pragma once
 #include "colour_order.h"
 
@@ -15,17 +15,6 @@ __device__ __forceinline__ int occupancy_cell(float n, int G) {
     return (int)fminf(fmaxf(f, 0.0f), (float)(G - 1));
 }
 
-// the kept lists of one occupancy launch, in the library's scratch: idx [N, S] rows of sample indices in sample order (the first count
-// entries are valid, the others -1), n [N] counts -- rewritten by live_order_kernel into packed entries like the live counts --, and the
-// order of dispatch of the density pass over them: slot [G], trip [G], G = ceil(N / RAYS2)
-struct KeptLists { int* idx; int* n; int* slot; int* trip; };
-
-// The scratch of an occupancy launch (colour_order.hip): the two-phase route's lists plus the kept lists.  false: the route declines (where
-// two_phase_lists declines, or the kept lists cannot be had) and the caller runs the plain route; the latest occupancy launch of the stream
-// is then forgotten (nvsr_internal_copy_kept_counts returns an error).
-bool occupancy_lists(int64_t N, int S, hipStream_t stream, LiveLists& live, KeptLists& kept);
-// the ray order and the order of dispatch of the density pass over the kept lists (live_order_kernel and group_order_kernel on the kept counts)
-void launch_kept_order(const KeptLists& kl, int64_t N, int S, hipStream_t stream);
 // occupancy.hip: one wave per ray -> kept[N, S], kept_n[N] (z = NULL: the depths of coarse_depth(near, far, s, S, lindisp))
 void launch_occupancy_cull(const SceneDev& sc, int64_t N, int S, const float* rays, const float* z, int lindisp, const uint32_t* grid, int G, int* kept, int* kept_n,
                            hipStream_t stream);

@@ -1039,56 +1039,59 @@ extern "C" int nvsr_pack_decoder_limbs_launch(const float* natural, float* packe
     return NVSR_CHECK_LAUNCH();
 }
 
-// ---- the launches of one render pass: the two-phase route (density pass, the colour pass's orders, colour pass on the lists `ll`), or the
-// fused kernel where two_phase_lists declines (ll = NULL).  z = NULL: the coarse pass with its depths computed in the kernel from
-// (near, far, s, S, lindisp); it always writes the weights.
-// occ (with ll): the occupancy route -- the cull kernel and the orders on its counts in front, the density pass over the kept lists.
+// ---- the launches of one render pass: what the extern "C" entry points below receive, by name.  z = NULL: the coarse pass with its depths
+// computed in the kernel from (near, far, s, S, lindisp); it always writes the weights.
+struct PassArgs { const nvsr_scene* scene; const float* packed; int64_t N; int S; const float *rays, *z; int lindisp; const float* noise; int white;
+                  float *rgb, *disp, *acc, *weights, *depth, *raw_out; hipStream_t stream; };
 struct OccLaunch { const uint32_t* grid; int G; KeptLists kept; };
+// ll: the two-phase route (density pass, the colour pass's orders, colour pass on the lists), NULL: the fused kernel.  occ (with ll): the occupancy
+// route -- the cull kernel and the orders on its counts in front, the density pass over the kept lists.
 template <int LIMBS>
-static int launch_pass3(const LiveLists* ll, const nvsr_scene* scene, const float* packed, int64_t N, int S, const float* rays, const float* z, int lindisp,
-                        const float* noise, int white, float* rgb, float* disp, float* acc, float* weights, float* depth, float* raw_out, hipStream_t stream,
-                        const OccLaunch* occ = nullptr) {
-    const SceneDev sc = to_dev(scene);
+static int launch_pass3(const PassArgs& a, const LiveLists* ll, const OccLaunch* occ) {
+    const SceneDev sc = to_dev(a.scene);
     unsigned* flag = nvsr_get_range_flag();
     auto launch = [&](auto kernel, auto... args) {      // (every kernel's arguments start alike)
-        hipLaunchKernelGGL(kernel, dim3((unsigned)((N + RAYS2 - 1) / RAYS2)), dim3(TPB2), 0, stream, sc, packed, (long)N, S, rays, args...);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((a.N + RAYS2 - 1) / RAYS2)), dim3(TPB2), 0, a.stream, sc, a.packed, (long)a.N, a.S, a.rays, args...);
     };
     if (ll) {
         if (occ) {
             const KeptLists& kl = occ->kept;
-            launch_occupancy_cull(sc, N, S, rays, z, lindisp, occ->grid, occ->G, kl.idx, kl.n, stream);
-            launch_kept_order(kl, N, S, stream);
+            launch_occupancy_cull(sc, a.N, a.S, a.rays, a.z, a.lindisp, occ->grid, occ->G, kl.idx, kl.n, a.stream);
+            launch_kept_order(kl, a.N, a.S, a.stream);
             // a culled sample has weight +0.0: the pass writes the kept samples' weights only
-            if (weights && hipMemsetAsync(weights, 0, (size_t)N * (size_t)S * sizeof(float), stream) != hipSuccess) return NVSR_ERR_LAUNCH;
-            if (z) launch(render_pass3_density_kept_kernel<LIMBS>, z, disp, acc, weights, depth, flag, ll->z, ll->w, ll->n, kl.slot, kl.idx, kl.n);
-            else launch(render_pass3_density_kept_z_kernel<LIMBS>, lindisp, disp, acc, weights, depth, flag, ll->z, ll->w, ll->n, kl.slot, kl.idx, kl.n);
-        } else if (z) launch(render_pass3_density_kernel<LIMBS>, z, noise, disp, acc, weights, depth, flag, ll->z, ll->w, ll->n);
-        else launch(render_pass3_density_z_kernel<LIMBS>, lindisp, noise, disp, acc, weights, depth, flag, ll->z, ll->w, ll->n);
-        launch_colour_order(*ll, N, S, stream);
+            if (a.weights && hipMemsetAsync(a.weights, 0, (size_t)a.N * (size_t)a.S * sizeof(float), a.stream) != hipSuccess) return NVSR_ERR_LAUNCH;
+            if (a.z) launch(render_pass3_density_kept_kernel<LIMBS>, a.z, a.disp, a.acc, a.weights, a.depth, flag, ll->z, ll->w, ll->n, kl.slot, kl.idx, kl.n);
+            else launch(render_pass3_density_kept_z_kernel<LIMBS>, a.lindisp, a.disp, a.acc, a.weights, a.depth, flag, ll->z, ll->w, ll->n, kl.slot, kl.idx, kl.n);
+        } else if (a.z) launch(render_pass3_density_kernel<LIMBS>, a.z, a.noise, a.disp, a.acc, a.weights, a.depth, flag, ll->z, ll->w, ll->n);
+        else launch(render_pass3_density_z_kernel<LIMBS>, a.lindisp, a.noise, a.disp, a.acc, a.weights, a.depth, flag, ll->z, ll->w, ll->n);
+        launch_colour_order(*ll, a.N, a.S, a.stream);
         if (ll->pts) {
-            launch_point_order(*ll, z ? rays : nullptr, N, S, stream);
-            if (z) launch(render_pass3_points_kernel<LIMBS>, white, rgb, acc, flag, ll->z, ll->w, ll->n, ll->slot, ll->pts, ll->steps, ll->views);
-            else launch(render_pass3_points_z_kernel<LIMBS>, lindisp, white, rgb, acc, flag, ll->z, ll->w, ll->n, ll->slot, ll->pts, ll->steps, ll->views);
-        } else if (z) launch(render_pass3_colour_kernel<LIMBS>, white, rgb, acc, flag, ll->z, ll->w, ll->n, ll->slot);
-        else launch(render_pass3_colour_z_kernel<LIMBS>, lindisp, white, rgb, acc, flag, ll->z, ll->w, ll->n, ll->slot);
-    } else if (!z) launch(render_pass3_coarse_z_kernel<LIMBS>, lindisp, noise, white, rgb, disp, acc, weights, depth, raw_out, flag);
-    else if (weights) launch(render_pass3_coarse_kernel<LIMBS>, z, noise, white, rgb, disp, acc, weights, depth, raw_out, flag);
-    else launch(render_pass3_kernel<LIMBS>, z, noise, white, rgb, disp, acc, depth, raw_out, flag);
+            launch_point_order(*ll, a.z ? a.rays : nullptr, a.N, a.S, a.stream);
+            if (a.z) launch(render_pass3_points_kernel<LIMBS>, a.white, a.rgb, a.acc, flag, ll->z, ll->w, ll->n, ll->slot, ll->pts, ll->steps, ll->views);
+            else launch(render_pass3_points_z_kernel<LIMBS>, a.lindisp, a.white, a.rgb, a.acc, flag, ll->z, ll->w, ll->n, ll->slot, ll->pts, ll->steps, ll->views);
+        } else if (a.z) launch(render_pass3_colour_kernel<LIMBS>, a.white, a.rgb, a.acc, flag, ll->z, ll->w, ll->n, ll->slot);
+        else launch(render_pass3_colour_z_kernel<LIMBS>, a.lindisp, a.white, a.rgb, a.acc, flag, ll->z, ll->w, ll->n, ll->slot);
+    } else if (!a.z) launch(render_pass3_coarse_z_kernel<LIMBS>, a.lindisp, a.noise, a.white, a.rgb, a.disp, a.acc, a.weights, a.depth, a.raw_out, flag);
+    else if (a.weights) launch(render_pass3_coarse_kernel<LIMBS>, a.z, a.noise, a.white, a.rgb, a.disp, a.acc, a.weights, a.depth, a.raw_out, flag);
+    else launch(render_pass3_kernel<LIMBS>, a.z, a.noise, a.white, a.rgb, a.disp, a.acc, a.depth, a.raw_out, flag);
     return NVSR_CHECK_LAUNCH();
 }
-static int launch_pass3(int limbs, const nvsr_scene* scene, const float* packed, int64_t N, int S, const float* rays, const float* z, int lindisp,
-                        const float* noise, int white, float* rgb, float* disp, float* acc, float* weights, float* depth, float* raw_out, hipStream_t stream) {
-    LiveLists lists;
-    const LiveLists* ll = two_phase_lists(raw_out, N, S, stream, lists) ? &lists : nullptr;
-    return limbs == 3 ? launch_pass3<3>(ll, scene, packed, N, S, rays, z, lindisp, noise, white, rgb, disp, acc, weights, depth, raw_out, stream)
-                      : launch_pass3<2>(ll, scene, packed, N, S, rays, z, lindisp, noise, white, rgb, disp, acc, weights, depth, raw_out, stream);
+// one pass: its scratch, asked for once, names the route; grid (NULL: none) asks for the occupancy route, which falls back to the plain one
+static int launch_pass3(int limbs, const PassArgs& a, const uint32_t* grid = nullptr, int G = 0) {
+    LiveLists lists; OccLaunch occ{grid, G, {}};
+    const PassRoute route = acquire_pass_scratch(a.N, a.S, a.stream, a.raw_out != nullptr, grid != nullptr, true, lists, occ.kept);
+    const LiveLists* ll = route == PassRoute::Fused ? nullptr : &lists;
+    const OccLaunch* oc = route == PassRoute::Occupancy ? &occ : nullptr;
+    return limbs == 3 ? launch_pass3<3>(a, ll, oc) : launch_pass3<2>(a, ll, oc);
 }
 
 extern "C" int nvsr_render_pass3_launch(int limbs, const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays, const float* z,
                                         const float* noise, int white_bkgd, float* rgb, float* disp, float* acc, float* weights, float* depth, float* raw_out,
                                         nvsr_stream_t stream) {
     if ((N + RAYS2 - 1) / RAYS2 > 0x7fffffff || (limbs != 2 && limbs != 3)) return NVSR_ERR_SHAPE;
-    return launch_pass3(limbs, scene, packed_decoder, N, S, rays, z, 0, noise, white_bkgd, rgb, disp, acc, weights, depth, raw_out, (hipStream_t)stream);
+    PassArgs a{}; a.scene = scene; a.packed = packed_decoder; a.N = N; a.S = S; a.rays = rays; a.z = z; a.noise = noise; a.white = white_bkgd;
+    a.rgb = rgb; a.disp = disp; a.acc = acc; a.weights = weights; a.depth = depth; a.raw_out = raw_out; a.stream = (hipStream_t)stream;
+    return launch_pass3(limbs, a);
 }
 
 // the coarse pass with its depths computed in the kernel (z = coarse_depth(near, far, s, S, lindisp)); weights are always written
@@ -1096,11 +1099,13 @@ extern "C" int nvsr_render_pass3_coarse_z_launch(int limbs, const nvsr_scene* sc
                                                  const float* noise, int white_bkgd, float* rgb, float* disp, float* acc, float* weights, float* depth,
                                                  float* raw_out, nvsr_stream_t stream) {
     if ((N + RAYS2 - 1) / RAYS2 > 0x7fffffff || (limbs != 2 && limbs != 3) || !weights) return NVSR_ERR_SHAPE;
-    return launch_pass3(limbs, scene, packed_decoder, N, S, rays, nullptr, lindisp, noise, white_bkgd, rgb, disp, acc, weights, depth, raw_out, (hipStream_t)stream);
+    PassArgs a{}; a.scene = scene; a.packed = packed_decoder; a.N = N; a.S = S; a.rays = rays; a.lindisp = lindisp; a.noise = noise; a.white = white_bkgd;
+    a.rgb = rgb; a.disp = disp; a.acc = acc; a.weights = weights; a.depth = depth; a.raw_out = raw_out; a.stream = (hipStream_t)stream;
+    return launch_pass3(limbs, a);
 }
 
-// The occupancy route (include/nvsr.h, "Occupancy grid"): the pass above with the density decoder run on the samples of set cells only.  Declines -- and
-// runs the plain route, which is what the grid approximates -- where the two-phase route declines or the kept lists cannot be had.
+// The occupancy route (include/nvsr.h, "Occupancy grid"): the pass above, without noise, with the density decoder run on the samples of set cells only.  Declines
+// -- and runs the plain route, which is what the grid approximates -- where the two-phase route declines or the kept lists cannot be had.
 // z == NULL: the depths of coarse_depth in registers (lindisp); weights are then required, as by the coarse_z launch.
 extern "C" int nvsr_render_pass_occupancy_arith(const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays, const float* z, int lindisp,
                                                 int white_bkgd, float* rgb, float* disp, float* acc, float* weights, float* depth, const uint32_t* grid, int G,
@@ -1112,13 +1117,7 @@ extern "C" int nvsr_render_pass_occupancy_arith(const nvsr_scene* scene, const f
     if (!aligned16(packed_decoder)) return NVSR_ERR_ALIGN;
     if (N < 0 || S < 1 || S > 4096 || (N + RAYS2 - 1) / RAYS2 > 0x7fffffff) return NVSR_ERR_SHAPE;
     if (N == 0) return NVSR_OK;
-    const int limbs = arith == NVSR_ARITH_F16X2 ? 2 : 3;
-    LiveLists lists;
-    OccLaunch occ{grid, G, {}};
-    if (!occupancy_lists(N, S, (hipStream_t)stream, lists, occ.kept))
-        return launch_pass3(limbs, scene, packed_decoder, N, S, rays, z, lindisp, nullptr, white_bkgd, rgb, disp, acc, weights, depth, nullptr, (hipStream_t)stream);
-    return limbs == 3 ? launch_pass3<3>(&lists, scene, packed_decoder, N, S, rays, z, lindisp, nullptr, white_bkgd, rgb, disp, acc, weights, depth, nullptr,
-                                        (hipStream_t)stream, &occ)
-                      : launch_pass3<2>(&lists, scene, packed_decoder, N, S, rays, z, lindisp, nullptr, white_bkgd, rgb, disp, acc, weights, depth, nullptr,
-                                        (hipStream_t)stream, &occ);
+    PassArgs a{}; a.scene = scene; a.packed = packed_decoder; a.N = N; a.S = S; a.rays = rays; a.z = z; a.lindisp = lindisp; a.white = white_bkgd;
+    a.rgb = rgb; a.disp = disp; a.acc = acc; a.weights = weights; a.depth = depth; a.stream = (hipStream_t)stream;
+    return launch_pass3(arith == NVSR_ARITH_F16X2 ? 2 : 3, a, grid, G);
 }

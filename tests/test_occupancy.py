@@ -348,6 +348,33 @@ def test_frame_equals_its_passes(hip, frame, arith):
 
 
 @pytest.mark.parametrize("arith", ARITHS)
+def test_jittered_frame_equals_its_passes(hip, frame, arith):
+    """stratified jitter (t_rand given) with both grids: the coarse depths are stored, so the frame is nvsr_coarse_z, the occupancy pass on
+    those depths, nvsr_importance_resample on them, the occupancy pass -- the frame driver's branch that test_frame_equals_its_passes
+    (depths in registers) does not take"""
+    mc, mf, rays = frame
+    capi = hip.capi
+    N, Nc, Nf, Gc, Gf = rays.shape[0], 8, 16, 16, 12
+    code = capi.ARITHMETIC[arith]
+    planes, consts = mc.scene_args()
+    grid_c = _to_dev(ref.pack_bits(np.random.default_rng(1).random(Gc ** 3) < 0.4, Gc))
+    grid_f = _to_dev(ref.pack_bits(np.random.default_rng(2).random(Gf ** 3) < 0.4, Gf))
+    t_rand = torch.rand(N, Nc, generator=torch.Generator(device="cpu").manual_seed(9)).to(DEV)
+    frame_of = lambda t: torch.ops.nvsr.render_rays_occupancy(planes, consts, mc.packed_decoder(), mf.packed_decoder(), rays, Nc, Nf, False, True, t, None,
+                                                              grid_c, Gc, grid_f, Gf, code)
+    got = frame_of(t_rand)
+    z_c = torch.full((N, Nc), float("nan"), device=DEV)
+    capi.call("nvsr_coarse_z", N, Nc, capi.ptr(rays), 0, capi.ptr(t_rand), capi.ptr(z_c), capi.stream())
+    rgb_c, disp_c, acc_c, w_c = torch.ops.nvsr.render_pass_occupancy(planes, consts, mc.packed_decoder(), rays, z_c, Nc, False, True, True, grid_c, Gc, code)
+    z_f = torch.full((N, Nc + Nf), float("nan"), device=DEV)
+    capi.call("nvsr_importance_resample", N, Nc, Nf, capi.ptr(z_c), capi.ptr(w_c), None, capi.ptr(z_f), capi.stream())
+    rgb_f, disp_f, acc_f, _ = torch.ops.nvsr.render_pass_occupancy(planes, consts, mf.packed_decoder(), rays, z_f, Nc + Nf, False, True, False, grid_f, Gf, code)
+    for g, w in zip(got, (rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f)):
+        assert _same(g, w)
+    assert not _same(got[0], frame_of(None)[0])            # (the jitter does move the samples)
+
+
+@pytest.mark.parametrize("arith", ARITHS)
 def test_frame_with_full_or_no_grids_equals_render_rays(hip, frame, arith):
     mc, mf, rays = frame
     Nc, Nf, G = 8, 16, 8

@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <set>
+#include <vector>
 
 #include "../neural-volume-super-resolution_amd/csrc/colour_order.h"
 #include "../neural-volume-super-resolution_amd/csrc/occupancy.h"
@@ -48,20 +49,24 @@ int main() {
     const hipStream_t s0 = nullptr, s1 = reinterpret_cast<hipStream_t>(0x10);
     auto lists_bytes = [](int64_t N, int S) { return (int64_t)(2 * 4 * N * S + 4 * N); };
     LiveLists ll;
+    KeptLists kl;
+    // one pass's acquisition (colour_order.h), as the pass launcher calls it: a plain pass takes the two-phase route or not; an occupancy pass takes its own or not
+    auto plain_pass = [&](const float* raw_out, int64_t N, int S, hipStream_t s) { return acquire_pass_scratch(N, S, s, raw_out != nullptr, false, true, ll, kl) == PassRoute::TwoPhase; };
+    auto occupancy_pass = [&](int64_t N, int S, hipStream_t s) { return acquire_pass_scratch(N, S, s, false, true, true, ll, kl) == PassRoute::Occupancy; };
     CHECK(nvsr_render_scratch_bytes() == 0);
     // point-major route: four buffers per (device, stream)
     unsetenv("NVSR_COLOUR_POINTS");
-    CHECK(two_phase_lists(nullptr, 4609, 8, s0, ll) && ll.pts && ll.steps && ll.views && g_live_allocs.size() == 4);
+    CHECK(plain_pass(nullptr, 4609, 8, s0) && ll.pts && ll.steps && ll.views && g_live_allocs.size() == 4);
     CHECK(ll.steps == ll.pts + (size_t)19 * 256 * 8 && ll.trip == ll.slot + 19);
     static_cast<char*>(static_cast<void*>(ll.views))[(size_t)19 * 256 * POINT_VIEW_FLOATS * 4 - 1] = 1;      // the last byte of each buffer is the buffer's
     reinterpret_cast<char*>(ll.steps + 2 * 19)[-1] = 1;
     reinterpret_cast<char*>(ll.n + 4609)[-1] = 1;
     CHECK(nvsr_render_scratch_bytes() == lists_bytes(4609, 8));
     // growth: larger S, then larger N; a smaller launch afterwards grows nothing
-    CHECK(two_phase_lists(nullptr, 4609, 24, s0, ll) && g_live_allocs.size() == 4 && nvsr_render_scratch_bytes() == lists_bytes(4609, 24));
-    CHECK(two_phase_lists(nullptr, 8705, 24, s0, ll) && g_live_allocs.size() == 4 && nvsr_render_scratch_bytes() == lists_bytes(8705, 24));
+    CHECK(plain_pass(nullptr, 4609, 24, s0) && g_live_allocs.size() == 4 && nvsr_render_scratch_bytes() == lists_bytes(4609, 24));
+    CHECK(plain_pass(nullptr, 8705, 24, s0) && g_live_allocs.size() == 4 && nvsr_render_scratch_bytes() == lists_bytes(8705, 24));
     const size_t allocs = g_allocs;
-    CHECK(two_phase_lists(nullptr, 4609, 8, s0, ll) && g_allocs == allocs && nvsr_render_scratch_bytes() == lists_bytes(8705, 24));
+    CHECK(plain_pass(nullptr, 4609, 8, s0) && g_allocs == allocs && nvsr_render_scratch_bytes() == lists_bytes(8705, 24));
     // what a launch leaves behind is asked for with its own N / G
     int dst[64];
     CHECK(nvsr_internal_copy_live_counts(dst, 8705, (nvsr_stream_t)s0) == NVSR_ERR_SHAPE);
@@ -72,27 +77,26 @@ int main() {
     CHECK(nvsr_internal_copy_live_counts(dst, 1000, (nvsr_stream_t)s1) == NVSR_ERR_SHAPE);
     // the handle off: the lockstep kernels, no growth of the points' buffers
     setenv("NVSR_COLOUR_POINTS", "0", 1);
-    CHECK(two_phase_lists(nullptr, 20000, 24, s1, ll) && !ll.pts && !ll.steps && !ll.views && g_live_allocs.size() == 8);
+    CHECK(plain_pass(nullptr, 20000, 24, s1) && !ll.pts && !ll.steps && !ll.views && g_live_allocs.size() == 8);
     CHECK(nvsr_internal_copy_point_steps(dst, (20000 + 255) / 256, (nvsr_stream_t)s1) == NVSR_ERR_SHAPE);      // that launch left no steps
     unsetenv("NVSR_COLOUR_POINTS");
     // a points buffer that cannot be had (the third allocation: group table, lists, points): the lockstep kernels, the lists stay
     g_fail_in = 3;
-    CHECK(two_phase_lists(nullptr, 30000, 24, s1, ll) && !ll.pts && ll.z && g_fail_in == 0);
-    CHECK(two_phase_lists(nullptr, 30000, 24, s1, ll) && ll.pts && ll.views);          // the next launch has it
+    CHECK(plain_pass(nullptr, 30000, 24, s1) && !ll.pts && ll.z && g_fail_in == 0);
+    CHECK(plain_pass(nullptr, 30000, 24, s1) && ll.pts && ll.views);          // the next launch has it
     // the routes that decline: raw outputs, S beyond a packed entry, the one-phase handle
     float raw = 0;
-    CHECK(!two_phase_lists(&raw, 1000, 8, s0, ll) && !two_phase_lists(nullptr, 1000, ORDER_MAX_S, s0, ll));
+    CHECK(!plain_pass(&raw, 1000, 8, s0) && !plain_pass(nullptr, 1000, ORDER_MAX_S, s0));
     setenv("NVSR_RENDER_ONE_PHASE", "1", 1);
-    CHECK(!two_phase_lists(nullptr, 1000, 8, s0, ll));
+    CHECK(!plain_pass(nullptr, 1000, 8, s0));
     unsetenv("NVSR_RENDER_ONE_PHASE");
     // the occupancy route: the kept lists (N S + N ints) and their group table, beside the others and not counted; a plain launch leaves them alone
     {
-        KeptLists kl;
         const hipStream_t s2 = reinterpret_cast<hipStream_t>(0x20);
         CHECK(nvsr_internal_copy_kept_counts(dst, 300, (nvsr_stream_t)s2) == NVSR_ERR_SHAPE);       // none ran
         const size_t before = g_live_allocs.size();
         const int64_t counted = nvsr_render_scratch_bytes();
-        CHECK(occupancy_lists(300, 4, s2, ll, kl) && g_live_allocs.size() == before + 6 && nvsr_render_scratch_bytes() == counted + lists_bytes(300, 4));
+        CHECK(occupancy_pass(300, 4, s2) && g_live_allocs.size() == before + 6 && nvsr_render_scratch_bytes() == counted + lists_bytes(300, 4));
         CHECK(kl.n == kl.idx + 300 * 4 && kl.trip == kl.slot + 2 && ll.z && ll.pts);
         reinterpret_cast<char*>(kl.n + 300)[-1] = 1;                                                // the last byte of each buffer is the buffer's
         reinterpret_cast<char*>(kl.trip + 2)[-1] = 1;
@@ -102,22 +106,25 @@ int main() {
         CHECK(nvsr_internal_copy_kept_counts(got, 301, (nvsr_stream_t)s2) == NVSR_ERR_SHAPE);       // asked for with the launch's own N
         CHECK(nvsr_internal_copy_live_counts(got, 300, (nvsr_stream_t)s2) == NVSR_OK);              // the two-phase launch it is part of
         // growth forgets the latest launch's counts until the launch that grew it is recorded; a smaller launch grows nothing
-        CHECK(occupancy_lists(900, 8, s2, ll, kl) && g_live_allocs.size() == before + 6);
+        CHECK(occupancy_pass(900, 8, s2) && g_live_allocs.size() == before + 6);
         CHECK(nvsr_internal_copy_kept_counts(got, 300, (nvsr_stream_t)s2) == NVSR_ERR_SHAPE);
         const size_t allocs2 = g_allocs;
-        CHECK(occupancy_lists(300, 4, s2, ll, kl) && g_allocs == allocs2);
+        CHECK(occupancy_pass(300, 4, s2) && g_allocs == allocs2);
         // a plain two-phase launch keeps the kept lists of the latest occupancy launch; a declining occupancy launch forgets them
-        CHECK(two_phase_lists(nullptr, 300, 4, s2, ll) && nvsr_internal_copy_kept_counts(got, 300, (nvsr_stream_t)s2) == NVSR_OK);
-        CHECK(!occupancy_lists(300, ORDER_MAX_S, s2, ll, kl) && nvsr_internal_copy_kept_counts(got, 300, (nvsr_stream_t)s2) == NVSR_ERR_SHAPE);
+        CHECK(plain_pass(nullptr, 300, 4, s2) && nvsr_internal_copy_kept_counts(got, 300, (nvsr_stream_t)s2) == NVSR_OK);
+        CHECK(!occupancy_pass(300, ORDER_MAX_S, s2) && nvsr_internal_copy_kept_counts(got, 300, (nvsr_stream_t)s2) == NVSR_ERR_SHAPE);
         // kept lists that cannot be had (the first allocation of a larger launch's kept buffers: the group table): the route declines, the plain lists stay
-        CHECK(two_phase_lists(nullptr, 5000, 8, s2, ll));
+        CHECK(plain_pass(nullptr, 5000, 8, s2));
         g_fail_in = 1;
-        CHECK(!occupancy_lists(5000, 8, s2, ll, kl) && g_fail_in == 0 && nvsr_internal_copy_live_counts(got, 5000, (nvsr_stream_t)s2) == NVSR_ERR_SHAPE);
-        CHECK(occupancy_lists(5000, 8, s2, ll, kl));
+        // (the one acquisition of that pass answers the plain route and records it as the plain launch it becomes -- the caller asks no second time)
+        std::vector<int> got5000(5000);
+        CHECK(!occupancy_pass(5000, 8, s2) && g_fail_in == 0 && ll.z && nvsr_internal_copy_live_counts(got5000.data(), 5000, (nvsr_stream_t)s2) == NVSR_OK);
+        CHECK(nvsr_internal_copy_kept_counts(got5000.data(), 5000, (nvsr_stream_t)s2) == NVSR_ERR_SHAPE);
+        CHECK(occupancy_pass(5000, 8, s2));
     }
     // release: everything, on every stream; later launches allocate anew
     CHECK(nvsr_release_render_scratch() == NVSR_OK && g_live_allocs.empty() && nvsr_render_scratch_bytes() == 0);
-    CHECK(two_phase_lists(nullptr, 300, 4, s0, ll) && g_live_allocs.size() == 4);
+    CHECK(plain_pass(nullptr, 300, 4, s0) && g_live_allocs.size() == 4);
     CHECK(nvsr_release_render_scratch() == NVSR_OK && g_live_allocs.empty());
     printf("ok: %zu allocations, %zu bytes, none left\n", g_allocs, g_bytes);
     return 0;
