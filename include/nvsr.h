@@ -591,6 +591,49 @@ int64_t nvsr_view_grad_workspace_floats(int64_t N, int S);
 /* grad_natural [NVSR_DECODER_NATURAL_FLOATS] += gradient of this pass (float atomics: zero it before the first pass) */
 int nvsr_decoder_weight_grad(int64_t N, int S, const float* record, float* grad_natural, nvsr_stream_t stream);
 
+/* ---- training: the deterministic route (opt-in) -----------------------------------------------------------
+ * The entries above add plane and decoder-weight gradients with float atomics: two runs from the same state differ in their last
+ * bits.  The entries below compute the same gradients in a fixed order, for the limb arithmetics (NVSR_ARITH_BF16X3 / _F16X2; an
+ * arithmetic that resolves to NVSR_ARITH_F32 is answered with NVSR_ERR_SHAPE).  None of them allocates, creates a stream or
+ * synchronises; what they need comes out of the caller's workspaces.
+ *
+ * nvsr_render_pass_backward_rows_arith: nvsr_render_pass_backward_gates_arith with the plane scatter replaced by plain stores.
+ *   rows: 3 pointers or NULL; rows[d] (or NULL: plane d is frozen, nothing is written) receives the feature gradient of every point
+ *   with respect to position plane d as rows[d][ray * S + s][48] -- whole 192-byte rows, no atomics, no plane is touched.
+ *   view_ws (or NULL: the view plane is frozen): nvsr_view_grad_workspace_floats(N, S) floats; receives one pre-summed row per
+ *   (ray, 32-sample chunk) as in the atomic route; nvsr_view_rows_reduce adds a ray's (S + 31) / 32 rows in ascending chunk order into
+ *   view_rows[ray][48].  record: as in nvsr_render_pass_backward_gates_arith.  At least one of rows, view_ws, record is given.
+ *
+ * nvsr_internal_plane_taps: texel[M][4] (int32, iy * W + ix) and weight[M][4] of the bilinear taps, in the order nw, ne, sw, se, formed
+ *   by the backward kernel's own tap functions; d in 0..2: M = N * S, one entry per point (m = ray * S + s); d == 3 (view plane, z may be
+ *   NULL): M = N, one entry per ray.  A neighbour clamped at the border names the border texel and carries weight 0, as in the kernels.
+ *
+ * nvsr_rows_scatter: rows[M][48], texel[M][4], weight[M][4] -> g[H * W][48] (a channel-last gradient plane), exactly:
+ *     entry e = 4 m + j belongs to texel texel[e];
+ *     for every texel t that at least one entry names, and every channel c:
+ *         s = +0.0f;  for that texel's entries in ascending e:  s = __fadd_rn(s, __fmul_rn(rows[m][c], weight[e]));
+ *         g[t][c] = __fadd_rn(g[t][c], s);
+ *     every entry takes part, weight 0 included (a NaN row reaches exactly its four texels); a texel no entry names is not written.
+ *   Texel numbers outside [0, H * W) are never written to.  workspace: nvsr_rows_scatter_workspace_bytes(M) bytes, 16-byte aligned
+ *   (sorted keys, sorted entry numbers and the temporary storage of the stable radix sort); its contents need not be initialised.
+ *   The cost is linear in M, also when every entry names the same texel.
+ *
+ * nvsr_decoder_weight_grad_det_arith: nvsr_decoder_weight_grad_arith's limb contractions with every slab of rows writing its block into a
+ *   partial blob of its own (workspace: nvsr_decoder_weight_grad_det_workspace_floats(N, S) floats, contents need not be initialised); a
+ *   reduce kernel adds the slabs in ascending order and adds the sum into grad_natural.  The slab boundaries depend on N * S alone. */
+int nvsr_render_pass_backward_rows_arith(const nvsr_scene* scene, const float* packed_decoder, const float* packed_bwd, int64_t N, int S,
+                                         const float* rays, const float* z, const float* g_raw, const uint32_t* gates, float* const* rows,
+                                         float* view_ws, float* record, int arithmetic, nvsr_stream_t stream);
+int nvsr_view_rows_reduce(int64_t N, int S, const float* view_ws, float* view_rows, nvsr_stream_t stream);
+int nvsr_internal_plane_taps(const nvsr_scene* scene, int d, int64_t N, int S, const float* rays, const float* z, int32_t* texel, float* weight,
+                             nvsr_stream_t stream);
+int64_t nvsr_rows_scatter_workspace_bytes(int64_t M);
+int nvsr_rows_scatter(int64_t M, const float* rows, const int32_t* texel, const float* weight, int H, int W, float* g, void* workspace,
+                      int64_t workspace_bytes, nvsr_stream_t stream);
+int64_t nvsr_decoder_weight_grad_det_workspace_floats(int64_t N, int S);
+int nvsr_decoder_weight_grad_det_arith(int64_t N, int S, const float* record, float* grad_natural, float* workspace, int arithmetic,
+                                       nvsr_stream_t stream);
+
 
 /* ---- training: gradients of the super-resolution CNN ('SR' in nerf.train.what) -------------------------------------------
  * torch.autograd through EDSR.forward (models.py:818-822), _Residual_Block.forward (:777-786), PlanesSR.forward (:884-926). */

@@ -238,6 +238,14 @@ _PROTOS_OPTIONAL = {   # feature-plane super-resolution (csrc/sr.hip)
     "nvsr_pe_nerf_backward_arith": ([_i64, _vp, _vp, _vp, _vp, _i, _vp], _i),
     "nvsr_pe_nerf_wgrad_workspace_floats": ([_i64], _i64),
     "nvsr_pe_nerf_weight_grad": ([_i64, _vp, _vp, _vp, _vp, _vp], _i),
+    # the deterministic route of the tri-plane training step (csrc/deterministic.hip, render_bwd_limb.hip, decoder_wgrad.hip)
+    "nvsr_render_pass_backward_rows_arith": ([C.POINTER(Scene), _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, C.POINTER(C.c_void_p), _vp, _vp, _i, _vp], _i),
+    "nvsr_view_rows_reduce": ([_i64, _i, _vp, _vp, _vp], _i),
+    "nvsr_internal_plane_taps": ([C.POINTER(Scene), _i, _i64, _i, _vp, _vp, _vp, _vp, _vp], _i),
+    "nvsr_rows_scatter_workspace_bytes": ([_i64], _i64),
+    "nvsr_rows_scatter": ([_i64, _vp, _vp, _vp, _i, _i, _vp, _vp, _i64, _vp], _i),
+    "nvsr_decoder_weight_grad_det_workspace_floats": ([_i64, _i], _i64),
+    "nvsr_decoder_weight_grad_det_arith": ([_i64, _i, _vp, _vp, _vp, _i, _vp], _i),
     # low-rank feature planes (csrc/lowrank.hip)
     "nvsr_lowrank_planes": ([LowrankPlanesArgs, _vp], _i),
     "nvsr_lowrank_planes_backward": ([LowrankPlanesArgs, _vp], _i),
@@ -311,6 +319,49 @@ def set_conv_arithmetic(mode):
 
 def get_conv_arithmetic():
     return {v: k for k, v in ARITHMETIC.items()}[lib().nvsr_get_conv_arithmetic()]
+
+
+_det_scope = []
+
+
+def deterministic(flag=None):
+    """Is the deterministic mode on for a call made now?  Resolved in this order: an explicit `flag` (a TrainStep built with
+    deterministic=... hands its own down through deterministic_scope); NVSR_DETERMINISTIC=1 in the environment, read at every call; torch's
+    own switch (torch.use_deterministic_algorithms).  In the mode the tri-plane training step adds plane and decoder-weight gradients in a
+    fixed order; what has no ordered route raises a RuntimeError instead of running its atomics."""
+    if flag is None and _det_scope:
+        flag = _det_scope[-1]
+    if flag is not None:
+        return bool(flag)
+    if os.environ.get("NVSR_DETERMINISTIC") == "1":
+        return True
+    return bool(torch.are_deterministic_algorithms_enabled())
+
+
+class deterministic_scope:
+    """with deterministic_scope(flag): calls of deterministic() inside resolve as if `flag` were their explicit argument (None: no effect)"""
+
+    def __init__(self, flag):
+        self.flag = flag
+
+    def __enter__(self):
+        _det_scope.append(self.flag)
+        return self
+
+    def __exit__(self, *exc):
+        _det_scope.pop()
+        return False
+
+
+class DeterministicModeError(RuntimeError):
+    pass
+
+
+def refuse_deterministic(what):
+    """raise for a path that has no ordered route (called before any launch)"""
+    raise DeterministicModeError("deterministic mode: %s has no ordered route and would add its gradients with float atomics; the mode covers the "
+                                 "native-geometry tri-plane model in 'bf16x3' / 'f16x2' with a recorded forward (NVSR_DETERMINISTIC, "
+                                 "torch.use_deterministic_algorithms or TrainStep(deterministic=...) turned it on)" % what)
 
 
 class RangeFlag:

@@ -351,6 +351,40 @@ __device__ __forceinline__ void store_view_rows(const f32x16 (&acc2)[2], float* 
     __builtin_amdgcn_wave_barrier();
 }
 
+// Taps of position plane d for the sample at depth zc of the packed ray r (11 floats), and the cell it falls into: what the limb backward
+// scatters with, and what nvsr_internal_plane_taps (deterministic.hip) emits for the ordered scatter -- ONE definition, so the two routes
+// weigh the same texels with the same bits.
+__device__ __forceinline__ Taps ray_pos_taps(const SceneDev& sc, const float* __restrict__ r, float zc, int d, int& ix, int& iy) {
+    const float n0 = norm_coord(__fadd_rn(r[0], __fmul_rn(r[3], zc)), sc.lo[0], sc.range[0]);
+    const float n1 = norm_coord(__fadd_rn(r[1], __fmul_rn(r[4], zc)), sc.lo[1], sc.range[1]);
+    const float n2 = norm_coord(__fadd_rn(r[2], __fmul_rn(r[5], zc)), sc.lo[2], sc.range[2]);
+    const float* M = sc.proj + 6 * d;
+    return make_taps_cell(sc, d, n0 * M[0] + n1 * M[2] + n2 * M[4], n0 * M[1] + n1 * M[3] + n2 * M[5], ix, iy);
+}
 
+// Deterministic route: the tile's feature gradients leave as plain rows rows[first + p][48], p < nvalid, instead of being
+// scattered -- no atomics, no plane touched.  The transposed LDS rows (TILE_STRIDE floats apart, 16-byte aligned) go out four channels per
+// lane: the nvalid rows are one contiguous run of nvalid x 192 bytes in HBM, six 16-byte stores per lane cover a whole tile.  Padding
+// samples of a partial tile write nothing.
+__device__ __forceinline__ void store_plane_rows(const f32x16 (&acc2)[2], float* tile, float* __restrict__ rows, long first, int nvalid, int lane) {
+    const int h = lane >> 5, pt = lane & 31;
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            if (b == 1 && r >= 8) continue;                        // rows 48..63 are padding
+            const int c = 32 * b + (r & 3) + 8 * (r >> 2) + 4 * h;
+            tile[pt * TILE_STRIDE + c] = acc2[b][r];
+        }
+    __builtin_amdgcn_wave_barrier();
+    f32x4* out = reinterpret_cast<f32x4*>(rows + first * C);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const int i = k * 64 + lane, p = i / 12, c4 = i - p * 12;          // f32x4 number i of the tile = channels 4 c4 .. 4 c4 + 3 of point p
+        if (p < nvalid) out[i] = *reinterpret_cast<const f32x4*>(tile + p * TILE_STRIDE + 4 * c4);
+    }
+    __builtin_amdgcn_wave_barrier();
+}
 
 }  // namespace nvsr

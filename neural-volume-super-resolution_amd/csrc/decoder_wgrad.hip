@@ -142,7 +142,10 @@ __global__ __launch_bounds__(WG_TPB, 2) void decoder_wgrad_kernel(WJobs jobs, lo
 // hidden layer (256 accumulators, AGPRs; one wave per SIMD) and G is read once per layer; the two 64-column leftovers (density layer 0,
 // columns 128..191 of rgb layer 0) are padded to whole blocks (see the launcher).  The next 16 rows are loaded while the current ones are
 // multiplied.
-template <int NB>
+// DET (the deterministic route): `grad` is not the gradient blob but the partial blob of THIS slab (the workspace of
+// nvsr_decoder_weight_grad_det_arith): the block is stored, not added -- every element of a slab's blob has one owner -- and
+// decoder_wgrad_reduce_kernel adds the slabs in ascending order.
+template <int NB, bool DET = false>
 __device__ __forceinline__ void wgrad_limb_block(const WJob& jb, long P, int slab, float* tile, float* __restrict__ grad) {
     typedef float xvec __attribute__((ext_vector_type(NB)));
     // (wave index in a scalar register, lane from the hardware counter: with 256 accumulators + two row sets in flight every vector register
@@ -229,7 +232,26 @@ __device__ __forceinline__ void wgrad_limb_block(const WJob& jb, long P, int sla
     }
     // the bias sums first (they die here: the flush below needs every vector register); lane indices recomputed, not kept across the loop
     const int lane2 = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)), i2 = lane2 & 31, kh2 = lane2 >> 5;
-    if (jb.b_off >= 0) {
+    if constexpr (DET) {
+        // every wave holds a partial bias sum of its quarter of the slab (the atomic route adds all four): they meet in LDS -- the tile is free
+        // until the flush -- and wave 0 adds them in wave order and stores the slab's sum
+        if (jb.b_off >= 0) {                                        // (workgroup-uniform)
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                const float v = bs[a] + __shfl_xor(bs[a], 32);
+                if (kh2 == 0) tile[wave * HID + 4 * i2 + a] = v;
+            }
+            __syncthreads();
+            if (wave == 0 && kh2 == 0) {
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    const int o = 4 * i2 + a;
+                    grad[jb.b_off + o] = ((tile[o] + tile[HID + o]) + tile[2 * HID + o]) + tile[3 * HID + o];
+                }
+            }
+            __syncthreads();
+        }
+    } else if (jb.b_off >= 0) {
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
             const float v = bs[a] + __shfl_xor(bs[a], 32);
@@ -263,22 +285,27 @@ __device__ __forceinline__ void wgrad_limb_block(const WJob& jb, long P, int sla
     }
     for (int idx = wave * 64 + lane2; idx < 128 * TW; idx += WG_TPB) {
         const int out = idx / TW, col = jb.col0 + (idx % TW);
-        if (col < jb.in_total) unsafeAtomicAdd(grad + jb.w_off + out * jb.in_total + col, tile[idx]);
+        if constexpr (DET) { if (col < jb.in_total) grad[jb.w_off + out * jb.in_total + col] = tile[idx]; }
+        else if (col < jb.in_total) unsafeAtomicAdd(grad + jb.w_off + out * jb.in_total + col, tile[idx]);
     }
 }
 
-template <int NB>
+template <int NB, bool DET = false>
 __global__ __launch_bounds__(WG_TPB, 1) void decoder_wgrad_limb_kernel(WJobs jobs, int job0, long P, int slab, float* __restrict__ grad) {
     __shared__ __attribute__((aligned(16))) float tile[128 * 32 * NB];
     NVSR_RACE_PROBE_DELAY(tile);      // (probe builds only, nvsr_common.h)
-    wgrad_limb_block<NB>(jobs.j[job0 + blockIdx.y], P, slab, tile, grad);
+    wgrad_limb_block<NB, DET>(jobs.j[job0 + blockIdx.y], P, slab, tile, DET ? grad + (long)blockIdx.x * NVSR_DECODER_NATURAL_FLOATS : grad);
 }
 
 // fc_alpha / fc_rgb: dW[k][f] = sum_q g4[q][k] * H3[q][f], db[k] = sum_q g4[q][k].  HBM-bound: 1 040 bytes of record per point.  A wave reads
 // ONE row of both branches per step as 16-byte loads -- lanes 0..31 the density row, lanes 32..63 the rgb row, 4 features per lane -- and the
 // workgroup's 8 waves take rows q0 + wave, q0 + wave + 8, ...; their sums meet in LDS and the workgroup adds its 516 partial sums once
 // (every workgroup adds into the same 516 addresses).  (Round 3: one feature per thread with 4-byte loads ran at 2.3 TB/s.)
+// DET: `grad` is the workspace's head region [slab][HEAD_FLOATS] (fc_rgb weight 3 x 128, fc_alpha weight 128, fc_rgb bias 3, fc_alpha bias): the
+// workgroup stores its 516 sums into its own slab.
 constexpr int HW_WAVES = 8;
+constexpr int HEAD_FLOATS = 4 * HID + 4;
+template <bool DET = false>
 __global__ __launch_bounds__(64 * HW_WAVES) void head_wgrad_kernel(const float* __restrict__ Hd3, const float* __restrict__ Hr3,
                                                                    const float* __restrict__ g4, long Pp, int rows, float* __restrict__ grad) {
     __shared__ float part[HW_WAVES][12][64];
@@ -318,6 +345,20 @@ __global__ __launch_bounds__(64 * HW_WAVES) void head_wgrad_kernel(const float* 
             for (int i = 0; i < 4; ++i) a[k][i] += part[w][k * 4 + i][lane];
         if (lane == 0) { s[0] += bsum[w][0]; s[1] += bsum[w][1]; s[2] += bsum[w][2]; s[3] += bsum[w][3]; }
     }
+    if constexpr (DET) {
+        float* hp = grad + (long)blockIdx.x * HEAD_FLOATS;
+        if (rgb) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) hp[k * HID + f4 + i] = a[k][i];
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) hp[3 * HID + f4 + i] = a[0][i];
+        }
+        if (lane == 0) { hp[4 * HID] = s[0]; hp[4 * HID + 1] = s[1]; hp[4 * HID + 2] = s[2]; hp[4 * HID + 3] = s[3]; }
+        return;
+    }
     if (rgb) {
 #pragma unroll
         for (int k = 0; k < 3; ++k)
@@ -333,9 +374,78 @@ __global__ __launch_bounds__(64 * HW_WAVES) void head_wgrad_kernel(const float* 
     }
 }
 
+// Deterministic route: element idx of the gradient blob = the sum of its slabs' partials in ascending slab order, added into grad_natural
+// (nerf_wgrad_reduce_kernel's scheme, nerf_mlp.h).  The head elements come from the head region [nh][HEAD_FLOATS], the rest from [nl][natural blob].
+__global__ __launch_bounds__(256) void decoder_wgrad_reduce_kernel(const float* __restrict__ part, int nl, const float* __restrict__ head, int nh,
+                                                                   float* __restrict__ grad) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= NVSR_DECODER_NATURAL_FLOATS) return;
+    int hidx = -1;
+    if (idx >= N_FCRGB_B) hidx = 4 * HID + (idx - N_FCRGB_B);
+    else if (idx >= N_FCRGB_W) hidx = idx - N_FCRGB_W;
+    else if (idx == N_ALPHA_B) hidx = 4 * HID + 3;
+    else if (idx >= N_ALPHA_W && idx < N_ALPHA_B) hidx = 3 * HID + (idx - N_ALPHA_W);
+    const float* p = hidx >= 0 ? head + hidx : part + idx;
+    const long stride = hidx >= 0 ? HEAD_FLOATS : NVSR_DECODER_NATURAL_FLOATS;
+    const int n = hidx >= 0 ? nh : nl;
+    float v = 0.0f;
+    for (int k = 0; k < n; ++k) v = __fadd_rn(v, p[k * stride]);
+    grad[idx] = __fadd_rn(grad[idx], v);
+}
+
+// slabs of the deterministic contraction: functions of P = N * S alone (never of the device or the environment)
+inline long det_limb_slab(long P) { long s4 = (P + 27) / 28; return ((s4 + 255) / 256) * 256; }           // the atomic route's slab: <= 28 slabs
+inline long det_head_rows(long P) { long r = ((P + 255) / 256 + 7) / 8 * 8; return r < 1024 ? 1024 : r; }  // 1024 rows, more beyond 256 slabs
+
 }  // namespace nvsr
 
 using namespace nvsr;
+
+extern "C" int64_t nvsr_decoder_weight_grad_det_workspace_floats(int64_t N, int S) {
+    if (N < 0 || S < 1 || S > 4096) return 0;
+    const long P = (long)N * S;
+    if (P == 0) return 0;
+    // monotone in P (the slab COUNTS are not: a larger pass may take fewer, larger slabs): at most 28 slabs of at least 256 rows, at most 256
+    // head slabs of at least 1024 rows
+    const long nl = (P + 255) / 256 < 28 ? (P + 255) / 256 : 28, nh = (P + 1023) / 1024 < 256 ? (P + 1023) / 1024 : 256;
+    return round4(nl * (int64_t)NVSR_DECODER_NATURAL_FLOATS) + nh * (int64_t)HEAD_FLOATS;
+}
+
+extern "C" int nvsr_decoder_weight_grad_det_arith(int64_t N, int S, const float* record, float* grad_natural, float* workspace, int arithmetic,
+                                                  nvsr_stream_t stream) {
+    const int arith = nvsr_internal_resolve_decoder_arith(arithmetic);
+    if (arith < 0 || arith == NVSR_ARITH_F32) return NVSR_ERR_SHAPE;      // the limb arithmetics only
+    if (!record || !grad_natural || !workspace) return NVSR_ERR_NULL;
+    if (!aligned16(record) || !aligned16(workspace)) return NVSR_ERR_ALIGN;
+    if (N < 0 || S < 1 || S > 4096) return NVSR_ERR_SHAPE;
+    if (N == 0) return NVSR_OK;
+    const DecRecord rec = make_record(const_cast<float*>(record), (long)N, S);
+    const long Pp = rec.Pp, P = rec.P;
+    const long LP = (long)HID * Pp;
+    WJobs jobs;
+    int n = 0;
+    auto add = [&](const float* G, const float* X, int xstride, int col0, int w_off, int in_total, int b_off, int nb) {
+        jobs.j[n++] = WJob{G, X, xstride, col0, w_off, in_total, b_off, nb};
+    };
+    // the nine [128 x 128] blocks of nvsr_decoder_weight_grad_arith's limb route, the same contractions
+    for (int l = 1; l <= 3; ++l) {
+        const int wd = N_DEN_W1 + (l - 1) * N_HID_STRIDE, wr = N_RGB_W1 + (l - 1) * N_HID_STRIDE;
+        add(rec.Gd + l * LP, rec.Hd + (l - 1) * LP, HID, 0, wd, HID, wd + HID * HID, 4);
+        add(rec.Gr + l * LP, rec.Hr + (l - 1) * LP, HID, 0, wr, HID, wr + HID * HID, 4);
+    }
+    add(rec.Gr, rec.Xr, 4 * C, 0, N_RGB_W0, 4 * C, N_RGB_B0, 4);
+    add(rec.Gr, rec.Xr, 4 * C, 128, N_RGB_W0, 4 * C, -1, 4);
+    add(rec.Gd, rec.Xd, 64, 0, N_DEN_W0, C, N_DEN_B0, 4);
+    const long s4 = det_limb_slab(P), hrows = det_head_rows(P);
+    const int nl = (int)((P + s4 - 1) / s4), nh = (int)((P + hrows - 1) / hrows);
+    float* head = workspace + round4((int64_t)nl * NVSR_DECODER_NATURAL_FLOATS);
+    hipLaunchKernelGGL((decoder_wgrad_limb_kernel<4, true>), dim3((unsigned)nl, 9), dim3(WG_TPB), 0, (hipStream_t)stream, jobs, 0, P, (int)s4, workspace);
+    hipLaunchKernelGGL(head_wgrad_kernel<true>, dim3((unsigned)nh), dim3(64 * HW_WAVES), 0, (hipStream_t)stream, rec.Hd + 3 * LP, rec.Hr + 3 * LP, rec.g4,
+                       P, (int)hrows, head);
+    hipLaunchKernelGGL(decoder_wgrad_reduce_kernel, dim3((NVSR_DECODER_NATURAL_FLOATS + 255) / 256), dim3(256), 0, (hipStream_t)stream, workspace, nl, head,
+                       nh, grad_natural);
+    return NVSR_CHECK_LAUNCH();
+}
 
 extern "C" int nvsr_decoder_weight_grad(int64_t N, int S, const float* record, float* grad_natural, nvsr_stream_t stream) {
     return nvsr_decoder_weight_grad_arith(N, S, record, grad_natural, NVSR_ARITH_INHERIT, stream);
@@ -396,7 +506,7 @@ extern "C" int nvsr_decoder_weight_grad_arith(int64_t N, int S, const float* rec
         hipLaunchKernelGGL(decoder_wgrad_kernel, dim3(nslabs, WJOBS), dim3(WG_TPB), 0, (hipStream_t)stream, jobs, P, (int)slab, grad_natural);
     }
     const int hrows = 1024;       // rows per workgroup (8 waves x 128 rows): 512 workgroups at 524k rows
-    hipLaunchKernelGGL(head_wgrad_kernel, dim3((unsigned)((P + hrows - 1) / hrows)), dim3(64 * HW_WAVES), 0, (hipStream_t)stream, rec.Hd + 3 * LP,
+    hipLaunchKernelGGL(head_wgrad_kernel<false>, dim3((unsigned)((P + hrows - 1) / hrows)), dim3(64 * HW_WAVES), 0, (hipStream_t)stream, rec.Hd + 3 * LP,
                        rec.Hr + 3 * LP, rec.g4, P, hrows, grad_natural);
     return NVSR_CHECK_LAUNCH();
 }

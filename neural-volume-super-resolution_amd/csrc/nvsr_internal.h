@@ -24,6 +24,10 @@ int nvsr_decode_rays_pair_launch(const nvsr_scene* scene, const float* packed_de
 int nvsr_render_pass_backward_gates_limb_launch(int limbs, const nvsr_scene* scene, const float* packed_decoder, const float* packed_bwd, int64_t N, int S, const float* rays,
                                                 const float* z, const float* g_raw, const uint32_t* gates, float* const* grad_planes, float* view_ws, float* record,
                                                 nvsr_stream_t stream);
+// the ROWS variant of the same kernel (deterministic route): rows[d][N * S][48] instead of gradient planes
+int nvsr_render_pass_backward_rows_limb_launch(int limbs, const nvsr_scene* scene, const float* packed_decoder, const float* packed_bwd, int64_t N, int S, const float* rays,
+                                               const float* z, const float* g_raw, const uint32_t* gates, float* const* rows, float* view_ws, float* record,
+                                               nvsr_stream_t stream);
 // render.hip: NVSR_ARITH_INHERIT -> the process default, anything that is not a mode -> -1; the mode named by an environment variable (dflt if unset)
 int nvsr_internal_resolve_decoder_arith(int arithmetic);
 int nvsr_internal_parse_arith_env(const char* name, int dflt);

@@ -497,6 +497,19 @@ __global__ __launch_bounds__(256) void view_reduce_scatter_kernel(SceneDev sc, l
     unsafeAtomicAdd(gplane + t.o11 + lane, v * t.se);
 }
 
+// The reduce-only twin for the deterministic route: a ray's nsc per-tile rows added in ascending chunk order into
+// view_rows[ray][48] -- no taps, no atomics; nvsr_rows_scatter then adds the N rows into the view plane in a fixed order.
+__global__ __launch_bounds__(256) void view_rows_reduce_kernel(long N, int nsc, const float* __restrict__ gview, float* __restrict__ view_rows) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;           // element (ray, channel)
+    if (i >= N * C) return;
+    const long ray = i / C;
+    const int c = (int)(i - ray * C);
+    const float* row = gview + ray * nsc * C + c;
+    float v = 0.0f;
+    for (int s = 0; s < nsc; ++s) v = __fadd_rn(v, row[s * C]);
+    view_rows[i] = v;
+}
+
 // =====================================================================================================================
 // volume_render_radiance_field backward: (g_rgb [N,3], g_acc [N] or NULL, g_dep [N] or NULL) -> g_raw [N,S,4]; one wave per ray, S <= 512
 // (g_dep = gradient of depth_map = sum_s w_s z_s, volume_rendering_utils.py:42-43; disp_map's gradient reaches this kernel through g_dep / g_acc)
@@ -711,6 +724,36 @@ int nvsr_render_pass_backward_gates_arith(const nvsr_scene* scene, const float* 
     if (int e = NVSR_CHECK_LAUNCH()) return e;
     if (view_ws && gp.p[3]) return launch_view_reduce(scene, N, S, rays, view_ws, gp.p[3], (hipStream_t)stream);
     return NVSR_OK;
+}
+
+int nvsr_render_pass_backward_rows_arith(const nvsr_scene* scene, const float* packed_decoder, const float* packed_bwd, int64_t N, int S,
+                                         const float* rays, const float* z, const float* g_raw, const uint32_t* gates, float* const* rows,
+                                         float* view_ws, float* record, int arithmetic, nvsr_stream_t stream) {
+    const int arith = nvsr_internal_resolve_decoder_arith(arithmetic);
+    if (arith < 0 || arith == NVSR_ARITH_F32) return NVSR_ERR_SHAPE;      // the limb arithmetics only: the exact-f32 backward has no rows variant
+    if (!scene || !packed_decoder || !packed_bwd || !rays || !z || !g_raw || !gates) return NVSR_ERR_NULL;
+    if (!rows && !view_ws && !record) return NVSR_ERR_NULL;
+    for (int d = 0; d < 4; ++d) {
+        if (!scene->planes[d]) return NVSR_ERR_NULL;
+        if (scene->ph[d] < 1 || scene->pw[d] < 1) return NVSR_ERR_SHAPE;
+    }
+    if (!aligned16(packed_decoder) || !aligned16(packed_bwd) || !aligned16(g_raw) || !aligned16(gates) || !aligned16(record) || !aligned16(view_ws))
+        return NVSR_ERR_ALIGN;
+    for (int d = 0; d < 3; ++d)
+        if (rows && !aligned16(rows[d])) return NVSR_ERR_ALIGN;
+    if (N < 0 || S < 1 || S > 4096) return NVSR_ERR_SHAPE;
+    if (N == 0) return NVSR_OK;
+    return nvsr_render_pass_backward_rows_limb_launch(arith == NVSR_ARITH_F16X2 ? 2 : 3, scene, packed_decoder, packed_bwd, N, S, rays, z, g_raw, gates,
+                                                      rows, view_ws, record, stream);
+}
+
+int nvsr_view_rows_reduce(int64_t N, int S, const float* view_ws, float* view_rows, nvsr_stream_t stream) {
+    if (!view_ws || !view_rows) return NVSR_ERR_NULL;
+    if (N < 0 || S < 1 || S > 4096 || N * (int64_t)C >= (int64_t)1 << 31) return NVSR_ERR_SHAPE;
+    if (N == 0) return NVSR_OK;
+    hipLaunchKernelGGL(view_rows_reduce_kernel, dim3((unsigned)((N * C + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (long)N, (S + 31) / 32, view_ws,
+                       view_rows);
+    return NVSR_CHECK_LAUNCH();
 }
 
 int nvsr_render_pass_backward(const nvsr_scene* scene, const float* packed_decoder, const float* packed_bwd, int64_t N, int S,

@@ -184,7 +184,10 @@ __device__ __forceinline__ void limb_mm2(const unsigned* wl, int lane, f32x16 (&
     }
 }
 
-template <bool RECORD, int LF = 3>
+// ROWS (the deterministic route): gp.p[d], d < 3, is not a gradient plane but the row buffer rows[d][N * S][48] of plane d -- the
+// tile's feature gradients are stored there as they are (store_plane_rows: no atomics, no plane touched; NULL = that plane is frozen) and
+// nvsr_rows_scatter adds them into the plane in a fixed order; gp.p[3] only says whether the view plane's per-tile rows (gview) are wanted.
+template <bool RECORD, int LF = 3, bool ROWS = false>
 __global__ __launch_bounds__(BL_TPB, BL_WG_PER_CU) void render_pass_backward_gates_limb_kernel(SceneDev sc, const float* __restrict__ packed,
                                                                                    const float* __restrict__ packed_bwd, long N, int S,
                                                                                    const float* __restrict__ rays, const float* __restrict__ z,
@@ -307,12 +310,8 @@ __global__ __launch_bounds__(BL_TPB, BL_WG_PER_CU) void render_pass_backward_gat
 #endif
         // ... and the taps of a plane, from the ray
         auto pos_taps = [&](int d) {
-            const float n0 = norm_coord(__fadd_rn(r[0], __fmul_rn(r[3], zc)), sc.lo[0], sc.range[0]);
-            const float n1 = norm_coord(__fadd_rn(r[1], __fmul_rn(r[4], zc)), sc.lo[1], sc.range[1]);
-            const float n2 = norm_coord(__fadd_rn(r[2], __fmul_rn(r[5], zc)), sc.lo[2], sc.range[2]);
-            const float* M = sc.proj + 6 * d;
             int ix, iy;
-            Taps t = make_taps_cell(sc, d, n0 * M[0] + n1 * M[2] + n2 * M[4], n0 * M[1] + n1 * M[3] + n2 * M[5], ix, iy);
+            Taps t = ray_pos_taps(sc, r, zc, d, ix, iy);
 #if BL_SCATTER >= 2
             t.o00 |= (ix & 1) | ((iy & 1) << 1);             // the cell's parity rides in the low bits (scatter_plane_cached)
 #endif
@@ -453,6 +452,11 @@ __global__ __launch_bounds__(BL_TPB, BL_WG_PER_CU) void render_pass_backward_gat
                         gview[wt * C + lane] = (v0 + v1) + (v2 + v3);            // wt = ray * nsc + chunk
                     }
                     __builtin_amdgcn_wave_barrier();
+                } else if constexpr (ROWS) {
+                    if (d < 3) {
+                        const int c0 = (int)(wt - ray0 * nsc) * 32;              // the tile's points are rows ray0 * S + c0 .. of rows[d]
+                        store_plane_rows(gF, tile, gp.p[d], ray0 < N ? ray0 * S + c0 : 0, ray0 < N ? (S - c0 < 32 ? S - c0 : 32) : 0, lane);
+                    }
                 } else {
                     const Taps t = (d < 3) ? pos_taps(d) : view_taps(sc, r[8], r[9], r[10]);
 #if BL_SCATTER == 3
@@ -583,5 +587,28 @@ extern "C" int nvsr_render_pass_backward_gates_limb_launch(int limbs, const nvsr
     else
         hipLaunchKernelGGL(render_pass_backward_gates_limb_kernel<false>, dim3((unsigned)grid), dim3(BL_TPB), 0, (hipStream_t)stream, to_dev(scene),
                            packed_decoder, packed_bwd, (long)N, S, rays, z, g_raw, gates, gp, view_ws, DecRecord{});
+    return NVSR_CHECK_LAUNCH();
+}
+
+// the same launch with the ROWS variant of the kernel (deterministic route): rows[d] instead of gradient planes; arguments validated by
+// nvsr_render_pass_backward_rows_arith (render_bwd.hip)
+extern "C" int nvsr_render_pass_backward_rows_limb_launch(int limbs, const nvsr_scene* scene, const float* packed_decoder, const float* packed_bwd,
+                                                          int64_t N, int S, const float* rays, const float* z, const float* g_raw,
+                                                          const uint32_t* gates, float* const* rows, float* view_ws, float* record,
+                                                          nvsr_stream_t stream) {
+    GradPlanes gp;
+    for (int d = 0; d < 3; ++d) gp.p[d] = rows ? rows[d] : nullptr;
+    gp.p[3] = view_ws;                                          // (wanted or not; the rows themselves go to view_ws)
+    const int64_t ntiles = (N * (int64_t)((S + 31) / 32) + BL_WAVES - 1) / BL_WAVES;
+    const int64_t grid = ntiles < 2048 ? ntiles : 2048;
+    const DecRecord rec = record ? make_record(record, (long)N, S) : DecRecord{};
+#define NVSR_ROWS_LAUNCH(REC, LF_)                                                                                                              \
+    hipLaunchKernelGGL((render_pass_backward_gates_limb_kernel<REC, LF_, true>), dim3((unsigned)grid), dim3(BL_TPB), 0, (hipStream_t)stream,   \
+                       to_dev(scene), packed_decoder, packed_bwd, (long)N, S, rays, z, g_raw, gates, gp, view_ws, rec)
+    if (limbs == 2 && !record) NVSR_ROWS_LAUNCH(false, 2);
+    else if (limbs == 2) NVSR_ROWS_LAUNCH(true, 2);
+    else if (record) NVSR_ROWS_LAUNCH(true, 3);
+    else NVSR_ROWS_LAUNCH(false, 3);
+#undef NVSR_ROWS_LAUNCH
     return NVSR_CHECK_LAUNCH();
 }

@@ -811,6 +811,9 @@ class _DecodePointsFn(torch.autograd.Function):
         ctx.plane_srcs = (p0, p1, p2, pv)
         planes_cl, consts = model.scene_args(planes=planes_cl)
         arith = capi.resolve_decoder_arithmetic(model.arithmetic)      # the backward runs in the mode the gates / record were made in
+        ctx.det = capi.deterministic()                                  # ... and on the route (atomic / ordered) resolved here
+        if ctx.det and arith == capi.ARITHMETIC["f32"]:
+            capi.refuse_deterministic("a differentiable model call in the 'f32' arithmetic")
         raw, gates, rec = torch.ops.nvsr.decode_rays(planes_cl, consts, model.packed_decoder(), rays, z, True, nat is not None, arith)
         ctx.model, ctx.state = model, (planes_cl, consts, rays, z, gates, rec if nat is not None else None, arith)
         return raw.reshape(P, 4)
@@ -825,9 +828,11 @@ class _DecodePointsFn(torch.autograd.Function):
         if not any(need_planes) and rec is None:
             return (None,) * 7
         g_raw = capi.f32c(g_out).reshape(P, 1, 4)
-        gplanes = torch.ops.nvsr.decode_rays_backward(planes_cl, consts, model.packed_decoder(), model.packed_decoder_bwd(), rays, z, g_raw, gates,
-                                                      rec, need_planes, arith)
-        gnat = torch.ops.nvsr.decoder_weight_grad(rec, P, 1, arith) if (rec is not None and need[6]) else None
+        nv = torch.ops.nvsr
+        bwd, wgrad = ((nv.decode_rays_backward_det, lambda *a: nv.decoder_weight_grad_det(*a, None)) if ctx.det else
+                      (nv.decode_rays_backward, nv.decoder_weight_grad))
+        gplanes = bwd(planes_cl, consts, model.packed_decoder(), model.packed_decoder_bwd(), rays, z, g_raw, gates, rec, need_planes, arith)
+        gnat = wgrad(rec, P, 1, arith) if (rec is not None and need[6]) else None
         return (None, None) + tuple(from_channel_last(g, like=p_) if n else None for g, p_, n in zip(gplanes, ctx.plane_srcs, need_planes)) + (gnat,)
 
 
@@ -838,6 +843,8 @@ class _GenericDecodeFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, x, nat, coord_noise, *plane_srcs):
+        if capi.deterministic():
+            capi.refuse_deterministic("training a generic decoder geometry (generic.hip)")
         planes_cl = [to_channel_last(p.detach()) for p in plane_srcs]
         planes_cl, consts = model.scene_args(planes=planes_cl, check_native=False)
         natural = model.natural_blob() if nat is None else nat.detach()

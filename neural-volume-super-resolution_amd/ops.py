@@ -548,6 +548,8 @@ def decode_rays_backward_recompute(planes: Sequence[Tensor], consts: Sequence[fl
     """backward of a decode pass that recomputes the forward (exact-f32 kernel), RECORD_RAYS rays at a time: the memory-bounded path for
     decoder gradients of very large batches, and the path for passes that published no gates.
     -> [g_plane0..3 (empty where not needed), g_natural (empty unless want_decoder_grad)]"""
+    if capi.deterministic():
+        capi.refuse_deterministic("decode_rays_backward_recompute (the backward of a pass that published no gates)")
     rays, z, g_raw = _c(rays), _c(z), _c(g_raw)
     sc = _scene(planes, consts)
     N, S = z.shape
@@ -577,6 +579,131 @@ def decode_rays_backward_recompute(planes: Sequence[Tensor], consts: Sequence[fl
 def _(planes, consts, packed, packed_bwd, rays, z, g_raw, need, want_decoder_grad, arithmetic):
     return [torch.empty_like(p) if need[d] else rays.new_empty((0,)) for d, p in enumerate(planes)] + \
         [rays.new_empty((capi.DECODER_NATURAL_FLOATS if want_decoder_grad else 0,))]
+
+
+# =====================================================================================================================================
+# the deterministic route (capi.deterministic): the same gradients in a fixed order, for the limb arithmetics
+# =====================================================================================================================================
+def _require_limb_arithmetic(arithmetic, who):
+    if capi.resolve_decoder_arithmetic(None if arithmetic == capi.ARITH_INHERIT else arithmetic) == capi.ARITHMETIC["f32"]:
+        capi.refuse_deterministic("%s in the 'f32' arithmetic" % who)
+
+
+def rows_scatter_workspace(M, like):
+    """an uninitialised workspace for rows_scatter of M rows"""
+    return torch.empty(capi.lib().nvsr_rows_scatter_workspace_bytes(int(M)), dtype=torch.uint8, device=like.device)
+
+
+@custom_op("nvsr::rows_scatter", mutates_args=("g", "workspace"), device_types="cuda")
+def rows_scatter(rows: Tensor, texel: Tensor, weight: Tensor, g: Tensor, workspace: Optional[Tensor]) -> None:
+    """ordered scatter (include/nvsr.h, nvsr_rows_scatter): rows [M,48] f32, texel [M,4] int32, weight [M,4] f32 are ADDED into the
+    channel-last plane g [H,W,48]: per texel the entries e = 4 m + j that name it are summed in ascending e from +0.0f, the sum is added to
+    g once; a texel no entry names keeps its bits.  workspace: uint8, at least nvsr_rows_scatter_workspace_bytes(M), or None (allocated
+    here); always passed (torch's bookkeeping of a mutated argument indexes it by position)."""
+    M = rows.shape[0]
+    capi.require_cuda(rows, texel, weight, g)
+    if not (rows.dtype == weight.dtype == g.dtype == torch.float32 and texel.dtype == torch.int32 and rows.is_contiguous() and texel.is_contiguous()
+            and weight.is_contiguous() and g.is_contiguous() and rows.shape == (M, PC) and texel.shape == (M, 4) and weight.shape == (M, 4)
+            and g.dim() == 3 and g.shape[2] == PC):
+        raise ValueError("rows_scatter: rows [M,%d] f32, texel [M,4] int32, weight [M,4] f32, g [H,W,%d] f32, all contiguous" % (PC, PC))
+    if M == 0:
+        return
+    ws = rows_scatter_workspace(M, rows) if workspace is None else workspace
+    capi.call("nvsr_rows_scatter", M, capi.ptr(rows), capi.ptr(texel), capi.ptr(weight), g.shape[0], g.shape[1], capi.ptr(g), capi.ptr(ws),
+              ws.numel() * ws.element_size(), capi.stream())
+
+
+@rows_scatter.register_fake
+def _(rows, texel, weight, g, workspace):
+    return None
+
+
+def _decode_rays_backward_det_launch(planes, consts, packed, packed_bwd, rays, z, g_raw, gates, record, need, arithmetic, grads):
+    """the gate-driven backward ADDING into `grads` in a fixed order: rows backward, then per wanted position plane taps + ordered scatter,
+    then the view plane (reduce-only kernel, taps per ray, ordered scatter with M = N).  One stream, in this order."""
+    _require_limb_arithmetic(arithmetic, "the gate-driven backward")
+    rays, z, g_raw = _c(rays), _c(z), _c(g_raw)
+    sc = _scene(planes, consts)
+    N, S = z.shape
+    if N == 0 or (not any(need) and record is None):
+        return
+    M, st = N * S, capi.stream()
+    rows = [_f(M, PC, like=rays) if need[d] else None for d in range(3)]
+    rptrs = (C.c_void_p * 3)(*[None if r is None else r.data_ptr() for r in rows]) if any(need[:3]) else None
+    view_ws = _f(capi.lib().nvsr_view_grad_workspace_floats(N, S), like=rays) if need[3] else None
+    capi.call("nvsr_render_pass_backward_rows_arith", C.byref(sc), capi.ptr(packed), capi.ptr(packed_bwd), N, S, capi.ptr(rays), capi.ptr(z),
+              capi.ptr(g_raw), capi.ptr(gates), rptrs, capi.ptr(view_ws), capi.ptr(record), arithmetic, st)
+    if not any(need):
+        return
+    texel = torch.empty((M, 4), dtype=torch.int32, device=rays.device)
+    weight = _f(M, 4, like=rays)
+    ws = rows_scatter_workspace(M, rays)
+    for d in range(3):
+        if need[d]:
+            capi.call("nvsr_internal_plane_taps", C.byref(sc), d, N, S, capi.ptr(rays), capi.ptr(z), capi.ptr(texel), capi.ptr(weight), st)
+            capi.call("nvsr_rows_scatter", M, capi.ptr(rows[d]), capi.ptr(texel), capi.ptr(weight), planes[d].shape[0], planes[d].shape[1],
+                      capi.ptr(grads[d]), capi.ptr(ws), ws.numel(), st)
+    if need[3]:
+        view_rows = _f(N, PC, like=rays)
+        capi.call("nvsr_view_rows_reduce", N, S, capi.ptr(view_ws), capi.ptr(view_rows), st)
+        capi.call("nvsr_internal_plane_taps", C.byref(sc), 3, N, S, capi.ptr(rays), None, capi.ptr(texel), capi.ptr(weight), st)
+        capi.call("nvsr_rows_scatter", N, capi.ptr(view_rows), capi.ptr(texel), capi.ptr(weight), planes[3].shape[0], planes[3].shape[1],
+                  capi.ptr(grads[3]), capi.ptr(ws), ws.numel(), st)
+
+
+@custom_op("nvsr::decode_rays_backward_det", mutates_args=("record",), device_types="cuda")
+def decode_rays_backward_det(planes: Sequence[Tensor], consts: Sequence[float], packed: Tensor, packed_bwd: Tensor, rays: Tensor, z: Tensor,
+                             g_raw: Tensor, gates: Tensor, record: Optional[Tensor], need: Sequence[bool], arithmetic: int) -> List[Tensor]:
+    """decode_rays_backward without float atomics: the same gradient planes, every texel summed in a fixed order (two calls on the same inputs
+    return the same bits).  Limb arithmetics only ('f32' raises)."""
+    _require_limb_arithmetic(arithmetic, "decode_rays_backward_det")
+    grads = [torch.zeros_like(p) if need[d] else _f(0, like=rays) for d, p in enumerate(planes)]
+    _decode_rays_backward_det_launch(planes, consts, packed, packed_bwd, rays, z, g_raw, gates, record, need, arithmetic, grads)
+    return grads
+
+
+@decode_rays_backward_det.register_fake
+def _(planes, consts, packed, packed_bwd, rays, z, g_raw, gates, record, need, arithmetic):
+    return [torch.empty_like(p) if need[d] else rays.new_empty((0,)) for d, p in enumerate(planes)]
+
+
+@custom_op("nvsr::decode_rays_backward_det_", mutates_args=("record", "grads"), device_types="cuda")
+def decode_rays_backward_det_(planes: Sequence[Tensor], consts: Sequence[float], packed: Tensor, packed_bwd: Tensor, rays: Tensor, z: Tensor,
+                              g_raw: Tensor, gates: Tensor, record: Optional[Tensor], need: Sequence[bool], arithmetic: int,
+                              grads: Sequence[Tensor]) -> None:
+    """decode_rays_backward_det ACCUMULATING into existing gradient planes: every texel this pass touches receives g + s, s being the sum
+    the functional form would have returned for it -- pass 2 onto pass 1's planes equals the sum of the two functional results bit for bit."""
+    _require_limb_arithmetic(arithmetic, "decode_rays_backward_det_")
+    for d, (g, p) in enumerate(zip(grads, planes)):
+        if need[d] and (g.shape != p.shape or not g.is_contiguous() or g.dtype != torch.float32 or not g.is_cuda):
+            raise ValueError("decode_rays_backward_det_: grads[%d] must be a contiguous float32 CUDA tensor shaped like planes[%d]" % (d, d))
+    _decode_rays_backward_det_launch(planes, consts, packed, packed_bwd, rays, z, g_raw, gates, record, need, arithmetic, grads)
+
+
+@decode_rays_backward_det_.register_fake
+def _(planes, consts, packed, packed_bwd, rays, z, g_raw, gates, record, need, arithmetic, grads):
+    return None
+
+
+@custom_op("nvsr::decoder_weight_grad_det", mutates_args=("workspace",), device_types="cuda")
+def decoder_weight_grad_det(record: Tensor, N: int, S: int, arithmetic: int, workspace: Optional[Tensor]) -> Tensor:
+    """decoder_weight_grad without float atomics: every slab of rows writes its partial blob into the workspace (f32, at least
+    nvsr_decoder_weight_grad_det_workspace_floats(N, S), or None: allocated here; always passed), a reduce kernel adds the slabs in
+    ascending order."""
+    _require_limb_arithmetic(arithmetic, "decoder_weight_grad_det")
+    gnat = torch.zeros(capi.DECODER_NATURAL_FLOATS, dtype=torch.float32, device=record.device)
+    if N:
+        need = capi.lib().nvsr_decoder_weight_grad_det_workspace_floats(N, S)
+        ws = _f(need, like=record) if workspace is None else workspace
+        if ws.dtype != torch.float32 or ws.numel() < need or not ws.is_contiguous():
+            raise ValueError("decoder_weight_grad_det: workspace must hold %d contiguous float32" % need)
+        capi.call("nvsr_decoder_weight_grad_det_arith", N, S, capi.ptr(record), capi.ptr(gnat), capi.ptr(ws), arithmetic, capi.stream())
+    return gnat
+
+
+@decoder_weight_grad_det.register_fake
+def _(record, N, S, arithmetic, workspace):
+    return record.new_empty((capi.DECODER_NATURAL_FLOATS,))
 
 
 @custom_op("nvsr::decoder_weight_grad", mutates_args=(), device_types="cuda")

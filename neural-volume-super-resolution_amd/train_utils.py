@@ -156,6 +156,7 @@ class _RenderRaysFn(torch.autograd.Function):
         need_planes_c = [bool(n) for n in need[7:11]] if sep else need_planes_f
         gplanes_f = [None, None, None, None]
         gplanes_c = [None, None, None, None] if sep else gplanes_f
+        det = bool(cfg.get("det"))
 
         def one_pass(S, z, raw, noise, planes, packed, packed_bwd, g_rgb, g_disp, g_acc, disp, acc, want_dec, gates, fwd_rec, arith, need_planes, gplanes):
             """-> decoder gradient of this pass (state-dict order) or None; plane gradients are added into `gplanes`"""
@@ -183,15 +184,20 @@ class _RenderRaysFn(torch.autograd.Function):
                         if need_planes[d]:
                             gplanes[d] = g
                     have = [True] * len(have)
+                # deterministic mode (capi.deterministic, resolved by the forward): the ordered operators -- same arguments, no float atomics
+                bwd_, bwd, wgrad = ((nv.decode_rays_backward_det_, nv.decode_rays_backward_det, lambda *a: nv.decoder_weight_grad_det(*a, None))
+                                    if det else (nv.decode_rays_backward_, nv.decode_rays_backward, nv.decoder_weight_grad))
                 if have and all(have) and all(gplanes[d].shape == planes[d].shape and gplanes[d].stride() == planes[d].stride()
                                               for d in range(4) if need_planes[d]):
                     # a second pass over the same planes scatters into the first pass's gradient planes (no second zero-fill, no add)
-                    nv.decode_rays_backward_(planes, cfg["consts"], packed, packed_bwd, rays, z, g_raw, gates, rec, need_planes, arith,
-                                             [g if g is not None else rays.new_empty((0,)) for g in gplanes])
+                    bwd_(planes, cfg["consts"], packed, packed_bwd, rays, z, g_raw, gates, rec, need_planes, arith,
+                         [g if g is not None else rays.new_empty((0,)) for g in gplanes])
                 else:
-                    add_planes(nv.decode_rays_backward(planes, cfg["consts"], packed, packed_bwd, rays, z, g_raw, gates, rec, need_planes, arith))
-                return nv.decoder_weight_grad(fwd_rec, N, S, arith) if want_dec else None
+                    add_planes(bwd(planes, cfg["consts"], packed, packed_bwd, rays, z, g_raw, gates, rec, need_planes, arith))
+                return wgrad(fwd_rec, N, S, arith) if want_dec else None
             # no gates published (pass too large for a forward record): recompute the forward in the backward, RECORD_RAYS rays at a time
+            if det:
+                capi.refuse_deterministic("the recomputing backward of a pass without a forward record (decode_rays_backward_recompute)")
             _record_limits()
             out = nv.decode_rays_backward_recompute(planes, cfg["consts"], packed, packed_bwd, rays, z, g_raw, need_planes, want_dec, arith)
             add_planes(out[:4])
@@ -205,9 +211,10 @@ class _RenderRaysFn(torch.autograd.Function):
         # The two passes' backward kernels are independent (both ADD into the gradient planes with float atomics): the coarse pass runs on a
         # second stream, so that its workgroups fill the fine pass's partly empty rounds (same-box A/B of the planes-only iteration: eager
         # 1.683 -> 1.631 ms, replayed from a graph 1.728 -> 1.709 ms; NVSR_BWD_STREAMS=0 keeps one stream).  Planes-only passes: nothing
-        # allocated on the second stream outlives the join.
+        # allocated on the second stream outlives the join.  Deterministic mode: ONE stream, coarse then fine -- the fine pass adds onto the
+        # coarse pass's sums, and that order is part of the result's bits.
         need_planes, gplanes = need_planes_f, gplanes_f
-        two = (os.environ.get("NVSR_BWD_STREAMS", "1") == "1" and not sep and cfg["coarse_grad"] and Nf > 0 and dev.type == "cuda" and any(need_planes)
+        two = (not det and os.environ.get("NVSR_BWD_STREAMS", "1") == "1" and not sep and cfg["coarse_grad"] and Nf > 0 and dev.type == "cuda" and any(need_planes)
                and not need[5] and not need[6] and sv["gates_c"] is not None and sv["gates_f"] is not None
                and all(a.shape == b.shape and a.stride() == b.stride() for a, b in zip(cfg["planes_c"], cfg["planes_f"])))
         if two:
@@ -304,9 +311,10 @@ def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, sc
     for mdl in (model_coarse, model_fine):
         mdl.set_cur_scene_id(scene_id)
     if not (model_coarse.is_native_geometry() and (Nf <= 0 or model_fine.is_native_geometry())):
+        if mode == "train" and torch.is_grad_enabled() and capi.deterministic() and any(
+                _planes_need_grad(mdl) or _decoder_needs_grad(mdl) for mdl in (model_coarse, model_fine)):
+            capi.refuse_deterministic("training a generic decoder geometry (generic.hip)")
         return _render_generic(rays, model_coarse, model_fine, m, Nc, Nf, t_rand, u, n_c, n_f, jit_c, jit_f)
-    packed_c = model_coarse.packed_decoder()
-    packed_f = model_fine.packed_decoder() if Nf > 0 else None
     top = model_fine if Nf > 0 else model_coarse
     dec_c_grad = _decoder_needs_grad(model_coarse)
     dec_f_grad = Nf > 0 and _decoder_needs_grad(model_fine)
@@ -314,6 +322,22 @@ def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, sc
     sr_grad = sr_on and torch.is_grad_enabled() and top.SR_model.training and \
         top.SR_model.inner_model.wants_grad(*top.SR_model.LR_planes.values())
     train_path = mode == "train" and N > 0 and (_planes_need_grad(top) or dec_c_grad or dec_f_grad or sr_grad)
+    # (an evaluation render whose operands leave the f16 limbs' range is found by the library's range flag and rendered again with
+    #  force_arith = bf16x3: run_one_iter_of_nerf; a training step raises: training.TrainStep)
+    arith_c = capi.resolve_decoder_arithmetic(model_coarse.arithmetic if force_arith is None else force_arith)
+    arith_f = capi.resolve_decoder_arithmetic(model_fine.arithmetic if force_arith is None else force_arith) if Nf > 0 else arith_c
+    det = train_path and capi.deterministic()
+    if det:
+        # what the deterministic mode does not cover is refused here, before anything is launched
+        for a_ in {arith_c, arith_f}:
+            if a_ == capi.ARITHMETIC["f32"]:
+                capi.refuse_deterministic("a training step in the 'f32' arithmetic")
+        _, fwd_max = _record_limits()
+        if (dec_c_grad and N * Nc > fwd_max) or (dec_f_grad and N * (Nc + Nf) > fwd_max):
+            capi.refuse_deterministic("a pass of more than RECORD_FORWARD_MAX_POINTS points with decoder gradients (its backward recomputes the "
+                                      "forward: decode_rays_backward_recompute)")
+    packed_c = model_coarse.packed_decoder()
+    packed_f = model_fine.packed_decoder() if Nf > 0 else None
     if not (train_path and sr_on):       # (the SR training path builds its scene from the ROI planes below)
         planes_c, consts = model_coarse.scene_args()
         if Nf > 0:
@@ -322,10 +346,6 @@ def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, sc
             same = all(a.data_ptr() == b.data_ptr() for a, b in zip(planes_c, planes_f))
         else:
             planes_f, same = planes_c, True
-    # (an evaluation render whose operands leave the f16 limbs' range is found by the library's range flag and rendered again with
-    #  force_arith = bf16x3: run_one_iter_of_nerf; a training step raises: training.TrainStep)
-    arith_c = capi.resolve_decoder_arithmetic(model_coarse.arithmetic if force_arith is None else force_arith)
-    arith_f = capi.resolve_decoder_arithmetic(model_fine.arithmetic if force_arith is None else force_arith) if Nf > 0 else arith_c
     white, lindisp = bool(m.white_background), bool(m.lindisp)
 
     if train_path:
@@ -357,7 +377,7 @@ def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, sc
                    packed_bwd_c=model_coarse.packed_decoder_bwd(), packed_bwd_f=model_fine.packed_decoder_bwd() if Nf > 0 else None,
                    plane_shapes=[tuple(k.shape) for k in planes_f], plane_leaves=leaves[:4], separate_coarse=bool(leaves_c),
                    plane_shapes_c=[tuple(k.shape) for k in planes_c], plane_leaves_c=leaves_c, coarse_grad=coarse_grad, dec_c_grad=dec_c_grad,
-                   dec_f_grad=dec_f_grad, arith_c=arith_c, arith_f=arith_f)
+                   dec_f_grad=dec_f_grad, arith_c=arith_c, arith_f=arith_f, det=det)
         outs = _RenderRaysFn.apply(cfg, *leaves)
         if Nf > 0:
             return outs[0], outs[1], outs[2], outs[3], outs[4], outs[5], None, None, None

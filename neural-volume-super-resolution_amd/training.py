@@ -312,13 +312,19 @@ class TrainStep:
     what2train  subset of {'LR_planes', 'decoder', 'SR'} (cfg.nerf.train.what, train_nerf.py:75-77)
     optimizer   decoder optimizer or None;  SR_optimizer or None;  planes_optimizer: any object with zero_grad() / step() (the
                 reference's PlanesOptimizer, or a torch optimizer over the plane parameters) or None
-    sr_loss     cfg.super_resolution.training.loss in {'both', 'fine', 'coarse'} (:885,:889)"""
+    sr_loss     cfg.super_resolution.training.loss in {'both', 'fine', 'coarse'} (:885,:889)
+    deterministic  True / False: the deterministic mode of this step's iterations, whatever the environment says; None: as
+                capi.deterministic() resolves it at every iteration (NVSR_DETERMINISTIC=1, torch.use_deterministic_algorithms).  In the mode
+                the plane and decoder gradients are summed in a fixed order: two steps from the same state give the same
+                bits.  `step.deterministic` is what an iteration started now would run in.  'SR' in what2train is refused in the mode."""
 
     def __init__(self, model_coarse, model_fine, options, what2train, optimizer=None, SR_optimizer=None, planes_optimizer=None, SR_model=None,
                  virtual_batch_size=1, rendering_loss_w=1.0, im_inconsistency_loss_w=None, sr_loss="both", ds_factor=1,
-                 separate_decoder_sr=False, grad_sync=None, pixel_sampler=None):
+                 separate_decoder_sr=False, grad_sync=None, pixel_sampler=None, deterministic=None):
         self.mc, self.mf, self.options = model_coarse, model_fine, options
         self.what = set(what2train)
+        self._deterministic = None if deterministic is None else bool(deterministic)
+        self._refuse_undetermined()
         self.optimizer, self.SR_optimizer, self.planes_optimizer, self.SR_model = optimizer, SR_optimizer, planes_optimizer, SR_model
         self.vbs = max(1, int(virtual_batch_size))
         self.rendering_loss_w, self.im_inconsistency_loss_w = rendering_loss_w, im_inconsistency_loss_w
@@ -346,6 +352,20 @@ class TrainStep:
                 self._pending.popleft()._read()
         return m
 
+    @property
+    def deterministic(self):
+        """the mode an iteration started now runs in (the constructor's argument, else the environment, else torch's switch)"""
+        return capi.deterministic(self._deterministic)
+
+    def _refuse_undetermined(self):
+        if not self.deterministic:
+            return
+        if "SR" in self.what:
+            capi.refuse_deterministic("'SR' in what2train (the super-resolution network's plane gradients)")
+        for m in (self.mc, self.mf):
+            if m is not None and hasattr(m, "arithmetic") and capi.resolve_decoder_arithmetic(m.arithmetic) == capi.ARITHMETIC["f32"]:
+                capi.refuse_deterministic("a training step in the 'f32' arithmetic")
+
     def _range_word(self, device):
         if device.type != "cuda":
             return None
@@ -360,6 +380,13 @@ class TrainStep:
             im_consistency_iter=False, confinements=(), randoms=None):
         """the iteration itself -> (loss, rendering_loss, coarse_loss, fine_loss, with_psnr), device scalars (what __call__ wraps in StepMetrics);
         nothing here waits for the device or allocates host memory: GraphedTrainStep captures it into a HIP graph"""
+        self._refuse_undetermined()
+        with capi.deterministic_scope(self._deterministic):       # (forward AND backward of the iteration: apply_gradients runs in here)
+            return self._run(it, img_target, pose_target, H, W, focal, cur_ds_factor, scene_id, scene_config, num_random_rays, sr_iter,
+                             im_consistency_iter, confinements, randoms)
+
+    def _run(self, it, img_target, pose_target, H, W, focal, cur_ds_factor, scene_id, scene_config, num_random_rays, sr_iter, im_consistency_iter,
+             confinements, randoms):
         first_v, last_v = it % self.vbs == 0, it % self.vbs == self.vbs - 1
         if "SR" in self.what and self.SR_model is not None:
             self.SR_model.train()
@@ -569,6 +596,8 @@ class GraphedTrainStep:
 
     def __init__(self, step, img_target, pose_target, H, W, focal, cur_ds_factor, scene_id, scene_config, num_random_rays, randoms_fn=None,
                  generators=(), warmup=3, **step_kwargs):
+        if step.deterministic:
+            capi.refuse_deterministic("GraphedTrainStep (a captured iteration)")
         if step.grad_sync is not None:
             raise ValueError("GraphedTrainStep: a data-parallel step (grad_sync) would capture its all-reduces -- RCCL collectives, or the host-staged "
                              "gloo path, inside a HIP graph have never been run on this pool; launch the multi-rank iteration with TrainStep")

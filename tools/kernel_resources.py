@@ -25,6 +25,8 @@ BENCHMARKED = [
     "render_pass3_kernel", "render_pass3_coarse", "importance_resample", "ray_bundle_kernel", "pack_rays_kernel",
     "decode_rays_limb_kernel", "render_pass_backward_gates_limb_kernel", "composite_kernel", "composite_backward_kernel",
     "view_reduce_scatter", "decoder_wgrad_limb_kernel", "head_wgrad_kernel",
+    # the deterministic route (NVSR_DETERMINISTIC=1; the ROWS / DET variants of the kernels above match by name): its own kernels and rocPRIM's sort
+    "plane_taps_kernel", "rows_gather_kernel", "view_rows_reduce_kernel", "decoder_wgrad_reduce_kernel", "radix_sort_onesweep", "radix_sort_block_sort",
     "conv3x3_limb_kernel", "conv3x3_limb16_kernel", "conv3x3_wgrad_limb_kernel", "sr_prepare_kernel", "sr_finish_kernel",
 ]
 # The gate covers EVERY kernel of the library (round 4; round 3 covered the benchmarked ones): no scratch memory, no spilled VGPRs -- except:
