@@ -112,6 +112,9 @@ int nvsr_version(void);
 #define NVSR_ARITH_INVALID (-2)     /* what nvsr_get_*_arithmetic returns when the environment variable holds an unknown string: every call
                                        that inherits the process default then fails with NVSR_ERR_SHAPE until nvsr_set_*_arithmetic is called */
 #define NVSR_ARITH_F32 0
+#define NVSR_ARITH_F16 1            /* CONVOLUTIONS ONLY (below, "NVSR_ARITH_F16"): every decoder, render, NeRF-baseline, low-rank, occupancy and
+                                       deterministic-route entry point refuses it, and so do nvsr_set_decoder_arithmetic and
+                                       NVSR_DECODER_ARITHMETIC.  The value of a limb mode is its limb count. */
 #define NVSR_ARITH_F16X2 2
 #define NVSR_ARITH_BF16X3 3
 #define NVSR_ARITH_DEFAULT NVSR_ARITH_F16X2
@@ -125,7 +128,8 @@ int nvsr_set_decoder_arithmetic(int mode);
  * (models.py:395-421); this is what keeps the drop-in's default arithmetic from ever returning NaN where the reference returns a number.
  * NULL (the initial state) disables the reporting.  The pointer is process-global like the default arithmetic and is read when a launch is
  * enqueued; the word must stay allocated until every launch enqueued while it was registered has finished.  Modes other than F16X2 never
- * touch it (they have no range limit; a NaN they return was a NaN in their inputs). */
+ * touch it (they have no range limit; a NaN they return was a NaN in their inputs) -- except the convolutions' NVSR_ARITH_F16, which shares
+ * F16X2's ranges and raises bit 2 like it. */
 int nvsr_set_range_flag(uint32_t* device_word);
 uint32_t* nvsr_get_range_flag(void);
 /* The two-phase render pass.  A fused limb pass (NVSR_ARITH_BF16X3 / _F16X2, N >= nvsr_fused_min_rays) whose caller does not ask for the
@@ -273,7 +277,25 @@ int nvsr_limb_gemm_probe(int arithmetic, int K, const float* W, const float* X, 
  * [2^12, 2^13) in place of the static activation scale (one reduction per layer: gradients span many decades from layer to layer and step to
  * step, a tensor's values a few) and their weight gradients (X with the static scale, dy with its tensor's); the narrow input / output layers run
  * 3 bf16 limbs in that mode.
- * Environment: NVSR_CONV_ARITHMETIC = f32 | bf16x3 | f16x2. */
+ *   NVSR_ARITH_F16 -- mixed precision, opt-in, convolutions only: both operands rounded ONCE to f16, f32 accumulation, f32 storage (activations,
+ * gradients and master weights stay f32 in memory).  The same layers, launches, scales and order of work as NVSR_ARITH_F16X2 with the high
+ * limb alone: one v_mfma_f32_16x16x32_f16 per product block on w^ = RN_f16(w 2^8) -- limb 0 of F16X2's packed fragments: packing "for F16"
+ * packs what packing for F16X2 packs, and the packed sizes do not change -- and x^ = RN_f16(x s), s = 2^4 for activations and the
+ * [2^12, 2^13) power of two of its tensor for a data-gradient input and for the dy operand of a weight gradient (X at 2^4); the scales are
+ * undone where F16X2 undoes them.  The narrow layers (conv_input, conv_output, any shape outside Cin % 32 == 0 and Cout % 128 == 0) run
+ * what they run under F16X2, weight gradients included -- inside a network (the EDSR / PlanesSR entry points) and under an inherited
+ * default; the single-layer entry points nvsr_conv3x3[_dgrad|_wgrad]_arith given NVSR_ARITH_F16 by name for such a shape return
+ * NVSR_ERR_SHAPE (the layer has no one-limb kernel: a missing kernel is an error, not another arithmetic).
+ *   Error model: w^ and x^ are exact inputs of the MFMA and their products are exact in f32, so the only further error is the f32 accumulation
+ * of n products, in whatever order:
+ *       |y - (sum w^ x^) / (2^8 s)|  <=  1.01 n 2^-24 (sum |w^||x^|) / (2^8 s)
+ * with n = 9 Cin for a convolution or data gradient and n = the contracted pixels over all planes of the launch for a weight gradient.  Against
+ * the true f32 operands the mode adds at most (2^-10 + 2^-22) sum |w||x| while both are in the normal f16 range -- the price of choosing it.
+ *   Range contract: exactly F16X2's.  |W| < 255 and |x| < 4094 (a lone limb overflows to inf where F16X2's high limb does); beyond, the
+ * outputs the operand reaches are NaN -- never a wrong number: F16X2's inf meets the -inf of its own low limb, a lone inf would give +-inf
+ * (and 0 behind a ReLU), so the kernels write an infinite accumulator as NaN (finite operands cannot produce one) -- an out-of-range weight
+ * poisons its outputs, and the PlanesSR entry points raise bit 2 of the range flag (nvsr_set_range_flag) as they do under F16X2.
+ * Environment: NVSR_CONV_ARITHMETIC = f32 | bf16x3 | f16x2 | f16. */
 #define NVSR_CONV_ARITH_DEFAULT NVSR_ARITH_F16X2
 int nvsr_get_conv_arithmetic(void);
 int nvsr_set_conv_arithmetic(int mode);
@@ -741,7 +763,8 @@ int nvsr_ray_points(int64_t N, int S, const float* rays, const float* z, float* 
 
 /* ---- per-call arithmetic -----------------------------------------------------------------------------------------------------
  * Twins of the entry points above that run decoder GEMMs or SR convolutions, with the arithmetic as an explicit argument
- * (NVSR_ARITH_F32 | NVSR_ARITH_BF16X3 | NVSR_ARITH_F16X2 | NVSR_ARITH_INHERIT).  Same arguments, same
+ * (NVSR_ARITH_F32 | NVSR_ARITH_BF16X3 | NVSR_ARITH_F16X2 | NVSR_ARITH_INHERIT; the convolution, EDSR and PlanesSR families -- nvsr_conv3x3*_arith,
+ * nvsr_edsr_*_arith, nvsr_planes_sr*_arith and their batch forms, nvsr_pack_edsr[_dgrad]_arith -- also NVSR_ARITH_F16).  Same arguments, same
  * semantics; the un-suffixed entry points are these called with NVSR_ARITH_INHERIT.  A backward call must be given the mode of the
  * forward whose gates / record / activations it consumes (the host mirror stores it with the autograd context).
  * rows_per_tile (convolutions): 0 = the launcher's choice, 2 | 3 | 4 = force that row-tile instantiation of the wide kernels (two output
@@ -749,7 +772,8 @@ int nvsr_ray_points(int64_t N, int S, const float* rays, const float* z, float* 
  * bits), 16 = the bf16-limb kernel on v_mfma_f32_16x16x32_bf16 (round 3; layers with Cin % 32 == 0 and Cout % 128 == 0 only, their default:
  * the K dimension of an instruction spans 32 input channels, so the f32 accumulation order -- not the limb products -- differs from the
  * other instantiations; same tolerance against the oracle), 18 | 19 | 20 = that kernel with 2 | 3 | 4 rows forced, 22 = its 6-row tile
- * (NVSR_ARITH_F16X2 only)
+ * (NVSR_ARITH_F16X2 and NVSR_ARITH_F16 only; NVSR_ARITH_F16 runs its one-limb kernel at 0 | 16 | 18 | 19 | 20 | 22 and, like F16X2, bf16
+ * limbs at 2 | 3 | 4 | 8)
  * (the results are identical; the parity tests force every instantiation). */
 int nvsr_render_pass_arith(const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays, const float* z,
                            const float* noise, int white_bkgd, float* rgb, float* disp, float* acc, float* weights, float* depth,

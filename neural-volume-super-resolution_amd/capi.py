@@ -267,6 +267,9 @@ _lib = None
 
 
 ARITHMETIC = {"f32": 0, "f16x2": 2, "bf16x3": 3}
+# the SR convolutions also take 'f16' (include/nvsr.h NVSR_ARITH_F16: operands rounded once to f16, f32 accumulation; opt-in); every decoder,
+# render and baseline call refuses it, so ARITHMETIC -- which tools and tests index for those calls -- does not list it
+CONV_ARITHMETIC = {**ARITHMETIC, "f16": 1}
 SR_BATCH_MAX = 4          # planes per nvsr_planes_sr_*_batch_arith call (csrc/sr_core.h CONV_RAGGED_MAX)
 ARITH_INHERIT = -1
 
@@ -296,8 +299,13 @@ def resolve_nerf_arithmetic(mode=None):
     return ARITHMETIC["bf16x3"] if code == ARITHMETIC["f16x2"] else code
 
 
+def conv_arith_code(mode):
+    """arith_code for the convolution, EDSR and PlanesSR entry points: also 'f16'"""
+    return CONV_ARITHMETIC[mode] if isinstance(mode, str) else arith_code(mode)
+
+
 def resolve_conv_arithmetic(mode=None):
-    code = arith_code(mode)
+    code = conv_arith_code(mode)
     return lib().nvsr_get_conv_arithmetic() if code == ARITH_INHERIT else code
 
 
@@ -312,13 +320,13 @@ def get_decoder_arithmetic():
 
 
 def set_conv_arithmetic(mode):
-    """Arithmetic of the wide 3x3 conv layers of the SR network: 'f32' | 'bf16x3' | 'f16x2' (forward convolutions, data and weight gradients; a
-    gradient tensor is scaled by the power of two of its largest magnitude)."""
-    call("nvsr_set_conv_arithmetic", ARITHMETIC[mode])
+    """Arithmetic of the wide 3x3 conv layers of the SR network: 'f32' | 'bf16x3' | 'f16x2' | 'f16' (forward convolutions, data and weight
+    gradients; a gradient tensor is scaled by the power of two of its largest magnitude)."""
+    call("nvsr_set_conv_arithmetic", CONV_ARITHMETIC[mode])
 
 
 def get_conv_arithmetic():
-    return {v: k for k, v in ARITHMETIC.items()}[lib().nvsr_get_conv_arithmetic()]
+    return {v: k for k, v in CONV_ARITHMETIC.items()}[lib().nvsr_get_conv_arithmetic()]
 
 
 _det_scope = []
@@ -421,10 +429,11 @@ def lib():
         for name, (args, res) in {**_PROTOS, **_PROTOS_OPTIONAL, **_PROTOS_LAUNCH}.items():
             fn = getattr(_lib, name)
             fn.argtypes, fn.restype = args, res
-        for var, get in (("NVSR_DECODER_ARITHMETIC", _lib.nvsr_get_decoder_arithmetic), ("NVSR_CONV_ARITHMETIC", _lib.nvsr_get_conv_arithmetic)):
-            if get() not in ARITHMETIC.values():          # (NVSR_ARITH_INVALID: an unknown string must not quietly select the default)
+        for var, get, modes in (("NVSR_DECODER_ARITHMETIC", _lib.nvsr_get_decoder_arithmetic, ARITHMETIC),
+                                ("NVSR_CONV_ARITHMETIC", _lib.nvsr_get_conv_arithmetic, CONV_ARITHMETIC)):
+            if get() not in modes.values():          # (NVSR_ARITH_INVALID: an unknown string must not quietly select the default)
                 bad, _lib = _lib, None
-                raise NvsrError("%s=%r is not one of %s" % (var, os.environ.get(var), " | ".join(ARITHMETIC)))
+                raise NvsrError("%s=%r is not one of %s" % (var, os.environ.get(var), " | ".join(modes)))
     return _lib
 
 

@@ -32,10 +32,11 @@ typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
 // side-work lambdas take their step index as an argument and use it as a register index or an instruction immediate: they must be inlined
 // whatever their size (left to its cost model, the inliner keeps the larger ones as calls and the index stops being a constant)
 #define NVSR_INL __attribute__((always_inline))
-NVSR_CX int limb_products(int limbs) { return limbs == 3 ? 6 : 3; }
+// (limbs == 1: the lone f16 limb of the SR convolutions' NVSR_ARITH_F16 -- one product, limb 0 of both operands)
+NVSR_CX int limb_products(int limbs) { return limbs == 3 ? 6 : limbs == 1 ? 1 : 3; }
 // product p of a (weight limb, activation limb) set, small terms first
-NVSR_CX int limb_w(int limbs, int p) { return limbs == 3 ? (p < 3 ? 0 : p < 5 ? 1 : 2) : (p < 2 ? 0 : 1); }
-NVSR_CX int limb_x(int limbs, int p) { return limbs == 3 ? (p == 0 ? 2 : p == 1 ? 1 : p == 2 ? 0 : p == 3 ? 1 : 0) : (p == 0 ? 1 : 0); }
+NVSR_CX int limb_w(int limbs, int p) { return limbs == 3 ? (p < 3 ? 0 : p < 5 ? 1 : 2) : limbs == 1 ? 0 : (p < 2 ? 0 : 1); }
+NVSR_CX int limb_x(int limbs, int p) { return limbs == 3 ? (p == 0 ? 2 : p == 1 ? 1 : p == 2 ? 0 : p == 3 ? 1 : 0) : limbs == 1 ? 0 : (p == 0 ? 1 : 0); }
 
 // K-blocks (16 input channels each) of the decoder in consumption order
 constexpr int KB_RGB0 = 0;          // 4 planes x 3
@@ -73,6 +74,9 @@ __device__ __forceinline__ unsigned round_pair(float e1, float e0) {          //
 // numbers for 2^-10 <= |W| < 255 and 2^-6 <= |x| < 4094; below, the low limb is a subnormal with an absolute error <= 2^-25-SW resp.
 // 2^-25-SX (1.2e-10 |x| / 1.9e-9 |W|: below an f32 ulp of any activation > 0.03); above, the conversion overflows to inf and the pixel
 // comes out NaN (loud, never a wrong number).
+// LIMBS = 1 (the SR convolutions' NVSR_ARITH_F16, sr.hip / sr_bwd.hip only): hi alone, one product -- operands rounded once to f16, error
+// <= (2^-10 + 2^-22) |W||x| per product; same scales and ranges.  An operand beyond the range is an inf with no -inf low limb beside it: the
+// kernels write an infinite accumulator as NaN (conv_write_out16).
 constexpr int F16_SW = 8, F16_SX = 4;
 constexpr float F16_W_SCALE = 256.0f, F16_X_SCALE = 16.0f, F16_ACC_UNSCALE = 1.0f / 256.0f, F16_HEAD_SCALE = 1.0f / 16.0f;
 __device__ __forceinline__ unsigned f16_pair(float e1, float e0) {            // v_cvt_pk_f16_f32, round to nearest even
@@ -129,6 +133,8 @@ __device__ __forceinline__ void split_slice(int slice, Get get, Limbs<LIMBS>& ou
         if (st == 3) { p.r0 = limb_rest(p.r0); }
         if (st == 4) { p.r1 = limb_rest(p.r1); }
         if (st == 5) { out.v[2][j] = trunc_pair(p.r1, p.r0); }
+    } else if (LIMBS == 1) {          // the high limb alone: one v_cvt_pk_f16_f32 per pair, one slice per pair
+        out.v[0][j] = f16_pair(get(2 * j + 1), get(2 * j));
     } else {
 #if F16_MIX_SPLIT
         if (st == 0) { out.v[0][j] = f16_pair(get(2 * j + 1), get(2 * j)); unsigned w; f16_low_limb_lo(w, get(2 * j), out.v[0][j]); out.v[1][j] = w; }

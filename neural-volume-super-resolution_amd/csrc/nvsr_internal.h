@@ -28,9 +28,10 @@ int nvsr_render_pass_backward_gates_limb_launch(int limbs, const nvsr_scene* sce
 int nvsr_render_pass_backward_rows_limb_launch(int limbs, const nvsr_scene* scene, const float* packed_decoder, const float* packed_bwd, int64_t N, int S, const float* rays,
                                                const float* z, const float* g_raw, const uint32_t* gates, float* const* rows, float* view_ws, float* record,
                                                nvsr_stream_t stream);
-// render.hip: NVSR_ARITH_INHERIT -> the process default, anything that is not a mode -> -1; the mode named by an environment variable (dflt if unset)
+// render.hip: NVSR_ARITH_INHERIT -> the process default, anything that is not a mode -> -1; the mode named by an environment variable (dflt if unset;
+// conv != 0: the variable of the convolutions, which also takes "f16")
 int nvsr_internal_resolve_decoder_arith(int arithmetic);
-int nvsr_internal_parse_arith_env(const char* name, int dflt);
+int nvsr_internal_parse_arith_env(const char* name, int dflt, int conv);
 // colour_order.hip: size the two-phase route's scratch for a pass of N rays x S samples before a frame's first launch (acquire_pass_scratch
 // of colour_order.h as a reservation: it leaves no launch behind)
 void nvsr_internal_reserve_render_scratch(int64_t N, int S, nvsr_stream_t stream);

@@ -237,21 +237,22 @@ static int g_decoder_arithmetic = -1;
 
 extern "C" {
 
-// "f32" | "bf16x3" | "f16x2" -> the mode; unset or empty -> dflt; anything else -> NVSR_ARITH_INVALID (said once on stderr): every call that
+// "f32" | "bf16x3" | "f16x2" (conv: | "f16", the convolutions' one-limb mode) -> the mode; unset or empty -> dflt; anything else -> NVSR_ARITH_INVALID (said once on stderr): every call that
 // inherits the process default then fails with NVSR_ERR_SHAPE instead of silently running the default (round 3 renamed bf16x2 -> f16x2:
 // a stale NVSR_DECODER_ARITHMETIC=bf16x2 must not quietly select another arithmetic)
-int nvsr_internal_parse_arith_env(const char* name, int dflt) {
+int nvsr_internal_parse_arith_env(const char* name, int dflt, int conv) {
     const char* e = getenv(name);
     if (!e || !*e) return dflt;
     if (!strcmp(e, "f32")) return NVSR_ARITH_F32;
     if (!strcmp(e, "bf16x3")) return NVSR_ARITH_BF16X3;
     if (!strcmp(e, "f16x2")) return NVSR_ARITH_F16X2;
-    fprintf(stderr, "nvsr: %s=%s is not one of f32 | bf16x3 | f16x2\n", name, e);
+    if (conv && !strcmp(e, "f16")) return NVSR_ARITH_F16;
+    fprintf(stderr, "nvsr: %s=%s is not one of f32 | bf16x3 | f16x2%s\n", name, e, conv ? " | f16" : "");
     return NVSR_ARITH_INVALID;
 }
 
 int nvsr_get_decoder_arithmetic(void) {
-    if (g_decoder_arithmetic == -1) g_decoder_arithmetic = nvsr_internal_parse_arith_env("NVSR_DECODER_ARITHMETIC", NVSR_ARITH_DEFAULT);
+    if (g_decoder_arithmetic == -1) g_decoder_arithmetic = nvsr_internal_parse_arith_env("NVSR_DECODER_ARITHMETIC", NVSR_ARITH_DEFAULT, 0);
     return g_decoder_arithmetic;
 }
 

@@ -526,7 +526,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_limb_kernel(ConvParams p, Conv
 // conv3x3_limb_kernel's, results agree to rounding (both are held to the CPU checker of the test suite at 3e-5).
 // F16 (the 2-f16-limb arithmetic): the accumulators carry 2^(F16_SW + F16_SX) and the ReLU lets a NaN through (an operand beyond the f16
 // range turns the accumulators into NaNs; fmaxf would return 0)
-template <int PB, bool F16 = false, int NCB = 2>
+// INF_IS_NAN (the lone f16 limb, LIMBS = 1): an operand beyond the range is an inf whose products are +-inf -- with two limbs the low limb of an
+// inf is -inf and their products meet as NaN -- so an infinite accumulator (finite operands cannot reach one: |products| < 2^32) is written as
+// NaN: the same outputs are NaN as with two limbs, and the ReLU cannot turn a -inf into a plausible 0
+template <int PB, bool F16 = false, int NCB = 2, bool INF_IS_NAN = false>
 __device__ __forceinline__ float conv_write_out16(const ConvParams& p, const f32x4 (&acc)[NCB][PB][2], int x0, int y0, int co0, int lane, int Ho, int Wo,
                                                   float unscale = 1.0f) {
     float amax = 0.0f;
@@ -563,6 +566,7 @@ __device__ __forceinline__ float conv_write_out16(const ConvParams& p, const f32
                     for (int r = 0; r < 4; ++r) {
                         float t = acc[cb][pb][hx][r];
                         if (F16) t *= unscale;
+                        if (INF_IS_NAN) t = fabsf(t) == __builtin_inff() ? __builtin_nanf("") : t;
                         if (EPI == EPI_RELU) t = F16 ? (t < 0.0f ? 0.0f : t) : fmaxf(t, 0.0f);
                         if (EPI == EPI_RESIDUAL) t = t * 0.1f + sk[r];
                         if (EPI == EPI_MASK_SCALE) t = (sk[r] > 0.0f) ? t * 0.1f : 0.0f;
@@ -599,7 +603,7 @@ __device__ __forceinline__ float conv_write_out16(const ConvParams& p, const f32
 #endif
 template <int LIMBS>
 __device__ __forceinline__ f32x4 mfma16_limb(u32x4 a, u32x4 b, f32x4 c) {
-    if constexpr (LIMBS == 2) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    if constexpr (LIMBS <= 2) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
     else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 __device__ __forceinline__ f32x4 mfma16_bf16(u32x4 a, u32x4 b, f32x4 c) {
@@ -609,7 +613,10 @@ __device__ __forceinline__ f32x4 mfma16_bf16(u32x4 a, u32x4 b, f32x4 c) {
 // WAVES = 4: 128 output channels per workgroup, two workgroups per CU; WAVES = 8 (experiment, -DCV16_WAVES=8): 256 channels per workgroup, one
 // workgroup per CU -- the patch is staged once for all 256 channels
 // LIMBS = 3: bf16 limbs (6 products); LIMBS = 2: f16 limbs rounded to nearest with the static scales of limb_core.h (3 products; forward
-// convolutions only -- gradients span too many decades for 5 exponent bits)
+// convolutions and -- with the power-of-two scale of the whole dy tensor, p.absmax -- data gradients)
+// LIMBS = 1 (NVSR_ARITH_F16): the high f16 limb of both operands alone, ONE product -- operands rounded once to f16, f32 accumulation.  Same
+// scales, same order of input-channel chunks, taps and output blocks as LIMBS = 2; the patch is staged as one limb (half the LDS) and the
+// weights are limb 0 of the 2-limb fragment region, whole 1 KB blocks read at a stride of two (WL = limbs per fragment IN MEMORY)
 // NCB = 16-channel output blocks per wave: 2 (a workgroup of 4 waves = 128 channels).  4 (256 channels: one workgroup per pixel tile reads the
 // patch once, every B fragment read from LDS feeds 12 MFMAs instead of 6, half the LDS and L2 streams per MFMA) was measured in round 4 and is
 // not instantiated: with 6 rows it needs 512 registers = one workgroup per CU and the EDSR(256 x 32) plane takes 20.4 instead of 17.0 ms; with
@@ -628,6 +635,8 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && NCB == 2) ? 2 : 1) void 
     constexpr int OSTR = (PR * PC + 15) / 16 * 16;
     constexpr int LIMB_WORDS = 4 * OSTR * 4;              // one limb of the patch
     constexpr int BUF = LIMBS * LIMB_WORDS;
+    constexpr bool F16 = LIMBS <= 2;                      // f16 limbs: scaled operands, NaN-preserving ReLU
+    constexpr int WL = LIMBS == 1 ? 2 : LIMBS;            // limbs per (co-block, tap) fragment of the packed region
     __shared__ __attribute__((aligned(16))) unsigned lds[2 * BUF];
     NVSR_RACE_PROBE_DELAY(lds);      // (probe builds only, nvsr_common.h)
 #define CV16_ITEM(R, O, COL) ((O) * OSTR + (R) * PC + (COL))
@@ -670,7 +679,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && NCB == 2) ? 2 : 1) void 
     // f16 limbs: the input's power-of-two scale -- static 2^F16_SX for activations; for a data gradient (p.absmax) the one that puts the largest
     // |dy| of the whole tensor into [2^12, 2^13): gradients span many decades from layer to layer and step to step, a tensor's values a few
     float xscale = F16_X_SCALE;
-    if (LIMBS == 2 && p.absmax) {
+    if (F16 && p.absmax) {
         xscale = f16_gradient_scale((unsigned)__builtin_amdgcn_readfirstlane((int)*p.absmax));
     }
 
@@ -688,9 +697,9 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && NCB == 2) ? 2 : 1) void 
             Limbs<LIMBS> L;
             float e[8];
 #pragma unroll
-            for (int c8 = 0; c8 < 8; ++c8) e[c8] = inside[k] ? (LIMBS == 2 ? st[k][c8] * xscale : st[k][c8]) : 0.0f;
+            for (int c8 = 0; c8 < 8; ++c8) e[c8] = inside[k] ? (F16 ? st[k][c8] * xscale : st[k][c8]) : 0.0f;
             if constexpr (LIMBS == 3) split8(e, L);
-            else split_all<2>([&](int i8) { return e[i8]; }, L);
+            else split_all<LIMBS>([&](int i8) { return e[i8]; }, L);
             if (item[k]) {
 #pragma unroll
                 for (int t = 0; t < LIMBS; ++t) *reinterpret_cast<u32x4*>(lds + buf * BUF + t * LIMB_WORDS + sl[k]) = L.v[t];
@@ -710,8 +719,8 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && NCB == 2) ? 2 : 1) void 
 #pragma unroll
             for (int c = 0; c < 2; ++c) acc[a][b][c] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     const int nchunks = p.Cin / 32;
-    const u32x4* wbase = reinterpret_cast<const u32x4*>(LIMBS == 2 ? p.wpk_f16 : p.wpk_limb16) + ((long)cb0 * 9 * LIMBS) * 64;     // wave-uniform
-    const long wchunk = (long)ncb16 * 9 * LIMBS * 64;       // u32x4 per chunk
+    const u32x4* wbase = reinterpret_cast<const u32x4*>(F16 ? p.wpk_f16 : p.wpk_limb16) + ((long)cb0 * 9 * WL) * 64;     // wave-uniform
+    const long wchunk = (long)ncb16 * 9 * WL * 64;       // u32x4 per chunk
     gload(0);
     sstore(0);
     __syncthreads();
@@ -727,7 +736,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && NCB == 2) ? 2 : 1) void 
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
-            for (int t = 0; t < LIMBS; ++t) A[cb][t] = wa[((cb * 9 + 0) * LIMBS + t) * 64 + lane];
+            for (int t = 0; t < LIMBS; ++t) A[cb][t] = wa[((cb * 9 + 0) * WL + t) * 64 + lane];
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             const int ky = tap / 3, kx = tap % 3;
@@ -736,7 +745,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && NCB == 2) ? 2 : 1) void 
 #pragma unroll
                 for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
-                    for (int t = 0; t < LIMBS; ++t) An[cb][t] = wa[((cb * 9 + tap + 1) * LIMBS + t) * 64 + lane];
+                    for (int t = 0; t < LIMBS; ++t) An[cb][t] = wa[((cb * 9 + tap + 1) * WL + t) * 64 + lane];
             }
             __builtin_amdgcn_sched_barrier(0);
 #if CV16_BPF
@@ -793,7 +802,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && NCB == 2) ? 2 : 1) void 
         if (chunk + 1 < nchunks) sstore(buf ^ 1);
         __syncthreads();
     }
-    conv_publish_absmax(p, conv_write_out16<PB, LIMBS == 2, NCB>(p, acc, x0, y0, cb0 * 16, lane, Ho, Wo, 1.0f / (F16_W_SCALE * xscale)));
+    conv_publish_absmax(p, conv_write_out16<PB, F16, NCB, LIMBS == 1>(p, acc, x0, y0, cb0 * 16, lane, Ho, Wo, 1.0f / (F16_W_SCALE * xscale)));
 #undef CV16_ITEM
 }
 
@@ -1003,11 +1012,11 @@ extern "C" int nvsr_get_sr_plane_interp(void) { return g_sr_bicubic ? NVSR_PLANE
 // arithmetic of the eligible conv layers (process-wide): -1 = not yet read from the environment
 static int g_conv_arithmetic = -1;
 extern "C" int nvsr_get_conv_arithmetic(void) {
-    if (g_conv_arithmetic == -1) g_conv_arithmetic = nvsr_internal_parse_arith_env("NVSR_CONV_ARITHMETIC", NVSR_CONV_ARITH_DEFAULT);
+    if (g_conv_arithmetic == -1) g_conv_arithmetic = nvsr_internal_parse_arith_env("NVSR_CONV_ARITHMETIC", NVSR_CONV_ARITH_DEFAULT, 1);
     return g_conv_arithmetic;
 }
 extern "C" int nvsr_set_conv_arithmetic(int mode) {
-    if (mode != NVSR_ARITH_F32 && mode != NVSR_ARITH_BF16X3 && mode != NVSR_ARITH_F16X2) return NVSR_ERR_SHAPE;
+    if (!conv_arith_ok(mode)) return NVSR_ERR_SHAPE;
     g_conv_arithmetic = mode;
     return NVSR_OK;
 }
@@ -1084,7 +1093,7 @@ const unsigned* launch_absmax_ragged(int n, const float* const* x, const long* c
 int launch_conv(const float* in, int Cin, int H, int W, const float* wpk, int Cout, int epilogue, const float* skip, float* out,
                 hipStream_t stream, int pad, int batch, ConvExec cx, const ConvRagged* rag) {
     const int arith = conv_resolve_arith(cx.arith);
-    if (arith != NVSR_ARITH_F32 && arith != NVSR_ARITH_BF16X3 && arith != NVSR_ARITH_F16X2) return NVSR_ERR_SHAPE;
+    if (!conv_arith_ok(arith)) return NVSR_ERR_SHAPE;
     if (rag) {
         // ragged batch: the grid is laid out for the largest plane (H, W = the maxima), the row count per tile is chosen for the tiles that exist
         if (rag->n < 1 || rag->n > CONV_RAGGED_MAX || arith == NVSR_ARITH_F32) return NVSR_ERR_SHAPE;
@@ -1108,7 +1117,8 @@ int launch_conv(const float* in, int Cin, int H, int W, const float* wpk, int Co
     // NVSR_ARITH_F16X2: the forward convolutions of the wide layers (16x16x32 kernel) on 2 f16 limbs; everything else that runs limbs -- the
     // narrow input / output layers, every data gradient (pad = 2, backward epilogues) -- stays on 3 bf16 limbs
     // (round 3, end: the data gradients of those layers too -- pad = 2, backward epilogues -- with the scale of the whole dy tensor, absmax_kernel)
-    const bool f16 = arith == NVSR_ARITH_F16X2;
+    // NVSR_ARITH_F16: the same launches with the high limb alone (conv3x3_limb16_kernel<.., 1>); the narrow layers run what they run under F16X2
+    const bool f16 = conv_arith_f16(arith), one_limb = arith == NVSR_ARITH_F16;
     const bool f16_dgrad = f16 && (pad != 0 || epilogue == EPI_MASK_SCALE || epilogue == EPI_ADD_CENTER);
     if (cx.rows != 0 && (cx.rows < 2 || cx.rows > 4) && cx.rows != 8 && cx.rows != 16 && !(cx.rows >= 18 && cx.rows <= 20) && cx.rows != 22) return NVSR_ERR_SHAPE;
     const long in_bs = (long)Cin * H * W;
@@ -1182,6 +1192,13 @@ int launch_conv(const float* in, int Cin, int H, int W, const float* wpk, int Co
                 if (rag && !cx.in_absmax) return NVSR_ERR_NULL;
                 p.absmax = cx.in_absmax ? cx.in_absmax : launch_absmax(in, in_bs * batch, stream);
                 if (!p.absmax) return NVSR_ERR_LAUNCH;
+            }
+            if (one_limb) {
+                if (best_pb == 6) hipLaunchKernelGGL((conv3x3_limb16_kernel<6, CV16_WAVES, 1>), grid, dim3(64 * CV16_WAVES), 0, stream, p, rg);
+                else if (best_pb == 4) hipLaunchKernelGGL((conv3x3_limb16_kernel<4, CV16_WAVES, 1>), grid, dim3(64 * CV16_WAVES), 0, stream, p, rg);
+                else if (best_pb == 3) hipLaunchKernelGGL((conv3x3_limb16_kernel<3, CV16_WAVES, 1>), grid, dim3(64 * CV16_WAVES), 0, stream, p, rg);
+                else hipLaunchKernelGGL((conv3x3_limb16_kernel<2, CV16_WAVES, 1>), grid, dim3(64 * CV16_WAVES), 0, stream, p, rg);
+                return NVSR_CHECK_LAUNCH();
             }
             if (best_pb == 6) hipLaunchKernelGGL((conv3x3_limb16_kernel<6, CV16_WAVES, 2>), grid, dim3(64 * CV16_WAVES), 0, stream, p, rg);
             else if (best_pb == 4) hipLaunchKernelGGL((conv3x3_limb16_kernel<4, CV16_WAVES, 2>), grid, dim3(64 * CV16_WAVES), 0, stream, p, rg);
@@ -1324,6 +1341,7 @@ int nvsr_conv3x3_dgrad_arith(const float* dy, int Cin, int H, int W, const float
     if (!dy || !packed_dgrad || !dx) return NVSR_ERR_NULL;
     if (!aligned16(packed_dgrad)) return NVSR_ERR_ALIGN;
     if (H < 3 || W < 3) return NVSR_ERR_SHAPE;
+    if (arithmetic == NVSR_ARITH_F16 && !conv_limb16_eligible(Cout, Cin)) return NVSR_ERR_SHAPE;      // (see nvsr_conv3x3_arith)
     return launch_conv(dy, Cout, H - 2, W - 2, packed_dgrad, Cin, EPI_NONE, nullptr, dx, (hipStream_t)stream, 2, 1, ConvExec{arithmetic, rows_per_tile});
 }
 int nvsr_conv3x3_dgrad(const float* dy, int Cin, int H, int W, const float* packed_dgrad, int Cout, float* dx, nvsr_stream_t stream) {
@@ -1336,6 +1354,9 @@ int nvsr_conv3x3_arith(const float* in, int Cin, int H, int W, const float* pack
     if (!in || !packed || !out) return NVSR_ERR_NULL;
     if (epilogue < 0 || epilogue > 3 || (epilogue == EPI_RESIDUAL && !skip) || (epilogue == EPI_PIXEL_SHUFFLE && Cout % 4)) return NVSR_ERR_SHAPE;
     if (!aligned16(packed)) return NVSR_ERR_ALIGN;
+    // a single layer asked for in NVSR_ARITH_F16 BY NAME must have the one-limb kernel: a missing kernel is an error, not another arithmetic.
+    // (Inside a network -- the EDSR / PlanesSR entry points -- and under an inherited default the narrow layers run what they run under F16X2.)
+    if (arithmetic == NVSR_ARITH_F16 && !conv_limb16_eligible(Cin, Cout)) return NVSR_ERR_SHAPE;
     return launch_conv(in, Cin, H, W, packed, Cout, epilogue, skip, out, (hipStream_t)stream, 0, 1, ConvExec{arithmetic, rows_per_tile});
 }
 int nvsr_conv3x3(const float* in, int Cin, int H, int W, const float* packed, int Cout, int epilogue, const float* skip, float* out,
@@ -1362,7 +1383,7 @@ int nvsr_pack_edsr_arith(const float* natural, int Cin, int Cout, int hid, int n
     if (!aligned16(packed)) return NVSR_ERR_ALIGN;
     if (arithmetic != NVSR_PACK_ALL_ARITHMETICS) {
         arithmetic = conv_resolve_arith(arithmetic);
-        if (arithmetic != NVSR_ARITH_F32 && arithmetic != NVSR_ARITH_F16X2 && arithmetic != NVSR_ARITH_BF16X3) return NVSR_ERR_SHAPE;
+        if (!conv_arith_ok(arithmetic)) return NVSR_ERR_SHAPE;
     }
     ConvLayer L[600]; int n;
     edsr_layers(Cin, Cout, hid, nblocks, n_up, L, &n);
@@ -1531,7 +1552,7 @@ int nvsr_planes_sr_batch_ex(const float* const* lr, int B, int Cc, int R0, int R
     const int64_t n_out = (int64_t)Cc * R0 * sf * R1 * sf;
     for (int b = 0; b < B; ++b) {
         hipLaunchKernelGGL(sr_finish_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, stream, diff + b * n_diff, Ho, Wo, over, lr[b],
-                           Cc, R0, R1, sf, lo[0], lo[1], hi[0], hi[1], out[b], conv_resolve_arith(arithmetic) == NVSR_ARITH_F16X2 ? nvsr_get_range_flag() : nullptr,
+                           Cc, R0, R1, sf, lo[0], lo[1], hi[0], hi[1], out[b], conv_arith_f16(conv_resolve_arith(arithmetic)) ? nvsr_get_range_flag() : nullptr,
                            align_corners ? 1 : 0, plane_interp == NVSR_PLANE_INTERP_BICUBIC ? 1 : 0);
         if (int e = NVSR_CHECK_LAUNCH()) return e;
     }
@@ -1603,7 +1624,7 @@ static int planes_sr_impl(const float* lr, int Cc, int R0, int R1, const float* 
     } else if (int e = nvsr_edsr_forward_batch_arith(xin, 1, Cc, Hp, Wp, packed, Cc, hid, nblocks, n_up, diff, ews, arithmetic, stream_)) return e;
     const int64_t n_out = (int64_t)Cc * R0 * sf * R1 * sf;
     hipLaunchKernelGGL(sr_finish_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, stream, diff, Ho, Wo, over, lr, Cc, R0, R1, sf,
-                       lo[0], lo[1], hi[0], hi[1], out, conv_resolve_arith(arithmetic) == NVSR_ARITH_F16X2 ? nvsr_get_range_flag() : nullptr, sr_align_corners(), sr_bicubic());
+                       lo[0], lo[1], hi[0], hi[1], out, conv_arith_f16(conv_resolve_arith(arithmetic)) ? nvsr_get_range_flag() : nullptr, sr_align_corners(), sr_bicubic());
     return NVSR_CHECK_LAUNCH();
 }
 
@@ -1695,7 +1716,7 @@ int nvsr_planes_sr_train_batch_arith(const float* const* lr, int B, int Cc, int 
     const int64_t n_out = (int64_t)Cc * R0 * sf * R1 * sf;
     for (int b = 0; b < B; ++b) {
         hipLaunchKernelGGL(sr_finish_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, stream, diff[b], P[b].Ho, P[b].Wo, over, lr[b], Cc, R0, R1,
-                           sf, lo[b][0], lo[b][1], hi[b][0], hi[b][1], out[b], arith == NVSR_ARITH_F16X2 ? nvsr_get_range_flag() : nullptr,
+                           sf, lo[b][0], lo[b][1], hi[b][0], hi[b][1], out[b], conv_arith_f16(arith) ? nvsr_get_range_flag() : nullptr,
                            align_corners ? 1 : 0, plane_interp == NVSR_PLANE_INTERP_BICUBIC ? 1 : 0);
         if (int e = NVSR_CHECK_LAUNCH()) return e;
     }

@@ -170,6 +170,11 @@ __device__ __forceinline__ void split4_f16(const float (&e)[4], float scale, u32
 #endif
     }
 }
+// the high limb alone (LF = 1, NVSR_ARITH_F16): one v_cvt_pk_f16_f32 per pair
+__device__ __forceinline__ void split4_f16_one(const float (&e)[4], float scale, u32x2 (&out)[3]) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) out[0][j] = f16_pair(e[2 * j + 1] * scale, e[2 * j] * scale);
+}
 constexpr int WL_ROW = 20;                                // words per row of 40 bf16 pixels
 constexpr int WL_DY_WORDS = WG_CO * WL_ROW;               // one limb of dy
 constexpr int WL_X_WORDS = WG_CI * 3 * WL_ROW;            // one limb of X
@@ -261,7 +266,7 @@ __device__ __forceinline__ void wgrad_limb_rows(const WgradParams& p, const Wgra
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             u32x2 L[3];
-            if constexpr (LF == 2) split4_f16(src[k], F16_X_SCALE, L); else split4(src[k], L);
+            if constexpr (LF == 1) split4_f16_one(src[k], F16_X_SCALE, L); else if constexpr (LF == 2) split4_f16(src[k], F16_X_SCALE, L); else split4(src[k], L);
             if (x_lane && xr + 28 * k < WG_CI) {
 #pragma unroll
                 for (int t = 0; t < LF; ++t) *reinterpret_cast<u32x2*>(x_st + t * WL_X_WORDS + (28 * k * 3 + slot) * WL_ROW) = L[t];
@@ -287,7 +292,7 @@ __device__ __forceinline__ void wgrad_limb_rows(const WgradParams& p, const Wgra
 #pragma unroll
             for (int j = 0; j < 4; ++j) rdy[k][j] = j < dy_valid ? rdy[k][j] : 0.0f;
             u32x2 L[3];
-            if constexpr (LF == 2) split4_f16(rdy[k], dscale, L); else split4(rdy[k], L);
+            if constexpr (LF == 1) split4_f16_one(rdy[k], dscale, L); else if constexpr (LF == 2) split4_f16(rdy[k], dscale, L); else split4(rdy[k], L);
 #pragma unroll
             for (int t = 0; t < LF; ++t) *reinterpret_cast<u32x2*>(dy_st + t * WL_DY_WORDS + 32 * k * WL_ROW) = L[t];
         }
@@ -346,7 +351,24 @@ __device__ __forceinline__ void wgrad_limb_rows(const WgradParams& p, const Wgra
         // 6 groups g = (K-block kb of 16 pixels, ky): 18 MFMAs each, products in the order of limb_w / limb_x (small terms first), which
         // starts with X limb 2: that limb's words of group g + 1 are requested before the MFMAs of group g, limbs 1 and 0 at the start of
         // their own group, under its first MFMAs
-        if constexpr (LF == 2) {
+        if constexpr (LF == 1) {
+            // 1 f16 limb: 3 MFMAs per group -- dy_hi X_hi, the middle product of the 2-limb groups, in their order; X of the next group is
+            // requested before this group's MFMAs
+            Raw nxt = read_x(0, rowoff[0]);
+            u32x4 A;
+#pragma unroll
+            for (int g = 0; g < 6; ++g) {
+                const int kb = g / 3, ky = g % 3;
+                __builtin_amdgcn_sched_barrier(0);
+                if (ky == 0) A = *reinterpret_cast<const u32x4*>(Ap + kb * 8);
+                u32x4 B0[3];
+                taps(nxt, B0);
+                if (g < 5) nxt = read_x(0, rowoff[(g + 1) % 3] + ((g + 1) / 3) * 8);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int kx = 0; kx < 3; ++kx) acc[ky * 3 + kx] = mfma_limb<2>(A, B0[kx], acc[ky * 3 + kx]);
+            }
+        } else if constexpr (LF == 2) {
             // 2 f16 limbs: 9 MFMAs per group -- dy_hi X_lo, dy_hi X_hi, dy_lo X_hi (limb_w / limb_x of 2 limbs); X_lo of the next group is
             // requested before this group's MFMAs
             static_assert(limb_x(2, 0) == 1 && limb_x(2, 1) == 0 && limb_x(2, 2) == 0 && limb_w(2, 0) == 0 && limb_w(2, 1) == 0 && limb_w(2, 2) == 1, "");
@@ -431,7 +453,7 @@ __global__ __launch_bounds__(WG_TPB, 2) void conv3x3_wgrad_limb_kernel(WgradPara
     __shared__ __attribute__((aligned(16))) unsigned lds[LF * (WL_DY_WORDS + WL_X_WORDS)];
     NVSR_RACE_PROBE_DELAY(lds);      // (probe builds only, nvsr_common.h)
     float dscale = 1.0f;          // f16 limbs: the power of two that puts the largest |dy| of the tensor into [2^12, 2^13) (sr.hip, the data gradient's rule)
-    if (LF == 2 && p.dy_absmax) {
+    if (LF <= 2 && p.dy_absmax) {
         dscale = f16_gradient_scale((unsigned)__builtin_amdgcn_readfirstlane((int)*p.dy_absmax));
     }
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, i = lane & 31, kh = lane >> 5;
@@ -485,6 +507,8 @@ __global__ __launch_bounds__(WG_TPB, 2) void conv3x3_wgrad_limb_kernel(WgradPara
             for (int t = 0; t < 9; ++t)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
+                    // (one limb: an activation beyond the range is an inf and its sums +-inf where two limbs give NaN -- written as NaN, see conv_write_out16)
+                    if (LF == 1) acc[t][r] = fabsf(acc[t][r]) == __builtin_inff() ? __builtin_nanf("") : acc[t][r];
                     dst[(t * WG_CO + cw * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh) * WG_CI] = acc[t][r];
                     acc[t][r] = 0.0f;
                 }
@@ -783,7 +807,10 @@ static int launch_wgrad_planes(int nplanes, const float* const* dy, const float*
     if (getenv("NVSR_WGRAD_PIECES")) n_wg = atoi(getenv("NVSR_WGRAD_PIECES"));
 #endif
     const unsigned* am = nullptr;
-    if (arith == NVSR_ARITH_F16X2) {       // 2 f16 limbs: X with the static activation scale, dy with its tensor's own (one reduction)
+    // NVSR_ARITH_F16: the wide layers (forward and data gradient on conv3x3_limb16_kernel) contract the high limbs alone; a narrow layer runs what
+    // it runs under F16X2
+    const bool one_limb = arith == NVSR_ARITH_F16 && conv_limb16_eligible(Cin, Cout);
+    if (conv_arith_f16(arith)) {       // f16 limbs: X with the static activation scale, dy with its tensor's own (one reduction)
         am = dy_absmax;
         if (!am && nplanes == 1) am = launch_absmax(dy[0], (long)Cout * (H[0] - 2) * (W[0] - 2), stream);
         if (!am) return nplanes == 1 ? NVSR_ERR_LAUNCH : NVSR_ERR_NULL;
@@ -799,7 +826,8 @@ static int launch_wgrad_planes(int nplanes, const float* const* dy, const float*
         if (rp->busy[k] && hipStreamWaitEvent(stream, rp->lane->done[k], 0) != hipSuccess) return NVSR_ERR_LAUNCH;   // the reduction that last read this buffer
         rp->busy[k] = false;
     }
-    if (am) hipLaunchKernelGGL(conv3x3_wgrad_limb_kernel<2>, dim3(n_wg), dim3(WG_TPB), 0, stream, p);
+    if (am && one_limb) hipLaunchKernelGGL(conv3x3_wgrad_limb_kernel<1>, dim3(n_wg), dim3(WG_TPB), 0, stream, p);
+    else if (am) hipLaunchKernelGGL(conv3x3_wgrad_limb_kernel<2>, dim3(n_wg), dim3(WG_TPB), 0, stream, p);
     else hipLaunchKernelGGL(conv3x3_wgrad_limb_kernel<3>, dim3(n_wg), dim3(WG_TPB), 0, stream, p);
     if (rstream != stream) {
         if (hipEventRecord(rp->lane->ready[k], stream) != hipSuccess || hipStreamWaitEvent(rstream, rp->lane->ready[k], 0) != hipSuccess) return NVSR_ERR_LAUNCH;
@@ -819,7 +847,7 @@ static int launch_wgrad(const float* dy, const float* x, int Cin, int H, int W, 
     const int Ho = H - 2, Wo = W - 2;
     if (Ho < 1 || Wo < 1) return NVSR_ERR_SHAPE;
     arith = conv_resolve_arith(arith);
-    if (arith != NVSR_ARITH_F32 && arith != NVSR_ARITH_BF16X3 && arith != NVSR_ARITH_F16X2) return NVSR_ERR_SHAPE;
+    if (!conv_arith_ok(arith)) return NVSR_ERR_SHAPE;
     if (arith != NVSR_ARITH_F32) return launch_wgrad_planes(1, &dy, &x, Cin, &H, &W, Cout, scale, dw, partial, stream, arith, dy_absmax, rp);
     const long n = 9L * Cout * Cin;
     const int ns = wgrad_slabs(Cin, Cout, Ho);
@@ -869,6 +897,7 @@ int nvsr_conv3x3_wgrad_arith(const float* dy, const float* x, int Cin, int H, in
                              int arithmetic, nvsr_stream_t stream) {
     if (!dy || !x || !dw || !workspace) return NVSR_ERR_NULL;
     if (Cin < 1 || Cout < 1 || H < 3 || W < 3) return NVSR_ERR_SHAPE;
+    if (arithmetic == NVSR_ARITH_F16 && !conv_limb16_eligible(Cin, Cout)) return NVSR_ERR_SHAPE;      // (sr.hip: nvsr_conv3x3_arith)
     return launch_wgrad(dy, x, Cin, H, W, Cout, scale, dw, workspace, (hipStream_t)stream, arithmetic);
 }
 int nvsr_conv3x3_wgrad(const float* dy, const float* x, int Cin, int H, int W, int Cout, float scale, float* dw, float* workspace,
@@ -892,7 +921,7 @@ int nvsr_pack_edsr_dgrad_arith(const float* natural, int Cin, int Cout, int hid,
     if (!aligned16(packed_dgrad)) return NVSR_ERR_ALIGN;
     if (arithmetic != NVSR_PACK_ALL_ARITHMETICS) {
         arithmetic = conv_resolve_arith(arithmetic);
-        if (arithmetic != NVSR_ARITH_F32 && arithmetic != NVSR_ARITH_F16X2 && arithmetic != NVSR_ARITH_BF16X3) return NVSR_ERR_SHAPE;
+        if (!conv_arith_ok(arithmetic)) return NVSR_ERR_SHAPE;
     }
     ConvLayer L[EDSR_MAX_LAYERS]; int n;
     edsr_layers(Cin, Cout, hid, nblocks, n_up, L, &n);
@@ -963,7 +992,7 @@ int nvsr_edsr_backward_arith(const float* x, int Cin, int H, int W, const float*
     // f16 limbs: the power-of-two scale of a gradient tensor comes from the bits of its largest magnitude, one word per tensor.  The word of the
     // caller's d_out is a reduction pass; every other gradient tensor is the output of a data-gradient launch, whose epilogue leaves the word
     // behind (ConvExec::out_absmax: an atomicMax per wave) -- no pass over the tensor; the un-shuffled gradient is a permutation of one that has it
-    const bool f16 = conv_resolve_arith(arith) == NVSR_ARITH_F16X2;
+    const bool f16 = conv_arith_f16(conv_resolve_arith(arith));
     if (f16 && hipMemsetAsync(amax_words, 0, sizeof(unsigned) * (P.n + 4), stream) != hipSuccess) return NVSR_ERR_LAUNCH;
     auto new_word = [&]() -> unsigned* { return f16 ? amax_words + amax_next++ : nullptr; };
     auto exec = [&](const unsigned* in_am, unsigned* out_am) { ConvExec c = cx; c.in_absmax = in_am; c.out_absmax = out_am; return c; };
@@ -1111,7 +1140,7 @@ static int edsr_backward_planes(int B, const EdsrPlan* P, const float* const* x,
         go += 9LL * P[0].L[l].Cin * P[0].L[l].Cout;
         po += conv_packed_floats(P[0].L[l].Cout, P[0].L[l].Cin);
     }
-    const bool f16 = arith == NVSR_ARITH_F16X2;
+    const bool f16 = conv_arith_f16(arith);
     const float* g[CONV_RAGGED_MAX];       // gradient with respect to the output of layer l (after its epilogue), per plane
     int gi = -1;                           // index of g in the buffers (-1: the caller's d_out)
     for (int b = 0; b < B; ++b) g[b] = d_out[b];

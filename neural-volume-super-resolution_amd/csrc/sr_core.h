@@ -103,13 +103,17 @@ inline int64_t conv_packed_floats(int Cin, int Cout) {
 // point passes) -- the same predicates in the same order as the launcher's branches.  A training iteration re-packs both blobs of the network (the
 // weights change every iteration): packing only these regions writes a fifth of the bytes (nvsr_pack_edsr_arith).  arith == NVSR_PACK_ALL_ARITHMETICS: every region.
 constexpr unsigned CONV_KINDS_ALL = 15u;
+// the arithmetics of the convolutions: the decoder's three and NVSR_ARITH_F16 (one f16 limb; nvsr.h)
+inline bool conv_arith_ok(int arith) { return arith == NVSR_ARITH_F32 || arith == NVSR_ARITH_F16 || arith == NVSR_ARITH_F16X2 || arith == NVSR_ARITH_BF16X3; }
+// f16 limbs, one or two: the scaled operands, the gradient tensors' magnitude words, the range flag
+inline bool conv_arith_f16(int arith) { return arith == NVSR_ARITH_F16X2 || arith == NVSR_ARITH_F16; }
 inline unsigned conv_kinds_for(int Cin, int Cout, int arith, bool use_16x16x32, bool wide_rows8) {
     if (arith == NVSR_PACK_ALL_ARITHMETICS) return CONV_KINDS_ALL;
     if (arith == NVSR_ARITH_F32) return 1u;
     const bool wl = conv_limb_eligible(Cin, Cout), w16 = conv_limb16_eligible(Cin, Cout);
     const int ncb = conv_ncb(Cout);
     if (wl && ncb == 2) return 2u;                                              // narrow layer: conv3x3_limb_kernel<2, 1>
-    if (w16 && use_16x16x32) return arith == NVSR_ARITH_F16X2 ? 8u : 4u;        // conv3x3_limb16_kernel
+    if (w16 && use_16x16x32) return conv_arith_f16(arith) ? 8u : 4u;            // conv3x3_limb16_kernel (F16 reads limb 0 of F16X2's region)
     (void)wide_rows8;                                                           // (the 8-row wide kernel reads region 1 like the 2..4-row one)
     if (wl) return 2u;                                                          // conv3x3_limb_kernel
     return 1u;                                                                  // no limb kernel eligible: exact-f32 kernels

@@ -935,7 +935,8 @@ class EDSR(nn.Module):
         self._extra_pad = int(math.ceil(extra))
         self._extra_crop = int(round((self._extra_pad - extra) * scale_factor))
         self._packed_cache = None
-        self.arithmetic = None     # 'f32' | 'bf16x3' | None = the process default (capi.set_conv_arithmetic / NVSR_CONV_ARITHMETIC)
+        # 'f32' | 'bf16x3' | 'f16x2' | 'f16' (capi.CONV_ARITHMETIC) | None = the process default (capi.set_conv_arithmetic / NVSR_CONV_ARITHMETIC)
+        self.arithmetic = None
 
     def invalidate(self):
         """forget the packed weight blobs (needed after writes through `.data`, which do not bump a tensor's version counter)"""
@@ -949,7 +950,7 @@ class EDSR(nn.Module):
         return super().train(mode)
 
     def arith(self):
-        return capi.arith_code(self.arithmetic)
+        return capi.conv_arith_code(self.arithmetic)
 
     def conv_parameters(self):
         """the convolution weights in state-dict order, as the reference shapes them (3 x 3 or 1 x 1)"""

@@ -457,14 +457,18 @@ def _sr_of(model):
     return model.SR_model if hasattr(model, "SR_model") and not model.skip_SR_ else None
 
 
+# the arithmetics of the SR convolutions that have f16's ranges and raise bit 2 of the range flag
+_SR_RANGED = (capi.CONV_ARITHMETIC["f16x2"], capi.CONV_ARITHMETIC["f16"])
+
+
 def _f16_in_play(*ms):
-    """does an evaluation of these models launch anything in NVSR_ARITH_F16X2?"""
+    """does an evaluation of these models launch anything in NVSR_ARITH_F16X2 -- or, the SR network, in the one-limb 'f16', which has the same ranges?"""
     f16 = capi.ARITHMETIC["f16x2"]
     for m in ms:
         if capi.resolve_decoder_arithmetic(m.arithmetic) == f16:
             return True
         sr = _sr_of(m)
-        if sr is not None and capi.resolve_conv_arithmetic(sr.inner_model.arithmetic) == f16:
+        if sr is not None and capi.resolve_conv_arithmetic(sr.inner_model.arithmetic) in _SR_RANGED:
             return True
     return False
 
@@ -483,7 +487,7 @@ def _range_key(*ms):
 
 def _sr_fallback(*ms, redo=False):
     """the SR networks of these models super-resolve in 'bf16x3' for the evaluation frame being rendered.  Cached SR planes are dropped when `redo`
-    says so (they come from an F16X2 pass that raised the range flag: NaN inside) or when they were NOT made in 'bf16x3' (`_planes_arith`, set by
+    says so (they come from an F16X2 or F16 pass that raised the range flag: NaN inside) or when they were NOT made in 'bf16x3' (`_planes_arith`, set by
     _sr_restore behind a fallback frame, forgotten by clear_SR_planes): planes a fallback frame has super-resolved stay cached for the next frames of
     the same parameters (the arithmetic was put back after every frame, so every later frame found 'f16x2', dropped the planes and ran the
     SR stage again, ~80 ms per scene and frame).  -> [(PlanesSR, its network's arithmetic before)]: the caller puts it back after the frame
@@ -494,7 +498,7 @@ def _sr_fallback(*ms, redo=False):
         if sr is None or id(sr) in seen:
             continue
         seen.add(id(sr))
-        if capi.resolve_conv_arithmetic(sr.inner_model.arithmetic) == capi.ARITHMETIC["f16x2"]:
+        if capi.resolve_conv_arithmetic(sr.inner_model.arithmetic) in _SR_RANGED:
             changed.append((sr, sr.inner_model.arithmetic))
             sr.inner_model.arithmetic = "bf16x3"
             if redo or sr.__dict__.get("_planes_arith") != "bf16x3":

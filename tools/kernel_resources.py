@@ -28,6 +28,10 @@ BENCHMARKED = [
     # the deterministic route (NVSR_DETERMINISTIC=1; the ROWS / DET variants of the kernels above match by name): its own kernels and rocPRIM's sort
     "plane_taps_kernel", "rows_gather_kernel", "view_rows_reduce_kernel", "decoder_wgrad_reduce_kernel", "radix_sort_onesweep", "radix_sort_block_sort",
     "conv3x3_limb_kernel", "conv3x3_limb16_kernel", "conv3x3_wgrad_limb_kernel", "sr_prepare_kernel", "sr_finish_kernel",
+    # NVSR_ARITH_F16 (one f16 limb, opt-in; tools/conv_f16_time.py times it): conv3x3_limb16_kernel<2 | 3 | 4 | 6, 4, 1, 2> and
+    # conv3x3_wgrad_limb_kernel<1> -- mangled-name substrings, the demangled names match the two entries above as well
+    "conv3x3_limb16_kernelILi2ELi4ELi1E", "conv3x3_limb16_kernelILi3ELi4ELi1E", "conv3x3_limb16_kernelILi4ELi4ELi1E", "conv3x3_limb16_kernelILi6ELi4ELi1E",
+    "conv3x3_wgrad_limb_kernelILi1E",
 ]
 # The gate covers EVERY kernel of the library (round 4; round 3 covered the benchmarked ones): no scratch memory, no spilled VGPRs -- except:
 #   ALLOW  name substring -> spilled VGPRs tolerated.  What is listed is debt, with the round that recorded it:
