@@ -586,7 +586,8 @@ __global__ __launch_bounds__(CB_WPB * 64) void composite_backward_kernel(long N,
                 const float gk = (k == 0) ? g0 : (k == 1 ? g1 : g2);
                 o[k] = w * gk * c * (1.0f - c);
             }
-            o[3] = (pre_sig > 0.0f) ? g_alpha * dist * (1.0f - alpha) : 0.0f;
+            // (relu's gate: only sn <= 0 shuts the gradient off -- a NaN density stays a NaN here as in the forward)
+            o[3] = (pre_sig <= 0.0f) ? 0.0f : g_alpha * dist * (1.0f - alpha);
             gout[s] = o;
         }
     }

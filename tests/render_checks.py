@@ -73,10 +73,10 @@ def _sum(term, e):
     return term.sum(-1), e.sum(-1) + gamma(n) * (np.abs(term) + e).sum(-1)
 
 
-def composite64(raw, z, rd_or_rays, noise, white, mip=False):
-    """raw [N, S, 4], z [N, S] (mip: [N, S + 1] interval edges), rd [N, 3] or packed rays [N, 11], noise [N, S] or None (all float32) ->
-    weights [N, S], acc, depth, disp [N], rgb [N, 3] in float64, .bound with the same fields, .sn [N, S] and .live [N] (samples with w != 0; a
-    NaN weight is live)"""
+def stages64(raw, z, rd_or_rays, noise, mip=False):
+    """the per-sample stages of one pass, each with its error as the header derives it: dist (r_x: the relative error of x), sn, x, E, alpha,
+    fac with its interval [lo, hi], n_mul, T, w, zs (every field [N, S]; r_nrm a number, r_delta [N, S] or a number) -- what composite64 sums,
+    and what render_backward_checks.backward64 differentiates"""
     raw = np.ascontiguousarray(raw, dtype=np.float32)
     N, S = raw.shape[:2]
     z = np.ascontiguousarray(z, dtype=np.float32).astype(np.float64)
@@ -119,16 +119,34 @@ def composite64(raw, z, rd_or_rays, noise, white, mip=False):
         e_T[:, 0] = np.where(np.isnan(T[:, 0]), np.nan, 0.0)                 # T_0 = 1 exactly
         w = alpha * T
         e_w = np.where(alpha == 0, 0.0 * T, _rnd(w, e_alpha * T + np.abs(alpha) * e_T + e_alpha * e_T))      # (0 x T = +0.0 exactly; NaN T stays NaN)
-        acc, e_acc = _sum(w, e_w)
-        p = w * zs
-        depth, e_depth = _sum(p, _rnd(p, e_w * np.abs(zs) + np.abs(w) * e_zs + e_w * e_zs))
-        r3 = raw[..., :3].astype(np.float64)
+    return NS(N=N, S=S, raw=raw, nrm=nrm, r_nrm=r_nrm, delta=delta, r_delta=r_delta, dist=dist, r_x=r_x, sn=sn, x=x, E=E, e_E=e_E, alpha=alpha,
+              e_alpha=e_alpha, fac=fac, e_fac=e_fac, lo=lo, hi=hi, n_mul=n_mul, T=T, e_T=e_T, w=w, e_w=e_w, zs=zs, e_zs=e_zs)
+
+
+def sigmoid64(r):
+    """1 / (1 + expf(-r)) of float32 logits -> sigmoid, its error, the relative error of the denominator D = 1 + expf(-r) (header: sigmoid)"""
+    with np.errstate(all="ignore"):
+        r3 = np.asarray(r, dtype=np.float32).astype(np.float64)
         Ec = np.exp(-r3)
         e_Ec = 2 * EXP_ULP * U * Ec + TINY
         D = 1 + Ec
         rel_D = np.where(np.isfinite(D), _rnd(D, e_Ec) / D, 0.5)
         sg = 1 / D
         e_sg = sg * rel_D / (1 - rel_D) + 2 * DIV_ULP * U * sg + TINY
+    return sg, e_sg, rel_D
+
+
+def composite64(raw, z, rd_or_rays, noise, white, mip=False):
+    """raw [N, S, 4], z [N, S] (mip: [N, S + 1] interval edges), rd [N, 3] or packed rays [N, 11], noise [N, S] or None (all float32) ->
+    weights [N, S], acc, depth, disp [N], rgb [N, 3] in float64, .bound with the same fields, .sn [N, S] and .live [N] (samples with w != 0; a
+    NaN weight is live)"""
+    st = stages64(raw, z, rd_or_rays, noise, mip)
+    raw, sn, w, e_w, zs, e_zs = st.raw, st.sn, st.w, st.e_w, st.zs, st.e_zs
+    with np.errstate(all="ignore"):
+        acc, e_acc = _sum(w, e_w)
+        p = w * zs
+        depth, e_depth = _sum(p, _rnd(p, e_w * np.abs(zs) + np.abs(w) * e_zs + e_w * e_zs))
+        sg, e_sg, _ = sigmoid64(raw[..., :3])
         q = w[..., None] * sg
         e_q = _rnd(q, e_w[..., None] * sg + np.abs(w)[..., None] * e_sg + e_w[..., None] * e_sg)
         rgb, e_rgb = _sum(np.moveaxis(q, 1, -1), np.moveaxis(e_q, 1, -1))
