@@ -261,6 +261,7 @@ _PROTOS_LAUNCH = {
     "nvsr_render_pass3_coarse_z_launch": ([_i, C.POINTER(Scene), _vp, _i64, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i),
     "nvsr_decode_rays_limb_launch": ([_i, C.POINTER(Scene), _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp], _i),
     "nvsr_decode_rays_pair_launch": ([C.POINTER(Scene), _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp], _i),
+    "nvsr_internal_conv_route": ([_i, _i, _i, _i, _i, _i, _ip, _ip, C.POINTER(C.c_uint)], _i),      # (host only) the route of a convolution launch
 }
 
 _lib = None

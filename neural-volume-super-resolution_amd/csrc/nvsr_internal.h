@@ -35,6 +35,9 @@ int nvsr_internal_parse_arith_env(const char* name, int dflt, int conv);
 // colour_order.hip: size the two-phase route's scratch for a pass of N rays x S samples before a frame's first launch (acquire_pass_scratch
 // of colour_order.h as a reservation: it leaves no launch behind)
 void nvsr_internal_reserve_render_scratch(int64_t N, int S, nvsr_stream_t stream);
+// sr.hip: the route of one convolution launch of H x W (sr_core.h: conv_route -- kernel family, packed region read; rows_per_tile as the *_arith
+// entry points take it) and the regions the packer writes for that arithmetic (conv_kinds_for); NVSR_PACK_ALL_ARITHMETICS: the packer's answer alone
+int nvsr_internal_conv_route(int Cin, int Cout, int H, int W, int arithmetic, int rows_per_tile, int* family, int* region, unsigned* packed_kinds);
 }  // extern "C"
 
 namespace nvsr {

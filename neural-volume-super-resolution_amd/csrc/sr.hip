@@ -23,32 +23,6 @@
 
 namespace nvsr {
 
-#ifndef NVSR_CONV_WIDE_4x1
-#define NVSR_CONV_WIDE_4x1 1     // 256-channel layers: 1 = two independent 4-wave workgroups per CU (4 rows each), 0 = one 8-wave workgroup (8 rows)
-#endif
-
-
-struct ConvParams {
-    const float* in;      // [Cin][H-2pad][W-2pad]
-    const float* wpk;     // packed weights [chunk][cb][t][lane]
-    const unsigned* wpk_limb;   // bf16-limb fragments behind them (conv_limb_eligible layers), else NULL
-    const unsigned* wpk_limb16; // 16x16x32 fragments behind those (conv_limb16_eligible layers), else NULL
-    const unsigned* wpk_f16;    // 16x16x32 fragments of the 2-f16-limb arithmetic behind those (same layers), else NULL
-    const unsigned* absmax;     // f16 limbs, data gradient: bits of max |in| over the whole input (absmax_kernel) -> the input's power-of-two scale; else NULL
-    float* out;           // [Cout][H-2][W-2]  (pixel shuffle: [Cout/4][2(H-2)][2(W-2)])
-    const float* skip;    // EPI_RESIDUAL: identity [Cout][H+2][W+2] (block input); EPI_MASK_SCALE: forward activation
-                          // [Cout][H-2][W-2] whose sign gates the result; EPI_ADD_CENTER: [Cout][H-6][W-6] added to the centre
-    int Cin, Cout, H, W;  // H, W = logical input size, INCLUDING the virtual zero border of `pad` pixels
-    int ncb_total;        // padded co-blocks in wpk (multiple of 2)
-    int nchunks;          // ceil(Cin/4)
-    int epilogue;
-    int pad;              // 0, or 2 for the data gradient of a valid conv ("full" correlation with the flipped kernel)
-    int ncg;              // co-groups of the grid; blockIdx.z = batch * ncg + co-group
-    long in_bs, out_bs, skip_bs;   // floats between consecutive planes of a batch (the 3 planes of a scene share the weights)
-    unsigned* out_absmax;          // NULL, or a word that receives (atomicMax) the bits of max |out| over everything this launch writes: the
-                                   // power-of-two scale of the NEXT f16-limb gradient launches that read `out` (no separate reduction pass)
-};
-
 __device__ float g_zero_word[4] = {0.0f, 0.0f, 0.0f, 0.0f};   // source of the virtual border
 
 // Epilogue shared by the conv kernels: acc[cb][pb] = 32 output channels (co0 + 32 cb + C/D row) x the 32 pixels of output row y0 + pb.
@@ -329,25 +303,6 @@ __global__ __launch_bounds__(CO_WAVES * PX_WAVES * 64, 2) void conv3x3_kernel(Co
 // Weight fragments are not staged: each wave streams its own two co-blocks from L2 (coalesced 1-KiB reads, 6 per tap).
 // CO_WAVES = 4: the 4 waves take 4 x 2 output blocks of the same PB rows; CO_WAVES = 1 (layers with <= 64 output channels): the 4 waves
 // take the same 2 output blocks of 4 consecutive groups of PB rows.
-#ifndef CV16_WAVES
-#define CV16_WAVES 4
-#endif
-#ifndef CV16_ROWCOST3
-#define CV16_ROWCOST3 1.05   // cost of an output row in a 3-row / 2-row tile of conv3x3_limb16_kernel relative to a 4-row tile (measured: 4.68 / 4.47 ms, 4.93 / 4.47 ms)
-#define CV16_ROWCOST2 1.10
-#endif
-#ifndef CV16_ROWCOST6
-#define CV16_ROWCOST6 0.97   // f16 limbs: cost of an output row in a 6-row tile relative to a 4-row tile (measured on a 1024^2 layer: 2.547 / 2.636 ms)
-#endif
-#ifndef CV_USE_16X16X32
-#define CV_USE_16X16X32 1   // limb layers with Cin % 32 == 0 and Cout % 128 == 0 (all of EDSR's trunk and up-sampling convolutions): 1 = conv3x3_limb16_kernel
-#endif
-#ifndef CV_WIDE_ROWS8
-#define CV_WIDE_ROWS8 0     // wide layers: 1 = one output block x 8 rows per wave, 0 = two output blocks x 2..4 rows (equally fast; see conv3x3_limb_kernel)
-#endif
-#ifndef CV_COST_MODEL
-#define CV_COST_MODEL 2     // rows per tile of the limb convolution: 0 round 1's model, 1 always 4 rows, 2 measured round / row costs (SR stage 31.5 / 32.1 / 32.3 planes/s)
-#endif
 #ifndef CV_ABLATE
 #define CV_ABLATE 0     // variant builds of tools/conv_ablate.sh: 1 weight fragments of tap 0 only, 2 no patch loads, 4 no split + LDS writes
 #endif
@@ -927,7 +882,7 @@ int pack_layers(const float* natural, const ConvLayer* layers, int nl, float* pa
             L.n[2] = conv_packed_limb16_words(ci, co);
             L.n[3] = conv_packed_f16_words(ci, co);
             L.off[0] = 0; L.off[1] = L.n[0]; L.off[2] = L.n[0] + L.n[1]; L.off[3] = L.n[0] + L.n[1] + L.n[2];
-            const unsigned kinds = conv_kinds_for(ci, co, arith, CV_USE_16X16X32 != 0, CV_WIDE_ROWS8 != 0);
+            const unsigned kinds = conv_kinds_for(ci, co, arith);
             for (int q = 0; q < 4; ++q) {
                 if (!(kinds >> q & 1u)) L.n[q] = 0;          // (a region this arithmetic never reads)
                 mx[q] = L.n[q] > mx[q] ? L.n[q] : mx[q];
@@ -1090,40 +1045,72 @@ const unsigned* launch_absmax_ragged(int n, const float* const* x, const long* c
     return owned;
 }
 
+// The one dispatch: every instantiation of the convolution kernels, by the route's (family, limbs, PB).  A route without a kernel is an error.
+constexpr int conv_key(int family, int limbs, int pb) { return (family * 4 + limbs) * 16 + pb; }
+static int dispatch_conv(const ConvRoute& rt, const ConvParams& p, const ConvRagged& rg, hipStream_t stream) {
+    const dim3 grid(rt.grid[0], rt.grid[1], rt.grid[2]), block(rt.block);
+#define CONV_LIMB_CASE(F, L, PB, ...) case conv_key(F, L, PB): hipLaunchKernelGGL((__VA_ARGS__), grid, block, 0, stream, p, rg); break;
+#define CONV_F32_CASE(F, PB, ...) case conv_key(F, 0, PB): hipLaunchKernelGGL((__VA_ARGS__), grid, block, 0, stream, p); break;
+    switch (conv_key(rt.family, rt.limbs, rt.pb)) {
+        CONV_LIMB_CASE(CONV_LIMB_NARROW, 3, 2, conv3x3_limb_kernel<2, 1>)
+        CONV_LIMB_CASE(CONV_LIMB16, 3, 4, conv3x3_limb16_kernel<4, CV16_WAVES, 3>)
+        CONV_LIMB_CASE(CONV_LIMB16, 3, 3, conv3x3_limb16_kernel<3, CV16_WAVES, 3>)
+        CONV_LIMB_CASE(CONV_LIMB16, 3, 2, conv3x3_limb16_kernel<2, CV16_WAVES, 3>)
+        CONV_LIMB_CASE(CONV_LIMB16, 2, 6, conv3x3_limb16_kernel<6, CV16_WAVES, 2>)
+        CONV_LIMB_CASE(CONV_LIMB16, 2, 4, conv3x3_limb16_kernel<4, CV16_WAVES, 2>)
+        CONV_LIMB_CASE(CONV_LIMB16, 2, 3, conv3x3_limb16_kernel<3, CV16_WAVES, 2>)
+        CONV_LIMB_CASE(CONV_LIMB16, 2, 2, conv3x3_limb16_kernel<2, CV16_WAVES, 2>)
+        CONV_LIMB_CASE(CONV_LIMB16, 1, 6, conv3x3_limb16_kernel<6, CV16_WAVES, 1>)
+        CONV_LIMB_CASE(CONV_LIMB16, 1, 4, conv3x3_limb16_kernel<4, CV16_WAVES, 1>)
+        CONV_LIMB_CASE(CONV_LIMB16, 1, 3, conv3x3_limb16_kernel<3, CV16_WAVES, 1>)
+        CONV_LIMB_CASE(CONV_LIMB16, 1, 2, conv3x3_limb16_kernel<2, CV16_WAVES, 1>)
+        CONV_LIMB_CASE(CONV_LIMB_WIDE8, 3, 8, conv3x3_limb_kernel<8, 4, 1>)
+        CONV_LIMB_CASE(CONV_LIMB_WIDE, 3, 4, conv3x3_limb_kernel<4>)
+        CONV_LIMB_CASE(CONV_LIMB_WIDE, 3, 3, conv3x3_limb_kernel<3>)
+        CONV_LIMB_CASE(CONV_LIMB_WIDE, 3, 2, conv3x3_limb_kernel<2>)
+        CONV_F32_CASE(CONV_F32_WIDE, 4, conv3x3_kernel<4, 1, 4>)
+        CONV_F32_CASE(CONV_F32_WIDE, 3, conv3x3_kernel<4, 1, 3>)
+        CONV_F32_CASE(CONV_F32_WIDE, 2, conv3x3_kernel<4, 1, 2>)
+        CONV_F32_CASE(CONV_F32_NARROW, 0, conv3x3_kernel<1, 8>)
+        default: return NVSR_ERR_SHAPE;
+    }
+#undef CONV_LIMB_CASE
+#undef CONV_F32_CASE
+    return NVSR_CHECK_LAUNCH();
+}
+
 int launch_conv(const float* in, int Cin, int H, int W, const float* wpk, int Cout, int epilogue, const float* skip, float* out,
                 hipStream_t stream, int pad, int batch, ConvExec cx, const ConvRagged* rag) {
     const int arith = conv_resolve_arith(cx.arith);
     if (!conv_arith_ok(arith)) return NVSR_ERR_SHAPE;
+    ConvShape s;
+    ConvRagged rg;          // (a second by-value kernel argument, read with constant indices: inside ConvParams -- which the kernels modify -- the
+                            //  whole parameter struct went to scratch)
     if (rag) {
-        // ragged batch: the grid is laid out for the largest plane (H, W = the maxima), the row count per tile is chosen for the tiles that exist
+        // ragged batch: ConvParams is laid out for the largest plane (H, W = the maxima), the planes' own sizes ride in rg with the border added
         if (rag->n < 1 || rag->n > CONV_RAGGED_MAX || arith == NVSR_ARITH_F32) return NVSR_ERR_SHAPE;
-        batch = rag->n;
+        rg = *rag;
+        s.n = batch = rag->n;
         H = W = 0;
         for (int b = 0; b < rag->n; ++b) {
             if (!rag->in[b] || !rag->out[b] || rag->H[b] + 2 * pad < 3 || rag->W[b] + 2 * pad < 3) return NVSR_ERR_SHAPE;
             if ((epilogue == EPI_RESIDUAL || epilogue == EPI_MASK_SCALE || epilogue == EPI_ADD_CENTER) && !rag->skip[b]) return NVSR_ERR_NULL;
             H = rag->H[b] > H ? rag->H[b] : H;
             W = rag->W[b] > W ? rag->W[b] : W;
+            rg.H[b] = s.rH[b] = rag->H[b] + 2 * pad; rg.W[b] = s.rW[b] = rag->W[b] + 2 * pad;
         }
         in = rag->in[0]; out = rag->out[0]; skip = rag->skip[0];
     }
-    // tiles of a launch with `rows` output rows per tile and gx-pixel column chunks: all planes of a ragged batch, or batch x the one size
-    auto count_tiles = [&](int rows, long per_tile_z) -> long {
-        if (!rag) return (long)((W - 2 + 31) / 32) * ((H - 2 + rows - 1) / rows) * per_tile_z * batch;      // (called below: H, W include the border by then)
-        long t = 0;
-        for (int b = 0; b < rag->n; ++b) t += (long)((rag->W[b] + 2 * pad - 2 + 31) / 32) * ((rag->H[b] + 2 * pad - 2 + rows - 1) / rows) * per_tile_z;
-        return t;
-    };
-    // NVSR_ARITH_F16X2: the forward convolutions of the wide layers (16x16x32 kernel) on 2 f16 limbs; everything else that runs limbs -- the
-    // narrow input / output layers, every data gradient (pad = 2, backward epilogues) -- stays on 3 bf16 limbs
-    // (round 3, end: the data gradients of those layers too -- pad = 2, backward epilogues -- with the scale of the whole dy tensor, absmax_kernel)
-    // NVSR_ARITH_F16: the same launches with the high limb alone (conv3x3_limb16_kernel<.., 1>); the narrow layers run what they run under F16X2
-    const bool f16 = conv_arith_f16(arith), one_limb = arith == NVSR_ARITH_F16;
-    const bool f16_dgrad = f16 && (pad != 0 || epilogue == EPI_MASK_SCALE || epilogue == EPI_ADD_CENTER);
-    if (cx.rows != 0 && (cx.rows < 2 || cx.rows > 4) && cx.rows != 8 && cx.rows != 16 && !(cx.rows >= 18 && cx.rows <= 20) && cx.rows != 22) return NVSR_ERR_SHAPE;
     const long in_bs = (long)Cin * H * W;
-    H += 2 * pad; W += 2 * pad;
-    if (H < 3 || W < 3 || batch < 1 || batch > 1024) return NVSR_ERR_SHAPE;
+    s.H = H += 2 * pad; s.W = W += 2 * pad; s.batch = batch;
+    ConvRoute rt;
+    if (int e = conv_route(Cin, Cout, s, pad, epilogue, arith, cx.rows, &rt)) return e;
+    if (rt.family == CONV_PLANEWISE) {
+        // a layer no limb kernel is eligible for (e.g. 48 -> 128 channels) runs on the exact-f32 kernels, which take no ragged batch
+        for (int b = 0; b < rag->n; ++b)
+            if (int e = launch_conv(rag->in[b], Cin, rag->H[b], rag->W[b], wpk, Cout, epilogue, rag->skip[b], rag->out[b], stream, pad, 1, cx, nullptr)) return e;
+        return NVSR_OK;
+    }
     const int Ho = H - 2, Wo = W - 2;
     const long out_bs = (long)Cout * Ho * Wo;       // (PixelShuffle only permutes the Cout*Ho*Wo elements)
     const long skip_bs = epilogue == EPI_RESIDUAL ? (long)Cout * (Ho + 4) * (Wo + 4)
@@ -1132,208 +1119,95 @@ int launch_conv(const float* in, int Cin, int H, int W, const float* wpk, int Co
     const unsigned* wlimb16 = conv_limb16_eligible(Cin, Cout)
                                   ? reinterpret_cast<const unsigned*>(wpk + conv_packed_f32_floats(Cin, Cout)) + conv_packed_limb_words(Cin, Cout) : nullptr;
     const unsigned* wf16 = wlimb16 ? wlimb16 + conv_packed_limb16_words(Cin, Cout) : nullptr;
-    ConvParams p{in, wpk, wlimb, wlimb16, wf16, nullptr, out, skip, Cin, Cout, H, W, conv_ncb(Cout), conv_nchunks(Cin), epilogue, pad, 1, in_bs, out_bs, skip_bs};
+    ConvParams p{in, wpk, wlimb, wlimb16, wf16, nullptr, out, skip, Cin, Cout, H, W, conv_ncb(Cout), conv_nchunks(Cin), epilogue, pad, rt.ncg, in_bs, out_bs, skip_bs};
     p.out_absmax = cx.out_absmax;
-    ConvRagged rg;          // (a second by-value kernel argument, read with constant indices: inside ConvParams -- which the kernels modify -- the
-                            //  whole parameter struct went to scratch)
-    if (rag) {
-        rg = *rag;
-        for (int b = 0; b < rag->n; ++b) { rg.H[b] += 2 * pad; rg.W[b] += 2 * pad; }
+    if (rag) memcpy(rg.tile0, rt.tile0, sizeof rg.tile0);
+    if (rt.in_scale) {          // f16 data gradient: the scale of the whole dy tensor
+        if (rag && !cx.in_absmax) return NVSR_ERR_NULL;
+        p.absmax = cx.in_absmax ? cx.in_absmax : launch_absmax(in, in_bs * batch, stream);
+        if (!p.absmax) return NVSR_ERR_LAUNCH;
     }
-    // ragged launch: a one-dimensional grid over the planes' tiles, plane after plane (ConvRagged::tile0; no empty tiles)
-    auto ragged_grid = [&](int rows, int ncg) {
-        unsigned t = 0;
-        for (int b = 0; b <= CONV_RAGGED_MAX; ++b) {
-            rg.tile0[b] = b <= rg.n ? t : 0xffffffffu;
-            if (b < rg.n) t += (unsigned)((rg.W[b] - 2 + 31) / 32) * (unsigned)((rg.H[b] - 2 + rows - 1) / rows) * (unsigned)ncg;
-        }
-        for (int b = rg.n; b < CONV_RAGGED_MAX; ++b) rg.tile0[b] = 0xffffffffu;
-        return dim3(t, 1, 1);
-    };
-    if (wlimb && arith != NVSR_ARITH_F32 && p.ncb_total == 2) {
-        // narrow layer: 4 waves x 2 rows each of the same 64 output channels
-        p.ncg = 1;
-        dim3 grid((Wo + 31) / 32, (Ho + 7) / 8, batch);
-        if (rag) grid = ragged_grid(8, 1);
-        hipLaunchKernelGGL((conv3x3_limb_kernel<2, 1>), grid, dim3(256), 0, stream, p, rg);
-        return NVSR_CHECK_LAUNCH();
-    }
-    // rows 16 = the 16x16x32 kernel with its own choice of rows per tile, 18 / 19 / 20 = that kernel with 2 / 3 / 4 rows forced
-    if (cx.rows >= 16 && !(wlimb16 && arith != NVSR_ARITH_F32)) return NVSR_ERR_SHAPE;            // (eligible limb layers only)
-    if (wlimb16 && arith != NVSR_ARITH_F32 && (cx.rows >= 16 || (cx.rows == 0 && CV_USE_16X16X32))) {
-        p.ncg = Cout / (32 * CV16_WAVES);
-        dim3 grid((Wo + 31) / 32, 1, p.ncg * batch);
-        int best_pb = 4;
-        double best_cost = 1e300;
-        // f16 limbs: a 6-row tile too (96 accumulator registers, 2 x 35 KB of LDS: still two workgroups per CU) -- with half the MFMAs per weight
-        // fragment the stream of fragments out of L2 (4 KB per wave and tap) is what a row costs, and 6 rows amortise it over 1.5 x the MFMAs
-        for (int pb = f16 ? 6 : 4; pb >= 2; --pb) {
-            if (pb == 5) continue;
-            // rounds of the 512 workgroup slots x rows x the measured cost of a row in a pb-row tile relative to a 4-row tile (tools/conv_time.py
-            // rows 18 / 19 / 20 on a layer of full rounds); a last round of at most 256 tiles has every CU to itself (~0.62 of a round's time)
-            const long tiles = count_tiles(pb, p.ncg);
-            constexpr long SLOTS = CV16_WAVES == 4 ? 512 : 256;
-            const long full = tiles / SLOTS, rest = tiles % SLOTS;
-            const double rounds = (double)full + (rest == 0 ? 0.0 : (CV16_WAVES == 4 && rest <= 256) ? 0.62 : 1.0);
-            const double cost = rounds * pb * (pb == 6 ? CV16_ROWCOST6 : pb == 4 ? 1.0 : pb == 3 ? CV16_ROWCOST3 : CV16_ROWCOST2);
-            if (cost < best_cost) { best_cost = cost; best_pb = pb; }
-        }
-        if (cx.rows >= 18) best_pb = cx.rows - 16;
-        if (best_pb == 6 && !f16) return NVSR_ERR_SHAPE;
-        {   // NVSR_CV16_ROWS=2|3|4 (environment, read once): force the row count of every launch (tools: per-layer comparison of the variants)
-            static int forced = -1;
-            if (forced < 0) { const char* e = getenv("NVSR_CV16_ROWS"); forced = e ? atoi(e) : 0; }
-            if (((forced >= 2 && forced <= 4) || (forced == 6 && f16)) && cx.rows < 18) best_pb = forced;
-        }
-        grid.y = (Ho + best_pb - 1) / best_pb;
-        if (rag) grid = ragged_grid(best_pb, p.ncg);
-        if (f16) {
-            if (f16_dgrad) {
-                if (rag && !cx.in_absmax) return NVSR_ERR_NULL;
-                p.absmax = cx.in_absmax ? cx.in_absmax : launch_absmax(in, in_bs * batch, stream);
-                if (!p.absmax) return NVSR_ERR_LAUNCH;
+    return dispatch_conv(rt, p, rg, stream);
+}
+
+// The one forward walk over a plan's layers.  tensor(l, b): where the input of layer l of plane b lives (l = 0: the network's input, l = n: its
+// output) -- the activation record of a training forward, or the three rotating buffers of the inference path (sr_core.h).  A residual block's
+// second conv adds the block's input, which the layer before it read.  nrag = 0: one launch per layer for `batch` consecutive planes of P[0]'s
+// size; else one ragged launch per layer for the planes P[0 .. nrag).
+template <class Tensor>
+static int edsr_forward_walk(const EdsrPlan* P, int nrag, int batch, const float* packed, ConvExec cx, hipStream_t stream, Tensor tensor) {
+    for (int l = 0; l < P[0].n; ++l) {
+        const ConvLayer& L = P[0].L[l];
+        const int epi = P[0].epi[l];
+        int e;
+        if (!nrag) {
+            e = launch_conv(tensor(l, 0), L.Cin, P[0].ih[l], P[0].iw[l], packed, L.Cout, epi, epi == EPI_RESIDUAL ? tensor(l - 1, 0) : nullptr,
+                            tensor(l + 1, 0), stream, 0, batch, cx);
+        } else {
+            ConvRagged r;
+            r.n = nrag;
+            for (int b = 0; b < nrag; ++b) {
+                r.H[b] = P[b].ih[l]; r.W[b] = P[b].iw[l];
+                r.in[b] = tensor(l, b); r.out[b] = tensor(l + 1, b); r.skip[b] = epi == EPI_RESIDUAL ? tensor(l - 1, b) : nullptr;
             }
-            if (one_limb) {
-                if (best_pb == 6) hipLaunchKernelGGL((conv3x3_limb16_kernel<6, CV16_WAVES, 1>), grid, dim3(64 * CV16_WAVES), 0, stream, p, rg);
-                else if (best_pb == 4) hipLaunchKernelGGL((conv3x3_limb16_kernel<4, CV16_WAVES, 1>), grid, dim3(64 * CV16_WAVES), 0, stream, p, rg);
-                else if (best_pb == 3) hipLaunchKernelGGL((conv3x3_limb16_kernel<3, CV16_WAVES, 1>), grid, dim3(64 * CV16_WAVES), 0, stream, p, rg);
-                else hipLaunchKernelGGL((conv3x3_limb16_kernel<2, CV16_WAVES, 1>), grid, dim3(64 * CV16_WAVES), 0, stream, p, rg);
-                return NVSR_CHECK_LAUNCH();
-            }
-            if (best_pb == 6) hipLaunchKernelGGL((conv3x3_limb16_kernel<6, CV16_WAVES, 2>), grid, dim3(64 * CV16_WAVES), 0, stream, p, rg);
-            else if (best_pb == 4) hipLaunchKernelGGL((conv3x3_limb16_kernel<4, CV16_WAVES, 2>), grid, dim3(64 * CV16_WAVES), 0, stream, p, rg);
-            else if (best_pb == 3) hipLaunchKernelGGL((conv3x3_limb16_kernel<3, CV16_WAVES, 2>), grid, dim3(64 * CV16_WAVES), 0, stream, p, rg);
-            else hipLaunchKernelGGL((conv3x3_limb16_kernel<2, CV16_WAVES, 2>), grid, dim3(64 * CV16_WAVES), 0, stream, p, rg);
-            return NVSR_CHECK_LAUNCH();
+            e = launch_conv(nullptr, L.Cin, 0, 0, packed, L.Cout, epi, nullptr, nullptr, stream, 0, nrag, cx, &r);
         }
-        if (best_pb == 4) hipLaunchKernelGGL((conv3x3_limb16_kernel<4, CV16_WAVES>), grid, dim3(64 * CV16_WAVES), 0, stream, p, rg);
-        else if (best_pb == 3) hipLaunchKernelGGL((conv3x3_limb16_kernel<3, CV16_WAVES>), grid, dim3(64 * CV16_WAVES), 0, stream, p, rg);
-        else hipLaunchKernelGGL((conv3x3_limb16_kernel<2, CV16_WAVES>), grid, dim3(64 * CV16_WAVES), 0, stream, p, rg);
-        return NVSR_CHECK_LAUNCH();
+        if (e) return e;
+        packed += conv_packed_floats(L.Cin, L.Cout);
     }
-    if (cx.rows == 8 && !(wlimb && arith != NVSR_ARITH_F32 && p.ncb_total % 4 == 0 && p.ncb_total > 2)) return NVSR_ERR_SHAPE;   // (only the wide limb kernel has it)
-    if (wlimb && arith != NVSR_ARITH_F32 && p.ncb_total % 4 == 0 && p.ncb_total > 2 && (cx.rows == 8 || (cx.rows == 0 && CV_WIDE_ROWS8))) {
-        // bf16-limb kernel, 1 output block x 8 rows per wave: 4-wave workgroups of 128 output channels x 8 rows x 32 pixels
-        p.ncg = p.ncb_total / 4;
-        dim3 grid((Wo + 31) / 32, (Ho + 7) / 8, p.ncg * batch);
-        if (rag) grid = ragged_grid(8, p.ncg);
-        hipLaunchKernelGGL((conv3x3_limb_kernel<8, 4, 1>), grid, dim3(256), 0, stream, p, rg);
-        return NVSR_CHECK_LAUNCH();
-    }
-    if (wlimb && arith != NVSR_ARITH_F32) {
-        // bf16-limb kernel: 4-wave workgroups of 256 output channels x PB rows x 32 pixels; same choice of the row count as below
-        p.ncg = p.ncb_total / 8;
-        dim3 grid((Wo + 31) / 32, 1, p.ncg * batch);
-        int best_pb = 4;
-        double best_cost = 1e300;
-        for (int pb = 4; pb >= 2; --pb) {
-            const long tiles = count_tiles(pb, p.ncg);
-#if CV_COST_MODEL == 0
-            const double cost = (double)((tiles + 511) / 512) * pb * (1.0 + 0.03 * (4 - pb));
-#elif CV_COST_MODEL == 1
-            const double cost = pb == 4 ? 0.0 : 1.0;
-#else
-            // rounds of the 512 workgroup slots; a last round of at most 256 tiles has every CU to itself (~0.62 of a full round's time);
-            // per row of a tile, 3-row tiles cost 1.13 x and 2-row tiles 1.39 x a 4-row tile's (their weight stream per MFMA is 4/3, 2 x)
-            const long full = tiles / 512, rest = tiles % 512;
-            const double rounds = (double)full + (rest == 0 ? 0.0 : rest <= 256 ? 0.62 : 1.0);
-            const double cost = rounds * pb * (pb == 4 ? 1.0 : pb == 3 ? 1.13 : 1.39);
-#endif
-            if (cost < best_cost) { best_cost = cost; best_pb = pb; }
-        }
-        if (cx.rows) best_pb = cx.rows;
-        grid.y = (Ho + best_pb - 1) / best_pb;
-        if (rag) grid = ragged_grid(best_pb, p.ncg);
-        if (best_pb == 4) hipLaunchKernelGGL((conv3x3_limb_kernel<4>), grid, dim3(256), 0, stream, p, rg);
-        else if (best_pb == 3) hipLaunchKernelGGL((conv3x3_limb_kernel<3>), grid, dim3(256), 0, stream, p, rg);
-        else hipLaunchKernelGGL((conv3x3_limb_kernel<2>), grid, dim3(256), 0, stream, p, rg);
-        return NVSR_CHECK_LAUNCH();
-    }
-    if (rag) {
-        // a layer no limb kernel is eligible for (e.g. 48 -> 128 channels) runs on the exact-f32 kernels below, which take no ragged batch:
-        // plane after plane
-        for (int b = 0; b < rag->n; ++b)
-            if (int e = launch_conv(rag->in[b], Cin, rag->H[b], rag->W[b], wpk, Cout, epilogue, rag->skip[b], rag->out[b], stream, pad, 1, cx, nullptr)) return e;
-        return NVSR_OK;
-    }
-    if (p.ncb_total >= 8 && p.ncb_total % 8 == 0) {
-        p.ncg = p.ncb_total / 8;
-        dim3 grid((Wo + 31) / 32, (Ho + 7) / 8, p.ncg * batch);
-#if NVSR_CONV_WIDE_4x1
-        // two independent 4-wave workgroups per CU (2 x 80 KB of LDS): one's chunk barrier is covered by the other's MFMAs.
-        // Rows per tile: all tiles of a launch take the same time, so the launch costs ceil(tiles / 512 slots) rounds of `rows` row-times;
-        // pick the row count (4, 3 or 2; fewer rows amortise the weight reads a little worse: +3 % per row dropped) with the cheapest total
-        int best_pb = 4;
-        double best_cost = 1e300;
-        for (int pb = 4; pb >= 2; --pb) {
-            const long tiles = (long)grid.x * ((Ho + pb - 1) / pb) * grid.z;
-            const double cost = (double)((tiles + 511) / 512) * pb * (1.0 + 0.03 * (4 - pb));
-            if (cost < best_cost) { best_cost = cost; best_pb = pb; }
-        }
-        if (cx.rows) best_pb = cx.rows;
-        grid.y = (Ho + best_pb - 1) / best_pb;
-        if (best_pb == 4) hipLaunchKernelGGL((conv3x3_kernel<4, 1, 4>), grid, dim3(256), 0, stream, p);
-        else if (best_pb == 3) hipLaunchKernelGGL((conv3x3_kernel<4, 1, 3>), grid, dim3(256), 0, stream, p);
-        else hipLaunchKernelGGL((conv3x3_kernel<4, 1, 2>), grid, dim3(256), 0, stream, p);
-#else
-        hipLaunchKernelGGL((conv3x3_kernel<4, 2>), grid, dim3(512), 0, stream, p);
-#endif
-    } else {
-        p.ncg = p.ncb_total / 2;
-        dim3 grid((Wo + 31) / 32, (Ho + 31) / 32, p.ncg * batch);
-        hipLaunchKernelGGL((conv3x3_kernel<1, 8>), grid, dim3(512), 0, stream, p);
-    }
-    return NVSR_CHECK_LAUNCH();
+    return NVSR_OK;
+}
+// the training policy: plane b's input x[b], output out[b], everything between in its activation record
+static auto record_tensors(const EdsrPlan* P, const float* const* x, float* const* acts, float* const* out) {
+    return [=](int l, int b) { return l == 0 ? const_cast<float*>(x[b]) : l == P[b].n ? out[b] : acts[b] + P[b].act_off[l]; };
 }
 
 }  // namespace nvsr
 
 using namespace nvsr;
 
+// route hook of the host tests (nvsr_internal.h): the family and packed region of a launch of H x W (rows_per_tile as ConvExec::rows), and the
+// regions the packer writes for that arithmetic
+extern "C" int nvsr_internal_conv_route(int Cin, int Cout, int H, int W, int arithmetic, int rows_per_tile, int* family, int* region, unsigned* packed_kinds) {
+    if (!family || !region || !packed_kinds) return NVSR_ERR_NULL;
+    ConvShape s;
+    s.H = H; s.W = W;
+    ConvRoute r;
+    *packed_kinds = conv_kinds_for(Cin, Cout, arithmetic);
+    *family = *region = -1;
+    if (arithmetic == NVSR_PACK_ALL_ARITHMETICS) return NVSR_OK;          // (no launch runs in "all arithmetics": the packer's answer alone)
+    if (int e = conv_route(Cin, Cout, s, 0, EPI_NONE, arithmetic, rows_per_tile, &r)) return e;
+    *family = r.family; *region = r.region;
+    return NVSR_OK;
+}
+
 extern "C" {
 
 /* one conv layer: weights [Cout][Cin][3][3] (nn.Conv2d layout) -> packed fragments */
 int64_t nvsr_conv3x3_packed_floats(int Cin, int Cout) { return conv_packed_floats(Cin, Cout); }
 
-int nvsr_pack_conv3x3(const float* w, int Cin, int Cout, float* packed, nvsr_stream_t stream) {
+// transposed: the fragments of the layer's data gradient (a Cout -> Cin conv with the flipped, transposed kernel)
+static int pack_conv(const float* w, int Cin, int Cout, float* packed, int transposed, hipStream_t stream) {
     if (!w || !packed) return NVSR_ERR_NULL;
     if (Cin < 1 || Cout < 1) return NVSR_ERR_SHAPE;
     if (!aligned16(packed)) return NVSR_ERR_ALIGN;
-    const int64_t n = conv_packed_f32_floats(Cin, Cout);
-    hipLaunchKernelGGL(pack_conv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, packed, Cin, Cout,
-                       conv_ncb(Cout), conv_nchunks(Cin), 0);
-    if (const int64_t nl = conv_packed_limb_words(Cin, Cout))
-        hipLaunchKernelGGL(pack_conv_limbs_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w,
-                           reinterpret_cast<unsigned*>(packed + n), Cin, Cout, conv_ncb(Cout), 0);
-    if (const int64_t n16 = conv_packed_limb16_words(Cin, Cout)) {
-        unsigned* r16 = reinterpret_cast<unsigned*>(packed + n) + conv_packed_limb_words(Cin, Cout);
-        hipLaunchKernelGGL(pack_conv_limbs16_kernel<3>, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, r16, Cin, Cout, 0);
-        const int64_t nf = conv_packed_f16_words(Cin, Cout);
-        hipLaunchKernelGGL(pack_conv_limbs16_kernel<2>, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, r16 + n16, Cin, Cout, 0);
+    const int ci = transposed ? Cout : Cin, co = transposed ? Cin : Cout;          // the packed conv's own (Cin, Cout)
+    const int64_t n = conv_packed_f32_floats(ci, co);
+    hipLaunchKernelGGL(pack_conv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, packed, ci, co, conv_ncb(co), conv_nchunks(ci), transposed);
+    if (const int64_t nl = conv_packed_limb_words(ci, co))
+        hipLaunchKernelGGL(pack_conv_limbs_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, stream, w, reinterpret_cast<unsigned*>(packed + n), ci, co,
+                           conv_ncb(co), transposed);
+    if (const int64_t n16 = conv_packed_limb16_words(ci, co)) {
+        unsigned* r16 = reinterpret_cast<unsigned*>(packed + n) + conv_packed_limb_words(ci, co);
+        hipLaunchKernelGGL(pack_conv_limbs16_kernel<3>, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, stream, w, r16, ci, co, transposed);
+        const int64_t nf = conv_packed_f16_words(ci, co);
+        hipLaunchKernelGGL(pack_conv_limbs16_kernel<2>, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, stream, w, r16 + n16, ci, co, transposed);
     }
     return NVSR_CHECK_LAUNCH();
 }
-
-/* weights [Cout][Cin][3][3] of a conv -> packed fragments of its data gradient (a Cout -> Cin conv with the flipped, transposed
- * kernel); nvsr_conv3x3_packed_floats(Cout, Cin) floats */
-int nvsr_pack_conv3x3_dgrad(const float* w, int Cin, int Cout, float* packed, nvsr_stream_t stream) {
-    if (!w || !packed) return NVSR_ERR_NULL;
-    if (Cin < 1 || Cout < 1) return NVSR_ERR_SHAPE;
-    if (!aligned16(packed)) return NVSR_ERR_ALIGN;
-    const int64_t n = conv_packed_f32_floats(Cout, Cin);
-    hipLaunchKernelGGL(pack_conv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, packed, Cout, Cin,
-                       conv_ncb(Cin), conv_nchunks(Cout), 1);
-    if (const int64_t nl = conv_packed_limb_words(Cout, Cin))
-        hipLaunchKernelGGL(pack_conv_limbs_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w,
-                           reinterpret_cast<unsigned*>(packed + n), Cout, Cin, conv_ncb(Cin), 1);
-    if (const int64_t n16 = conv_packed_limb16_words(Cout, Cin)) {
-        unsigned* r16 = reinterpret_cast<unsigned*>(packed + n) + conv_packed_limb_words(Cout, Cin);
-        hipLaunchKernelGGL(pack_conv_limbs16_kernel<3>, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, r16, Cout, Cin, 1);
-        const int64_t nf = conv_packed_f16_words(Cout, Cin);
-        hipLaunchKernelGGL(pack_conv_limbs16_kernel<2>, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, r16 + n16, Cout, Cin, 1);
-    }
-    return NVSR_CHECK_LAUNCH();
-}
+int nvsr_pack_conv3x3(const float* w, int Cin, int Cout, float* packed, nvsr_stream_t stream) { return pack_conv(w, Cin, Cout, packed, 0, (hipStream_t)stream); }
+/* weights [Cout][Cin][3][3] of a conv -> packed fragments of its data gradient; nvsr_conv3x3_packed_floats(Cout, Cin) floats */
+int nvsr_pack_conv3x3_dgrad(const float* w, int Cin, int Cout, float* packed, nvsr_stream_t stream) { return pack_conv(w, Cin, Cout, packed, 1, (hipStream_t)stream); }
 
 /* data gradient of nvsr_conv3x3 (epilogue 0): dy [Cout][H-2][W-2] -> dx [Cin][H][W]; packed_dgrad from nvsr_pack_conv3x3_dgrad */
 int nvsr_conv3x3_dgrad_arith(const float* dy, int Cin, int H, int W, const float* packed_dgrad, int Cout, float* dx, int arithmetic,
@@ -1370,8 +1244,8 @@ int64_t nvsr_edsr_natural_floats(int Cin, int Cout, int hid, int nblocks, int n_
     return 9LL * ((int64_t)hid * Cin + (2LL * nblocks + 1) * hid * hid + (int64_t)n_up * 4 * hid * hid + (int64_t)Cout * hid);
 }
 int64_t nvsr_edsr_packed_floats(int Cin, int Cout, int hid, int nblocks, int n_up) {
-    ConvLayer L[600]; int n;
-    if (nblocks < 0 || nblocks > 290 || n_up < 0 || n_up > 8) return -1;
+    ConvLayer L[EDSR_MAX_LAYERS]; int n;
+    if (!edsr_geometry_ok(nblocks, n_up)) return -1;
     edsr_layers(Cin, Cout, hid, nblocks, n_up, L, &n);
     int64_t s = 0;
     for (int i = 0; i < n; ++i) s += conv_packed_floats(L[i].Cin, L[i].Cout);
@@ -1379,13 +1253,13 @@ int64_t nvsr_edsr_packed_floats(int Cin, int Cout, int hid, int nblocks, int n_u
 }
 int nvsr_pack_edsr_arith(const float* natural, int Cin, int Cout, int hid, int nblocks, int n_up, float* packed, int arithmetic, nvsr_stream_t stream) {
     if (!natural || !packed) return NVSR_ERR_NULL;
-    if (nvsr_edsr_packed_floats(Cin, Cout, hid, nblocks, n_up) < 0) return NVSR_ERR_SHAPE;
+    if (!edsr_geometry_ok(nblocks, n_up)) return NVSR_ERR_SHAPE;
     if (!aligned16(packed)) return NVSR_ERR_ALIGN;
     if (arithmetic != NVSR_PACK_ALL_ARITHMETICS) {
         arithmetic = conv_resolve_arith(arithmetic);
         if (!conv_arith_ok(arithmetic)) return NVSR_ERR_SHAPE;
     }
-    ConvLayer L[600]; int n;
+    ConvLayer L[EDSR_MAX_LAYERS]; int n;
     edsr_layers(Cin, Cout, hid, nblocks, n_up, L, &n);
     return pack_layers(natural, L, n, packed, 0, (hipStream_t)stream, arithmetic);       // (4 launches per 36 layers instead of 4 per layer)
 }
@@ -1395,21 +1269,14 @@ int nvsr_pack_edsr(const float* natural, int Cin, int Cout, int hid, int nblocks
 
 /* spatial size of the EDSR output for an [*, H, W] input */
 int nvsr_edsr_out_size(int H, int W, int nblocks, int n_up, int* Ho, int* Wo) {
-    int64_t h = (int64_t)H - 2 - 4 * nblocks - 2, w = (int64_t)W - 2 - 4 * nblocks - 2;
-    for (int u = 0; u < n_up; ++u) { h = (h - 2) * 2; w = (w - 2) * 2; }
-    h -= 2; w -= 2;
-    if (h < 1 || w < 1) return NVSR_ERR_SHAPE;
-    *Ho = (int)h; *Wo = (int)w;
+    const EdsrExtent x = edsr_extent(H, W, 1, nblocks, n_up);
+    if (x.Ho < 1 || x.Wo < 1) return NVSR_ERR_SHAPE;
+    *Ho = (int)x.Ho; *Wo = (int)x.Wo;
     return NVSR_OK;
 }
 
-/* two ping-pong activation buffers sized for the largest intermediate */
-int64_t nvsr_edsr_workspace_floats(int hid, int nblocks, int n_up, int H, int W) {
-    int64_t h = H - 2, w = W - 2, mx = (int64_t)hid * h * w;
-    h -= 4 * nblocks + 2; w -= 4 * nblocks + 2;
-    for (int u = 0; u < n_up; ++u) { h = (h - 2) * 2; w = (w - 2) * 2; if ((int64_t)hid * h * w > mx) mx = (int64_t)hid * h * w; }
-    return 3 * mx;
-}
+/* three rotating activation buffers sized for the largest intermediate */
+int64_t nvsr_edsr_workspace_floats(int hid, int nblocks, int n_up, int H, int W) { return 3 * edsr_extent(H, W, hid, nblocks, n_up).max_rotating; }
 
 /* B planes at once ([B][Cin][H][W] -> [B][Cout][Ho][Wo]): one launch per layer, the batch index rides in the grid.  A 256-channel
  * layer of one 200^2 plane is only ~1.2-1.8 workgroup rounds on 256 CUs (28 % of the issue slots idle in the partial last round);
@@ -1418,41 +1285,12 @@ int nvsr_edsr_forward_batch_arith(const float* x, int B, int Cin, int H, int W, 
                                   float* out, float* workspace, int arithmetic, nvsr_stream_t stream_) {
     if (!x || !packed || !out || !workspace) return NVSR_ERR_NULL;
     if (B < 1) return NVSR_ERR_SHAPE;
-    const ConvExec cx{conv_resolve_arith(arithmetic), 0};
-    int Ho, Wo;
-    if (int e = nvsr_edsr_out_size(H, W, nblocks, n_up, &Ho, &Wo)) return e;
-    hipStream_t stream = (hipStream_t)stream_;
-    const int64_t third = nvsr_edsr_workspace_floats(hid, nblocks, n_up, H, W) / 3 * B;
-    float* bufs[3] = {workspace, workspace + third, workspace + 2 * third};
-    const float* wp = packed;
-    int h = H, w = W, e;
-    // conv_input
-    float* cur = bufs[0];
-    if ((e = launch_conv(x, Cin, h, w, wp, hid, EPI_NONE, nullptr, cur, stream, 0, B, cx))) return e;
-    wp += conv_packed_floats(Cin, hid); h -= 2; w -= 2;
-    int ci = 0;                                   // index of `cur` in bufs
-    for (int b = 0; b < nblocks; ++b) {           // _Residual_Block (models.py:777-786)
-        float* t1 = bufs[(ci + 1) % 3];
-        float* t2 = bufs[(ci + 2) % 3];
-        if ((e = launch_conv(cur, hid, h, w, wp, hid, EPI_RELU, nullptr, t1, stream, 0, B, cx))) return e;
-        wp += conv_packed_floats(hid, hid);
-        if ((e = launch_conv(t1, hid, h - 2, w - 2, wp, hid, EPI_RESIDUAL, cur, t2, stream, 0, B, cx))) return e;
-        wp += conv_packed_floats(hid, hid);
-        cur = t2; ci = (ci + 2) % 3; h -= 4; w -= 4;
-    }
-    {   // conv_mid
-        float* t = bufs[(ci + 1) % 3];
-        if ((e = launch_conv(cur, hid, h, w, wp, hid, EPI_NONE, nullptr, t, stream, 0, B, cx))) return e;
-        wp += conv_packed_floats(hid, hid);
-        cur = t; ci = (ci + 1) % 3; h -= 2; w -= 2;
-    }
-    for (int u = 0; u < n_up; ++u) {              // conv hid -> 4 hid + PixelShuffle(2), fused
-        float* t = bufs[(ci + 1) % 3];
-        if ((e = launch_conv(cur, hid, h, w, wp, 4 * hid, EPI_PIXEL_SHUFFLE, nullptr, t, stream, 0, B, cx))) return e;
-        wp += conv_packed_floats(hid, 4 * hid);
-        cur = t; ci = (ci + 1) % 3; h = (h - 2) * 2; w = (w - 2) * 2;
-    }
-    return launch_conv(cur, hid, h, w, wp, Cout, EPI_NONE, nullptr, out, stream, 0, B, cx);
+    EdsrPlan P;
+    if (int e = edsr_plan(Cin, Cout, hid, nblocks, n_up, H, W, &P)) return e;
+    const int64_t third = edsr_extent(H, W, hid, nblocks, n_up).max_rotating * B;
+    return edsr_forward_walk(&P, 0, B, packed, ConvExec{conv_resolve_arith(arithmetic), 0}, (hipStream_t)stream_, [&](int l, int) {
+        return l == 0 ? const_cast<float*>(x) : l == P.n ? out : workspace + edsr_rotating_slot(l) * third;
+    });
 }
 int nvsr_edsr_forward_batch(const float* x, int B, int Cin, int H, int W, const float* packed, int Cout, int hid, int nblocks, int n_up,
                             float* out, float* workspace, nvsr_stream_t stream_) {
@@ -1478,52 +1316,30 @@ int nvsr_edsr_forward_train(const float* x, int Cin, int H, int W, const float* 
 int nvsr_edsr_forward_train_arith(const float* x, int Cin, int H, int W, const float* packed, int Cout, int hid, int nblocks, int n_up, float* out,
                                   float* acts, int arithmetic, nvsr_stream_t stream_) {
     if (!x || !packed || !out || !acts) return NVSR_ERR_NULL;
-    const ConvExec cx{conv_resolve_arith(arithmetic), 0};
     if (!aligned16(packed)) return NVSR_ERR_ALIGN;
     EdsrPlan P;
     if (int e = edsr_plan(Cin, Cout, hid, nblocks, n_up, H, W, &P)) return e;
-    const float* wp = packed;
-    for (int l = 0; l < P.n; ++l) {
-        const float* in = l ? acts + P.act_off[l] : x;
-        float* o = (l + 1 < P.n) ? acts + P.act_off[l + 1] : out;
-        const float* skip = (P.epi[l] == EPI_RESIDUAL) ? (l >= 2 ? acts + P.act_off[l - 1] : x) : nullptr;   // the block's input
-        if (int e = launch_conv(in, P.L[l].Cin, P.ih[l], P.iw[l], wp, P.L[l].Cout, P.epi[l], skip, o, (hipStream_t)stream_, 0, 1, cx)) return e;
-        wp += conv_packed_floats(P.L[l].Cin, P.L[l].Cout);
-    }
-    return NVSR_OK;
+    return edsr_forward_walk(&P, 0, 1, packed, ConvExec{conv_resolve_arith(arithmetic), 0}, (hipStream_t)stream_, record_tensors(&P, &x, &acts, &out));
 }
 
 /* PlanesSR.forward (models.py:884-926).  lr [C][R0][R1]; roi = NULL (full plane) or 4 HOST floats [[ymin,xmin],[ymax,xmax]] in
  * [-1,1]; pad = inner_model.required_padding, over = HR_overpadding; mean/std optional [C] (device).
  * out [C][sf*R0][sf*R1] (NaN outside the ROI).  workspace: nvsr_planes_sr_workspace_floats(...) floats. */
 int64_t nvsr_planes_sr_workspace_floats(int Cc, int R0, int R1, int hid, int nblocks, int n_up, int pad, const float* roi) {
-    int lo[2], hi[2];
-    sr_roi(R0, R1, roi, lo, hi);
-    const int Hp = hi[0] - lo[0] + 2 * pad, Wp = hi[1] - lo[1] + 2 * pad;
-    int Ho, Wo;
-    if (nvsr_edsr_out_size(Hp, Wp, nblocks, n_up, &Ho, &Wo)) return -1;
-    return (int64_t)Cc * Hp * Wp + (int64_t)Cc * Ho * Wo + nvsr_edsr_workspace_floats(hid, nblocks, n_up, Hp, Wp);
+    SrRegions g;
+    if (sr_regions(1, Cc, R0, R1, hid, nblocks, n_up, pad, -1, roi, nullptr, &g)) return -1;
+    return g.p[0].inf_ews(1) + nvsr_edsr_workspace_floats(hid, nblocks, n_up, g.p[0].Hp, g.p[0].Wp);
+}
+/* floats kept between nvsr_planes_sr_train and nvsr_planes_sr_backward: the prepared network input + the activation record */
+int64_t nvsr_planes_sr_keep_floats(int Cc, int R0, int R1, int hid, int nblocks, int n_up, int pad, const float* roi) {
+    return nvsr_planes_sr_batch_keep_floats(1, Cc, R0, R1, hid, nblocks, n_up, pad, roi);
 }
 
-/* B planes of the same size through the SR network in one batch (the 3 position planes of a scene, models.py:289-310).
- * lr / out: HOST arrays of B device pointers.  workspace: B * nvsr_planes_sr_workspace_floats(...) floats. */
-int nvsr_planes_sr_batch(const float* const* lr, int B, int Cc, int R0, int R1, const float* packed, int hid, int nblocks, int n_up, int pad,
-                         int over, const float* roi, const float* mean, const float* stdv, float* const* out, float* workspace,
-                         nvsr_stream_t stream_) {
-    return nvsr_planes_sr_batch_arith(lr, B, Cc, R0, R1, packed, hid, nblocks, n_up, pad, over, roi, mean, stdv, out, workspace, NVSR_ARITH_INHERIT,
-                                      stream_);
-}
-int nvsr_planes_sr_batch_arith(const float* const* lr, int B, int Cc, int R0, int R1, const float* packed, int hid, int nblocks, int n_up, int pad,
-                               int over, const float* roi, const float* mean, const float* stdv, float* const* out, float* workspace,
-                               int arithmetic, nvsr_stream_t stream_) {
-    return nvsr_planes_sr_batch_ex(lr, B, Cc, R0, R1, packed, hid, nblocks, n_up, pad, over, roi, mean, stdv, out, workspace, arithmetic,
-                                   sr_align_corners(), sr_bicubic() ? NVSR_PLANE_INTERP_BICUBIC : NVSR_PLANE_INTERP_BILINEAR, stream_);
-}
-/* the same with align_corners / plane_interp of the residual up-sampling as ARGUMENTS (re-entrant: two PlanesSR models with different settings
- * in one process, backward passes on other threads and streams -- ADVICE r4) */
-int nvsr_planes_sr_batch_ex(const float* const* lr, int B, int Cc, int R0, int R1, const float* packed, int hid, int nblocks, int n_up, int pad,
-                            int over, const float* roi, const float* mean, const float* stdv, float* const* out, float* workspace,
-                            int arithmetic, int align_corners, int plane_interp, nvsr_stream_t stream_) {
+/* The forward of B planes of the SAME region: the inference entry points (keep = NULL: B planes in one batch through the rotating buffers;
+ * workspace B * nvsr_planes_sr_workspace_floats) and the one-plane training forward (B = 1, keep: the prepared input + the activation record) */
+static int planes_sr_forward(const float* const* lr, int B, int Cc, int R0, int R1, const float* packed, int hid, int nblocks, int n_up, int pad,
+                             int over, const float* roi, const float* mean, const float* stdv, float* const* out, float* workspace, float* keep,
+                             int arithmetic, int align_corners, int plane_interp, nvsr_stream_t stream_) {
     if (!lr || !packed || !out || !workspace) return NVSR_ERR_NULL;
     if (plane_interp != NVSR_PLANE_INTERP_BILINEAR && plane_interp != NVSR_PLANE_INTERP_BICUBIC) return NVSR_ERR_SHAPE;
     if ((mean == nullptr) != (stdv == nullptr)) return NVSR_ERR_NULL;
@@ -1531,101 +1347,78 @@ int nvsr_planes_sr_batch_ex(const float* const* lr, int B, int Cc, int R0, int R
     for (int b = 0; b < B; ++b)
         if (!lr[b] || !out[b]) return NVSR_ERR_NULL;
     hipStream_t stream = (hipStream_t)stream_;
-    const int sf = 1 << n_up;
-    int lo[2], hi[2];
-    sr_roi(R0, R1, roi, lo, hi);
-    const int ch = hi[0] - lo[0], cw = hi[1] - lo[1];
-    const int Hp = ch + 2 * pad, Wp = cw + 2 * pad;
-    int Ho, Wo;
-    if (int e = nvsr_edsr_out_size(Hp, Wp, nblocks, n_up, &Ho, &Wo)) return e;
-    if (Ho != ch * sf + 2 * over || Wo != cw * sf + 2 * over) return NVSR_ERR_SHAPE;
-    const int64_t n_in = (int64_t)Cc * Hp * Wp, n_diff = (int64_t)Cc * Ho * Wo;
-    float* xin = workspace;                       // [B][C][Hp][Wp]
-    float* diff = xin + B * n_in;                 // [B][C][Ho][Wo]
-    float* ews = diff + B * n_diff;
+    SrRegions g;
+    if (int e = sr_regions(1, Cc, R0, R1, hid, nblocks, n_up, pad, over, roi, nullptr, &g)) return e;
+    const SrPlane& s = g.p[0];
+    float* xin = keep ? keep + s.keep_xin : workspace;        // [B][C][Hp][Wp]
+    float* diff = workspace + s.inf_diff(B);                  // [B][C][Ho][Wo]
     for (int b = 0; b < B; ++b) {
-        hipLaunchKernelGGL(sr_prepare_kernel, dim3((unsigned)((n_in + 255) / 256)), dim3(256), 0, stream, lr[b], Cc, R0, R1, lo[0], lo[1], Hp,
-                           Wp, pad, mean, stdv, xin + b * n_in);
+        hipLaunchKernelGGL(sr_prepare_kernel, dim3((unsigned)((s.n_in + 255) / 256)), dim3(256), 0, stream, lr[b], Cc, R0, R1, s.lo[0], s.lo[1], s.Hp,
+                           s.Wp, pad, mean, stdv, xin + b * s.n_in);
         if (int e = NVSR_CHECK_LAUNCH()) return e;
     }
-    if (int e = nvsr_edsr_forward_batch_arith(xin, B, Cc, Hp, Wp, packed, Cc, hid, nblocks, n_up, diff, ews, arithmetic, stream_)) return e;
+    if (int e = keep ? nvsr_edsr_forward_train_arith(xin, Cc, s.Hp, s.Wp, packed, Cc, hid, nblocks, n_up, diff, keep + s.keep_acts, arithmetic, stream_)
+                     : nvsr_edsr_forward_batch_arith(xin, B, Cc, s.Hp, s.Wp, packed, Cc, hid, nblocks, n_up, diff, workspace + s.inf_ews(B), arithmetic, stream_))
+        return e;
+    const int sf = 1 << n_up;
     const int64_t n_out = (int64_t)Cc * R0 * sf * R1 * sf;
     for (int b = 0; b < B; ++b) {
-        hipLaunchKernelGGL(sr_finish_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, stream, diff + b * n_diff, Ho, Wo, over, lr[b],
-                           Cc, R0, R1, sf, lo[0], lo[1], hi[0], hi[1], out[b], conv_arith_f16(conv_resolve_arith(arithmetic)) ? nvsr_get_range_flag() : nullptr,
+        hipLaunchKernelGGL(sr_finish_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, stream, diff + b * s.n_diff, s.Ho, s.Wo, over, lr[b],
+                           Cc, R0, R1, sf, s.lo[0], s.lo[1], s.hi[0], s.hi[1], out[b], conv_arith_f16(conv_resolve_arith(arithmetic)) ? nvsr_get_range_flag() : nullptr,
                            align_corners ? 1 : 0, plane_interp == NVSR_PLANE_INTERP_BICUBIC ? 1 : 0);
         if (int e = NVSR_CHECK_LAUNCH()) return e;
     }
     return NVSR_OK;
 }
+static int sr_plane_interp() { return sr_bicubic() ? NVSR_PLANE_INTERP_BICUBIC : NVSR_PLANE_INTERP_BILINEAR; }
 
-/* floats kept between nvsr_planes_sr_train and nvsr_planes_sr_backward: the prepared network input + the activation record */
-int64_t nvsr_planes_sr_keep_floats(int Cc, int R0, int R1, int hid, int nblocks, int n_up, int pad, const float* roi) {
-    int lo[2], hi[2];
-    sr_roi(R0, R1, roi, lo, hi);
-    const int Hp = hi[0] - lo[0] + 2 * pad, Wp = hi[1] - lo[1] + 2 * pad;
-    const int64_t a = nvsr_edsr_acts_floats(Cc, Cc, hid, nblocks, n_up, Hp, Wp);
-    if (a < 0) return -1;
-    return ((int64_t)Cc * Hp * Wp + 3) / 4 * 4 + a;
+/* B planes of the same size through the SR network in one batch (the 3 position planes of a scene, models.py:289-310).
+ * lr / out: HOST arrays of B device pointers.  workspace: B * nvsr_planes_sr_workspace_floats(...) floats. */
+int nvsr_planes_sr_batch(const float* const* lr, int B, int Cc, int R0, int R1, const float* packed, int hid, int nblocks, int n_up, int pad,
+                         int over, const float* roi, const float* mean, const float* stdv, float* const* out, float* workspace,
+                         nvsr_stream_t stream_) {
+    return planes_sr_forward(lr, B, Cc, R0, R1, packed, hid, nblocks, n_up, pad, over, roi, mean, stdv, out, workspace, nullptr, NVSR_ARITH_INHERIT,
+                             sr_align_corners(), sr_plane_interp(), stream_);
 }
-
-static int planes_sr_impl(const float* lr, int Cc, int R0, int R1, const float* packed, int hid, int nblocks, int n_up, int pad, int over,
-                          const float* roi, const float* mean, const float* stdv, float* out, float* workspace, float* keep,
-                          int arithmetic, nvsr_stream_t stream_);
+int nvsr_planes_sr_batch_arith(const float* const* lr, int B, int Cc, int R0, int R1, const float* packed, int hid, int nblocks, int n_up, int pad,
+                               int over, const float* roi, const float* mean, const float* stdv, float* const* out, float* workspace,
+                               int arithmetic, nvsr_stream_t stream_) {
+    return planes_sr_forward(lr, B, Cc, R0, R1, packed, hid, nblocks, n_up, pad, over, roi, mean, stdv, out, workspace, nullptr, arithmetic,
+                             sr_align_corners(), sr_plane_interp(), stream_);
+}
+/* the same with align_corners / plane_interp of the residual up-sampling as ARGUMENTS (re-entrant: two PlanesSR models with different settings
+ * in one process, backward passes on other threads and streams -- ADVICE r4) */
+int nvsr_planes_sr_batch_ex(const float* const* lr, int B, int Cc, int R0, int R1, const float* packed, int hid, int nblocks, int n_up, int pad,
+                            int over, const float* roi, const float* mean, const float* stdv, float* const* out, float* workspace,
+                            int arithmetic, int align_corners, int plane_interp, nvsr_stream_t stream_) {
+    return planes_sr_forward(lr, B, Cc, R0, R1, packed, hid, nblocks, n_up, pad, over, roi, mean, stdv, out, workspace, nullptr, arithmetic,
+                             align_corners, plane_interp, stream_);
+}
 
 int nvsr_planes_sr(const float* lr, int Cc, int R0, int R1, const float* packed, int hid, int nblocks, int n_up, int pad, int over,
                    const float* roi, const float* mean, const float* stdv, float* out, float* workspace, nvsr_stream_t stream_) {
-    return planes_sr_impl(lr, Cc, R0, R1, packed, hid, nblocks, n_up, pad, over, roi, mean, stdv, out, workspace, nullptr, NVSR_ARITH_INHERIT, stream_);
+    return nvsr_planes_sr_arith(lr, Cc, R0, R1, packed, hid, nblocks, n_up, pad, over, roi, mean, stdv, out, workspace, NVSR_ARITH_INHERIT, stream_);
 }
 int nvsr_planes_sr_arith(const float* lr, int Cc, int R0, int R1, const float* packed, int hid, int nblocks, int n_up, int pad, int over,
                          const float* roi, const float* mean, const float* stdv, float* out, float* workspace, int arithmetic,
                          nvsr_stream_t stream_) {
-    return planes_sr_impl(lr, Cc, R0, R1, packed, hid, nblocks, n_up, pad, over, roi, mean, stdv, out, workspace, nullptr, arithmetic, stream_);
+    if (!lr || !out) return NVSR_ERR_NULL;
+    return planes_sr_forward(&lr, 1, Cc, R0, R1, packed, hid, nblocks, n_up, pad, over, roi, mean, stdv, &out, workspace, nullptr, arithmetic,
+                             sr_align_corners(), sr_plane_interp(), stream_);
 }
 
 /* nvsr_planes_sr that keeps what the backward needs in `keep` (nvsr_planes_sr_keep_floats floats); same workspace */
 int nvsr_planes_sr_train(const float* lr, int Cc, int R0, int R1, const float* packed, int hid, int nblocks, int n_up, int pad, int over,
                          const float* roi, const float* mean, const float* stdv, float* out, float* workspace, float* keep,
                          nvsr_stream_t stream_) {
-    if (!keep) return NVSR_ERR_NULL;
-    return planes_sr_impl(lr, Cc, R0, R1, packed, hid, nblocks, n_up, pad, over, roi, mean, stdv, out, workspace, keep, NVSR_ARITH_INHERIT, stream_);
+    return nvsr_planes_sr_train_arith(lr, Cc, R0, R1, packed, hid, nblocks, n_up, pad, over, roi, mean, stdv, out, workspace, keep, NVSR_ARITH_INHERIT, stream_);
 }
 int nvsr_planes_sr_train_arith(const float* lr, int Cc, int R0, int R1, const float* packed, int hid, int nblocks, int n_up, int pad, int over,
                                const float* roi, const float* mean, const float* stdv, float* out, float* workspace, float* keep,
                                int arithmetic, nvsr_stream_t stream_) {
-    if (!keep) return NVSR_ERR_NULL;
-    return planes_sr_impl(lr, Cc, R0, R1, packed, hid, nblocks, n_up, pad, over, roi, mean, stdv, out, workspace, keep, arithmetic, stream_);
-}
-
-static int planes_sr_impl(const float* lr, int Cc, int R0, int R1, const float* packed, int hid, int nblocks, int n_up, int pad, int over,
-                          const float* roi, const float* mean, const float* stdv, float* out, float* workspace, float* keep,
-                          int arithmetic, nvsr_stream_t stream_) {
-    if (!lr || !packed || !out || !workspace) return NVSR_ERR_NULL;
-    if ((mean == nullptr) != (stdv == nullptr)) return NVSR_ERR_NULL;
-    hipStream_t stream = (hipStream_t)stream_;
-    const int sf = 1 << n_up;
-    int lo[2], hi[2];
-    sr_roi(R0, R1, roi, lo, hi);
-    const int ch = hi[0] - lo[0], cw = hi[1] - lo[1];
-    const int Hp = ch + 2 * pad, Wp = cw + 2 * pad;
-    int Ho, Wo;
-    if (int e = nvsr_edsr_out_size(Hp, Wp, nblocks, n_up, &Ho, &Wo)) return e;
-    if (Ho != ch * sf + 2 * over || Wo != cw * sf + 2 * over) return NVSR_ERR_SHAPE;   // pad/over inconsistent with the net
-    float* xin = keep ? keep : workspace;
-    float* diff = workspace + (int64_t)Cc * Hp * Wp;
-    float* ews = diff + (int64_t)Cc * Ho * Wo;
-    const int64_t n_in = (int64_t)Cc * Hp * Wp;
-    hipLaunchKernelGGL(sr_prepare_kernel, dim3((unsigned)((n_in + 255) / 256)), dim3(256), 0, stream, lr, Cc, R0, R1, lo[0], lo[1], Hp, Wp,
-                       pad, mean, stdv, xin);
-    if (int e = NVSR_CHECK_LAUNCH()) return e;
-    if (keep) {
-        if (int e = nvsr_edsr_forward_train_arith(xin, Cc, Hp, Wp, packed, Cc, hid, nblocks, n_up, diff, keep + ((int64_t)Cc * Hp * Wp + 3) / 4 * 4, arithmetic, stream_))
-            return e;
-    } else if (int e = nvsr_edsr_forward_batch_arith(xin, 1, Cc, Hp, Wp, packed, Cc, hid, nblocks, n_up, diff, ews, arithmetic, stream_)) return e;
-    const int64_t n_out = (int64_t)Cc * R0 * sf * R1 * sf;
-    hipLaunchKernelGGL(sr_finish_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, stream, diff, Ho, Wo, over, lr, Cc, R0, R1, sf,
-                       lo[0], lo[1], hi[0], hi[1], out, conv_arith_f16(conv_resolve_arith(arithmetic)) ? nvsr_get_range_flag() : nullptr, sr_align_corners(), sr_bicubic());
-    return NVSR_CHECK_LAUNCH();
+    if (!keep || !lr || !out) return NVSR_ERR_NULL;
+    return planes_sr_forward(&lr, 1, Cc, R0, R1, packed, hid, nblocks, n_up, pad, over, roi, mean, stdv, &out, workspace, keep, arithmetic,
+                             sr_align_corners(), sr_plane_interp(), stream_);
 }
 
 
@@ -1634,36 +1427,15 @@ static int planes_sr_impl(const float* lr, int Cc, int R0, int R1, const float* 
  * NULL (full planes).  keep: ONE buffer of nvsr_planes_sr_batch_keep_floats floats (plane after plane: prepared input + activation record);
  * workspace: nvsr_planes_sr_batch_workspace_floats floats.  align_corners / plane_interp of the residual up-sampling are ARGUMENTS here
  * (the one-plane entry points read the process-wide setting).  B <= 4. */
-static int batch_geometry(int B, int Cc, int R0, int R1, int hid, int nblocks, int n_up, int pad, const float* rois, int (*lo)[2], int (*hi)[2],
-                          int* Hp, int* Wp, EdsrPlan* P) {
-    if (B < 1 || B > CONV_RAGGED_MAX) return NVSR_ERR_SHAPE;
-    for (int b = 0; b < B; ++b) {
-        sr_roi(R0, R1, rois ? rois + 4 * b : nullptr, lo[b], hi[b]);
-        Hp[b] = hi[b][0] - lo[b][0] + 2 * pad; Wp[b] = hi[b][1] - lo[b][1] + 2 * pad;
-        if (P) { if (int e = edsr_plan(Cc, Cc, hid, nblocks, n_up, Hp[b], Wp[b], &P[b])) return e; }
-    }
-    return NVSR_OK;
-}
 int64_t nvsr_planes_sr_batch_keep_floats(int B, int Cc, int R0, int R1, int hid, int nblocks, int n_up, int pad, const float* rois) {
-    if (B < 1 || B > CONV_RAGGED_MAX) return -1;
-    int64_t s = 0;
-    for (int b = 0; b < B; ++b) {
-        const int64_t k = nvsr_planes_sr_keep_floats(Cc, R0, R1, hid, nblocks, n_up, pad, rois ? rois + 4 * b : nullptr);
-        if (k < 0) return -1;
-        s += k;
-    }
-    return s;
+    static thread_local EdsrPlan P[CONV_RAGGED_MAX];
+    SrRegions g;
+    return sr_regions(B, Cc, R0, R1, hid, nblocks, n_up, pad, -1, rois, P, &g) ? -1 : g.keep_floats;
 }
+/* the network's output of every plane (the one-plane workspace also holds its input and the rotating buffers) */
 int64_t nvsr_planes_sr_batch_workspace_floats(int B, int Cc, int R0, int R1, int hid, int nblocks, int n_up, int pad, const float* rois) {
-    if (B < 1 || B > CONV_RAGGED_MAX) return -1;
-    int64_t s = 0;
-    for (int b = 0; b < B; ++b) {       // the network's output of every plane (the one-plane workspace also holds its input and ping-pong buffers)
-        int lo[2], hi[2], Ho, Wo;
-        sr_roi(R0, R1, rois ? rois + 4 * b : nullptr, lo, hi);
-        if (nvsr_edsr_out_size(hi[0] - lo[0] + 2 * pad, hi[1] - lo[1] + 2 * pad, nblocks, n_up, &Ho, &Wo)) return -1;
-        s += ((int64_t)Cc * Ho * Wo + 3) / 4 * 4;
-    }
-    return s;
+    SrRegions g;
+    return sr_regions(B, Cc, R0, R1, hid, nblocks, n_up, pad, -1, rois, nullptr, &g) ? -1 : g.fwd_floats;
 }
 int nvsr_planes_sr_train_batch_arith(const float* const* lr, int B, int Cc, int R0, int R1, const float* packed, int hid, int nblocks, int n_up,
                                      int pad, int over, const float* rois, const float* mean, const float* stdv, float* const* out, float* workspace,
@@ -1678,45 +1450,26 @@ int nvsr_planes_sr_train_batch_arith(const float* const* lr, int B, int Cc, int 
     hipStream_t stream = (hipStream_t)stream_;
     const int sf = 1 << n_up;
     const int arith = conv_resolve_arith(arithmetic);
-    int lo[CONV_RAGGED_MAX][2], hi[CONV_RAGGED_MAX][2], Hp[CONV_RAGGED_MAX], Wp[CONV_RAGGED_MAX];
     static thread_local EdsrPlan P[CONV_RAGGED_MAX];
-    if (int e = batch_geometry(B, Cc, R0, R1, hid, nblocks, n_up, pad, rois, lo, hi, Hp, Wp, P)) return e;
-    float* xin[CONV_RAGGED_MAX]; float* acts[CONV_RAGGED_MAX]; float* diff[CONV_RAGGED_MAX];
-    float* k = keep; float* w = workspace;
+    SrRegions g;
+    if (int e = sr_regions(B, Cc, R0, R1, hid, nblocks, n_up, pad, over, rois, P, &g)) return e;
+    const float* xin[CONV_RAGGED_MAX]; float* acts[CONV_RAGGED_MAX]; float* diff[CONV_RAGGED_MAX];
     for (int b = 0; b < B; ++b) {
-        if (P[b].Ho != (hi[b][0] - lo[b][0]) * sf + 2 * over || P[b].Wo != (hi[b][1] - lo[b][1]) * sf + 2 * over) return NVSR_ERR_SHAPE;
-        const int64_t n_in = (int64_t)Cc * Hp[b] * Wp[b];
-        xin[b] = k; acts[b] = k + (n_in + 3) / 4 * 4;
-        k = acts[b] + P[b].acts_floats;
-        diff[b] = w; w += ((int64_t)Cc * P[b].Ho * P[b].Wo + 3) / 4 * 4;
-        hipLaunchKernelGGL(sr_prepare_kernel, dim3((unsigned)((n_in + 255) / 256)), dim3(256), 0, stream, lr[b], Cc, R0, R1, lo[b][0], lo[b][1], Hp[b],
-                           Wp[b], pad, mean, stdv, xin[b]);
+        const SrPlane& s = g.p[b];
+        xin[b] = keep + s.keep_xin; acts[b] = keep + s.keep_acts; diff[b] = workspace + s.fwd_diff;
+        hipLaunchKernelGGL(sr_prepare_kernel, dim3((unsigned)((s.n_in + 255) / 256)), dim3(256), 0, stream, lr[b], Cc, R0, R1, s.lo[0], s.lo[1], s.Hp,
+                           s.Wp, pad, mean, stdv, keep + s.keep_xin);
         if (int e = NVSR_CHECK_LAUNCH()) return e;
     }
-    if (arith == NVSR_ARITH_F32 || B == 1) {
-        // the exact-f32 kernels take no ragged batch (and one plane needs none): plane after plane
-        for (int b = 0; b < B; ++b)
-            if (int e = nvsr_edsr_forward_train_arith(xin[b], Cc, Hp[b], Wp[b], packed, Cc, hid, nblocks, n_up, diff[b], acts[b], arith, stream_)) return e;
-    } else {
-        const ConvExec cx{arith, 0};
-        const float* wp = packed;
-        for (int l = 0; l < P[0].n; ++l) {
-            ConvRagged r;
-            r.n = B;
-            for (int b = 0; b < B; ++b) {
-                r.H[b] = P[b].ih[l]; r.W[b] = P[b].iw[l];
-                r.in[b] = l ? acts[b] + P[b].act_off[l] : xin[b];
-                r.out[b] = (l + 1 < P[b].n) ? acts[b] + P[b].act_off[l + 1] : diff[b];
-                r.skip[b] = (P[b].epi[l] == EPI_RESIDUAL) ? (l >= 2 ? acts[b] + P[b].act_off[l - 1] : xin[b]) : nullptr;      // the block's input
-            }
-            if (int e = launch_conv(nullptr, P[0].L[l].Cin, 0, 0, wp, P[0].L[l].Cout, P[0].epi[l], nullptr, nullptr, stream, 0, B, cx, &r)) return e;
-            wp += conv_packed_floats(P[0].L[l].Cin, P[0].L[l].Cout);
-        }
-    }
+    // the exact-f32 kernels take no ragged batch (and one plane needs none): plane after plane
+    const bool ragged = arith != NVSR_ARITH_F32 && B > 1;
+    for (int b = 0; b < (ragged ? 1 : B); ++b)
+        if (int e = edsr_forward_walk(P + b, ragged ? B : 0, 1, packed, ConvExec{arith, 0}, stream, record_tensors(P + b, xin + b, acts + b, diff + b))) return e;
     const int64_t n_out = (int64_t)Cc * R0 * sf * R1 * sf;
     for (int b = 0; b < B; ++b) {
-        hipLaunchKernelGGL(sr_finish_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, stream, diff[b], P[b].Ho, P[b].Wo, over, lr[b], Cc, R0, R1,
-                           sf, lo[b][0], lo[b][1], hi[b][0], hi[b][1], out[b], conv_arith_f16(arith) ? nvsr_get_range_flag() : nullptr,
+        const SrPlane& s = g.p[b];
+        hipLaunchKernelGGL(sr_finish_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, stream, diff[b], s.Ho, s.Wo, over, lr[b], Cc, R0, R1,
+                           sf, s.lo[0], s.lo[1], s.hi[0], s.hi[1], out[b], conv_arith_f16(arith) ? nvsr_get_range_flag() : nullptr,
                            align_corners ? 1 : 0, plane_interp == NVSR_PLANE_INTERP_BICUBIC ? 1 : 0);
         if (int e = NVSR_CHECK_LAUNCH()) return e;
     }
@@ -1724,3 +1477,4 @@ int nvsr_planes_sr_train_batch_arith(const float* const* lr, int B, int Cc, int 
 }
 
 }  // extern "C"
+

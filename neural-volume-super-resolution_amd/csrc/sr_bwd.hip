@@ -881,6 +881,160 @@ static int finish_backward(const float* d_out, int Cc, int R0, int R1, int sf, c
     return NVSR_CHECK_LAUNCH();
 }
 
+// marks: events the caller wants recorded on `stream` as soon as the weight gradients of layer mark_layers[i] AND of every layer behind it (the
+// backward walks the layers from the last to the first) are final in grad_natural -- a data-parallel caller starts the all-reduce of that part of
+// the blob while the rest of the backward is still running (nvsr_planes_sr_backward_batch_marks)
+struct LayerMarks { int n = 0; const int32_t* layers = nullptr; void* const* events = nullptr; };
+static int record_marks(const LayerMarks& mk, int layer, hipStream_t stream) {      // layer < 0: every mark (the pass is over)
+    for (int i = 0; i < mk.n; ++i)
+        if ((layer < 0 || mk.layers[i] == layer) && mk.events[i] && hipEventRecord((hipEvent_t)mk.events[i], stream) != hipSuccess) return NVSR_ERR_LAUNCH;
+    return NVSR_OK;
+}
+
+// Workspace of the backward walk on the planes P[0 .. B): 3 gradient buffers + 1 un-shuffled gradient, each holding one tensor per plane (plane b at
+// toff[b]), two buffers of weight-gradient partial sums (ReduceLane) of `part` floats, and one word per gradient tensor for its largest magnitude
+// (f16 limbs) -- caller-owned, so that backward passes queued on different streams never share a result word
+struct BwdLayout { int64_t toff[CONV_RAGGED_MAX + 1], part, total; };
+static BwdLayout edsr_backward_layout(int B, bool ragged, const EdsrPlan* P) {
+    BwdLayout y{};
+    for (int b = 0; b < B; ++b) y.toff[b + 1] = y.toff[b] + round4(P[b].max_tensor);
+    for (int l = 0; l < P[0].n; ++l) {
+        const ConvLayer& L = P[0].L[l];
+        const int64_t f = ragged ? wgrad_partial_floats_ragged(L.Cin, L.Cout) : wgrad_partial_floats(L.Cin, L.Cout, P[0].ih[l] - 2, P[0].iw[l] - 2);
+        if (f > y.part) y.part = f;
+    }
+    y.part = round4(y.part);
+    y.total = 4 * y.toff[B] + 2 * y.part + (P[0].n + 7) / 4 * 4;
+    return y;
+}
+
+// The one backward walk of the EDSR forward on the planes P[0 .. B) (x, acts: each plane's forward input and activation record; d_out: its output
+// gradient; grad_natural += the weight gradients of all planes; dx: NULL or where each plane's input gradient goes).  It owns the reverse layer
+// loop, the rotation of the three gradient buffers, the magnitude words, the offsets into the two blobs, the marks and the reduce pass; the three
+// primitives under it launch in one of two ways:
+//   ragged: per layer ONE weight-gradient pass over all planes (launch_wgrad_planes), ONE ragged data-gradient launch and -- f16 limbs -- ONE
+//           magnitude reduction across the planes (limb arithmetics only);
+//   else:   B = 1, the one-plane launches (launch_wgrad, launch_conv, launch_absmax) -- every arithmetic.
+static int edsr_backward_walk(int B, bool ragged, const EdsrPlan* P, const float* const* x, const float* const* acts, const float* packed_dgrad,
+                              const float* const* d_out, float* grad_natural, float* const* dx, float* workspace, int arith, hipStream_t stream,
+                              const LayerMarks& marks = LayerMarks{}) {
+    const int n = P[0].n;
+    const BwdLayout lay = edsr_backward_layout(B, ragged, P);
+    const int64_t T = lay.toff[B];
+    auto buf = [&](int k, int b) { return workspace + k * T + lay.toff[b]; };           // k = 3: the un-shuffled gradient
+    float* partial = workspace + 4 * T;
+    unsigned* amax_words = reinterpret_cast<unsigned*>(partial + 2 * lay.part);         // n + 4 words
+    ReducePass rp;                                                                       // (its destructor joins the lane on every exit)
+    if (arith != NVSR_ARITH_F32) reduce_pass_begin(rp, partial, lay.part, stream);
+    // per-layer offsets into the natural gradient blob and the packed data-gradient blob
+    int64_t goff[EDSR_MAX_LAYERS], poff[EDSR_MAX_LAYERS], go = 0, po = 0;
+    for (int l = 0; l < n; ++l) {
+        goff[l] = go; poff[l] = po;
+        go += 9LL * P[0].L[l].Cin * P[0].L[l].Cout;
+        po += conv_packed_floats(P[0].L[l].Cout, P[0].L[l].Cin);
+    }
+    const float* g[CONV_RAGGED_MAX];       // gradient with respect to the output of layer l (after its epilogue), per plane
+    int gi = -1;                           // index of g in the buffers (-1: the caller's d_out)
+    for (int b = 0; b < B; ++b) g[b] = d_out[b];
+    auto next_buf = [&](int a, int c) { for (int k = 0; k < 3; ++k) if (k != a && k != c) return k; return 0; };
+    auto input_of = [&](int l, int b) { return l ? acts[b] + P[b].act_off[l] : x[b]; };
+    // f16 limbs: the power-of-two scale of a gradient tensor comes from the bits of its largest magnitude, one word per tensor (over all planes).
+    // The word of the caller's d_out is a reduction pass; every other gradient tensor is the output of a data-gradient launch, whose epilogue leaves
+    // the word behind (ConvExec::out_absmax: an atomicMax per wave) -- no pass over the tensor; the un-shuffled gradient is a permutation of one that has it
+    const bool f16 = conv_arith_f16(arith);
+    int amax_next = 0;
+    if (f16 && hipMemsetAsync(amax_words, 0, sizeof(unsigned) * (n + 4), stream) != hipSuccess) return NVSR_ERR_LAUNCH;
+    auto new_word = [&]() -> unsigned* { return f16 ? amax_words + amax_next++ : nullptr; };
+    const unsigned* g_am = nullptr;
+    if (f16) {
+        long cnt[CONV_RAGGED_MAX];
+        for (int b = 0; b < B; ++b) cnt[b] = (long)P[0].L[n - 1].Cout * (P[b].ih[n - 1] - 2) * (P[b].iw[n - 1] - 2);
+        g_am = ragged ? launch_absmax_ragged(B, d_out, cnt, stream, new_word()) : launch_absmax(d_out[0], cnt[0], stream, new_word());
+        if (!g_am) return NVSR_ERR_LAUNCH;
+    }
+    // weight gradient of layer l from dy, into the layer's part of grad_natural; then the layer's marks
+    auto wgrad = [&](const float* const* dy, int l, float scale, const unsigned* am) {
+        const float* xs[CONV_RAGGED_MAX]; int H[CONV_RAGGED_MAX], W[CONV_RAGGED_MAX];
+        for (int b = 0; b < B; ++b) { xs[b] = input_of(l, b); H[b] = P[b].ih[l]; W[b] = P[b].iw[l]; }
+        const ConvLayer& L = P[0].L[l];
+        if (int e_ = ragged ? launch_wgrad_planes(B, dy, xs, L.Cin, H, W, L.Cout, scale, grad_natural + goff[l], partial, stream, arith, am, &rp)
+                            : launch_wgrad(dy[0], xs[0], L.Cin, H[0], W[0], L.Cout, scale, grad_natural + goff[l], partial, stream, arith, am, &rp))
+            return e_;
+        bool wanted = false;
+        for (int i = 0; i < marks.n; ++i) wanted = wanted || marks.layers[i] == l;
+        if (!wanted) return (int)NVSR_OK;
+        rp.join();                                 // (a reduce lane's reductions of this and the earlier layers, before the mark; the product has no lane)
+        return rp.failed ? (int)NVSR_ERR_LAUNCH : record_marks(marks, l, stream);
+    };
+    // data gradient of layer l: dy [Cout][ih-2][iw-2] -> out [Cin][ih][iw] with the given backward epilogue
+    auto dgrad = [&](const float* const* dy, int l, int epi, const float* const* skip, float* const* out, const unsigned* am, unsigned* out_am) {
+        const ConvLayer& L = P[0].L[l];
+        ConvExec cx{arith, 0};
+        cx.in_absmax = am;
+        cx.out_absmax = out_am;
+        if (!ragged) return launch_conv(dy[0], L.Cout, P[0].ih[l] - 2, P[0].iw[l] - 2, packed_dgrad + poff[l], L.Cin, epi, skip ? skip[0] : nullptr, out[0], stream, 2, 1, cx);
+        ConvRagged r;
+        r.n = B;
+        for (int b = 0; b < B; ++b) {
+            r.H[b] = P[b].ih[l] - 2; r.W[b] = P[b].iw[l] - 2;
+            r.in[b] = dy[b]; r.out[b] = out[b]; r.skip[b] = skip ? skip[b] : nullptr;
+        }
+        return launch_conv(nullptr, L.Cout, 0, 0, packed_dgrad + poff[l], L.Cin, epi, nullptr, nullptr, stream, 2, B, cx, &r);
+    };
+    // the data gradient of layer l into buffer o (or the caller's dx), which becomes g
+    float* outs[CONV_RAGGED_MAX];
+    auto dgrad_into = [&](int o, const float* const* dy, int l, int epi, const float* const* skip, const unsigned* am, unsigned* out_am) {
+        for (int b = 0; b < B; ++b) outs[b] = o < 0 ? dx[b] : buf(o, b);
+        return dgrad(dy, l, epi, skip, outs, am, out_am);
+    };
+    auto advance = [&](int o, unsigned* w) { for (int b = 0; b < B; ++b) g[b] = outs[b]; gi = o; g_am = w; };
+    int e;
+    for (int l = n - 1; l >= 0; --l) {
+        const int co = P[0].L[l].Cout;
+        if (P[0].epi[l] == EPI_PIXEL_SHUFFLE) {           // g is [co/4][2(ih-2)][2(iw-2)]: undo the shuffle first
+            const float* un[CONV_RAGGED_MAX];
+            for (int b = 0; b < B; ++b) {
+                const long cnt = (long)co * (P[b].ih[l] - 2) * (P[b].iw[l] - 2);
+                hipLaunchKernelGGL(pixel_unshuffle_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, g[b], co / 4, P[b].ih[l] - 2,
+                                   P[b].iw[l] - 2, buf(3, b));
+                un[b] = buf(3, b);
+            }
+            if ((e = NVSR_CHECK_LAUNCH())) return e;
+            if ((e = wgrad(un, l, 1.0f, g_am))) return e;
+            const int o = next_buf(gi, -1);
+            unsigned* w = new_word();
+            if ((e = dgrad_into(o, un, l, EPI_NONE, nullptr, g_am, w))) return e;
+            advance(o, w);
+        } else if (P[0].epi[l] == EPI_RESIDUAL) {         // block: y = 0.1 conv2(relu(conv1(xb))) + crop(xb); layers l-1 (conv1), l (conv2)
+            const int l1 = l - 1;
+            const float* t1[CONV_RAGGED_MAX];              // relu(conv1(xb)), [hid][ih][iw]
+            const float* d1[CONV_RAGGED_MAX];
+            for (int b = 0; b < B; ++b) t1[b] = input_of(l, b);
+            if ((e = wgrad(g, l, 0.1f, g_am))) return e;
+            const int o1 = next_buf(gi, -1);
+            unsigned* w1 = new_word();
+            if ((e = dgrad_into(o1, g, l, EPI_MASK_SCALE, t1, g_am, w1))) return e;
+            for (int b = 0; b < B; ++b) d1[b] = outs[b];
+            if ((e = wgrad(d1, l1, 1.0f, w1))) return e;
+            const int o2 = next_buf(gi, o1);
+            unsigned* w2 = new_word();
+            if ((e = dgrad_into(o2, d1, l1, EPI_ADD_CENTER, g, w1, w2))) return e;
+            advance(o2, w2);
+            --l;                                           // conv1 is done too
+        } else {                                           // plain conv (conv_input, conv_mid, conv_output)
+            if ((e = wgrad(g, l, 1.0f, g_am))) return e;
+            if (l > 0) {
+                const int o = next_buf(gi, -1);
+                unsigned* w = new_word();
+                if ((e = dgrad_into(o, g, l, EPI_NONE, nullptr, g_am, w))) return e;
+                advance(o, w);
+            } else if (dx && (e = dgrad_into(-1, g, l, EPI_NONE, nullptr, g_am, nullptr))) return e;
+        }
+    }
+    rp.join();
+    return rp.failed ? NVSR_ERR_LAUNCH : NVSR_OK;
+}
+
 }  // namespace nvsr
 
 using namespace nvsr;
@@ -931,19 +1085,11 @@ int nvsr_pack_edsr_dgrad(const float* natural, int Cin, int Cout, int hid, int n
     return nvsr_pack_edsr_dgrad_arith(natural, Cin, Cout, hid, nblocks, n_up, packed_dgrad, NVSR_PACK_ALL_ARITHMETICS, stream);
 }
 
-/* 3 gradient tensors + 1 un-shuffled gradient + the weight-gradient partial sums */
+/* 3 gradient tensors + 1 un-shuffled gradient + the weight-gradient partial sums + the magnitude words (edsr_backward_layout) */
 int64_t nvsr_edsr_backward_workspace_floats(int Cin, int Cout, int hid, int nblocks, int n_up, int H, int W) {
     EdsrPlan P;
     if (edsr_plan(Cin, Cout, hid, nblocks, n_up, H, W, &P)) return -1;
-    int64_t part = 0;
-    for (int l = 0; l < P.n; ++l) {
-        const int64_t f = wgrad_partial_floats(P.L[l].Cin, P.L[l].Cout, P.ih[l] - 2, P.iw[l] - 2);
-        if (f > part) part = f;
-    }
-    const int64_t t = (P.max_tensor + 3) / 4 * 4;
-    // + one word per gradient tensor for its largest magnitude (f16 limbs: absmax_kernel) -- caller-owned, so that backward passes queued on
-    // different streams never share a result word
-    return 4 * t + 2 * ((part + 3) / 4 * 4) + (P.n + 7) / 4 * 4;       // (two buffers of partial sums: ReduceLane)
+    return edsr_backward_layout(1, false, &P).total;
 }
 
 /* Backward of nvsr_edsr_forward_train.  x, acts: the forward's input and activation record; d_out [Cout][Ho][Wo];
@@ -957,100 +1103,19 @@ int nvsr_edsr_backward_arith(const float* x, int Cin, int H, int W, const float*
                              int n_up, const float* d_out, float* grad_natural, float* dx, float* workspace, int arithmetic,
                              nvsr_stream_t stream_) {
     if (!x || !acts || !packed_dgrad || !d_out || !grad_natural || !workspace) return NVSR_ERR_NULL;
-    const int arith = conv_resolve_arith(arithmetic);
-    const ConvExec cx{arith, 0};
     if (!aligned16(packed_dgrad) || !aligned16(workspace)) return NVSR_ERR_ALIGN;
     EdsrPlan P;
     if (int e = edsr_plan(Cin, Cout, hid, nblocks, n_up, H, W, &P)) return e;
-    hipStream_t stream = (hipStream_t)stream_;
-    const int64_t t = (P.max_tensor + 3) / 4 * 4;
-    float* buf[3] = {workspace, workspace + t, workspace + 2 * t};
-    float* unsh = workspace + 3 * t;
-    float* partial = workspace + 4 * t;
-    int64_t part_floats = 0;
-    for (int l = 0; l < P.n; ++l) {
-        const int64_t f = wgrad_partial_floats(P.L[l].Cin, P.L[l].Cout, P.ih[l] - 2, P.iw[l] - 2);
-        if (f > part_floats) part_floats = f;
-    }
-    part_floats = (part_floats + 3) / 4 * 4;
-    unsigned* amax_words = reinterpret_cast<unsigned*>(partial + 2 * part_floats);     // P.n + 4 words, one per gradient tensor
-    int amax_next = 0;
-    ReducePass rp;                                                                      // (joins the lane on every exit)
-    if (arith != NVSR_ARITH_F32) reduce_pass_begin(rp, partial, part_floats, stream);
-    // per-layer offsets into the natural gradient blob and the packed data-gradient blob
-    int64_t goff[EDSR_MAX_LAYERS], poff[EDSR_MAX_LAYERS], go = 0, po = 0;
-    for (int l = 0; l < P.n; ++l) {
-        goff[l] = go; poff[l] = po;
-        go += 9LL * P.L[l].Cin * P.L[l].Cout;
-        po += conv_packed_floats(P.L[l].Cout, P.L[l].Cin);
-    }
-    auto input_of = [&](int l) { return l ? acts + P.act_off[l] : x; };
-    const float* g = d_out;       // gradient with respect to the output of layer l (after its epilogue)
-    int gi = -1;                   // index of g in buf (-1: the caller's d_out)
-    auto next_buf = [&](int a, int b) { for (int k = 0; k < 3; ++k) if (k != a && k != b) return k; return 0; };
-    int e;
-    // f16 limbs: the power-of-two scale of a gradient tensor comes from the bits of its largest magnitude, one word per tensor.  The word of the
-    // caller's d_out is a reduction pass; every other gradient tensor is the output of a data-gradient launch, whose epilogue leaves the word
-    // behind (ConvExec::out_absmax: an atomicMax per wave) -- no pass over the tensor; the un-shuffled gradient is a permutation of one that has it
-    const bool f16 = conv_arith_f16(conv_resolve_arith(arith));
-    if (f16 && hipMemsetAsync(amax_words, 0, sizeof(unsigned) * (P.n + 4), stream) != hipSuccess) return NVSR_ERR_LAUNCH;
-    auto new_word = [&]() -> unsigned* { return f16 ? amax_words + amax_next++ : nullptr; };
-    auto exec = [&](const unsigned* in_am, unsigned* out_am) { ConvExec c = cx; c.in_absmax = in_am; c.out_absmax = out_am; return c; };
-    const unsigned* g_am = nullptr;
-    if (f16) {
-        const int lz = P.n - 1;
-        g_am = launch_absmax(d_out, (long)P.L[lz].Cout * (P.ih[lz] - 2) * (P.iw[lz] - 2), stream, new_word());
-        if (!g_am) return NVSR_ERR_LAUNCH;
-    }
-    for (int l = P.n - 1; l >= 0; --l) {
-        const int ci = P.L[l].Cin, co = P.L[l].Cout, ih = P.ih[l], iw = P.iw[l];
-        const bool need_dx = l > 0 || dx;
-        if (P.epi[l] == EPI_PIXEL_SHUFFLE) {           // g is [co/4][2(ih-2)][2(iw-2)]: undo the shuffle first
-            const long n = (long)co * (ih - 2) * (iw - 2);
-            hipLaunchKernelGGL(pixel_unshuffle_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, g, co / 4, ih - 2, iw - 2, unsh);
-            if ((e = NVSR_CHECK_LAUNCH())) return e;
-            if ((e = launch_wgrad(unsh, input_of(l), ci, ih, iw, co, 1.0f, grad_natural + goff[l], partial, stream, arith, g_am, &rp))) return e;
-            const int o = next_buf(gi, -1);
-            unsigned* w = new_word();
-            if ((e = launch_conv(unsh, co, ih - 2, iw - 2, packed_dgrad + poff[l], ci, EPI_NONE, nullptr, buf[o], stream, 2, 1, exec(g_am, w)))) return e;
-            g = buf[o]; gi = o; g_am = w;
-        } else if (P.epi[l] == EPI_RESIDUAL) {         // block: y = 0.1 conv2(relu(conv1(xb))) + crop(xb); layers l-1 (conv1), l (conv2)
-            const float* t1 = input_of(l);             // relu(conv1(xb)), [hid][ih][iw]
-            const float* xb = input_of(l - 1);         // [hid][ih+2][iw+2]
-            if ((e = launch_wgrad(g, t1, ci, ih, iw, co, 0.1f, grad_natural + goff[l], partial, stream, arith, g_am, &rp))) return e;
-            const int o1 = next_buf(gi, -1);
-            unsigned* w1 = new_word();
-            if ((e = launch_conv(g, co, ih - 2, iw - 2, packed_dgrad + poff[l], ci, EPI_MASK_SCALE, t1, buf[o1], stream, 2, 1, exec(g_am, w1)))) return e;
-            const int l1 = l - 1;
-            if ((e = launch_wgrad(buf[o1], xb, P.L[l1].Cin, P.ih[l1], P.iw[l1], P.L[l1].Cout, 1.0f, grad_natural + goff[l1], partial, stream, arith, w1, &rp))) return e;
-            const int o2 = next_buf(gi, o1);
-            unsigned* w2 = new_word();
-            if ((e = launch_conv(buf[o1], P.L[l1].Cout, ih, iw, packed_dgrad + poff[l1], P.L[l1].Cin, EPI_ADD_CENTER, g, buf[o2], stream, 2, 1, exec(w1, w2)))) return e;
-            g = buf[o2]; gi = o2; g_am = w2;
-            --l;                                        // conv1 is done too
-        } else {                                        // plain conv (conv_input, conv_mid, conv_output)
-            if ((e = launch_wgrad(g, input_of(l), ci, ih, iw, co, 1.0f, grad_natural + goff[l], partial, stream, arith, g_am, &rp))) return e;
-            if (need_dx) {
-                float* o = (l == 0) ? dx : buf[next_buf(gi, -1)];
-                unsigned* w = l ? new_word() : nullptr;
-                if ((e = launch_conv(g, co, ih - 2, iw - 2, packed_dgrad + poff[l], ci, EPI_NONE, nullptr, o, stream, 2, 1, exec(g_am, w)))) return e;
-                if (l) { gi = next_buf(gi, -1); g = buf[gi]; g_am = w; }
-            }
-        }
-    }
-    rp.join();
-    return rp.failed ? NVSR_ERR_LAUNCH : NVSR_OK;
+    return edsr_backward_walk(1, false, &P, &x, &acts, packed_dgrad, &d_out, grad_natural, dx ? &dx : nullptr, workspace, conv_resolve_arith(arithmetic),
+                              (hipStream_t)stream_);
 }
 
 /* 1 d_diff + the prepared-input gradient + the EDSR backward workspace */
 int64_t nvsr_planes_sr_backward_workspace_floats(int Cc, int R0, int R1, int hid, int nblocks, int n_up, int pad, const float* roi) {
-    int lo[2], hi[2];
-    sr_roi(R0, R1, roi, lo, hi);
-    const int Hp = hi[0] - lo[0] + 2 * pad, Wp = hi[1] - lo[1] + 2 * pad;
     EdsrPlan P;
-    if (edsr_plan(Cc, Cc, hid, nblocks, n_up, Hp, Wp, &P)) return -1;
-    const int64_t w = nvsr_edsr_backward_workspace_floats(Cc, Cc, hid, nblocks, n_up, Hp, Wp);
-    return ((int64_t)Cc * P.Ho * P.Wo + 3) / 4 * 4 + ((int64_t)Cc * Hp * Wp + 3) / 4 * 4 + w;
+    SrRegions g;
+    if (sr_regions(1, Cc, R0, R1, hid, nblocks, n_up, pad, -1, roi, &P, &g)) return -1;
+    return g.bwd_floats + edsr_backward_layout(1, false, &P).total;
 }
 
 /* Backward of nvsr_planes_sr_train.  d_out [C][sf R0][sf R1] (entries outside the ROI are ignored); grad_natural += EDSR weight
@@ -1062,205 +1127,82 @@ int nvsr_planes_sr_backward(int Cc, int R0, int R1, const float* keep, const flo
     return nvsr_planes_sr_backward_arith(Cc, R0, R1, keep, packed_dgrad, hid, nblocks, n_up, pad, over, roi, stdv, d_out, grad_natural, d_lr,
                                          workspace, NVSR_ARITH_INHERIT, stream_);
 }
-int nvsr_planes_sr_backward_arith(int Cc, int R0, int R1, const float* keep, const float* packed_dgrad, int hid, int nblocks, int n_up, int pad,
-                                  int over, const float* roi, const float* stdv, const float* d_out, float* grad_natural, float* d_lr,
-                                  float* workspace, int arithmetic, nvsr_stream_t stream_) {
-    if (!keep || !packed_dgrad || !d_out || !grad_natural || !workspace) return NVSR_ERR_NULL;
-    hipStream_t stream = (hipStream_t)stream_;
-    const int sf = 1 << n_up;
-    int lo[2], hi[2];
-    sr_roi(R0, R1, roi, lo, hi);
-    const int ch = hi[0] - lo[0], cw = hi[1] - lo[1];
-    const int Hp = ch + 2 * pad, Wp = cw + 2 * pad;
-    EdsrPlan P;
-    if (int e = edsr_plan(Cc, Cc, hid, nblocks, n_up, Hp, Wp, &P)) return e;
-    if (P.Ho != ch * sf + 2 * over || P.Wo != cw * sf + 2 * over) return NVSR_ERR_SHAPE;
-    const int64_t n_diff = (int64_t)Cc * P.Ho * P.Wo, n_in = (int64_t)Cc * Hp * Wp;
-    float* d_diff = workspace;
-    float* dxin = d_diff + (n_diff + 3) / 4 * 4;
-    float* ews = dxin + (n_in + 3) / 4 * 4;
-    if (int e = finish_backward(d_out, Cc, R0, R1, sf, lo, hi, P.Ho, P.Wo, over, d_diff, d_lr, sr_align_corners(), sr_bicubic(), stream)) return e;
-    const float* xin = keep;
-    const float* acts = keep + (n_in + 3) / 4 * 4;
-    if (int e = nvsr_edsr_backward_arith(xin, Cc, Hp, Wp, acts, packed_dgrad, Cc, hid, nblocks, n_up, d_diff, grad_natural, d_lr ? dxin : nullptr, ews,
-                                         arithmetic, stream_))
-        return e;
-    if (d_lr) {
-        hipLaunchKernelGGL(sr_prepare_backward_kernel, dim3((unsigned)((n_in + 255) / 256)), dim3(256), 0, stream, dxin, Cc, R0, R1, lo[0], lo[1],
-                           Hp, Wp, pad, stdv, d_lr);
+
+/* ---- backward of nvsr_planes_sr_train[_batch]_arith: B regions of interest at once -----------------------------------------------------------
+ * keep: the forward's buffer; d_out: B HOST pointers to [C][sf R0][sf R1] gradients (entries outside a plane's ROI are ignored); grad_natural +=
+ * the EDSR weight gradients of all planes; d_lr: NULL or B HOST pointers, each NULL (plane detached, models.py:272) or [C][R0][R1] += that LR
+ * plane's gradient.  Limb arithmetics with B > 1 walk the layers once for all planes (edsr_backward_walk, ragged); exact f32 and B = 1 walk them
+ * plane by plane, and every layer's gradient is then final only after the last plane: all marks are recorded at the end.
+ * check_align: the batched entry points answer a misaligned keep / workspace / blob first; the one-plane entry point has always answered it
+ * after the geometry (nvsr_edsr_backward_arith's own check). */
+static int planes_sr_backward(int B, int Cc, int R0, int R1, const float* keep, const float* packed_dgrad, int hid, int nblocks, int n_up, int pad, int over,
+                              const float* rois, const float* stdv, const float* const* d_out, float* grad_natural, float* const* d_lr, float* workspace,
+                              int arithmetic, int align_corners, int plane_interp, const LayerMarks& marks, bool check_align, hipStream_t stream) {
+    if (B < 1 || B > CONV_RAGGED_MAX) return NVSR_ERR_SHAPE;
+    if (plane_interp != NVSR_PLANE_INTERP_BILINEAR && plane_interp != NVSR_PLANE_INTERP_BICUBIC) return NVSR_ERR_SHAPE;
+    if (check_align && (!aligned16(packed_dgrad) || !aligned16(workspace) || !aligned16(keep))) return NVSR_ERR_ALIGN;
+    const int sf = 1 << n_up, arith = conv_resolve_arith(arithmetic);
+    static thread_local EdsrPlan P[CONV_RAGGED_MAX];
+    SrRegions g;
+    const int bad = sr_regions(B, Cc, R0, R1, hid, nblocks, n_up, pad, over, rois, P, &g);
+    for (int b = 0; b < B && b <= g.ok; ++b)           // (answered in plane order: plane b's pointer before plane b's geometry)
+        if (!d_out[b]) return NVSR_ERR_NULL;
+    if (bad) return bad;
+    const float* xin[CONV_RAGGED_MAX]; const float* acts[CONV_RAGGED_MAX];
+    const float* d_diff[CONV_RAGGED_MAX]; float* dxin[CONV_RAGGED_MAX];
+    float* ews = workspace + g.bwd_floats;
+    bool any_lr = false;
+    for (int b = 0; b < B; ++b) {
+        const SrPlane& s = g.p[b];
+        xin[b] = keep + s.keep_xin; acts[b] = keep + s.keep_acts;
+        d_diff[b] = workspace + s.bwd_diff; dxin[b] = workspace + s.bwd_dxin;
+        any_lr = any_lr || (d_lr && d_lr[b]);
+        if (int e = finish_backward(d_out[b], Cc, R0, R1, sf, s.lo, s.hi, s.Ho, s.Wo, over, workspace + s.bwd_diff, d_lr ? d_lr[b] : nullptr, align_corners ? 1 : 0,
+                                    plane_interp == NVSR_PLANE_INTERP_BICUBIC ? 1 : 0, stream))
+            return e;
+    }
+    if (arith == NVSR_ARITH_F32 || B == 1) {
+        if (!check_align && (!aligned16(packed_dgrad) || !aligned16(ews))) return NVSR_ERR_ALIGN;
+        for (int b = 0; b < B; ++b) {
+            float* const dxb = (d_lr && d_lr[b]) ? dxin[b] : nullptr;
+            if (int e = edsr_backward_walk(1, false, P + b, xin + b, acts + b, packed_dgrad, d_diff + b, grad_natural, dxb ? &dxb : nullptr, ews, arith, stream)) return e;
+        }
+        if (int e = record_marks(marks, -1, stream)) return e;
+    } else {
+        // (a plane whose LR gradient nobody wants still gets its first layer's data gradient when another plane needs it: 0.3 % of the pass)
+        for (int i = 0; i < marks.n; ++i)
+            if (marks.layers[i] < 0 || marks.layers[i] >= P[0].n) return NVSR_ERR_SHAPE;
+        if (int e = edsr_backward_walk(B, true, P, xin, acts, packed_dgrad, d_diff, grad_natural, any_lr ? dxin : nullptr, ews, arith, stream, marks)) return e;
+    }
+    for (int b = 0; b < B; ++b) {
+        if (!(d_lr && d_lr[b])) continue;
+        const SrPlane& s = g.p[b];
+        hipLaunchKernelGGL(sr_prepare_backward_kernel, dim3((unsigned)((s.n_in + 255) / 256)), dim3(256), 0, stream, dxin[b], Cc, R0, R1, s.lo[0], s.lo[1],
+                           s.Hp, s.Wp, pad, stdv, d_lr[b]);
         if (int e = NVSR_CHECK_LAUNCH()) return e;
     }
     return NVSR_OK;
 }
 
-
-/* ---- backward of nvsr_planes_sr_train_batch_arith: B regions of interest at once ------------------------------------------------------------
- * Per layer ONE weight-gradient pass over all planes (one set of partial sums, one reduction: launch_wgrad_planes), ONE data-gradient launch
- * (ragged batch) and -- f16 limbs -- ONE magnitude reduction per gradient tensor across the planes.  keep: the forward's buffer;
- * d_out: B HOST pointers to [C][sf R0][sf R1] gradients (entries outside a plane's ROI are ignored); grad_natural += the EDSR weight gradients
- * of all planes; d_lr: NULL or B HOST pointers, each NULL (plane detached, models.py:272) or [C][R0][R1] += that LR plane's gradient. */
-}  // extern "C"   (helpers below are C++)
-
-namespace nvsr {
-
-// backward of the EDSR forward on B inputs of different sizes (nvsr_edsr_backward_arith with one launch per layer and operation for all planes)
-// marks: events the caller wants recorded on `stream` as soon as the weight gradients of layer mark_layers[i] AND of every layer behind it (the
-// backward walks the layers from the last to the first) are final in grad_natural -- a data-parallel caller starts the all-reduce of that part of
-// the blob while the rest of the backward is still running (nvsr_planes_sr_backward_batch_marks)
-struct LayerMarks { int n = 0; const int32_t* layers = nullptr; void* const* events = nullptr; };
-static int record_marks(const LayerMarks& mk, int layer, hipStream_t stream) {      // layer < 0: every mark (the pass is over)
-    for (int i = 0; i < mk.n; ++i)
-        if ((layer < 0 || mk.layers[i] == layer) && mk.events[i] && hipEventRecord((hipEvent_t)mk.events[i], stream) != hipSuccess) return NVSR_ERR_LAUNCH;
-    return NVSR_OK;
+int nvsr_planes_sr_backward_arith(int Cc, int R0, int R1, const float* keep, const float* packed_dgrad, int hid, int nblocks, int n_up, int pad,
+                                  int over, const float* roi, const float* stdv, const float* d_out, float* grad_natural, float* d_lr,
+                                  float* workspace, int arithmetic, nvsr_stream_t stream_) {
+    if (!keep || !packed_dgrad || !d_out || !grad_natural || !workspace) return NVSR_ERR_NULL;
+    return planes_sr_backward(1, Cc, R0, R1, keep, packed_dgrad, hid, nblocks, n_up, pad, over, roi, stdv, &d_out, grad_natural, d_lr ? &d_lr : nullptr, workspace,
+                              arithmetic, sr_align_corners(), sr_bicubic() ? NVSR_PLANE_INTERP_BICUBIC : NVSR_PLANE_INTERP_BILINEAR, LayerMarks{}, false,
+                              (hipStream_t)stream_);
 }
-
-static int edsr_backward_planes(int B, const EdsrPlan* P, const float* const* x, const float* const* acts, const float* packed_dgrad,
-                                const float* const* d_out, float* grad_natural, float* const* dx, float* workspace, int arith, hipStream_t stream,
-                                const LayerMarks& marks = LayerMarks{}) {
-    const int n = P[0].n;
-    // workspace: 3 gradient buffers + 1 un-shuffled gradient, each holding one tensor per plane, + the partial sums + one word per gradient tensor
-    int64_t toff[CONV_RAGGED_MAX + 1] = {0};
-    for (int b = 0; b < B; ++b) toff[b + 1] = toff[b] + (P[b].max_tensor + 3) / 4 * 4;
-    const int64_t T = toff[B];
-    auto buf = [&](int k, int b) { return workspace + k * T + toff[b]; };
-    float* partial = workspace + 4 * T;
-    int64_t part_floats = 0;
-    for (int l = 0; l < n; ++l) {
-        const int64_t f = wgrad_partial_floats_ragged(P[0].L[l].Cin, P[0].L[l].Cout);
-        if (f > part_floats) part_floats = f;
-    }
-    part_floats = (part_floats + 3) / 4 * 4;
-    unsigned* amax_words = reinterpret_cast<unsigned*>(partial + 2 * part_floats);      // (two buffers of partial sums: ReduceLane)
-    ReducePass rp;                                                                       // (its destructor joins the lane on every exit)
-    reduce_pass_begin(rp, partial, part_floats, stream);
-    int amax_next = 0;
-    int64_t goff[EDSR_MAX_LAYERS], poff[EDSR_MAX_LAYERS], go = 0, po = 0;
-    for (int l = 0; l < n; ++l) {
-        goff[l] = go; poff[l] = po;
-        go += 9LL * P[0].L[l].Cin * P[0].L[l].Cout;
-        po += conv_packed_floats(P[0].L[l].Cout, P[0].L[l].Cin);
-    }
-    const bool f16 = conv_arith_f16(arith);
-    const float* g[CONV_RAGGED_MAX];       // gradient with respect to the output of layer l (after its epilogue), per plane
-    int gi = -1;                           // index of g in the buffers (-1: the caller's d_out)
-    for (int b = 0; b < B; ++b) g[b] = d_out[b];
-    auto next_buf = [&](int a, int c) { for (int k = 0; k < 3; ++k) if (k != a && k != c) return k; return 0; };
-    auto input_of = [&](int l, int b) { return l ? acts[b] + P[b].act_off[l] : x[b]; };
-    // one magnitude word per gradient tensor, over all planes: a reduction pass for the caller's d_out, the data-gradient launches' epilogues for
-    // every other tensor (see nvsr_edsr_backward_arith)
-    if (f16 && hipMemsetAsync(amax_words, 0, sizeof(unsigned) * (n + 4), stream) != hipSuccess) return NVSR_ERR_LAUNCH;
-    auto new_word = [&]() -> unsigned* { return f16 ? amax_words + amax_next++ : nullptr; };
-    const unsigned* g_am = nullptr;
-    if (f16) {
-        long cnt[CONV_RAGGED_MAX];
-        for (int b = 0; b < B; ++b) cnt[b] = (long)P[0].L[n - 1].Cout * (P[b].ih[n - 1] - 2) * (P[b].iw[n - 1] - 2);
-        g_am = launch_absmax_ragged(B, d_out, cnt, stream, new_word());
-        if (!g_am) return NVSR_ERR_LAUNCH;
-    }
-    auto wgrad = [&](const float* const* dy, int l, float scale, const unsigned* am) {
-        const float* xs[CONV_RAGGED_MAX]; int H[CONV_RAGGED_MAX], W[CONV_RAGGED_MAX];
-        for (int b = 0; b < B; ++b) { xs[b] = input_of(l, b); H[b] = P[b].ih[l]; W[b] = P[b].iw[l]; }
-        if (int e_ = launch_wgrad_planes(B, dy, xs, P[0].L[l].Cin, H, W, P[0].L[l].Cout, scale, grad_natural + goff[l], partial, stream, arith, am, &rp)) return e_;
-        bool wanted = false;
-        for (int i = 0; i < marks.n; ++i) wanted = wanted || marks.layers[i] == l;
-        if (!wanted) return (int)NVSR_OK;
-        rp.join();                                 // (a reduce lane's reductions of this and the earlier layers, before the mark; the product has no lane)
-        return rp.failed ? (int)NVSR_ERR_LAUNCH : record_marks(marks, l, stream);
-    };
-    // data gradient of layer l: dy [Cout][ih-2][iw-2] -> [Cin][ih][iw] with the given backward epilogue
-    auto dgrad = [&](const float* const* dy, int l, int epi, const float* const* skip, float* const* out, const unsigned* am, unsigned* out_am) {
-        ConvRagged r;
-        r.n = B;
-        for (int b = 0; b < B; ++b) {
-            r.H[b] = P[b].ih[l] - 2; r.W[b] = P[b].iw[l] - 2;
-            r.in[b] = dy[b]; r.out[b] = out[b]; r.skip[b] = skip ? skip[b] : nullptr;
-        }
-        ConvExec cx{arith, 0};
-        cx.in_absmax = am;
-        cx.out_absmax = out_am;
-        return launch_conv(nullptr, P[0].L[l].Cout, 0, 0, packed_dgrad + poff[l], P[0].L[l].Cin, epi, nullptr, nullptr, stream, 2, B, cx, &r);
-    };
-    int e;
-    for (int l = n - 1; l >= 0; --l) {
-        const int co = P[0].L[l].Cout;
-        const bool need_dx = l > 0 || dx;
-        if (P[0].epi[l] == EPI_PIXEL_SHUFFLE) {           // g is [co/4][2(ih-2)][2(iw-2)]: undo the shuffle first
-            const float* un[CONV_RAGGED_MAX];
-            for (int b = 0; b < B; ++b) {
-                const long cnt = (long)co * (P[b].ih[l] - 2) * (P[b].iw[l] - 2);
-                hipLaunchKernelGGL(pixel_unshuffle_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, g[b], co / 4, P[b].ih[l] - 2,
-                                   P[b].iw[l] - 2, buf(3, b));
-                un[b] = buf(3, b);
-            }
-            if ((e = NVSR_CHECK_LAUNCH())) return e;
-            if ((e = wgrad(un, l, 1.0f, g_am))) return e;
-            const int o = next_buf(gi, -1);
-            float* outs[CONV_RAGGED_MAX];
-            for (int b = 0; b < B; ++b) outs[b] = buf(o, b);
-            unsigned* w = new_word();
-            if ((e = dgrad(un, l, EPI_NONE, nullptr, outs, g_am, w))) return e;
-            for (int b = 0; b < B; ++b) g[b] = outs[b];
-            gi = o; g_am = w;
-        } else if (P[0].epi[l] == EPI_RESIDUAL) {         // block: y = 0.1 conv2(relu(conv1(xb))) + crop(xb); layers l-1 (conv1), l (conv2)
-            const int l1 = l - 1;
-            const float* t1[CONV_RAGGED_MAX];              // relu(conv1(xb))
-            for (int b = 0; b < B; ++b) t1[b] = input_of(l, b);
-            if ((e = wgrad(g, l, 0.1f, g_am))) return e;
-            const int o1 = next_buf(gi, -1);
-            float* d1[CONV_RAGGED_MAX]; const float* d1c[CONV_RAGGED_MAX];
-            for (int b = 0; b < B; ++b) d1c[b] = d1[b] = buf(o1, b);
-            unsigned* w1 = new_word();
-            if ((e = dgrad(g, l, EPI_MASK_SCALE, t1, d1, g_am, w1))) return e;
-            if ((e = wgrad(d1c, l1, 1.0f, w1))) return e;
-            const int o2 = next_buf(gi, o1);
-            float* d2[CONV_RAGGED_MAX];
-            for (int b = 0; b < B; ++b) d2[b] = buf(o2, b);
-            unsigned* w2 = new_word();
-            if ((e = dgrad(d1c, l1, EPI_ADD_CENTER, g, d2, w1, w2))) return e;
-            for (int b = 0; b < B; ++b) g[b] = d2[b];
-            gi = o2; g_am = w2;
-            --l;                                           // conv1 is done too
-        } else {                                           // plain conv (conv_input, conv_mid, conv_output)
-            if ((e = wgrad(g, l, 1.0f, g_am))) return e;
-            if (need_dx) {
-                const int o = next_buf(gi, -1);
-                float* outs[CONV_RAGGED_MAX];
-                for (int b = 0; b < B; ++b) outs[b] = (l == 0) ? dx[b] : buf(o, b);
-                unsigned* w = l ? new_word() : nullptr;
-                if ((e = dgrad(g, l, EPI_NONE, nullptr, outs, g_am, w))) return e;
-                if (l) { for (int b = 0; b < B; ++b) g[b] = outs[b]; gi = o; g_am = w; }
-            }
-        }
-    }
-    rp.join();
-    return rp.failed ? NVSR_ERR_LAUNCH : NVSR_OK;
-}
-
-}  // namespace nvsr
-
-extern "C" {
 
 int64_t nvsr_planes_sr_batch_backward_workspace_floats(int B, int Cc, int R0, int R1, int hid, int nblocks, int n_up, int pad, const float* rois) {
-    if (B < 1 || B > CONV_RAGGED_MAX) return -1;
-    static thread_local EdsrPlan P;
-    int64_t s = 0, T = 0, one = 0;
+    static thread_local EdsrPlan P[CONV_RAGGED_MAX];
+    SrRegions g;
+    if (sr_regions(B, Cc, R0, R1, hid, nblocks, n_up, pad, -1, rois, P, &g)) return -1;
+    int64_t w = edsr_backward_layout(B, true, P).total;                             // the ragged walk, or the plane-by-plane path (exact f32, B = 1)
     for (int b = 0; b < B; ++b) {
-        int lo[2], hi[2];
-        sr_roi(R0, R1, rois ? rois + 4 * b : nullptr, lo, hi);
-        const int Hp = hi[0] - lo[0] + 2 * pad, Wp = hi[1] - lo[1] + 2 * pad;
-        if (edsr_plan(Cc, Cc, hid, nblocks, n_up, Hp, Wp, &P)) return -1;
-        s += ((int64_t)Cc * P.Ho * P.Wo + 3) / 4 * 4 + ((int64_t)Cc * Hp * Wp + 3) / 4 * 4;      // d_diff + the prepared input's gradient
-        T += (P.max_tensor + 3) / 4 * 4;
-        const int64_t w1 = nvsr_edsr_backward_workspace_floats(Cc, Cc, hid, nblocks, n_up, Hp, Wp);   // (the plane-by-plane path of exact f32)
-        if (w1 > one) one = w1;
+        const int64_t one = edsr_backward_layout(1, false, P + b).total;
+        if (one > w) w = one;
     }
-    int64_t part = 0;
-    for (int l = 0; l < P.n; ++l) {
-        const int64_t f = wgrad_partial_floats_ragged(P.L[l].Cin, P.L[l].Cout);
-        if (f > part) part = f;
-    }
-    const int64_t ragged = 4 * T + 2 * ((part + 3) / 4 * 4) + (P.n + 7) / 4 * 4;       // (edsr_backward_planes: 4 tensors, 2 x partial sums, the words)
-    return s + (ragged > one ? ragged : one);
+    return g.bwd_floats + w;
 }
 
 int nvsr_planes_sr_backward_batch_arith(int B, int Cc, int R0, int R1, const float* keep, const float* packed_dgrad, int hid, int nblocks, int n_up,
@@ -1279,55 +1221,8 @@ int nvsr_planes_sr_backward_batch_marks(int B, int Cc, int R0, int R1, const flo
     if (n_marks < 0 || (n_marks > 0 && (!mark_layers || !mark_events))) return NVSR_ERR_NULL;
     LayerMarks marks;
     marks.n = n_marks; marks.layers = mark_layers; marks.events = mark_events;
-    if (B < 1 || B > CONV_RAGGED_MAX) return NVSR_ERR_SHAPE;
-    if (plane_interp != NVSR_PLANE_INTERP_BILINEAR && plane_interp != NVSR_PLANE_INTERP_BICUBIC) return NVSR_ERR_SHAPE;
-    if (!aligned16(packed_dgrad) || !aligned16(workspace) || !aligned16(keep)) return NVSR_ERR_ALIGN;
-    hipStream_t stream = (hipStream_t)stream_;
-    const int sf = 1 << n_up, arith = conv_resolve_arith(arithmetic);
-    static thread_local EdsrPlan P[CONV_RAGGED_MAX];
-    int lo[CONV_RAGGED_MAX][2], hi[CONV_RAGGED_MAX][2], Hp[CONV_RAGGED_MAX], Wp[CONV_RAGGED_MAX];
-    const float* xin[CONV_RAGGED_MAX]; const float* acts[CONV_RAGGED_MAX];
-    float* d_diff[CONV_RAGGED_MAX]; float* dxin[CONV_RAGGED_MAX];
-    const float* k = keep; float* w = workspace;
-    bool any_lr = false;
-    for (int b = 0; b < B; ++b) {
-        if (!d_out[b]) return NVSR_ERR_NULL;
-        sr_roi(R0, R1, rois ? rois + 4 * b : nullptr, lo[b], hi[b]);
-        Hp[b] = hi[b][0] - lo[b][0] + 2 * pad; Wp[b] = hi[b][1] - lo[b][1] + 2 * pad;
-        if (int e = edsr_plan(Cc, Cc, hid, nblocks, n_up, Hp[b], Wp[b], &P[b])) return e;
-        if (P[b].Ho != (hi[b][0] - lo[b][0]) * sf + 2 * over || P[b].Wo != (hi[b][1] - lo[b][1]) * sf + 2 * over) return NVSR_ERR_SHAPE;
-        const int64_t n_in = (int64_t)Cc * Hp[b] * Wp[b];
-        xin[b] = k; acts[b] = k + (n_in + 3) / 4 * 4;
-        k = acts[b] + P[b].acts_floats;
-        d_diff[b] = w; w += ((int64_t)Cc * P[b].Ho * P[b].Wo + 3) / 4 * 4;
-        dxin[b] = w; w += (n_in + 3) / 4 * 4;
-        any_lr = any_lr || (d_lr && d_lr[b]);
-    }
-    for (int b = 0; b < B; ++b)
-        if (int e = finish_backward(d_out[b], Cc, R0, R1, sf, lo[b], hi[b], P[b].Ho, P[b].Wo, over, d_diff[b], d_lr ? d_lr[b] : nullptr, align_corners ? 1 : 0,
-                                    plane_interp == NVSR_PLANE_INTERP_BICUBIC ? 1 : 0, stream))
-            return e;
-    if (arith == NVSR_ARITH_F32 || B == 1) {
-        for (int b = 0; b < B; ++b)
-            if (int e = nvsr_edsr_backward_arith(xin[b], Cc, Hp[b], Wp[b], acts[b], packed_dgrad, Cc, hid, nblocks, n_up, d_diff[b], grad_natural,
-                                                 (d_lr && d_lr[b]) ? dxin[b] : nullptr, w, arith, stream_))
-                return e;
-        // (plane by plane every layer's gradient is final only after the last plane: all marks here)
-        if (int e = record_marks(marks, -1, stream)) return e;
-    } else {
-        // (a plane whose LR gradient nobody wants still gets its first layer's data gradient when another plane needs it: 0.3 % of the pass)
-        for (int i = 0; i < n_marks; ++i)
-            if (mark_layers[i] < 0 || mark_layers[i] >= P[0].n) return NVSR_ERR_SHAPE;
-        if (int e = edsr_backward_planes(B, P, xin, acts, packed_dgrad, d_diff, grad_natural, any_lr ? dxin : nullptr, w, arith, stream, marks)) return e;
-    }
-    for (int b = 0; b < B; ++b) {
-        if (!(d_lr && d_lr[b])) continue;
-        const int64_t n_in = (int64_t)Cc * Hp[b] * Wp[b];
-        hipLaunchKernelGGL(sr_prepare_backward_kernel, dim3((unsigned)((n_in + 255) / 256)), dim3(256), 0, stream, dxin[b], Cc, R0, R1, lo[b][0], lo[b][1],
-                           Hp[b], Wp[b], pad, stdv, d_lr[b]);
-        if (int e = NVSR_CHECK_LAUNCH()) return e;
-    }
-    return NVSR_OK;
+    return planes_sr_backward(B, Cc, R0, R1, keep, packed_dgrad, hid, nblocks, n_up, pad, over, rois, stdv, d_out, grad_natural, d_lr, workspace, arithmetic,
+                              align_corners, plane_interp, marks, true, (hipStream_t)stream_);
 }
 
 }  // extern "C"
