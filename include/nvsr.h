@@ -112,14 +112,35 @@ int nvsr_version(void);
 #define NVSR_ARITH_INVALID (-2)     /* what nvsr_get_*_arithmetic returns when the environment variable holds an unknown string: every call
                                        that inherits the process default then fails with NVSR_ERR_SHAPE until nvsr_set_*_arithmetic is called */
 #define NVSR_ARITH_F32 0
-#define NVSR_ARITH_F16 1            /* CONVOLUTIONS ONLY (below, "NVSR_ARITH_F16"): every decoder, render, NeRF-baseline, low-rank, occupancy and
-                                       deterministic-route entry point refuses it, and so do nvsr_set_decoder_arithmetic and
-                                       NVSR_DECODER_ARITHMETIC.  The value of a limb mode is its limb count. */
+#define NVSR_ARITH_F16 1            /* THE CONVOLUTIONS (below, "NVSR_ARITH_F16") AND THE EVALUATION RENDERS ("NVSR_ARITH_F16 in the render pass",
+                                       right below): nvsr_render_pass_arith, nvsr_render_rays_arith and the fused launches behind them.  Every other
+                                       decoder, render, NeRF-baseline, low-rank, occupancy, shared-decoder and deterministic-route entry point
+                                       refuses it, and so do nvsr_set_decoder_arithmetic and NVSR_DECODER_ARITHMETIC.  The value of a limb mode is
+                                       its limb count. */
 #define NVSR_ARITH_F16X2 2
 #define NVSR_ARITH_BF16X3 3
 #define NVSR_ARITH_DEFAULT NVSR_ARITH_F16X2
 int nvsr_get_decoder_arithmetic(void);
 int nvsr_set_decoder_arithmetic(int mode);
+/* NVSR_ARITH_F16 in the render pass -- mixed precision for evaluation frames, opt-in, BY NAME only (never a process default: nvsr_set_decoder_arithmetic(1)
+ * and NVSR_DECODER_ARITHMETIC=f16 answer NVSR_ERR_SHAPE / NVSR_ARITH_INVALID as before).
+ *   Arithmetic.  Per layer w^ = RN_f16(W 2^8), x^ = RN_f16(x 2^4) -- F16X2's scales, its high limbs alone -- ONE v_mfma_f32_32x32x16_f16 per product
+ *   block in F16X2's K-block and output-block order, f32 accumulation; bias, ReLU, heads and compositing are F16X2's, in f32.  Error: 2^-11 per
+ *   operand instead of 2^-23; the decoder's outputs sit about 1e-3 (sigma) / 5e-4 (rgb logits) rms of their own rms from float64
+ *   (tests/render_f16_ref.py is the arithmetic in numpy; tests/test_render_f16.py holds the kernels to it).  The weights are limb 0 of F16X2's
+ *   fragment region: the packed blob and its size functions are unchanged.
+ *   Who takes it.  nvsr_render_pass_arith (raw outputs included) from 16 384 rays on -- below that, and under NVSR_RENDER_V1, it runs the exact-f32
+ *   kernel like every other mode -- nvsr_render_rays_arith, and the internal launches nvsr_render_pass3_launch / _coarse_z_launch (limbs = 1).  The
+ *   fused kernel, the two-phase route (lockstep and point-major colour pass), their orders and the scratch are chosen exactly as for F16X2, and all
+ *   routes give the same bits.  A FRAME BELOW nvsr_fused_min_rays() RAYS (nvsr_render_rays_arith) RUNS ITS UN-FUSED PASSES IN NVSR_ARITH_F16X2: the
+ *   decode kernels have no one-limb mode.
+ *   Who answers NVSR_ERR_SHAPE to it: nvsr_set_decoder_arithmetic, nvsr_triplane_decode_arith, nvsr_decode_rays*, every backward and weight-gradient
+ *   entry, nvsr_render_rays_shared_arith, the occupancy entries (nvsr_occupancy_build, nvsr_render_pass_occupancy_arith,
+ *   nvsr_render_rays_occupancy_arith), the Mip-NeRF and PE entries, nvsr_generic_*.
+ *   Range contract.  F16X2's ranges (|W| < 255, |feature / activation| < 4094), and never a finite wrong number beyond them.  A lone limb has no
+ *   -inf low limb to meet its inf, so an out-of-range operand can leave +-inf in an accumulator where F16X2 leaves NaN: every layer's accumulator and
+ *   every head turn +-inf into NaN before the ReLU (the integer-max ReLU would make -inf a 0; an all-positive row would carry +inf to alpha = 1).  A
+ *   weight beyond the range poisons the head biases as for F16X2.  A NaN pixel raises bit 1 of the range flag (below) as under F16X2. */
 /* Range flag of NVSR_ARITH_F16X2 (round 4).  A launch in that mode whose operands leave the ranges above produces NaN -- which the caller
  * would otherwise have to find by reading its outputs.  With a device word registered here, every F16X2 launch that WRITES A NON-FINITE
  * RESULT also ORs a bit into that word (1 -- the fused render passes: a non-finite rgb / opacity of a ray; nvsr_decode_rays*: a non-finite raw
@@ -128,8 +149,8 @@ int nvsr_set_decoder_arithmetic(int mode);
  * (models.py:395-421); this is what keeps the drop-in's default arithmetic from ever returning NaN where the reference returns a number.
  * NULL (the initial state) disables the reporting.  The pointer is process-global like the default arithmetic and is read when a launch is
  * enqueued; the word must stay allocated until every launch enqueued while it was registered has finished.  Modes other than F16X2 never
- * touch it (they have no range limit; a NaN they return was a NaN in their inputs) -- except the convolutions' NVSR_ARITH_F16, which shares
- * F16X2's ranges and raises bit 2 like it. */
+ * touch it (they have no range limit; a NaN they return was a NaN in their inputs) -- except NVSR_ARITH_F16, which shares F16X2's ranges: the
+ * convolutions raise bit 2 like F16X2's, the render passes bit 1. */
 int nvsr_set_range_flag(uint32_t* device_word);
 uint32_t* nvsr_get_range_flag(void);
 /* The two-phase render pass.  A fused limb pass (NVSR_ARITH_BF16X3 / _F16X2, N >= nvsr_fused_min_rays) whose caller does not ask for the

@@ -269,8 +269,11 @@ _lib = None
 
 ARITHMETIC = {"f32": 0, "f16x2": 2, "bf16x3": 3}
 # the SR convolutions also take 'f16' (include/nvsr.h NVSR_ARITH_F16: operands rounded once to f16, f32 accumulation; opt-in); every decoder,
-# render and baseline call refuses it, so ARITHMETIC -- which tools and tests index for those calls -- does not list it
+# training and baseline call refuses it, so ARITHMETIC -- which tools and tests index for those calls -- does not list it
 CONV_ARITHMETIC = {**ARITHMETIC, "f16": 1}
+# so do the entry points that render evaluation frames (nvsr_render_pass_arith, nvsr_render_rays_arith and the coarse_z launch): their fused
+# limb passes run on one f16 limb; never a process default (set_decoder_arithmetic refuses it), never a training arithmetic
+RENDER_ARITHMETIC = {**ARITHMETIC, "f16": 1}
 SR_BATCH_MAX = 4          # planes per nvsr_planes_sr_*_batch_arith call (csrc/sr_core.h CONV_RAGGED_MAX)
 ARITH_INHERIT = -1
 
@@ -298,6 +301,28 @@ def resolve_nerf_arithmetic(mode=None):
         return code
     code = lib().nvsr_get_decoder_arithmetic()
     return ARITHMETIC["bf16x3"] if code == ARITHMETIC["f16x2"] else code
+
+
+def render_arith_code(mode):
+    """arith_code for the entry points that render evaluation frames: also 'f16'"""
+    return RENDER_ARITHMETIC[mode] if isinstance(mode, str) else arith_code(mode)
+
+
+def resolve_render_arithmetic(mode=None):
+    """the concrete NVSR_ARITH_* code an evaluation render made now with `mode` runs its fused passes in ('f16' by name only: the process
+    default is never 'f16')"""
+    code = render_arith_code(mode)
+    return lib().nvsr_get_decoder_arithmetic() if code == ARITH_INHERIT else code
+
+
+def refuse_f16_training(*models):
+    """raise for a training iteration with a model whose arithmetic is 'f16' (called before any launch): the mode renders evaluation frames;
+    no decode, backward or weight-gradient kernel has it"""
+    for m in models:
+        a = getattr(m, "arithmetic", None)
+        if a == "f16" or (a == RENDER_ARITHMETIC["f16"] and not isinstance(a, bool)):
+            raise NvsrError("arithmetic 'f16' (one f16 limb, NVSR_ARITH_F16) renders evaluation frames only: a training iteration has no kernel "
+                            "in it; train in 'f16x2' or 'bf16x3' and set model.arithmetic = 'f16' for eval_nerf / validation renders")
 
 
 def conv_arith_code(mode):

@@ -968,8 +968,11 @@ static int render_frame(const nvsr_scene* scene, const float* packed_coarse, con
     float* w_c = z_c + round4(N * (int64_t)Nc);
     float* z_f = w_c + round4(N * (int64_t)Nc);
     float* raw_ws = z_f + (Nf > 0 ? round4(N * (int64_t)(Nc + Nf)) : 0);
-    const int arith = nvsr_internal_resolve_decoder_arith(arithmetic);
+    const int arith = nvsr_internal_resolve_render_arith(arithmetic);
     const bool fused = fused_limb_passes(N, arith);
+    // NVSR_ARITH_F16 is a mode of the fused limb passes alone (the decode kernels have no one-limb form): a frame of fewer rays, or under
+    // NVSR_RENDER_V1, runs its passes in NVSR_ARITH_F16X2
+    if (arith == NVSR_ARITH_F16 && !fused) arithmetic = NVSR_ARITH_F16X2;
     if (!fused) grids.coarse = nullptr;
     if (!fused || Nf <= 0) grids.fine = nullptr;
     // Inference frames (no stratified jitter) on the fused limb passes: the coarse depths are a function of (near, far, s) -- the coarse
@@ -1010,7 +1013,7 @@ int nvsr_render_rays_occupancy_arith(const nvsr_scene* scene, const float* packe
                                      const float* rays, int lindisp, int white_bkgd, const float* t_rand, const float* u, float* rgb_c, float* disp_c,
                                      float* acc_c, float* rgb_f, float* disp_f, float* acc_f, float* workspace, const uint32_t* grid_coarse, int G_coarse,
                                      const uint32_t* grid_fine, int G_fine, int arithmetic, nvsr_stream_t stream) {
-    if ((grid_coarse && (G_coarse < 1 || G_coarse > 512)) || (grid_fine && (G_fine < 1 || G_fine > 512))) return NVSR_ERR_SHAPE;
+    if ((grid_coarse && (G_coarse < 1 || G_coarse > 512)) || (grid_fine && (G_fine < 1 || G_fine > 512)) || arithmetic == NVSR_ARITH_F16) return NVSR_ERR_SHAPE;
     return render_frame(scene, packed_coarse, packed_fine, N, Nc, Nf, rays, lindisp, white_bkgd, t_rand, u, nullptr, nullptr, rgb_c, disp_c, acc_c, rgb_f, disp_f,
                         acc_f, workspace, arithmetic, stream, FrameGrids{grid_coarse, G_coarse, grid_fine, G_fine});
 }
@@ -1032,6 +1035,7 @@ int nvsr_render_rays_shared_arith(const nvsr_scene* scene, const float* packed, 
                                   int white_bkgd, const float* t_rand, const float* u, const float* noise_coarse, const float* noise_fine,
                                   float* rgb_c, float* disp_c, float* acc_c, float* rgb_f, float* disp_f, float* acc_f, float* workspace,
                                   int arithmetic, nvsr_stream_t stream) {
+    if (arithmetic == NVSR_ARITH_F16) return NVSR_ERR_SHAPE;      // (the evaluation renders' one-limb mode: the two-decoder frame alone takes it)
     if (!shared_path(N, Nf, t_rand, arithmetic))
         return nvsr_render_rays_arith(scene, packed, packed, N, Nc, Nf, rays, lindisp, white_bkgd, t_rand, u, noise_coarse, noise_fine, rgb_c, disp_c,
                                       acc_c, rgb_f, disp_f, acc_f, workspace, arithmetic, stream);

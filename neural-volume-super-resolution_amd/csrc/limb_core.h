@@ -49,6 +49,12 @@ constexpr int P_LIMB3 = NVSR_DECODER_PACKED_F32_FLOATS;                       //
 constexpr int P_LIMB2 = P_LIMB3 + KB_TOTAL * kb_words(3);
 static_assert(P_LIMB2 + KB_TOTAL * kb_words(2) == NVSR_DECODER_PACKED_FLOATS, "packed blob size");
 constexpr int limb_region(int limbs) { return limbs == 3 ? P_LIMB3 : P_LIMB2; }
+// "f16 mode" is not "two limbs": one and two limbs are f16 numbers under the static scales below (scaled taps, biases and heads, the range flag,
+// the poison slot, the LDS layout of pair_core.h); three are bf16 numbers without a scale
+NVSR_CX bool limb_f16(int limbs) { return limbs != 3; }
+// limbs of the packed region a kernel reads: the lone f16 limb is limb 0 of the two-limb region (no region of its own), whose 1-KiB pieces
+// [ob][limb] it takes at a stride of two
+NVSR_CX int region_limbs(int limbs) { return limbs == 1 ? 2 : limbs; }
 
 __device__ __forceinline__ f32x16 mfma_bf16(u32x4 a, u32x4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
@@ -74,9 +80,9 @@ __device__ __forceinline__ unsigned round_pair(float e1, float e0) {          //
 // numbers for 2^-10 <= |W| < 255 and 2^-6 <= |x| < 4094; below, the low limb is a subnormal with an absolute error <= 2^-25-SW resp.
 // 2^-25-SX (1.2e-10 |x| / 1.9e-9 |W|: below an f32 ulp of any activation > 0.03); above, the conversion overflows to inf and the pixel
 // comes out NaN (loud, never a wrong number).
-// LIMBS = 1 (the SR convolutions' NVSR_ARITH_F16, sr.hip / sr_bwd.hip only): hi alone, one product -- operands rounded once to f16, error
+// LIMBS = 1 (NVSR_ARITH_F16: the SR convolutions, sr.hip / sr_bwd.hip, and the render pass, render3.hip): hi alone, one product -- operands rounded once to f16, error
 // <= (2^-10 + 2^-22) |W||x| per product; same scales and ranges.  An operand beyond the range is an inf with no -inf low limb beside it: the
-// kernels write an infinite accumulator as NaN (conv_write_out16).
+// kernels write an infinite accumulator as NaN (conv_write_out16; relu_bias_step and the heads of the render pass).
 constexpr int F16_SW = 8, F16_SX = 4;
 constexpr float F16_W_SCALE = 256.0f, F16_X_SCALE = 16.0f, F16_ACC_UNSCALE = 1.0f / 256.0f, F16_HEAD_SCALE = 1.0f / 16.0f;
 __device__ __forceinline__ unsigned f16_pair(float e1, float e0) {            // v_cvt_pk_f16_f32, round to nearest even
@@ -109,7 +115,7 @@ __device__ __forceinline__ void f16_low_limb_hi(unsigned& lo, float x1, unsigned
 }
 template <int LIMBS>
 __device__ __forceinline__ f32x16 mfma_limb(u32x4 a, u32x4 b, f32x16 c) {
-    if constexpr (LIMBS == 2) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    if constexpr (limb_f16(LIMBS)) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
     else return mfma_bf16(a, b, c);
 }
 

@@ -31,6 +31,7 @@ int nvsr_render_pass_backward_rows_limb_launch(int limbs, const nvsr_scene* scen
 // render.hip: NVSR_ARITH_INHERIT -> the process default, anything that is not a mode -> -1; the mode named by an environment variable (dflt if unset;
 // conv != 0: the variable of the convolutions, which also takes "f16")
 int nvsr_internal_resolve_decoder_arith(int arithmetic);
+int nvsr_internal_resolve_render_arith(int arithmetic);      // + NVSR_ARITH_F16 by name (the evaluation renders' fused passes)
 int nvsr_internal_parse_arith_env(const char* name, int dflt, int conv);
 // colour_order.hip: size the two-phase route's scratch for a pass of N rays x S samples before a frame's first launch (acquire_pass_scratch
 // of colour_order.h as a reservation: it leaves no launch behind)

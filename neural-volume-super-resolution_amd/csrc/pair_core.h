@@ -64,26 +64,27 @@ namespace nvsr {
 // step streams 432 instead of 504 KB.  (3 bf16 limbs: 108 KB would not fit beside the 96 KB ring.)
 template <int LIMBS>
 struct Lds3 {
-    static constexpr int SLOT = 4 * kb_words(LIMBS);                 // words: 48 KB (3 limbs) / 32 KB
+    static constexpr bool F16 = limb_f16(LIMBS);                     // one or two f16 limbs: the same layout, a ring and a resident region of half the size
+    static constexpr int SLOT = 4 * kb_words(LIMBS);                 // words: 48 KB (3 limbs) / 32 KB / 16 KB (one limb)
     static constexpr int SMALL = 2 * SLOT;
     static constexpr int RAYS = SMALL + SMALL_FLOATS;
     // ray cache: RAY_FLOATS per ray (origin, direction, norm, near) + TAP_FLOATS (the view plane's four tap offsets and weights).  f16 limbs: the
     // taps live in a region of their own, 2 KB per wave, that is dead after the prologue -- the wave's accumulator bounce slot (relu_bias_step)
-    static constexpr int RAY_FLOATS = LIMBS == 2 ? 8 : 20;
-    static constexpr int TAP_FLOATS = LIMBS == 2 ? 8 : 0;
+    static constexpr int RAY_FLOATS = F16 ? 8 : 20;
+    static constexpr int TAP_FLOATS = F16 ? 8 : 0;
     static constexpr int VTAPS = RAYS + RAYS2 * RAY_FLOATS;
-    static constexpr int FAR = LIMBS == 2 ? VTAPS + RAYS2 * TAP_FLOATS : -1;
-    static constexpr int RES = VTAPS + RAYS2 * TAP_FLOATS + (LIMBS == 2 ? RAYS2 : 0);
-    static constexpr int RES_KB = LIMBS == 2 ? 9 : 0;
+    static constexpr int FAR = F16 ? VTAPS + RAYS2 * TAP_FLOATS : -1;
+    static constexpr int RES = VTAPS + RAYS2 * TAP_FLOATS + (F16 ? RAYS2 : 0);
+    static constexpr int RES_KB = F16 ? 9 : 0;
     // the point-major colour pass's exchange (render3.hip, PHASE 3): the rays' colour sums and a step's terms, 3 RAYS2 floats each, the step's
-    // slots and the slots' rays, RAYS2 ints each -- 8 KB.  f16 limbs have under 1 KB to spare: the region is the taps' (dead after the prologue
+    // slots and the slots' rays, RAYS2 ints each -- 8 KB.  Two f16 limbs have under 1 KB to spare: the region is the taps' (dead after the prologue
     // while R3_BOUNCE is off), so neither the ring nor the resident weights pay for it; 3 bf16 limbs have the room behind the ring.
     static constexpr int PTS_WORDS = 8 * RAYS2;
-    static constexpr int PTS = LIMBS == 2 ? VTAPS : RES + RES_KB * kb_words(LIMBS);
-    static_assert(LIMBS != 2 || RAYS2 * TAP_FLOATS >= PTS_WORDS, "the points' region fits the taps'");
-    static constexpr int TOTAL = RES + RES_KB * kb_words(LIMBS) + (LIMBS == 2 ? 0 : PTS_WORDS);
+    static constexpr int PTS = F16 ? VTAPS : RES + RES_KB * kb_words(LIMBS);
+    static_assert(!F16 || RAYS2 * TAP_FLOATS >= PTS_WORDS, "the points' region fits the taps'");
+    static constexpr int TOTAL = RES + RES_KB * kb_words(LIMBS) + (F16 ? 0 : PTS_WORDS);
 };
-static_assert(Lds3<3>::TOTAL * 4 <= 160 * 1024 && Lds3<2>::TOTAL * 4 <= 160 * 1024, "LDS budget");
+static_assert(Lds3<3>::TOTAL * 4 <= 160 * 1024 && Lds3<2>::TOTAL * 4 <= 160 * 1024 && Lds3<1>::TOTAL * 4 <= 160 * 1024, "LDS budget");
 
 struct Tile3 {
     f32x16 acc[4];   // layer accumulators (AGPRs), written by MFMAs only
@@ -252,7 +253,15 @@ __device__ __forceinline__ void relu_bias_step(int k, const float* bias, int h, 
 #endif
     if (k >= 4) {
         const int r = k - 4;
-        if constexpr (LIMBS == 2) {
+        if constexpr (LIMBS == 1) {
+            // A lone limb has no -inf low limb to meet its inf: an operand beyond the range leaves +-inf in the accumulator, not NaN -- and the integer
+            // max would turn -inf into 0, an all-positive row carry +inf on.  t = 0 acc is a NaN exactly when acc is not finite; |t| (the modifier
+            // makes whatever NaN the multiplier returns a positive one) is added behind the FMA: + 0 for every number.
+            float v, t;
+            asm("v_mul_f32 %1, 0, %2\n\tv_fma_f32 %0, -%2, %3, %4\n\tv_add_f32 %0, %0, |%1|\n\tv_max_i32 %0, 0, %0"
+                : "=v"(v), "=&v"(t) : "v"(acc[r >> 4][r & 15]), "s"(nsc[0]), "v"(pend.v[(r >> 2) & 1][r & 3]));
+            act[r >> 4][r & 15] = v;
+        } else if constexpr (LIMBS == 2) {
 #if R3_ABLATE & 1024
             float v;
             asm("v_fma_f32 %0, -%1, %2, %3\n\tv_max_i32 %0, 0, %0" : "=v"(v) : "v"((r & 15) == 0 ? acc[r >> 4][0] : act[r >> 4][r & 15]), "s"(nsc[0]), "v"(pend.v[(r >> 2) & 1][r & 3]));
@@ -287,6 +296,12 @@ struct Ring3 {
     int wave, lane;
     unsigned voff;
 };
+// source of round i of a copy from K-block kb0 on (bytes; the lane's part is Ring3::voff = ring3_voff): the 1-KiB pieces of the region are
+// [K-block][ob][limb of the region]; the lone limb takes limb 0 of every pair -- a source stride of two pieces -- and lies dense in LDS
+template <int LIMBS>
+constexpr int ring3_src(int kb0, int i) { return kb0 * kb_words(region_limbs(LIMBS)) * 4 + i * (NW2 * 1024 * (region_limbs(LIMBS) / LIMBS)); }
+template <int LIMBS>
+__device__ __forceinline__ unsigned ring3_voff(unsigned tid) { return (tid >> 6) * (1024u * (region_limbs(LIMBS) / LIMBS)) + (tid & 63) * 16u; }
 template <int LIMBS, int NKB>
 __device__ __forceinline__ const unsigned* ring3_issue(Ring3<LIMBS>& rs, int kb0) {
     unsigned* dst = rs.lds + rs.slot * Lds3<LIMBS>::SLOT;
@@ -295,7 +310,7 @@ __device__ __forceinline__ const unsigned* ring3_issue(Ring3<LIMBS>& rs, int kb0
 #pragma unroll
     for (int i = 0; i < BLOCKS / NW2; ++i)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs.rsrc, (__attribute__((address_space(3))) void*)(dst + (i * NW2 + rs.wave) * 256), 16,
-                                             (int)rs.voff, kb0 * kb_words(LIMBS) * 4 + i * (NW2 * 1024), 0, R3_DMA_AUX);
+                                             (int)rs.voff, ring3_src<LIMBS>(kb0, i), 0, R3_DMA_AUX);
     rs.slot ^= 1;
     return dst;
 }
@@ -308,7 +323,7 @@ __device__ __forceinline__ void ring3_load_resident(const Ring3<LIMBS>& rs, unsi
 #pragma unroll
     for (int i = 0; i < BLOCKS / NW2; ++i)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs.rsrc, (__attribute__((address_space(3))) void*)(dst + (i * NW2 + rs.wave) * 256), 16,
-                                                 (int)rs.voff, kb0 * kb_words(LIMBS) * 4 + i * (NW2 * 1024), 0, R3_DMA_AUX);
+                                                 (int)rs.voff, ring3_src<LIMBS>(kb0, i), 0, R3_DMA_AUX);
 }
 
 // The same copy issued piece by piece from the gaps of the block that follows the ring wait: a chunk is 36-48 KB, the 4 waves push it
@@ -330,10 +345,10 @@ __device__ __forceinline__ void dma_side(int slot, const Ring3<LIMBS>& rs, unsig
         const int i = slot / 3;
 #if R3_ABLATE & 512        // timing experiment: the same number of copy instructions, a quarter of the bytes (dword instead of dwordx4)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs.rsrc, (__attribute__((address_space(3))) void*)(dst + (i * NW2 + rs.wave) * 256), 4,
-                                                 (int)rs.voff, kb0 * kb_words(LIMBS) * 4 + i * (NW2 * 1024), 0, R3_DMA_AUX);
+                                                 (int)rs.voff, ring3_src<LIMBS>(kb0, i), 0, R3_DMA_AUX);
 #else
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs.rsrc, (__attribute__((address_space(3))) void*)(dst + (i * NW2 + rs.wave) * 256), 16,
-                                                 (int)rs.voff, kb0 * kb_words(LIMBS) * 4 + i * (NW2 * 1024), 0, R3_DMA_AUX);
+                                                 (int)rs.voff, ring3_src<LIMBS>(kb0, i), 0, R3_DMA_AUX);
 #endif
     }
 }

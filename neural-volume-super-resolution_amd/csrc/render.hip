@@ -262,6 +262,12 @@ int nvsr_internal_resolve_decoder_arith(int arithmetic) {
     return (arithmetic == NVSR_ARITH_F32 || arithmetic == NVSR_ARITH_BF16X3 || arithmetic == NVSR_ARITH_F16X2) ? arithmetic : -1;
 }
 
+/* the same for the entries that render evaluation frames (nvsr_render_pass_arith, nvsr_render_rays_arith): they also take NVSR_ARITH_F16 BY NAME --
+   never inherited, nvsr_set_decoder_arithmetic refuses it -- for their fused limb passes (render3.hip, one f16 limb) */
+int nvsr_internal_resolve_render_arith(int arithmetic) {
+    return arithmetic == NVSR_ARITH_F16 ? NVSR_ARITH_F16 : nvsr_internal_resolve_decoder_arith(arithmetic);
+}
+
 static uint32_t* g_range_flag = nullptr;
 int nvsr_set_range_flag(uint32_t* device_word) { g_range_flag = device_word; return NVSR_OK; }
 uint32_t* nvsr_get_range_flag(void) { return g_range_flag; }
@@ -361,7 +367,7 @@ int nvsr_render_pass_ex(const nvsr_scene* scene, const float* packed_decoder, in
 int nvsr_render_pass_arith(const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays, const float* z,
                            const float* noise, int white_bkgd, float* rgb, float* disp, float* acc, float* weights, float* depth,
                            float* raw_out, int arithmetic, nvsr_stream_t stream) {
-    const int arith = nvsr_internal_resolve_decoder_arith(arithmetic);
+    const int arith = nvsr_internal_resolve_render_arith(arithmetic);
     if (arith < 0) return NVSR_ERR_SHAPE;
     if (int e = check_scene(scene)) return e;
     if (!packed_decoder || !rays || !z || !rgb || !disp || !acc) return NVSR_ERR_NULL;
@@ -369,7 +375,7 @@ int nvsr_render_pass_arith(const nvsr_scene* scene, const float* packed_decoder,
     if (N < 0 || S < 1 || S > 4096) return NVSR_ERR_SHAPE;
     if (N == 0) return NVSR_OK;
     if (N >= PER_RAY_MIN_RAYS && !getenv("NVSR_RENDER_V1")) {   // two-tiles-per-wave kernels; NVSR_RENDER_V1=1 selects the first-generation kernel
-        if (arith != NVSR_ARITH_F32)                 // bf16-limb matrix pipe (render3.hip)
+        if (arith != NVSR_ARITH_F32)                 // limb matrix pipe (render3.hip): the mode's number is its limb count
             return nvsr_render_pass3_launch(arith, scene, packed_decoder, N, S, rays, z, noise, white_bkgd, rgb, disp, acc, weights, depth, raw_out, stream);
         return nvsr_render_pass2_launch(scene, packed_decoder, N, S, rays, z, noise, white_bkgd, rgb, disp, acc, weights, depth, raw_out, stream);
     }

@@ -74,21 +74,22 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
     constexpr bool ZCOMP = (LZ & 8) != 0;
     constexpr int PHASE = (LZ >> 4) & 7;
     constexpr bool FUSED = PHASE == 0, KEPT = PHASE == 4, DENSITY = PHASE == 1 || KEPT, POINTS = PHASE == 3, COLOUR = PHASE == 2 || POINTS;
+    constexpr bool F16 = limb_f16(LIMBS);             // the f16 mode (static scales, range flag, LDS layout) -- not the limb count
     using L = Lds3<LIMBS>;
     constexpr int NP = limb_products(LIMBS);
     constexpr int NSF = 3 * 4 * NP, NSH = 4 * 4 * NP;          // slots of a feature block / of half a hidden layer
     __shared__ __attribute__((aligned(16))) unsigned lds[L::TOTAL];
     NVSR_RACE_PROBE_DELAY(lds);      // (probe builds only, nvsr_common.h)
-    Ring3<LIMBS> rs{__builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(packed + limb_region(LIMBS)), 0, KB_TOTAL * kb_words(LIMBS) * 4, 0x00020000),
-                    lds, 0, __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), (int)(threadIdx.x & 63), (threadIdx.x >> 6) * 1024u + (threadIdx.x & 63) * 16u};
+    Ring3<LIMBS> rs{__builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(packed + limb_region(LIMBS)), 0, KB_TOTAL * kb_words(region_limbs(LIMBS)) * 4, 0x00020000),
+                    lds, 0, __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), (int)(threadIdx.x & 63), ring3_voff<LIMBS>(threadIdx.x)};
     // (wave index as a SCALAR: the LDS destination of every weight-copy piece is then scalar arithmetic into M0 instead of a vector add + v_readfirstlane per piece)
     float* ldsf = reinterpret_cast<float*>(lds);
     // (f16 limbs: activations are held as x 2^F16_SX -- biases scaled up, head weights scaled down, all exact; limb_core.h)
     // A weight beyond the f16 range was packed as inf: the packer then left a NaN in the blob's spare slot S_F16_POISON, which goes into
     // the head biases here -- every output of such a decoder is NaN instead of a wrong number.
     for (int i = threadIdx.x; i < SMALL_FLOATS; i += TPB2) {
-        float v = packed[P_SMALL + i] * (LIMBS != 2 ? 1.0f : i < S_ALPHA_W ? F16_X_SCALE : i < S_HEAD_B ? F16_HEAD_SCALE : 1.0f);
-        if (LIMBS == 2 && i >= S_HEAD_B && i < S_HEAD_B + 4) v += packed[P_SMALL + S_F16_POISON];
+        float v = packed[P_SMALL + i] * (!F16 ? 1.0f : i < S_ALPHA_W ? F16_X_SCALE : i < S_HEAD_B ? F16_HEAD_SCALE : 1.0f);
+        if (F16 && i >= S_HEAD_B && i < S_HEAD_B + 4) v += packed[P_SMALL + S_F16_POISON];
         ldsf[L::SMALL + i] = v;
     }
     const float* small = ldsf + L::SMALL;
@@ -119,8 +120,8 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
     const int ownX = rs.wave * 64 + (lane0 & 31), ownY = ownX + 32;      // the slots whose ray the lane loads (and, but for POINTS, owns)
     float* rcX = ldsf + L::RAYS + ownX * RAY3_FLOATS;
     float* rcY = rcX + 32 * RAY3_FLOATS;
-    float* rtX = LIMBS == 2 ? ldsf + L::VTAPS + (rs.wave * 64 + (lane0 & 31)) * L::TAP_FLOATS : rcX + 8;     // view-plane taps of the ray
-    float* rtY = rtX + 32 * (LIMBS == 2 ? L::TAP_FLOATS : RAY3_FLOATS);
+    float* rtX = F16 ? ldsf + L::VTAPS + (rs.wave * 64 + (lane0 & 31)) * L::TAP_FLOATS : rcX + 8;     // view-plane taps of the ray
+    float* rtY = rtX + 32 * (F16 ? L::TAP_FLOATS : RAY3_FLOATS);
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         const float* r = rays + (k ? rayY : rayX) * 11;
@@ -248,7 +249,7 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
     };
     // f16 limbs: features carry the activation scale 2^F16_SX, put on the four blend weights (exact; D = (F0 + F1 + F2) / 3 inherits it)
     auto scale_taps = [](Taps& t) NVSR_INL {
-        if constexpr (LIMBS == 2) { t.nw *= F16_X_SCALE; t.ne *= F16_X_SCALE; t.sw *= F16_X_SCALE; t.se *= F16_X_SCALE; }
+        if constexpr (F16) { t.nw *= F16_X_SCALE; t.ne *= F16_X_SCALE; t.sw *= F16_X_SCALE; t.se *= F16_X_SCALE; }
     };
     auto view_job = [&](const float* rtp) NVSR_INL {
         const f32x4 c2 = reinterpret_cast<const f32x4*>(rtp)[0], c3 = reinterpret_cast<const f32x4*>(rtp)[1];
@@ -320,6 +321,8 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
             }
         }
     }
+    // one limb: a head that overflowed is NaN, like an accumulator (relu_bias_step): no +-inf leaves the decoder
+    auto head_out = [](float v) NVSR_INL { if constexpr (LIMBS == 1) return fabsf(v) == __builtin_inff() ? __builtin_nanf("") : v; else return v; };
     Limbs<LIMBS> cur, fa;
     f32x2_t nsc = {-F16_ACC_UNSCALE, -F16_ACC_UNSCALE};                  // relu_bias_step
     asm volatile("" : "+s"(nsc));
@@ -404,9 +407,9 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
         const unsigned* const w_view = RESIDENT ? res : cw;
         R3_MARK(1)      // first ring wait
         R3_RESET
-#define NVSR_ROLL(TL, JL, TB, JB, LOADS, BLENDS) [&](int slot) NVSR_INL { gather_roll<NSF, LOADS, BLENDS, LIMBS == 2 && R3_BLEND_PK>(slot, JL, TL.F, JB, TB.F, h, rt); }
+#define NVSR_ROLL(TL, JL, TB, JB, LOADS, BLENDS) [&](int slot) NVSR_INL { gather_roll<NSF, LOADS, BLENDS, F16 && R3_BLEND_PK>(slot, JL, TL.F, JB, TB.F, h, rt); }
 #define NVSR_ROLL_DMA(TL, JL, TB, JB, LOADS, BLENDS, NKB, KB0) \
-        [&](int slot) NVSR_INL { gather_roll<NSF, LOADS, BLENDS, LIMBS == 2 && R3_BLEND_PK>(slot, JL, TL.F, JB, TB.F, h, rt); dma_side<LIMBS, NKB>(slot, rs, nw, KB0); }
+        [&](int slot) NVSR_INL { gather_roll<NSF, LOADS, BLENDS, F16 && R3_BLEND_PK>(slot, JL, TL.F, JB, TB.F, h, rt); dma_side<LIMBS, NKB>(slot, rs, nw, KB0); }
         // X view | loads X plane 0
         ja.plane = sc.plane[0]; ja.t = pos_taps2(sc, 0, xn0, xn1, xn2); scale_taps(ja.t);
         split_feat(X.V);
@@ -549,7 +552,7 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
                                          },
                                          NoTail{});
 #pragma unroll
-        for (int c = 0; c < 3; ++c) X.raw[c] = (hx[c] + __shfl_xor(hx[c], 32)) + small[S_HEAD_B + 1 + c];
+        for (int c = 0; c < 3; ++c) X.raw[c] = head_out((hx[c] + __shfl_xor(hx[c], 32)) + small[S_HEAD_B + 1 + c]);
         // Y density 0 | Y: rgb heads, then X: act of density layer 0; tail X kb 0
         float hy[3] = {0.0f, 0.0f, 0.0f};
         split_feat(Y.D);
@@ -560,7 +563,7 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
                                           },
                                           tail_of(X.act, 0));
 #pragma unroll
-        for (int c = 0; c < 3; ++c) Y.raw[c] = (hy[c] + __shfl_xor(hy[c], 32)) + small[S_HEAD_B + 1 + c];
+        for (int c = 0; c < 3; ++c) Y.raw[c] = head_out((hy[c] + __shfl_xor(hy[c], 32)) + small[S_HEAD_B + 1 + c]);
         cw = nw;
 
         R3_MARK(4)      // density layer 0
@@ -645,7 +648,7 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
 #undef NVSR_D_AVG
 #undef NVSR_HALF
 #undef NVSR_JOB
-        X.raw[3] = (sx[0] + __shfl_xor(sx[0], 32)) + small[S_HEAD_B];
+        X.raw[3] = head_out((sx[0] + __shfl_xor(sx[0], 32)) + small[S_HEAD_B]);
         }
         if constexpr (FUSED) {
         // density layer 3: the chunk issued last is chunk 0 of the NEXT sample (after the last sample: a harmless copy);
@@ -658,7 +661,7 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
                                                                   spread<64, NSH / 2, NSH>(slot, [&](int k) NVSR_INL { heads_side<1>(k >> 2, k & 3, small + S_ALPHA_W, h, X.act, sx, hp1); });
                                                               },
                                                               NoTail{})))
-        X.raw[3] = (sx[0] + __shfl_xor(sx[0], 32)) + small[S_HEAD_B];
+        X.raw[3] = head_out((sx[0] + __shfl_xor(sx[0], 32)) + small[S_HEAD_B]);
         }
         R3_MARK(5)      // density layers 1..3
         if constexpr (!COLOUR) {
@@ -680,7 +683,7 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
         {
             float hd[1];
             head_dots<1>(small + S_ALPHA_W, h, Y.act, hd);
-            Y.raw[3] = hd[0] + small[S_HEAD_B];
+            Y.raw[3] = head_out(hd[0] + small[S_HEAD_B]);
         }
         if (raw_out && lane < 32) {
             if (validX) *reinterpret_cast<f32x4*>(raw_out + (rayX * S + s) * 4) = f32x4{X.raw[0], X.raw[1], X.raw[2], X.raw[3]};
@@ -730,14 +733,14 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
         } else {
         // ---- colour pass epilogue (exposed): X's raw colours, Y's last activation + rgb heads, both tiles' w sigmoid(raw) ------------
 #pragma unroll
-        for (int c = 0; c < 3; ++c) X.raw[c] = (hx[c] + __shfl_xor(hx[c], 32)) + small[S_HEAD_B + 1 + c];
+        for (int c = 0; c < 3; ++c) X.raw[c] = head_out((hx[c] + __shfl_xor(hx[c], 32)) + small[S_HEAD_B + 1 + c]);
 #pragma unroll
         for (int k = 0; k < RELU_STEPS; ++k) relu_bias_step<LIMBS>(k, small + S_BIAS + 7 * HID, h, Y.acc, Y.act, bp, nsc);
         {
             float hd[3];
             head_dots<3>(small + S_RGB_W, h, Y.act, hd);        // (the fmaf chain and the half-wave sum of heads_side)
 #pragma unroll
-            for (int c = 0; c < 3; ++c) Y.raw[c] = hd[c] + small[S_HEAD_B + 1 + c];
+            for (int c = 0; c < 3; ++c) Y.raw[c] = head_out(hd[c] + small[S_HEAD_B + 1 + c]);
         }
         if constexpr (POINTS) {
             // the step's terms and slots -> LDS; the first point of every run (position p: lane p of the workgroup) adds its run to the ray's sums
@@ -808,7 +811,7 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
                 rgb[ray * 3 + 0] = cr; rgb[ray * 3 + 1] = cg; rgb[ray * 3 + 2] = cb;
             }
             // range flag of the f16 limbs (nvsr.h: nvsr_set_range_flag): a non-finite colour / opacity is an operand beyond the static scales
-            if (LIMBS == 2 && flag && !(fabsf(cr + cg + cb + ac) <= 3.0e38f)) __hip_atomic_fetch_or(flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (F16 && flag && !(fabsf(cr + cg + cb + ac) <= 3.0e38f)) __hip_atomic_fetch_or(flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }
@@ -1055,13 +1058,17 @@ static int launch_pass3(const PassArgs& a, const LiveLists* ll, const OccLaunch*
     };
     if (ll) {
         if (occ) {
-            const KeptLists& kl = occ->kept;
-            launch_occupancy_cull(sc, a.N, a.S, a.rays, a.z, a.lindisp, occ->grid, occ->G, kl.idx, kl.n, a.stream);
-            launch_kept_order(kl, a.N, a.S, a.stream);
-            // a culled sample has weight +0.0: the pass writes the kept samples' weights only
-            if (a.weights && hipMemsetAsync(a.weights, 0, (size_t)a.N * (size_t)a.S * sizeof(float), a.stream) != hipSuccess) return NVSR_ERR_LAUNCH;
-            if (a.z) launch(render_pass3_density_kept_kernel<LIMBS>, a.z, a.disp, a.acc, a.weights, a.depth, flag, ll->z, ll->w, ll->n, kl.slot, kl.idx, kl.n);
-            else launch(render_pass3_density_kept_z_kernel<LIMBS>, a.lindisp, a.disp, a.acc, a.weights, a.depth, flag, ll->z, ll->w, ll->n, kl.slot, kl.idx, kl.n);
+            // (the kept kernels have no one-limb instantiation: the occupancy entry refuses the mode)
+            if constexpr (LIMBS == 1) return NVSR_ERR_SHAPE;
+            else {
+                const KeptLists& kl = occ->kept;
+                launch_occupancy_cull(sc, a.N, a.S, a.rays, a.z, a.lindisp, occ->grid, occ->G, kl.idx, kl.n, a.stream);
+                launch_kept_order(kl, a.N, a.S, a.stream);
+                // a culled sample has weight +0.0: the pass writes the kept samples' weights only
+                if (a.weights && hipMemsetAsync(a.weights, 0, (size_t)a.N * (size_t)a.S * sizeof(float), a.stream) != hipSuccess) return NVSR_ERR_LAUNCH;
+                if (a.z) launch(render_pass3_density_kept_kernel<LIMBS>, a.z, a.disp, a.acc, a.weights, a.depth, flag, ll->z, ll->w, ll->n, kl.slot, kl.idx, kl.n);
+                else launch(render_pass3_density_kept_z_kernel<LIMBS>, a.lindisp, a.disp, a.acc, a.weights, a.depth, flag, ll->z, ll->w, ll->n, kl.slot, kl.idx, kl.n);
+            }
         } else if (a.z) launch(render_pass3_density_kernel<LIMBS>, a.z, a.noise, a.disp, a.acc, a.weights, a.depth, flag, ll->z, ll->w, ll->n);
         else launch(render_pass3_density_z_kernel<LIMBS>, a.lindisp, a.noise, a.disp, a.acc, a.weights, a.depth, flag, ll->z, ll->w, ll->n);
         launch_colour_order(*ll, a.N, a.S, a.stream);
@@ -1082,13 +1089,13 @@ static int launch_pass3(int limbs, const PassArgs& a, const uint32_t* grid = nul
     const PassRoute route = acquire_pass_scratch(a.N, a.S, a.stream, a.raw_out != nullptr, grid != nullptr, true, lists, occ.kept);
     const LiveLists* ll = route == PassRoute::Fused ? nullptr : &lists;
     const OccLaunch* oc = route == PassRoute::Occupancy ? &occ : nullptr;
-    return limbs == 3 ? launch_pass3<3>(a, ll, oc) : launch_pass3<2>(a, ll, oc);
+    return limbs == 3 ? launch_pass3<3>(a, ll, oc) : limbs == 1 ? launch_pass3<1>(a, ll, oc) : launch_pass3<2>(a, ll, oc);
 }
 
 extern "C" int nvsr_render_pass3_launch(int limbs, const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays, const float* z,
                                         const float* noise, int white_bkgd, float* rgb, float* disp, float* acc, float* weights, float* depth, float* raw_out,
                                         nvsr_stream_t stream) {
-    if ((N + RAYS2 - 1) / RAYS2 > 0x7fffffff || (limbs != 2 && limbs != 3)) return NVSR_ERR_SHAPE;
+    if ((N + RAYS2 - 1) / RAYS2 > 0x7fffffff || limbs < 1 || limbs > 3) return NVSR_ERR_SHAPE;
     PassArgs a{}; a.scene = scene; a.packed = packed_decoder; a.N = N; a.S = S; a.rays = rays; a.z = z; a.noise = noise; a.white = white_bkgd;
     a.rgb = rgb; a.disp = disp; a.acc = acc; a.weights = weights; a.depth = depth; a.raw_out = raw_out; a.stream = (hipStream_t)stream;
     return launch_pass3(limbs, a);
@@ -1098,7 +1105,7 @@ extern "C" int nvsr_render_pass3_launch(int limbs, const nvsr_scene* scene, cons
 extern "C" int nvsr_render_pass3_coarse_z_launch(int limbs, const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays, int lindisp,
                                                  const float* noise, int white_bkgd, float* rgb, float* disp, float* acc, float* weights, float* depth,
                                                  float* raw_out, nvsr_stream_t stream) {
-    if ((N + RAYS2 - 1) / RAYS2 > 0x7fffffff || (limbs != 2 && limbs != 3) || !weights) return NVSR_ERR_SHAPE;
+    if ((N + RAYS2 - 1) / RAYS2 > 0x7fffffff || limbs < 1 || limbs > 3 || !weights) return NVSR_ERR_SHAPE;
     PassArgs a{}; a.scene = scene; a.packed = packed_decoder; a.N = N; a.S = S; a.rays = rays; a.lindisp = lindisp; a.noise = noise; a.white = white_bkgd;
     a.rgb = rgb; a.disp = disp; a.acc = acc; a.weights = weights; a.depth = depth; a.raw_out = raw_out; a.stream = (hipStream_t)stream;
     return launch_pass3(limbs, a);

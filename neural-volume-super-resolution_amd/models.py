@@ -726,8 +726,9 @@ class TwoDimPlanesModel(nn.Module):
         return ops._scene(planes, consts), planes
 
     def arith(self):
-        """NVSR_ARITH_* code of this model's calls (-1 = the process default)"""
-        return capi.arith_code(self.arithmetic)
+        """NVSR_ARITH_* code of this model's calls (-1 = the process default; 'f16' is an arithmetic of evaluation renders: the library
+        refuses it to a direct model call, a grid build or a training step)"""
+        return capi.render_arith_code(self.arithmetic)
 
     # |value| limits of NVSR_ARITH_F16X2's static scales (include/nvsr.h): weights are packed as W 2^8, features held as x 2^4
     F16_WEIGHT_LIMIT, F16_FEATURE_LIMIT = 255.0, 4094.0
@@ -756,8 +757,8 @@ class TwoDimPlanesModel(nn.Module):
         """the NVSR_ARITH_* code a render of `planes` through this model runs in: the model's / the process's choice, except that an
         EVALUATION render whose operands do not fit the f16 limbs falls back to the 3-bf16-limb arithmetic (warned once) instead of
         rendering NaN pixels.  Hidden activations beyond the range cannot be known beforehand: those still render NaN."""
-        code = capi.resolve_decoder_arithmetic(self.arithmetic)
-        if code == capi.ARITHMETIC["f16x2"] and not training and not self.f16_operands_in_range(planes):
+        code = capi.resolve_render_arithmetic(self.arithmetic)
+        if code in (capi.RENDER_ARITHMETIC["f16x2"], capi.RENDER_ARITHMETIC["f16"]) and not training and not self.f16_operands_in_range(planes):
             if not self.__dict__.get("_f16_warned"):
                 import warnings
                 warnings.warn("decoder weights or plane values beyond NVSR_ARITH_F16X2's range (|W| < 255, |feature| < 4094): rendering this "

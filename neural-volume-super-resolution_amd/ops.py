@@ -10,7 +10,8 @@ Conventions
   * a scene is passed as `planes` = 4 CHANNEL-LAST [H,W,48] tensors (position planes D0..D2, view-direction plane) and `consts` = 28
     python floats: lo[5], range[5], proj[3][6] (struct nvsr_scene, include/nvsr.h);
   * `arithmetic` is the NVSR_ARITH_* code of the decoder GEMMs / SR convolutions for THIS call (-1 = the process default): a per-call
-    argument, nothing global (capi.arith_code turns 'f32' / 'bf16x3' / 'f16x2' / None into it);
+    argument, nothing global (capi.arith_code turns 'f32' / 'bf16x3' / 'f16x2' / None into it; render_pass and render_rays also take
+    capi.RENDER_ARITHMETIC['f16'], the convolution operators capi.CONV_ARITHMETIC['f16']);
   * operators cannot return None: an output that was not asked for comes back as an empty tensor.
 
 Reference functions behind the operators: models.py:381-421 (decoder), train_utils.py:71-182 (render passes), volume_rendering_utils.py:6-51
@@ -339,8 +340,9 @@ def render_rays(planes: Sequence[Tensor], consts: Sequence[float], packed_coarse
         rgb_f, disp_f, acc_f = _f(N, 3, like=rays), _f(N, like=rays), _f(N, like=rays)
     else:
         rgb_f, disp_f, acc_f = _f(0, 3, like=rays), _f(0, like=rays), _f(0, like=rays)
-    # one decoder for both passes (models.fine.type == 'use_same'): the fine pass evaluates the importance samples only (nvsr.h)
-    if N and Nf > 0 and packed_fine is not None and packed_fine.data_ptr() == packed_coarse.data_ptr():
+    # one decoder for both passes (models.fine.type == 'use_same'): the fine pass evaluates the importance samples only (nvsr.h) -- but in
+    # 'f16' (one f16 limb), which the shared route does not have: such a frame takes the two-decoder route with the blob given twice
+    if N and Nf > 0 and packed_fine is not None and packed_fine.data_ptr() == packed_coarse.data_ptr() and arithmetic != capi.RENDER_ARITHMETIC["f16"]:
         ws = _f(capi.lib().nvsr_render_shared_workspace_floats(N, Nc, Nf), like=rays)
         capi.call("nvsr_render_rays_shared_arith", C.byref(sc), capi.ptr(packed_coarse), N, Nc, Nf, capi.ptr(rays), int(lindisp), int(white),
                   capi.ptr(t_rand), capi.ptr(u), capi.ptr(noise_coarse), capi.ptr(noise_fine), capi.ptr(rgb_c), capi.ptr(disp_c), capi.ptr(acc_c),

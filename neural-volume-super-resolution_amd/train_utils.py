@@ -324,8 +324,11 @@ def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, sc
     train_path = mode == "train" and N > 0 and (_planes_need_grad(top) or dec_c_grad or dec_f_grad or sr_grad)
     # (an evaluation render whose operands leave the f16 limbs' range is found by the library's range flag and rendered again with
     #  force_arith = bf16x3: run_one_iter_of_nerf; a training step raises: training.TrainStep)
-    arith_c = capi.resolve_decoder_arithmetic(model_coarse.arithmetic if force_arith is None else force_arith)
-    arith_f = capi.resolve_decoder_arithmetic(model_fine.arithmetic if force_arith is None else force_arith) if Nf > 0 else arith_c
+    # ('f16', one f16 limb: evaluation renders only -- the fused passes of the two-decoder frame; no occupancy grid, no shared decoder)
+    if mode == "train":
+        capi.refuse_f16_training(model_coarse, model_fine)
+    arith_c = capi.resolve_render_arithmetic(model_coarse.arithmetic if force_arith is None else force_arith)
+    arith_f = capi.resolve_render_arithmetic(model_fine.arithmetic if force_arith is None else force_arith) if Nf > 0 else arith_c
     det = train_path and capi.deterministic()
     if det:
         # what the deterministic mode does not cover is refused here, before anything is launched
@@ -413,6 +416,8 @@ def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, sc
                 return nv.render_pass_occupancy(planes, consts, packed, rays, z, z.shape[1], lindisp, white, want_w, occ[0], occ[1], arith)
             if fused:
                 return nv.render_pass(planes, consts, packed, rays, z, noise, white, want_w, arith)
+            if arith == capi.RENDER_ARITHMETIC["f16"]:      # (the decode kernels have no one-limb mode: an un-fused pass runs in 'f16x2')
+                arith = capi.ARITHMETIC["f16x2"]
             raw, _, _ = nv.decode_rays(planes, consts, packed, rays, z, False, False, arith)
             return nv.composite_rays(raw, z, rays, noise, white, want_w)
 
@@ -462,10 +467,10 @@ _SR_RANGED = (capi.CONV_ARITHMETIC["f16x2"], capi.CONV_ARITHMETIC["f16"])
 
 
 def _f16_in_play(*ms):
-    """does an evaluation of these models launch anything in NVSR_ARITH_F16X2 -- or, the SR network, in the one-limb 'f16', which has the same ranges?"""
-    f16 = capi.ARITHMETIC["f16x2"]
+    """does an evaluation of these models launch anything in NVSR_ARITH_F16X2 -- or in the one-limb 'f16' (render passes, SR network), which has the same ranges?"""
+    f16 = (capi.RENDER_ARITHMETIC["f16x2"], capi.RENDER_ARITHMETIC["f16"])
     for m in ms:
-        if capi.resolve_decoder_arithmetic(m.arithmetic) == f16:
+        if capi.resolve_render_arithmetic(m.arithmetic) in f16:
             return True
         sr = _sr_of(m)
         if sr is not None and capi.resolve_conv_arithmetic(sr.inner_model.arithmetic) in _SR_RANGED:
@@ -587,6 +592,8 @@ def run_one_iter_of_nerf(H, W, focal, model_coarse, model_fine, batch_rays, opti
         return _run_nerf_baseline(b, H, W, focal, model_coarse, model_fine, batch_rays, options, scene_id, mode, scene_config, randoms)
     if not isinstance(model_coarse, models.TwoDimPlanesModel):
         raise NotImplementedError("only the tri-plane model is on the accelerated path")
+    if mode == "train":
+        capi.refuse_f16_training(model_coarse, model_fine)      # (before the first launch: pack_rays below)
     if not options.nerf.use_viewdirs:
         raise NotImplementedError("the decoder kernel expects use_viewdirs=True (all shipped configs)")
     rays = pack_rays(batch_rays[0], batch_rays[1], _cfg(scene_config, "near"), _cfg(scene_config, "far"), H, W, focal,
@@ -661,7 +668,7 @@ def run_one_iter_of_nerf(H, W, focal, model_coarse, model_fine, batch_rays, opti
             if bits:
                 import warnings
                 if not model_fine.__dict__.get("_f16_unfit_warned"):
-                    warnings.warn("weights, plane values or activations beyond NVSR_ARITH_F16X2's range (|W| < 255, |feature / activation| < 4094): this "
+                    warnings.warn("weights, plane values or activations beyond NVSR_ARITH_F16X2's range (|W| < 255, |feature / activation| < 4094; 'f16' has the same): this "
                                   "model renders in 'bf16x3' while its parameters stay as they are (set model.arithmetic = 'bf16x3' to render there in "
                                   "the first place)")
                     model_fine.__dict__["_f16_unfit_warned"] = True

@@ -380,6 +380,7 @@ class TrainStep:
             im_consistency_iter=False, confinements=(), randoms=None):
         """the iteration itself -> (loss, rendering_loss, coarse_loss, fine_loss, with_psnr), device scalars (what __call__ wraps in StepMetrics);
         nothing here waits for the device or allocates host memory: GraphedTrainStep captures it into a HIP graph"""
+        capi.refuse_f16_training(self.mc, self.mf)          # ('f16' renders evaluation frames only)
         self._refuse_undetermined()
         with capi.deterministic_scope(self._deterministic):       # (forward AND backward of the iteration: apply_gradients runs in here)
             return self._run(it, img_target, pose_target, H, W, focal, cur_ds_factor, scene_id, scene_config, num_random_rays, sr_iter,

@@ -32,6 +32,10 @@ BENCHMARKED = [
     # conv3x3_wgrad_limb_kernel<1> -- mangled-name substrings, the demangled names match the two entries above as well
     "conv3x3_limb16_kernelILi2ELi4ELi1E", "conv3x3_limb16_kernelILi3ELi4ELi1E", "conv3x3_limb16_kernelILi4ELi4ELi1E", "conv3x3_limb16_kernelILi6ELi4ELi1E",
     "conv3x3_wgrad_limb_kernelILi1E",
+    # the two-phase route of the render pass (every limb count), and with them the render pass on one f16 limb (NVSR_ARITH_F16 by name, opt-in;
+    # tools/render_f16_time.py times it): render_pass3_kernel<1>, _coarse<1>, _coarse_z<1> match the first two entries, these its other kernels
+    "render_pass3_density_kernel", "render_pass3_density_z_kernel", "render_pass3_colour_kernel", "render_pass3_colour_z_kernel",
+    "render_pass3_points_kernel", "render_pass3_points_z_kernel",
 ]
 # The gate covers EVERY kernel of the library (round 4; round 3 covered the benchmarked ones): no scratch memory, no spilled VGPRs -- except:
 #   ALLOW  name substring -> spilled VGPRs tolerated.  What is listed is debt, with the round that recorded it:
