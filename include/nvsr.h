@@ -778,6 +778,21 @@ int nvsr_generic_decode_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geom
 int nvsr_generic_decode_backward_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural, int64_t P,
                                      const float* x, const float* coord_noise, const float* d_out, float* d_natural, float* const* d_planes,
                                      float* workspace, nvsr_stream_t stream);
+/* ---- generic decoder, fused evaluation ----------------------------------------------------------------------------------------
+ * TwoDimPlanesModel.forward (models.py:381-421) of a generic geometry in ONE launch: the input features, every layer of both decoders and
+ * both heads; the activations stay in LDS.  The result has the bits of nvsr_generic_decode_ext (the same v_mfma_f32_32x32x2_f32 chains over
+ * the same operand pairs in the same order); there is no backward -- training keeps the layered route.
+ * Capacity: a point's row in LDS holds the decoder inputs and one hidden activation,
+ *   row = Kr (+ Kd where the density decoder's input is not a prefix of the colour decoder's: 'sum' / 'avg' position features under
+ *         'concat_pos') + hidden floats, rounded up to 2 x an odd number;
+ * supported = hidden <= 256, max(Kd, Kr) <= 512 and 32 rows fit in 160 KB (Kd, Kr: in_features of the decoders' first layers).
+ * nvsr_generic_fused_supported (models.py:381-421; host only, no device needed): 1 / 0, or the negated status (-NVSR_ERR_NULL,
+ * -NVSR_ERR_SHAPE) for a geometry that nvsr_generic_decoder_natural_floats_ext refuses. */
+int nvsr_generic_fused_supported(const nvsr_decoder_geometry* geometry, int num_position_planes);
+/* nvsr_generic_decode_ext (models.py:381-421) without a workspace: one launch for any P (pieces of whole point blocks only where the grid
+ * limit forces them); NVSR_ERR_SHAPE for a geometry beyond the capacity above; P == 0: NVSR_OK without a launch. */
+int nvsr_generic_decode_fused_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural, int64_t P,
+                                  const float* x, const float* coord_noise, float* out, nvsr_stream_t stream);
 
 /* run_network's model input for a pass (train_utils.py:15-64,111): x [N*S,6] = [ro + rd * z, viewdir] from packed rays [N,11], z [N,S] */
 int nvsr_ray_points(int64_t N, int S, const float* rays, const float* z, float* x, nvsr_stream_t stream);

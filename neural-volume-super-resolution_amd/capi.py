@@ -165,6 +165,9 @@ _PROTOS_OPTIONAL = {   # feature-plane super-resolution (csrc/sr.hip)
     "nvsr_generic_decode_workspace_floats_ext": ([C.POINTER(DecoderGeometry), _i, _i64], _i64),
     "nvsr_generic_decode_backward_workspace_floats_ext": ([C.POINTER(DecoderGeometry), _i, _i64], _i64),
     "nvsr_generic_decode_ext": ([C.POINTER(SceneExt), C.POINTER(DecoderGeometry), _vp, _i64, _vp, _vp, _vp, _vp, _vp], _i),
+    # ... their evaluation in one launch (csrc/generic_fused.hip)
+    "nvsr_generic_fused_supported": ([C.POINTER(DecoderGeometry), _i], _i),
+    "nvsr_generic_decode_fused_ext": ([C.POINTER(SceneExt), C.POINTER(DecoderGeometry), _vp, _i64, _vp, _vp, _vp, _vp], _i),
     "nvsr_generic_decode_backward_ext": ([C.POINTER(SceneExt), C.POINTER(DecoderGeometry), _vp, _i64, _vp, _vp, _vp, _vp, C.POINTER(C.c_void_p),
                                           _vp, _vp], _i),
     "nvsr_ray_points": ([_i64, _i, _vp, _vp, _vp, _vp], _i),

@@ -644,6 +644,34 @@ class TwoDimPlanesModel(nn.Module):
                 self.SR_model.SR_planes.pop(n, None)            # (super-resolved from the stale plane)
                 _PLANE_CACHE.pop(n + "/SR", None)
 
+    def _generic_graph(self):
+        """(the decoder's parameters take gradients, super-resolution is on, _generic_forward would record a graph) with gradients enabled"""
+        names = [get_plane_name(self.cur_id, d) for d in range(self.num_density_planes + 1)] if getattr(self, "cur_id", None) is not None else []
+        dec = any(p.requires_grad for p in self.decoder_parameters())
+        sr_on = hasattr(self, "SR_model") and not self.skip_SR_
+        sr_grad = sr_on and self.SR_model.training and self.SR_model.inner_model.wants_grad(*self.SR_model.LR_planes.values())
+        return dec, sr_on, bool(dec or sr_grad or any(n in self.planes_ and self.planes_[n].requires_grad for n in names))
+
+    def generic_route(self):
+        """'fused' or 'layered': what a forward through the generic kernels runs if called now.  'fused' = one launch, activations in LDS
+        (csrc/generic_fused.hip, torch.ops.nvsr.triplane_decode_generic_fused); it is taken when no graph is being recorded (gradients off, or
+        nothing involved requires them), the geometry is within the kernel's capacity (nvsr_generic_fused_supported) and dec_channels is at
+        most GENERIC_FUSED_DEFAULT_MAX_HIDDEN: the widths at which it was measured faster (profiles/generic_fused_ab.txt; at 256 it holds one
+        wave per workgroup and takes twice the layered route's time).  'layered' = a launch per layer (csrc/generic.hip): training and
+        everything else.  NVSR_GENERIC_FUSED (read at every call): 0 forces 'layered', 1 takes 'fused' wherever the capacity allows.
+        The two give the same bits.  The decision touches no GPU."""
+        handle = os.environ.get("NVSR_GENERIC_FUSED", "")
+        if handle == "0":
+            return "layered"
+        if torch.is_grad_enabled() and self._generic_graph()[2]:
+            return "layered"
+        if handle != "1" and self.dec_channels > self.GENERIC_FUSED_DEFAULT_MAX_HIDDEN:
+            return "layered"
+        geo = capi.DecoderGeometry(*[int(v) for v in self.generic_geometry()])
+        return "fused" if capi.lib().nvsr_generic_fused_supported(C.byref(geo), int(self.num_density_planes)) == 1 else "layered"
+
+    GENERIC_FUSED_DEFAULT_MAX_HIDDEN = 128
+
     def _generic_forward(self, x, coord_noise=None):
         """forward through the generic kernels (any geometry); in training mode with gradients for the planes and the decoder.
         coord_noise [P,3]: the jitter of the normalised sample positions (models.py:291-293) when the caller has drawn it (run_one_iter_of_nerf
@@ -656,10 +684,8 @@ class TwoDimPlanesModel(nn.Module):
             coord_noise = capi.f32c(coord_noise.to(x.device))
         if torch.is_grad_enabled():                                    # (like any torch module: a graph whenever gradients are on)
             names = [get_plane_name(self.cur_id, d) for d in range(self.num_density_planes + 1)]
-            dec = any(p.requires_grad for p in self.decoder_parameters())
-            sr_on = hasattr(self, "SR_model") and not self.skip_SR_
-            sr_grad = sr_on and self.SR_model.training and self.SR_model.inner_model.wants_grad(*self.SR_model.LR_planes.values())
-            if dec or sr_grad or any(n in self.planes_ and self.planes_[n].requires_grad for n in names):
+            dec, sr_on, graph = self._generic_graph()
+            if graph:
                 if self.training:
                     np.random.randint(self.ensemble_size)             # models.py:393 (see forward())
                 if sr_on:
@@ -681,8 +707,8 @@ class TwoDimPlanesModel(nn.Module):
         planes, consts = self.scene_args(planes=planes, check_native=False)
         nat = self.natural_blob()
         capi.require_cuda(nat)
-        return torch.ops.nvsr.triplane_decode_generic(planes, consts, nat, self.generic_geometry(), x, bool(self.align_corners), coord_noise,
-                                                      self.plane_interp == "bicubic")
+        op = torch.ops.nvsr.triplane_decode_generic_fused if self.generic_route() == "fused" else torch.ops.nvsr.triplane_decode_generic
+        return op(planes, consts, nat, self.generic_geometry(), x, bool(self.align_corners), coord_noise, self.plane_interp == "bicubic")
 
     def scene_args(self, planes=None, check_native=True):
         """(planes, consts) of the current scene id as the torch.ops.nvsr operators take them: the channel-last planes (position planes, then

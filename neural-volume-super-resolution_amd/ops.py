@@ -259,6 +259,32 @@ def _(planes, consts, natural, geometry, x, align_corners=True, coord_noise=None
     return x.new_empty((x.shape[0], 4))
 
 
+@custom_op("nvsr::triplane_decode_generic_fused", mutates_args=(), device_types="cuda")
+def triplane_decode_generic_fused(planes: Sequence[Tensor], consts: Sequence[float], natural: Tensor, geometry: Sequence[int], x: Tensor,
+                                  align_corners: bool = True, coord_noise: Optional[Tensor] = None, bicubic: bool = False) -> Tensor:
+    """triplane_decode_generic in ONE launch, for evaluation (csrc/generic_fused.hip): the input features, every layer of both decoders and both
+    heads with the activations in LDS; same arguments, the same bits in the result, no workspace and no autograd (training keeps
+    triplane_decode_generic).  Raises for a geometry beyond the kernel's capacity (nvsr_generic_fused_supported, include/nvsr.h: hidden <= 256,
+    first-layer inputs <= 512 columns, 32 points' rows in 160 KB of LDS) -- TwoDimPlanesModel.generic_route() picks the operator."""
+    x, natural = _c(x), _c(natural)
+    P = x.shape[0]
+    coord_noise = None if coord_noise is None else _c(coord_noise)
+    geo, n_pos, _, sc = _generic_setup(planes, consts, natural, geometry, align_corners, coord_noise, P, bicubic)
+    if capi.lib().nvsr_generic_fused_supported(C.byref(geo), n_pos) != 1:
+        raise capi.NvsrError("this decoder geometry is beyond the fused generic kernel's capacity (nvsr_generic_fused_supported); "
+                             "torch.ops.nvsr.triplane_decode_generic runs it layer by layer")
+    out = _f(P, 4, like=x)
+    if P:
+        capi.call("nvsr_generic_decode_fused_ext", C.byref(sc), C.byref(geo), capi.ptr(natural), P, capi.ptr(x),
+                  None if coord_noise is None else capi.ptr(coord_noise), capi.ptr(out), capi.stream())
+    return out
+
+
+@triplane_decode_generic_fused.register_fake
+def _(planes, consts, natural, geometry, x, align_corners=True, coord_noise=None, bicubic=False):
+    return x.new_empty((x.shape[0], 4))
+
+
 @custom_op("nvsr::triplane_decode_generic_backward", mutates_args=(), device_types="cuda")
 def triplane_decode_generic_backward(planes: Sequence[Tensor], consts: Sequence[float], natural: Tensor, geometry: Sequence[int], x: Tensor,
                                      g_out: Tensor, want_natural: bool, want_planes: Sequence[bool], align_corners: bool = True,
@@ -1524,7 +1550,7 @@ lowrank_planes.register_autograd(_lowrank_bwd, setup_context=_lowrank_setup)
 
 
 FORWARD_OPS = ["plane_to_channel_last", "plane_from_channel_last", "pack_decoder", "coarse_z", "importance_resample", "triplane_decode",
-               "triplane_decode_generic", "ray_points", "lowrank_planes",
+               "triplane_decode_generic", "triplane_decode_generic_fused", "ray_points", "lowrank_planes",
                "render_pass", "render_rays", "decode_rays", "composite", "composite_rays", "edsr", "planes_sr", "cumprod_exclusive"]
 
 
