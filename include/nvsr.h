@@ -136,7 +136,8 @@ int nvsr_set_decoder_arithmetic(int mode);
  *   decode kernels have no one-limb mode.
  *   Who answers NVSR_ERR_SHAPE to it: nvsr_set_decoder_arithmetic, nvsr_triplane_decode_arith, nvsr_decode_rays*, every backward and weight-gradient
  *   entry, nvsr_render_rays_shared_arith, the occupancy entries (nvsr_occupancy_build, nvsr_render_pass_occupancy_arith,
- *   nvsr_render_rays_occupancy_arith), the Mip-NeRF and PE entries, nvsr_generic_*.
+ *   nvsr_render_rays_occupancy_arith), the Mip-NeRF and PE entries, nvsr_generic_* (of which nvsr_generic_decode_fused_arith_ext takes
+ *   NVSR_ARITH_F16X2 by name; the others have no arithmetic argument and run exact f32).
  *   Range contract.  F16X2's ranges (|W| < 255, |feature / activation| < 4094), and never a finite wrong number beyond them.  A lone limb has no
  *   -inf low limb to meet its inf, so an out-of-range operand can leave +-inf in an accumulator where F16X2 leaves NaN: every layer's accumulator and
  *   every head turn +-inf into NaN before the ReLU (the integer-max ReLU would make -inf a 0; an all-positive row would carry +inf to alpha = 1).  A
@@ -793,6 +794,36 @@ int nvsr_generic_fused_supported(const nvsr_decoder_geometry* geometry, int num_
  * limit forces them); NVSR_ERR_SHAPE for a geometry beyond the capacity above; P == 0: NVSR_OK without a launch. */
 int nvsr_generic_decode_fused_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural, int64_t P,
                                   const float* x, const float* coord_noise, float* out, nvsr_stream_t stream);
+/* ---- generic decoder, fused evaluation in NVSR_ARITH_F16X2 (csrc/generic_fused_limb.hip) ---------------------------------------------
+ * The launch above with the HIDDEN layers of both decoders in two f16 limbs: per layer w^ = limbs of 2^8 W, x^ = limbs of 2^4 x (hi = RN_f16(v),
+ * lo = RN_f16(v - hi)), the products Wh xl, Wh xh, Wl xh on v_mfma_f32_32x32x16_f16 per 16-column K-block of [X1 | X2] in ascending order, f32
+ * accumulation, act = relu(fma(acc, 2^-12, b)) with a ReLU that keeps NaN.  The input features, the biases, both heads (on the f32 activations,
+ * from the natural blob) and the outputs are f32 and computed exactly as by nvsr_generic_decode_fused_ext.  BY NAME only: there is no process
+ * default here, and no backward (training keeps the layered route).
+ * Range contract: F16X2's -- |W| < 255 for the hidden matrices, |feature / activation| < 4094; beyond them the outputs that depend on the
+ * operand are NaN, never a finite wrong number, and a NaN in the planes, the points or the weights comes out as NaN.  A launch that writes a
+ * non-finite out row ORs 1 into the range flag (nvsr_set_range_flag), wherever the NaN came from.
+ * Packed weights (nvsr_pack_generic_decoder_ext; nvsr_generic_packed_floats_ext 32-bit words, or the negated status for a geometry that
+ * nvsr_generic_decoder_natural_floats_ext refuses): every hidden layer in state-dict order -- the density layers, then the rgb layers; heads and
+ * biases are NOT packed.  A layer with K = in_features (the natural matrix's columns [X1 | X2]) holds KB = ceil(K / 16) x TT = ceil(hidden / 32)
+ * x 2 fragments of 256 words, ordered [kb][t][limb].  Word 4 lane + j (j = 0 .. 3) of lane (m = lane & 31, h = lane >> 5) holds the f16
+ * W~[32 t + m][16 kb + 8 h + 2 j] in its low half and W~[32 t + m][16 kb + 8 h + 2 j + 1] in its high half, W~ = 2^8 W and +0 beyond row
+ * hidden and column K; limb 0 = RN_f16(W~), limb 1 = RN_f16(W~ - limb 0) (the subtraction is exact in f32).  A lane's A operand of one MFMA is
+ * 16 contiguous bytes.  tests/generic_limb_ref.py restates the layout and the arithmetic in numpy.
+ * Capacity: nvsr_generic_fused_supported's limits with rows whose parts start at multiples of 4 floats: row = Kr (+ Kd, as above) + hidden, each
+ * rounded up to 4 floats, the sum rounded up to 4 x an odd number.
+ * nvsr_generic_fused_supported_arith (host only): NVSR_ARITH_F32 answers nvsr_generic_fused_supported, NVSR_ARITH_F16X2 the limb kernel's
+ * capacity (1 / 0), any other arithmetic 0; the negated status for an inconsistent geometry.
+ * nvsr_generic_decode_fused_arith_ext: NVSR_ARITH_F32 forwards to nvsr_generic_decode_fused_ext (`packed` may be NULL); NVSR_ARITH_F16X2
+ * launches the limb kernel (NVSR_ERR_NULL without `packed`, NVSR_ERR_SHAPE beyond the capacity); NVSR_ARITH_F16, NVSR_ARITH_BF16X3,
+ * NVSR_ARITH_INHERIT and everything else: NVSR_ERR_SHAPE.  P == 0: NVSR_OK without a launch. */
+int64_t nvsr_generic_packed_floats_ext(const nvsr_decoder_geometry* geometry, int num_position_planes);
+int nvsr_pack_generic_decoder_ext(const nvsr_decoder_geometry* geometry, int num_position_planes, const float* natural, float* packed,
+                                  nvsr_stream_t stream);
+int nvsr_generic_fused_supported_arith(const nvsr_decoder_geometry* geometry, int num_position_planes, int arith);
+int nvsr_generic_decode_fused_arith_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural,
+                                        const float* packed, int64_t P, const float* x, const float* coord_noise, float* out, int arith,
+                                        nvsr_stream_t stream);
 
 /* run_network's model input for a pass (train_utils.py:15-64,111): x [N*S,6] = [ro + rd * z, viewdir] from packed rays [N,11], z [N,S] */
 int nvsr_ray_points(int64_t N, int S, const float* rays, const float* z, float* x, nvsr_stream_t stream);

@@ -168,6 +168,11 @@ _PROTOS_OPTIONAL = {   # feature-plane super-resolution (csrc/sr.hip)
     # ... their evaluation in one launch (csrc/generic_fused.hip)
     "nvsr_generic_fused_supported": ([C.POINTER(DecoderGeometry), _i], _i),
     "nvsr_generic_decode_fused_ext": ([C.POINTER(SceneExt), C.POINTER(DecoderGeometry), _vp, _i64, _vp, _vp, _vp, _vp], _i),
+    # ... and that launch with the hidden layers in two f16 limbs (csrc/generic_fused_limb.hip)
+    "nvsr_generic_packed_floats_ext": ([C.POINTER(DecoderGeometry), _i], _i64),
+    "nvsr_pack_generic_decoder_ext": ([C.POINTER(DecoderGeometry), _i, _vp, _vp, _vp], _i),
+    "nvsr_generic_fused_supported_arith": ([C.POINTER(DecoderGeometry), _i, _i], _i),
+    "nvsr_generic_decode_fused_arith_ext": ([C.POINTER(SceneExt), C.POINTER(DecoderGeometry), _vp, _vp, _i64, _vp, _vp, _vp, _i, _vp], _i),
     "nvsr_generic_decode_backward_ext": ([C.POINTER(SceneExt), C.POINTER(DecoderGeometry), _vp, _i64, _vp, _vp, _vp, _vp, C.POINTER(C.c_void_p),
                                           _vp, _vp], _i),
     "nvsr_ray_points": ([_i64, _i, _vp, _vp, _vp, _vp], _i),

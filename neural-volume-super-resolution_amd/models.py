@@ -671,6 +671,43 @@ class TwoDimPlanesModel(nn.Module):
         return "fused" if capi.lib().nvsr_generic_fused_supported(C.byref(geo), int(self.num_density_planes)) == 1 else "layered"
 
     GENERIC_FUSED_DEFAULT_MAX_HIDDEN = 128
+    # dec_channels (lowest, highest) at which the fused route in 'f16x2' was measured faster, by more than the spread of the alternations, than
+    # the better of the two f32 routes: 1.28 - 1.54 x on 2^22 points, 1.39 - 1.69 x on a 400 x 400 frame at 64, 128 and 256
+    # (profiles/generic_limb_ab.txt).  Narrower decoders were not measured: there the arithmetic needs NVSR_GENERIC_FUSED=1.  None: nowhere.
+    GENERIC_LIMB_DEFAULT_HIDDEN = (64, 256)
+
+    def generic_arithmetic(self):
+        """'f16x2' or 'f32': the arithmetic of the hidden layers if a forward through the generic kernels were called now.  'f16x2' = the fused
+        launch on two f16 limbs (csrc/generic_fused_limb.hip, torch.ops.nvsr.triplane_decode_generic_fused_arith), taken exactly when
+        model.arithmetic is 'f16x2' BY NAME (None, the process default and NVSR_DECODER_ARITHMETIC never select it), no graph is being
+        recorded (generic_route's rule), NVSR_GENERIC_FUSED is not 0, the geometry is within the limb kernel's capacity
+        (nvsr_generic_fused_supported_arith) and dec_channels is a width at which it was measured faster (GENERIC_LIMB_DEFAULT_HIDDEN;
+        NVSR_GENERIC_FUSED=1 lifts this last condition).  Any other model.arithmetic is ignored by the generic kernels, as ever: 'f32' means
+        what generic_route() says.  An evaluation frame that left the limbs' range is rendered again in 'f32' (train_utils.run_one_iter_of_nerf),
+        which holds this answer at 'f32' while it does.  The decision touches no GPU."""
+        if not (isinstance(self.arithmetic, str) and self.arithmetic == "f16x2") or self.__dict__.get("_generic_limb_off"):
+            return "f32"
+        handle = os.environ.get("NVSR_GENERIC_FUSED", "")
+        if handle == "0" or (torch.is_grad_enabled() and self._generic_graph()[2]):
+            return "f32"
+        span = self.GENERIC_LIMB_DEFAULT_HIDDEN
+        if handle != "1" and not (span is not None and span[0] <= self.dec_channels <= span[1]):
+            return "f32"
+        geo = capi.DecoderGeometry(*[int(v) for v in self.generic_geometry()])
+        ok = capi.lib().nvsr_generic_fused_supported_arith(C.byref(geo), int(self.num_density_planes), capi.ARITHMETIC["f16x2"]) == 1
+        return "f16x2" if ok else "f32"
+
+    def packed_generic_decoder(self):
+        """the hidden layers' f16-limb fragments for generic_arithmetic() == 'f16x2' (nvsr_pack_generic_decoder_ext), cached like packed_decoder()"""
+        params = self.decoder_parameters()
+        key = tuple((p.data_ptr(), p._version) for p in params)
+        cache = self.__dict__.get("_packed_generic_cache")
+        if cache is None or cache[0] != key:
+            nat = self.natural_blob()
+            capi.require_cuda(nat)
+            cache = (key, torch.ops.nvsr.pack_generic_decoder(nat, self.generic_geometry(), int(self.num_density_planes)))
+            self.__dict__["_packed_generic_cache"] = cache
+        return cache[1]
 
     def _generic_forward(self, x, coord_noise=None):
         """forward through the generic kernels (any geometry); in training mode with gradients for the planes and the decoder.
@@ -707,6 +744,10 @@ class TwoDimPlanesModel(nn.Module):
         planes, consts = self.scene_args(planes=planes, check_native=False)
         nat = self.natural_blob()
         capi.require_cuda(nat)
+        if self.generic_arithmetic() == "f16x2":
+            return torch.ops.nvsr.triplane_decode_generic_fused_arith(planes, consts, nat, self.packed_generic_decoder(), self.generic_geometry(), x,
+                                                                      bool(self.align_corners), coord_noise, self.plane_interp == "bicubic",
+                                                                      capi.ARITHMETIC["f16x2"])
         op = torch.ops.nvsr.triplane_decode_generic_fused if self.generic_route() == "fused" else torch.ops.nvsr.triplane_decode_generic
         return op(planes, consts, nat, self.generic_geometry(), x, bool(self.align_corners), coord_noise, self.plane_interp == "bicubic")
 

@@ -285,6 +285,56 @@ def _(planes, consts, natural, geometry, x, align_corners=True, coord_noise=None
     return x.new_empty((x.shape[0], 4))
 
 
+@custom_op("nvsr::pack_generic_decoder", mutates_args=(), device_types="cuda")
+def pack_generic_decoder(natural: Tensor, geometry: Sequence[int], n_pos: int) -> Tensor:
+    """the hidden layers of a generic geometry's natural blob -> the f16-limb fragments of the fused evaluation kernel in 'f16x2'
+    (csrc/generic_fused_limb.hip; include/nvsr.h has the layout).  Evaluation only: no autograd."""
+    nat = capi.f32c(natural)
+    geo = capi.DecoderGeometry(*[int(v) for v in geometry])
+    n = capi.lib().nvsr_generic_decoder_natural_floats_ext(C.byref(geo), int(n_pos))
+    if n < 0:
+        raise capi.NvsrError("this decoder geometry is inconsistent (the reference's own layer sizes do not admit it)")
+    assert nat.numel() == n, "natural blob: %d floats, the geometry needs %d" % (nat.numel(), n)
+    packed = _f(capi.lib().nvsr_generic_packed_floats_ext(C.byref(geo), int(n_pos)), like=nat)
+    capi.call("nvsr_pack_generic_decoder_ext", C.byref(geo), int(n_pos), capi.ptr(nat), capi.ptr(packed), capi.stream())
+    return packed
+
+
+@pack_generic_decoder.register_fake
+def _(natural, geometry, n_pos):
+    geo = capi.DecoderGeometry(*[int(v) for v in geometry])
+    return natural.new_empty((capi.lib().nvsr_generic_packed_floats_ext(C.byref(geo), int(n_pos)),), dtype=torch.float32)
+
+
+@custom_op("nvsr::triplane_decode_generic_fused_arith", mutates_args=(), device_types="cuda")
+def triplane_decode_generic_fused_arith(planes: Sequence[Tensor], consts: Sequence[float], natural: Tensor, packed: Tensor, geometry: Sequence[int],
+                                        x: Tensor, align_corners: bool = True, coord_noise: Optional[Tensor] = None, bicubic: bool = False,
+                                        arith: int = 2) -> Tensor:
+    """triplane_decode_generic_fused with the arithmetic of the hidden layers as an argument: capi.ARITHMETIC['f16x2'] runs them in two f16
+    limbs from `packed` (pack_generic_decoder of the same natural blob), capi.ARITHMETIC['f32'] is triplane_decode_generic_fused (`packed`
+    is not read).  Every other code raises: the mode is chosen by name, never inherited.  Beyond f16x2's ranges the result is NaN and the
+    range flag (capi.range_flag) is raised.  Evaluation only: no autograd."""
+    x, natural, packed = _c(x), _c(natural), _c(packed)
+    P = x.shape[0]
+    coord_noise = None if coord_noise is None else _c(coord_noise)
+    geo, n_pos, _, sc = _generic_setup(planes, consts, natural, geometry, align_corners, coord_noise, P, bicubic)
+    if capi.lib().nvsr_generic_fused_supported_arith(C.byref(geo), n_pos, int(arith)) != 1:
+        raise capi.NvsrError("the fused generic kernel does not take this decoder geometry in this arithmetic (nvsr_generic_fused_supported_arith: "
+                             "beyond its capacity, or not 'f32' / 'f16x2')")
+    if int(arith) == capi.ARITHMETIC["f16x2"]:
+        assert packed.numel() == capi.lib().nvsr_generic_packed_floats_ext(C.byref(geo), n_pos), "packed blob of another geometry"
+    out = _f(P, 4, like=x)
+    if P:
+        capi.call("nvsr_generic_decode_fused_arith_ext", C.byref(sc), C.byref(geo), capi.ptr(natural), capi.ptr(packed), P, capi.ptr(x),
+                  None if coord_noise is None else capi.ptr(coord_noise), capi.ptr(out), int(arith), capi.stream())
+    return out
+
+
+@triplane_decode_generic_fused_arith.register_fake
+def _(planes, consts, natural, packed, geometry, x, align_corners=True, coord_noise=None, bicubic=False, arith=2):
+    return x.new_empty((x.shape[0], 4))
+
+
 @custom_op("nvsr::triplane_decode_generic_backward", mutates_args=(), device_types="cuda")
 def triplane_decode_generic_backward(planes: Sequence[Tensor], consts: Sequence[float], natural: Tensor, geometry: Sequence[int], x: Tensor,
                                      g_out: Tensor, want_natural: bool, want_planes: Sequence[bool], align_corners: bool = True,
@@ -1550,7 +1600,7 @@ lowrank_planes.register_autograd(_lowrank_bwd, setup_context=_lowrank_setup)
 
 
 FORWARD_OPS = ["plane_to_channel_last", "plane_from_channel_last", "pack_decoder", "coarse_z", "importance_resample", "triplane_decode",
-               "triplane_decode_generic", "triplane_decode_generic_fused", "ray_points", "lowrank_planes",
+               "triplane_decode_generic", "triplane_decode_generic_fused", "pack_generic_decoder", "triplane_decode_generic_fused_arith", "ray_points", "lowrank_planes",
                "render_pass", "render_rays", "decode_rays", "composite", "composite_rays", "edsr", "planes_sr", "cumprod_exclusive"]
 
 

@@ -490,6 +490,42 @@ def _range_key(*ms):
     return tuple(key)
 
 
+def _generic_limb_frame(launch_all, limb_models, model_coarse, model_fine, device):
+    """an evaluation frame of generic geometries of which `limb_models` evaluate in 'f16x2' (csrc/generic_fused_limb.hip), range-checked like
+    a native frame (run_one_iter_of_nerf): operands beyond the limbs' range -- found beforehand (f16_operands_in_range) or by the range flag
+    after the frame -- send this frame and the later ones of the same parameter versions through the exact-f32 generic route, warned once.
+    model.arithmetic stays as it is."""
+    key = _range_key(model_coarse, model_fine)
+
+    def f32_frame():
+        for mdl in limb_models:
+            mdl.__dict__["_generic_limb_off"] = True
+        try:
+            return launch_all()
+        finally:
+            for mdl in limb_models:
+                mdl.__dict__.pop("_generic_limb_off", None)
+
+    if model_fine.__dict__.get("_f16_unfit") == key:
+        return f32_frame()
+    fit = all(mdl.f16_operands_in_range(mdl.scene_args(check_native=False)[0]) for mdl in limb_models)
+    if fit:
+        flag = capi.range_flag(device)
+        flag.reset()
+        out = launch_all()
+        if not capi.RangeFlag.raised(flag.read_async()):
+            return out
+        flag.reset()
+    if not model_fine.__dict__.get("_f16_unfit_warned"):
+        import warnings
+        warnings.warn("weights, plane values or activations beyond NVSR_ARITH_F16X2's range (|W| < 255, |feature / activation| < 4094): this generic "
+                      "decoder geometry renders in 'f32' while its parameters stay as they are (set model.arithmetic = None to render there in the "
+                      "first place)")
+        model_fine.__dict__["_f16_unfit_warned"] = True
+    model_fine.__dict__["_f16_unfit"] = key
+    return f32_frame()
+
+
 def _sr_fallback(*ms, redo=False):
     """the SR networks of these models super-resolve in 'bf16x3' for the evaluation frame being rendered.  Cached SR planes are dropped when `redo`
     says so (they come from an F16X2 or F16 pass that raised the range flag: NaN inside) or when they were NOT made in 'bf16x3' (`_planes_arith`, set by
@@ -648,6 +684,12 @@ def run_one_iter_of_nerf(H, W, focal, model_coarse, model_fine, batch_rays, opti
     # device word, zeroed before the frame and read back after it (the only host wait of an evaluation frame; a frame is >= 100 ms of
     # kernels at 800 x 800): raised -> the frame is rendered again in the 3-bf16-limb arithmetic (warned once), and later frames of the same
     # parameters go there directly.  Covers hidden activations, which no check of the operands could see beforehand.
+    # Generic geometries: the same healing for a frame of which a model evaluates in 'f16x2' (models.generic_arithmetic: by name only), except
+    # that the frame is rendered again through the exact-f32 generic route -- the bits of arithmetic=None.
+    limb_models = [] if (mode == "train" or native or N == 0) else [
+        mdl for mdl in {id(x_): x_ for x_ in (model_coarse, model_fine)}.values() if not mdl.is_native_geometry() and mdl.generic_arithmetic() == "f16x2"]
+    if limb_models:
+        return _generic_limb_frame(launch_all, limb_models, model_coarse, model_fine, rays.device)      # (no patch order: that is a native frame's)
     range_checked = mode != "train" and native and N > 0 and _f16_in_play(model_coarse, model_fine)
     force, sr_changed = None, []
     if range_checked:
