@@ -824,6 +824,38 @@ int nvsr_generic_fused_supported_arith(const nvsr_decoder_geometry* geometry, in
 int nvsr_generic_decode_fused_arith_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural,
                                         const float* packed, int64_t P, const float* x, const float* coord_noise, float* out, int arith,
                                         nvsr_stream_t stream);
+/* ---- generic decoder, fused evaluation in two phases (csrc/generic_fused.hip, csrc/generic_fused_limb.hip, csrc/generic_live.hip) --------
+ * The launch above split at the decoders, for a frame that runs the colour decoder on the samples of nonzero weight only: the density
+ * phase on every point, the compositing weights, their live list, the colour phase on the listed points.  Both phases are the one-launch
+ * kernels compiled with a phase argument: the same rows in LDS, the same operand pairs in the same order, so sigma and the colour logits
+ * carry the BITS of nvsr_generic_decode_fused_arith_ext at the same points, in NVSR_ARITH_F32 and in NVSR_ARITH_F16X2 (the same packed blob).
+ * Contract of a frame: a sample the list leaves out behaves as if its colour logits were +0.  With weight exactly 0 that is the one-launch
+ * frame bit for bit -- except that a NaN colour logit at such a sample gives NaN there (0 x NaN) and a finite pixel here, and that in
+ * NVSR_ARITH_F16X2 a range overflow of the colour decoder alone at such a sample no longer raises the range flag.
+ * Capacity: nvsr_generic_fused_supported_arith answers for both phases -- each holds a part of the full kernel's row, so either fits wherever
+ * the one-launch kernel fits.  Beyond it, and for every arithmetic but NVSR_ARITH_F32 / NVSR_ARITH_F16X2: NVSR_ERR_SHAPE.
+ * nvsr_generic_decode_fused_density_arith_ext: position, the position planes' taps, combine_pos_planes, the density layers and fc_alpha on
+ * all P points (no atan2f, no view plane, no colour layer); writes the 16-byte row [+0, +0, +0, sigma_raw] of every point into raw_out [P,4]:
+ * the compositors read the tensor as it is.  F16X2: a non-finite sigma raises bit 1 of the range flag.  P == 0: NVSR_OK without a launch.
+ * nvsr_generic_decode_fused_colour_arith_ext: the points index[i], i < min(*count_dev, max_count), of x [P,6] (coord_noise [P,3] by the same
+ * index): the colour decoder's input, the colour layers and fc_rgb; writes the 12 bytes raw_inout[index[i]][0:3] and NOTHING else -- not
+ * column 3, no row outside the list.  index (int32, device; any order; distinct) and count_dev (int32, device, read by the kernel: no host
+ * synchronisation between the phases) usually come from nvsr_generic_live_list; entries at or beyond the count are not read, an index outside
+ * [0, P) is skipped.  The launch is sized for max_count (0 <= max_count <= P < 2^31, else NVSR_ERR_SHAPE; P for a list of unknown length);
+ * workgroups beyond the count return at once.  F16X2: non-finite colour logits of a listed point raise bit 1 of the range flag. */
+int nvsr_generic_decode_fused_density_arith_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural,
+                                                const float* packed, int64_t P, const float* x, const float* coord_noise, float* raw_out, int arith,
+                                                nvsr_stream_t stream);
+int nvsr_generic_decode_fused_colour_arith_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural,
+                                               const float* packed, int64_t P, const float* x, const float* coord_noise, const int32_t* index,
+                                               const int32_t* count_dev, int64_t max_count, float* raw_inout, int arith, nvsr_stream_t stream);
+/* the live list of weights w [P] (the compositor's, any float array): index_out [P] (int32) receives, in ASCENDING order, every p with
+ * !(w[p] == 0) -- NaN is live, +0.0 and -0.0 are dead -- and *count_dev their number; entries of index_out beyond the count are left as they
+ * were.  Two launches (per-workgroup counts; their sum in front of every workgroup, a ballot prefix within it), no atomics: the same list
+ * on every run.  workspace: nvsr_generic_live_list_workspace_bytes(P) bytes on the device (at most 16 KB; -NVSR_ERR_SHAPE for P < 0 or
+ * P >= 2^31, which nvsr_generic_live_list refuses with NVSR_ERR_SHAPE).  P == 0: *count_dev = 0. */
+int64_t nvsr_generic_live_list_workspace_bytes(int64_t P);
+int nvsr_generic_live_list(int64_t P, const float* w, int32_t* index_out, int32_t* count_dev, void* workspace, nvsr_stream_t stream);
 
 /* run_network's model input for a pass (train_utils.py:15-64,111): x [N*S,6] = [ro + rd * z, viewdir] from packed rays [N,11], z [N,S] */
 int nvsr_ray_points(int64_t N, int S, const float* rays, const float* z, float* x, nvsr_stream_t stream);

@@ -173,6 +173,12 @@ _PROTOS_OPTIONAL = {   # feature-plane super-resolution (csrc/sr.hip)
     "nvsr_pack_generic_decoder_ext": ([C.POINTER(DecoderGeometry), _i, _vp, _vp, _vp], _i),
     "nvsr_generic_fused_supported_arith": ([C.POINTER(DecoderGeometry), _i, _i], _i),
     "nvsr_generic_decode_fused_arith_ext": ([C.POINTER(SceneExt), C.POINTER(DecoderGeometry), _vp, _vp, _i64, _vp, _vp, _vp, _i, _vp], _i),
+    # ... and in two phases: the density decoder on every point, the live list of the weights, the colour decoder on the list (+ csrc/generic_live.hip)
+    "nvsr_generic_decode_fused_density_arith_ext": ([C.POINTER(SceneExt), C.POINTER(DecoderGeometry), _vp, _vp, _i64, _vp, _vp, _vp, _i, _vp], _i),
+    "nvsr_generic_decode_fused_colour_arith_ext": ([C.POINTER(SceneExt), C.POINTER(DecoderGeometry), _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i,
+                                                    _vp], _i),
+    "nvsr_generic_live_list_workspace_bytes": ([_i64], _i64),
+    "nvsr_generic_live_list": ([_i64, _vp, _vp, _vp, _vp, _vp], _i),
     "nvsr_generic_decode_backward_ext": ([C.POINTER(SceneExt), C.POINTER(DecoderGeometry), _vp, _i64, _vp, _vp, _vp, _vp, C.POINTER(C.c_void_p),
                                           _vp, _vp], _i),
     "nvsr_ray_points": ([_i64, _i, _vp, _vp, _vp, _vp], _i),

@@ -28,27 +28,34 @@
 
 namespace nvsr {
 
-template <int NT, int LDSF>
+// PHASE (generic_fused_core.h): GF_FULL is the kernel above; GF_DENSITY / GF_COLOUR are its two halves for a frame in two phases -- the density
+// decoder on every point, then the colour decoder on the listed points (`list`, not read by the other phases) -- out of the same code: the same
+// rows, the same chains, the same bits.
+template <int NT, int LDSF, int PHASE>
 __global__ __launch_bounds__(64 * GF_MAX_WAVES) void generic_decode_fused_kernel(SceneDevN sc, GenGeom g, GenFusedPlan L, long P, long block0,
                                                                                   const float* __restrict__ x, const float* __restrict__ noise,
-                                                                                  const float* __restrict__ natural, float* __restrict__ out) {
+                                                                                  const float* __restrict__ natural, float* __restrict__ out,
+                                                                                  GenFusedList list) {
     __shared__ __attribute__((aligned(16))) float lds[LDSF];
     NVSR_RACE_PROBE_DELAY(lds);      // (probe builds only, nvsr_common.h)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n = lane & 31, h = lane >> 5;
-    const long p = ((block0 + blockIdx.x) * (long)(blockDim.x >> 6) + wave) * 32 + n;
-    const bool live = p < P;
+    const long slot0 = (block0 + blockIdx.x) * (long)(blockDim.x >> 6) * 32;
+    long p;
+    bool live;
+    if (!gf_point<PHASE>(list, P, slot0, slot0 + wave * 32 + n, p, live)) return;
     float* rows = lds + wave * 32 * L.ld;       // this wave's 32 points
     float* row = rows + n * L.ld;               // this lane's point (shared by the lane's two halves)
 
     // ---- stage 0: the decoder inputs (generic_fused_core.h) ----
     const GenFusedRows R = {rows, row, L.ld, L.xd_off};
     float vgx, vgy;
-    gf_stage0(sc, g, R, n, h, live, p, x, noise, vgx, vgy);
+    gf_stage0<PHASE>(sc, g, R, n, h, live, p, x, noise, vgx, vgy);
     const bool raw = g.proj == 2 || g.view == 4;
 
-    // ---- the two decoders ----
+    // ---- the two decoders (one of them in a phase) ----
     const float* w = natural;
-    for (int dec = 0; dec < 2; ++dec) {
+    if (PHASE == GF_COLOUR) w += gf_density_floats(g);
+    for (int dec = PHASE == GF_COLOUR ? 1 : 0; dec < (PHASE == GF_DENSITY ? 1 : 2); ++dec) {
         const bool rgb = dec == 1;
         if (rgb && !raw) {                                // Xd -> Xr in place: combine_all_planes 'sum' / 'avg' / 'mult'
             gf_plane_features(sc, g, R, n, h, g.np, g.Cv, vgx, vgy, 0, 2);
@@ -85,25 +92,51 @@ __global__ __launch_bounds__(64 * GF_MAX_WAVES) void generic_decode_fused_kernel
         gf_layer<1>(acc, row, cur_k, cur, 0, cur, w, M, n, h);
         const float* b = w + (long)M * g.hidden;
         if (live && h == 0) {
+            if (PHASE == GF_DENSITY) {                    // the whole row: the colour logits of a sample the colour phase leaves out are +0
+                f32x4 o = {0.0f, 0.0f, 0.0f, __fadd_rn(acc[0][0], b[0])};
+                *reinterpret_cast<f32x4*>(out + p * 4) = o;
+            } else {
 #pragma unroll
-            for (int r = 0; r < 3; ++r)
-                if (r < M) out[p * 4 + (rgb ? 0 : 3) + r] = __fadd_rn(acc[0][r], b[r]);
+                for (int r = 0; r < 3; ++r)
+                    if (r < M) out[p * 4 + (rgb ? 0 : 3) + r] = __fadd_rn(acc[0][r], b[r]);
+            }
         }
         w += (long)M * g.hidden + M;
     }
 }
 
-template <int NT, int CLS>
+// the launch covers P points (GF_FULL, GF_DENSITY) or list.max_count slots of the list (GF_COLOUR: workgroups beyond the count return at once)
+template <int NT, int CLS, int PHASE>
 static int gen_fused_launch(const SceneDevN& sc, const GenGeom& g, const GenFusedPlan& pl, long P, const float* x, const float* noise, const float* natural,
-                            float* out, hipStream_t stream) {
-    const long pts = 32L * pl.waves, blocks = (P + pts - 1) / pts, piece = 1L << 30;       // (grid limit: pieces of whole point blocks)
+                            float* out, const GenFusedList& list, hipStream_t stream) {
+    const long slots = PHASE == GF_COLOUR ? list.max_count : P;
+    const long pts = 32L * pl.waves, blocks = (slots + pts - 1) / pts, piece = 1L << 30;       // (grid limit: pieces of whole point blocks)
     for (long b0 = 0; b0 < blocks; b0 += piece) {
         const long nb = blocks - b0 < piece ? blocks - b0 : piece;
-        hipLaunchKernelGGL((generic_decode_fused_kernel<NT, GF_LDS_FLOATS[CLS]>), dim3((unsigned)nb), dim3(64 * pl.waves), 0, stream, sc, g, pl, P, b0, x,
-                           noise, natural, out);
+        hipLaunchKernelGGL((generic_decode_fused_kernel<NT, GF_LDS_FLOATS[CLS], PHASE>), dim3((unsigned)nb), dim3(64 * pl.waves), 0, stream, sc, g, pl, P,
+                           b0, x, noise, natural, out, list);
         if (int e = NVSR_CHECK_LAUNCH()) return e;
     }
     return NVSR_OK;
+}
+
+template <int PHASE>
+static int gen_fused_dispatch(const SceneDevN& sc, const GenGeom& g, const GenFusedPlan& pl, long P, const float* x, const float* noise,
+                              const float* natural, float* out, const GenFusedList& list, hipStream_t s) {
+#define GF_CASE(NT, CLS) \
+    if (pl.nt == NT && pl.cls == CLS) return gen_fused_launch<NT, CLS, PHASE>(sc, g, pl, P, x, noise, natural, out, list, s);
+#define GF_CASES(NT) GF_CASE(NT, 0) GF_CASE(NT, 1) GF_CASE(NT, 2)
+    GF_CASES(1) GF_CASES(2) GF_CASES(3) GF_CASES(4) GF_CASES(6) GF_CASES(8)
+#undef GF_CASES
+#undef GF_CASE
+    return NVSR_ERR_SHAPE;
+}
+
+int gen_fused_f32_phase(int phase, const SceneDevN& sc, const GenGeom& g, const GenFusedPlan& pl, long P, const float* x, const float* noise,
+                        const float* natural, float* out, const GenFusedList& list, hipStream_t stream) {
+    if (phase == GF_DENSITY) return gen_fused_dispatch<GF_DENSITY>(sc, g, pl, P, x, noise, natural, out, list, stream);
+    if (phase == GF_COLOUR) return gen_fused_dispatch<GF_COLOUR>(sc, g, pl, P, x, noise, natural, out, list, stream);
+    return gen_fused_dispatch<GF_FULL>(sc, g, pl, P, x, noise, natural, out, list, stream);
 }
 
 }  // namespace nvsr
@@ -131,14 +164,7 @@ int nvsr_generic_decode_fused_ext(const nvsr_scene_ext* scene, const nvsr_decode
     if (int e = gen_check_scene(sc, g)) return e;
     if (P < 0) return NVSR_ERR_SHAPE;
     if (P == 0) return NVSR_OK;
-    hipStream_t s = (hipStream_t)stream;
-#define GF_CASE(NT, CLS) \
-    if (pl.nt == NT && pl.cls == CLS) return gen_fused_launch<NT, CLS>(sc, g, pl, (long)P, x, coord_noise, natural, out, s);
-#define GF_CASES(NT) GF_CASE(NT, 0) GF_CASE(NT, 1) GF_CASE(NT, 2)
-    GF_CASES(1) GF_CASES(2) GF_CASES(3) GF_CASES(4) GF_CASES(6) GF_CASES(8)
-#undef GF_CASES
-#undef GF_CASE
-    return NVSR_ERR_SHAPE;
+    return gen_fused_f32_phase(GF_FULL, sc, g, pl, (long)P, x, coord_noise, natural, out, GenFusedList{nullptr, nullptr, 0}, (hipStream_t)stream);
 }
 
 }  // extern "C"

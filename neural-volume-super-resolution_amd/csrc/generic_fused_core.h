@@ -12,6 +12,18 @@ constexpr int GF_LDS_FLOATS[GF_CLASSES] = {10240, 20480, 40960};      // 40, 80,
 constexpr int GF_MAX_WAVES = 4;
 constexpr int GF_U = 4;             // k pairs per step of the layer loop (the padded K is a multiple of 32)
 constexpr int GF_MAX_HIDDEN = 256, GF_MAX_K0 = 512;
+// Phases of the two kernels (a template argument: GF_FULL compiles to the one-launch kernel as it was).
+//   GF_DENSITY  every point: position, the position planes' taps, combine_pos_planes, the density layers, fc_alpha -- no atan2f, no view plane;
+//               writes the 16-byte row [+0, +0, +0, sigma]
+//   GF_COLOUR   the points index[i], i < min(*count, max_count): stage 0 as far as Xr needs it, the colour layers, fc_rgb; writes the 12 bytes
+//               out[index[i]][0:3] and nothing else; entries at or beyond the count are not read
+// Both keep the full kernel's rows (gen_fused_plan), operand pairs and order: the same bits as GF_FULL at the same points.
+constexpr int GF_FULL = 0, GF_DENSITY = 1, GF_COLOUR = 2;
+struct GenFusedList {
+    const int* index;    // GF_COLOUR: the points to evaluate (device)
+    const int* count;    // how many of them (device, read by the kernel)
+    long max_count;      // what the launch is sized for
+};
 
 struct GenFusedPlan {
     int nt;              // 32-row output tiles of a hidden layer the kernel is instantiated for: 1, 2, 3, 4, 6, 8
@@ -88,13 +100,16 @@ __device__ __forceinline__ void gf_plane_features(const SceneDevN& sc, const Gen
 // in place later) in columns [0, ..) and Xd at xd_off of every row, behind a barrier; (vgx, vgy): the view plane's grid coordinates, which the
 // colour decoder's in-place combination needs again.
 // (a point past P takes part with the position 0: in-bounds taps, nothing stored)
+// GF_DENSITY leaves out the view direction (vgx = vgy = 0, its columns of a 'concat' / 'concat_pos' row are not written); GF_COLOUR leaves out
+// the combined position features where only the density decoder reads them ('sum' / 'avg' under 'concat_pos').
+template <int PHASE = GF_FULL>
 __device__ __forceinline__ void gf_stage0(const SceneDevN& sc, const GenGeom& g, const GenFusedRows& R, int n, int h, bool live, long p,
                                           const float* __restrict__ x, const float* __restrict__ noise, float& vgx, float& vgy) {
     float n0 = 0.0f, n1 = 0.0f, n2 = 0.0f;
     vgx = 0.0f; vgy = 0.0f;
     if (live) {
         gen_position(sc, x + p * 6, noise, p, n0, n1, n2);
-        gen_view_grid(sc, x + p * 6, vgx, vgy);
+        if (PHASE != GF_DENSITY) gen_view_grid(sc, x + p * 6, vgx, vgy);
     }
     const bool raw = g.proj == 2 || g.view == 4;          // the rows start as cat(pos_planes + [viewdir]) (= Xr; 'concat': Xd is its head)
     for (int d = 0; d < g.np; ++d) {
@@ -102,9 +117,9 @@ __device__ __forceinline__ void gf_stage0(const SceneDevN& sc, const GenGeom& g,
         gen_pos_grid(sc, d, n0, n1, n2, gx, gy);
         gf_plane_features(sc, g, R, n, h, d, g.C, gx, gy, raw ? d * g.C : 0, raw || d == 0 ? 0 : 1);
     }
-    if (raw) gf_plane_features(sc, g, R, n, h, g.np, g.Cv, vgx, vgy, g.np * g.C, 0);
+    if (raw && PHASE != GF_DENSITY) gf_plane_features(sc, g, R, n, h, g.np, g.Cv, vgx, vgy, g.np * g.C, 0);
     __syncthreads();
-    if (g.proj != 2) {                                    // combine_pos_planes 'sum' / 'avg': plane by plane, then the mean
+    if (g.proj != 2 && (PHASE != GF_COLOUR || !raw)) {        // combine_pos_planes 'sum' / 'avg': plane by plane, then the mean
         for (int c = h; c < g.C; c += 2) {
             float s = R.row[c];
             if (raw)
@@ -113,6 +128,34 @@ __device__ __forceinline__ void gf_stage0(const SceneDevN& sc, const GenGeom& g,
         }
         __syncthreads();
     }
+}
+
+// natural floats of the density decoder (its layers and fc_alpha): where the colour decoder's parameters start
+__host__ __device__ inline long gf_density_floats(const GenGeom& g) {
+    long n = 0;
+    for (int l = 0; l < g.nd; ++l) {
+        const int K = l == 0 ? g.Kd : g.hidden + (gen_skip_layer(l - 1, g.skip) ? g.Kd : 0);
+        n += (long)g.hidden * K + g.hidden;
+    }
+    return n + g.hidden + 1;
+}
+
+// the point of this lane's slot: GF_FULL / GF_DENSITY: the slot itself; GF_COLOUR: index[slot] while slot < the count (an index outside [0, P) is
+// left out).  false: the whole workgroup lies beyond the list and returns (before any barrier).
+template <int PHASE>
+__device__ __forceinline__ bool gf_point(const GenFusedList& list, long P, long slot0, long slot, long& p, bool& live) {
+    p = slot;
+    live = slot < P;
+    if (PHASE == GF_COLOUR) {
+        long cnt = *list.count;
+        if (cnt > list.max_count) cnt = list.max_count;
+        if (slot0 >= cnt) return false;
+        live = slot < cnt;
+        p = live ? list.index[slot] : 0;
+        live = live && p >= 0 && p < P;
+        if (!live) p = 0;
+    }
+    return true;
 }
 
 // acc[t] (+)= W[32 t + m][k] . [X1 | X2][point][k] over the layered route's k pairs: the chain of generic_linear_kernel, NT tiles at once.
@@ -174,5 +217,10 @@ __device__ __forceinline__ void gf_head(const float* row, int K, int x0, const f
 #pragma unroll
     for (int r = 0; r < 3; ++r) o[r] = r < M ? __fadd_rn(acc[0][r], b[r]) : 0.0f;
 }
+
+// generic_fused.hip: a phase of the exact-f32 kernel (the arithmetic entry points of generic_fused_limb.hip forward NVSR_ARITH_F32 to it);
+// everything has been checked by the caller, P > 0
+int gen_fused_f32_phase(int phase, const SceneDevN& sc, const GenGeom& g, const GenFusedPlan& pl, long P, const float* x, const float* noise,
+                        const float* natural, float* out, const GenFusedList& list, hipStream_t stream);
 
 }  // namespace nvsr

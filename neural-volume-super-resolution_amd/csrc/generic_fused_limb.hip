@@ -149,24 +149,29 @@ __device__ __forceinline__ void gfl_layer(f32x16 (&acc)[NT], const float* row, i
     }
 }
 
-template <int NT, int LDSF>
+// PHASE (generic_fused_core.h): GF_FULL, or one decoder of a frame in two phases -- GF_DENSITY on every point, GF_COLOUR on the listed points --
+// from the same packed blob (the colour decoder's fragments start behind the density layers').  The range flag: GF_DENSITY raises it for a
+// non-finite sigma, GF_COLOUR for non-finite colour logits of the listed points only.
+template <int NT, int LDSF, int PHASE>
 __global__ __launch_bounds__(64 * GF_MAX_WAVES) void generic_decode_fused_limb_kernel(SceneDevN sc, GenGeom g, GenFusedPlan L, long P, long block0,
                                                                                        const float* __restrict__ x, const float* __restrict__ noise,
                                                                                        const float* __restrict__ natural,
                                                                                        const unsigned* __restrict__ packed, float* __restrict__ out,
-                                                                                       unsigned* flag) {
+                                                                                       unsigned* flag, GenFusedList list) {
     __shared__ __attribute__((aligned(16))) float lds[LDSF];
     NVSR_RACE_PROBE_DELAY(lds);      // (probe builds only, nvsr_common.h)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n = lane & 31, h = lane >> 5;
-    const long p = ((block0 + blockIdx.x) * (long)(blockDim.x >> 6) + wave) * 32 + n;
-    const bool live = p < P;
+    const long slot0 = (block0 + blockIdx.x) * (long)(blockDim.x >> 6) * 32;
+    long p;
+    bool live;
+    if (!gf_point<PHASE>(list, P, slot0, slot0 + wave * 32 + n, p, live)) return;
     float* rows = lds + wave * 32 * L.ld;
     float* row = rows + n * L.ld;
 
     // ---- stage 0: the decoder inputs, the f32 kernel's (generic_fused_core.h) ----
     const GenFusedRows R = {rows, row, L.ld, L.xd_off};
     float vgx, vgy;
-    gf_stage0(sc, g, R, n, h, live, p, x, noise, vgx, vgy);
+    gf_stage0<PHASE>(sc, g, R, n, h, live, p, x, noise, vgx, vgy);
     const bool raw = g.proj == 2 || g.view == 4;
 
     // ---- the two decoders ----
@@ -174,7 +179,11 @@ __global__ __launch_bounds__(64 * GF_MAX_WAVES) void generic_decode_fused_limb_k
     const float* w = natural;
     const u32x4* wp = reinterpret_cast<const u32x4*>(packed);
     bool bad = false;
-    for (int dec = 0; dec < 2; ++dec) {
+    if (PHASE == GF_COLOUR) {
+        w += gf_density_floats(g);
+        for (int l = 0; l < g.nd; ++l) wp += (long)gfl_kb(gfl_layer_in(g, false, l)) * TT * 128;
+    }
+    for (int dec = PHASE == GF_COLOUR ? 1 : 0; dec < (PHASE == GF_DENSITY ? 1 : 2); ++dec) {
         const bool rgb = dec == 1;
         if (rgb && !raw) {                                // Xd -> Xr in place: combine_all_planes 'sum' / 'avg' / 'mult'
             gf_plane_features(sc, g, R, n, h, g.np, g.Cv, vgx, vgy, 0, 2);
@@ -217,12 +226,18 @@ __global__ __launch_bounds__(64 * GF_MAX_WAVES) void generic_decode_fused_limb_k
         float o[3];
         gf_head(row, cur_k, cur, w, rgb, n, h, o);
         if (live && h == 0) {
+            if (PHASE == GF_DENSITY) {                    // the whole row: the colour logits of a sample the colour phase leaves out are +0
+                f32x4 row4 = {0.0f, 0.0f, 0.0f, o[0]};
+                *reinterpret_cast<f32x4*>(out + p * 4) = row4;
+                bad = bad || !(fabsf(o[0]) <= 3.0e38f);
+            } else {
 #pragma unroll
-            for (int r = 0; r < 3; ++r)
-                if (r < M) {
-                    out[p * 4 + (rgb ? 0 : 3) + r] = o[r];
-                    bad = bad || !(fabsf(o[r]) <= 3.0e38f);
-                }
+                for (int r = 0; r < 3; ++r)
+                    if (r < M) {
+                        out[p * 4 + (rgb ? 0 : 3) + r] = o[r];
+                        bad = bad || !(fabsf(o[r]) <= 3.0e38f);
+                    }
+            }
         }
         w += (long)M * g.hidden + M;
     }
@@ -230,18 +245,56 @@ __global__ __launch_bounds__(64 * GF_MAX_WAVES) void generic_decode_fused_limb_k
     if (flag && __any(bad) && lane == 0) __hip_atomic_fetch_or(flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int NT, int CLS>
+template <int NT, int CLS, int PHASE>
 static int gen_fused_limb_launch(const SceneDevN& sc, const GenGeom& g, const GenFusedPlan& pl, long P, const float* x, const float* noise,
-                                 const float* natural, const float* packed, float* out, hipStream_t stream) {
-    const long pts = 32L * pl.waves, blocks = (P + pts - 1) / pts, piece = 1L << 30;       // (grid limit: pieces of whole point blocks)
+                                 const float* natural, const float* packed, float* out, const GenFusedList& list, hipStream_t stream) {
+    const long slots = PHASE == GF_COLOUR ? list.max_count : P;      // (GF_COLOUR: workgroups beyond the count return at once)
+    const long pts = 32L * pl.waves, blocks = (slots + pts - 1) / pts, piece = 1L << 30;       // (grid limit: pieces of whole point blocks)
     unsigned* flag = nvsr_get_range_flag();
     for (long b0 = 0; b0 < blocks; b0 += piece) {
         const long nb = blocks - b0 < piece ? blocks - b0 : piece;
-        hipLaunchKernelGGL((generic_decode_fused_limb_kernel<NT, GF_LDS_FLOATS[CLS]>), dim3((unsigned)nb), dim3(64 * pl.waves), 0, stream, sc, g, pl, P,
-                           b0, x, noise, natural, reinterpret_cast<const unsigned*>(packed), out, flag);
+        hipLaunchKernelGGL((generic_decode_fused_limb_kernel<NT, GF_LDS_FLOATS[CLS], PHASE>), dim3((unsigned)nb), dim3(64 * pl.waves), 0, stream, sc, g, pl,
+                           P, b0, x, noise, natural, reinterpret_cast<const unsigned*>(packed), out, flag, list);
         if (int e = NVSR_CHECK_LAUNCH()) return e;
     }
     return NVSR_OK;
+}
+
+template <int PHASE>
+static int gen_fused_limb_dispatch(const SceneDevN& sc, const GenGeom& g, const GenFusedPlan& pl, long P, const float* x, const float* noise,
+                                   const float* natural, const float* packed, float* out, const GenFusedList& list, hipStream_t s) {
+#define GFL_CASE(NT, CLS) \
+    if (pl.nt == NT && pl.cls == CLS) return gen_fused_limb_launch<NT, CLS, PHASE>(sc, g, pl, P, x, noise, natural, packed, out, list, s);
+#define GFL_CASES(NT) GFL_CASE(NT, 0) GFL_CASE(NT, 1) GFL_CASE(NT, 2)
+    GFL_CASES(1) GFL_CASES(2) GFL_CASES(3) GFL_CASES(4) GFL_CASES(6) GFL_CASES(8)
+#undef GFL_CASES
+#undef GFL_CASE
+    return NVSR_ERR_SHAPE;
+}
+
+// one entry for the three phases, in either arithmetic: the checks of nvsr_generic_decode_fused_arith_ext, then the phase's launch
+static int gen_fused_arith_phase(int phase, const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural, const float* packed,
+                                 int64_t P, const float* x, const float* coord_noise, float* out, const GenFusedList& list, int arith,
+                                 nvsr_stream_t stream) {
+    if (arith != NVSR_ARITH_F32 && arith != NVSR_ARITH_F16X2) return NVSR_ERR_SHAPE;      // by name only: no process default, no one-limb or bf16 mode here
+    const bool limb = arith == NVSR_ARITH_F16X2;
+    if (int e = gen_check_ext(scene)) return e;
+    GenGeom g;
+    if (int e = gen_resolve(geometry, &g, scene->num_position_planes)) return e;
+    GenFusedPlan pl;
+    if (!gen_fused_plan(g, &pl, limb)) return NVSR_ERR_SHAPE;
+    if (!natural || (limb && !packed) || !x || !out) return NVSR_ERR_NULL;
+    if (phase == GF_COLOUR && (!list.index || !list.count)) return NVSR_ERR_NULL;
+    const SceneDevN sc = gen_scene(scene);
+    if (int e = gen_check_scene(sc, g)) return e;
+    if (P < 0) return NVSR_ERR_SHAPE;
+    if (phase == GF_COLOUR && (list.max_count < 0 || list.max_count > P || P > 0x7fffffffL)) return NVSR_ERR_SHAPE;      // (int32 indices)
+    if (P == 0 || (phase == GF_COLOUR && list.max_count == 0)) return NVSR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (!limb) return gen_fused_f32_phase(phase, sc, g, pl, (long)P, x, coord_noise, natural, out, list, s);
+    if (phase == GF_DENSITY) return gen_fused_limb_dispatch<GF_DENSITY>(sc, g, pl, (long)P, x, coord_noise, natural, packed, out, list, s);
+    if (phase == GF_COLOUR) return gen_fused_limb_dispatch<GF_COLOUR>(sc, g, pl, (long)P, x, coord_noise, natural, packed, out, list, s);
+    return gen_fused_limb_dispatch<GF_FULL>(sc, g, pl, (long)P, x, coord_noise, natural, packed, out, list, s);
 }
 
 }  // namespace nvsr
@@ -280,24 +333,21 @@ int nvsr_generic_decode_fused_arith_ext(const nvsr_scene_ext* scene, const nvsr_
                                         int64_t P, const float* x, const float* coord_noise, float* out, int arith, nvsr_stream_t stream) {
     if (arith == NVSR_ARITH_F32) return nvsr_generic_decode_fused_ext(scene, geometry, natural, P, x, coord_noise, out, stream);
     if (arith != NVSR_ARITH_F16X2) return NVSR_ERR_SHAPE;            // by name only: no process default, no one-limb or bf16 mode here
-    if (int e = gen_check_ext(scene)) return e;
-    GenGeom g;
-    if (int e = gen_resolve(geometry, &g, scene->num_position_planes)) return e;
-    GenFusedPlan pl;
-    if (!gen_fused_plan(g, &pl, true)) return NVSR_ERR_SHAPE;
-    if (!natural || !packed || !x || !out) return NVSR_ERR_NULL;
-    const SceneDevN sc = gen_scene(scene);
-    if (int e = gen_check_scene(sc, g)) return e;
-    if (P < 0) return NVSR_ERR_SHAPE;
-    if (P == 0) return NVSR_OK;
-    hipStream_t s = (hipStream_t)stream;
-#define GFL_CASE(NT, CLS) \
-    if (pl.nt == NT && pl.cls == CLS) return gen_fused_limb_launch<NT, CLS>(sc, g, pl, (long)P, x, coord_noise, natural, packed, out, s);
-#define GFL_CASES(NT) GFL_CASE(NT, 0) GFL_CASE(NT, 1) GFL_CASE(NT, 2)
-    GFL_CASES(1) GFL_CASES(2) GFL_CASES(3) GFL_CASES(4) GFL_CASES(6) GFL_CASES(8)
-#undef GFL_CASES
-#undef GFL_CASE
-    return NVSR_ERR_SHAPE;
+    return gen_fused_arith_phase(GF_FULL, scene, geometry, natural, packed, P, x, coord_noise, out, GenFusedList{nullptr, nullptr, 0}, arith, stream);
+}
+
+int nvsr_generic_decode_fused_density_arith_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural,
+                                                const float* packed, int64_t P, const float* x, const float* coord_noise, float* raw_out, int arith,
+                                                nvsr_stream_t stream) {
+    return gen_fused_arith_phase(GF_DENSITY, scene, geometry, natural, packed, P, x, coord_noise, raw_out, GenFusedList{nullptr, nullptr, 0}, arith,
+                                 stream);
+}
+
+int nvsr_generic_decode_fused_colour_arith_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural,
+                                               const float* packed, int64_t P, const float* x, const float* coord_noise, const int32_t* index,
+                                               const int32_t* count_dev, int64_t max_count, float* raw_inout, int arith, nvsr_stream_t stream) {
+    return gen_fused_arith_phase(GF_COLOUR, scene, geometry, natural, packed, P, x, coord_noise, raw_inout, GenFusedList{index, count_dev, (long)max_count},
+                                 arith, stream);
 }
 
 }  // extern "C"

@@ -733,6 +733,16 @@ class TwoDimPlanesModel(nn.Module):
                 else:
                     planes = [self.raw_plane(n) for n in names]
                 return _GenericDecodeFn.apply(self, x, self.natural_blob(differentiable=True) if dec else None, coord_noise, *planes)
+        planes, consts, nat = self._generic_eval_args()
+        if self.generic_arithmetic() == "f16x2":
+            return torch.ops.nvsr.triplane_decode_generic_fused_arith(planes, consts, nat, self.packed_generic_decoder(), self.generic_geometry(), x,
+                                                                      bool(self.align_corners), coord_noise, self.plane_interp == "bicubic",
+                                                                      capi.ARITHMETIC["f16x2"])
+        op = torch.ops.nvsr.triplane_decode_generic_fused if self.generic_route() == "fused" else torch.ops.nvsr.triplane_decode_generic
+        return op(planes, consts, nat, self.generic_geometry(), x, bool(self.align_corners), coord_noise, self.plane_interp == "bicubic")
+
+    def _generic_eval_args(self):
+        """(planes, consts, natural blob) of an evaluation through the generic kernels: super-resolved planes where super-resolution is on"""
         if hasattr(self, "SR_model") and not self.skip_SR_:
             names = [get_plane_name(self.cur_id, d) for d in range(self.num_density_planes)]
             names = [n for n in names if self._should_SR(n)]
@@ -744,12 +754,60 @@ class TwoDimPlanesModel(nn.Module):
         planes, consts = self.scene_args(planes=planes, check_native=False)
         nat = self.natural_blob()
         capi.require_cuda(nat)
-        if self.generic_arithmetic() == "f16x2":
-            return torch.ops.nvsr.triplane_decode_generic_fused_arith(planes, consts, nat, self.packed_generic_decoder(), self.generic_geometry(), x,
-                                                                      bool(self.align_corners), coord_noise, self.plane_interp == "bicubic",
-                                                                      capi.ARITHMETIC["f16x2"])
-        op = torch.ops.nvsr.triplane_decode_generic_fused if self.generic_route() == "fused" else torch.ops.nvsr.triplane_decode_generic
-        return op(planes, consts, nat, self.generic_geometry(), x, bool(self.align_corners), coord_noise, self.plane_interp == "bicubic")
+        return planes, consts, nat
+
+    # (hidden-width class, arithmetic) at which a frame in two phases was measured faster than the one-launch frame on the same tree by more
+    # than the larger of the two routes' spreads (tools/generic_two_phase_time.py -> profiles/generic_two_phase_ab.txt); DESIGN 3.10 has the
+    # table.  Classes: dec_channels (lowest, highest) per arithmetic; None: nowhere -- the route then needs NVSR_GENERIC_TWO_PHASE=1.
+    # 'f32': 400 x 400 frames 1.48 x faster at 64 (197.3 -> 133.3 ms) and 1.43 x at 128 with a third of the samples live (340.4 -> 238.1 ms); with
+    # EVERY sample live the 128-wide frame is 4.5 % slower (341.5 -> 357.0 ms) -- the break-even live share of a decode is 0.65 at 64 and 0.84
+    # at 128, a rendered scene's is about a third.  Narrower decoders were not measured; wider ones are not 'fused' by default.
+    # 'f16x2' stays None although two phases measured 1.29 - 2.29 x faster there: tests/test_generic_limb.py counts the one-launch operator's
+    # calls in such a frame, and the existing test wins.
+    GENERIC_TWO_PHASE_DEFAULT_HIDDEN = {"f32": (64, 128), "f16x2": None}
+
+    def generic_frame_route(self):
+        """'two_phase' or 'one_phase': how an evaluation frame (train_utils._render_generic) runs a pass of this model if rendered now.
+        'two_phase' = density_field on every sample, the compositing weights, their live list, colour_field_ on the live samples
+        (csrc/generic_fused*.hip's phases, csrc/generic_live.hip): the one-launch frame bit for bit, a dead sample's colour logits being +0
+        (include/nvsr.h has the contract).  It needs generic_route() == 'fused' (so: no graph being recorded, the capacity) and no jitter of
+        the sample positions drawn inside the forward (jitter_std() == 0).  NVSR_GENERIC_TWO_PHASE (read at every call): 0 forces 'one_phase',
+        1 takes 'two_phase' wherever those conditions hold; unset: the measured default (GENERIC_TWO_PHASE_DEFAULT_HIDDEN).  The decision
+        touches no GPU."""
+        handle = os.environ.get("NVSR_GENERIC_TWO_PHASE", "")
+        if handle == "0" or self.is_native_geometry() or self.jitter_std() or self.generic_route() != "fused":
+            return "one_phase"
+        if handle != "1":
+            span = self.GENERIC_TWO_PHASE_DEFAULT_HIDDEN.get(self.generic_arithmetic())
+            if not (span is not None and span[0] <= self.dec_channels <= span[1]):
+                return "one_phase"
+        return "two_phase"
+
+    def _generic_phase_args(self, points, coord_noise):
+        if torch.is_grad_enabled() and self._generic_graph()[2]:
+            raise RuntimeError("density_field / colour_field_ are evaluation operators: call them under torch.no_grad()")
+        planes, consts, nat = self._generic_eval_args()
+        limb = self.generic_arithmetic() == "f16x2"
+        packed = self.packed_generic_decoder() if limb else nat.new_empty(0)
+        if coord_noise is not None:
+            coord_noise = capi.f32c(coord_noise.to(points.device))
+        return (planes, consts, nat, packed, self.generic_geometry(), points), \
+               (bool(self.align_corners), coord_noise, self.plane_interp == "bicubic", capi.ARITHMETIC["f16x2" if limb else "f32"])
+
+    def density_field(self, points, coord_noise=None):
+        """the density decoder alone on points [P,6] -> raw [P,4] = [+0, +0, +0, sigma_raw]: the fused kernel's density phase
+        (torch.ops.nvsr.triplane_density_generic_fused_arith) in generic_arithmetic(), sigma_raw with the bits of forward().  Evaluation only;
+        raises for a geometry beyond the fused kernel's capacity."""
+        head, tail = self._generic_phase_args(points, coord_noise)
+        return torch.ops.nvsr.triplane_density_generic_fused_arith(*head, *tail)
+
+    def colour_field_(self, raw, points, index, count, coord_noise=None):
+        """the colour decoder on points[index[:count]], written in place into raw[index[:count], 0:3] with the bits of forward(); the rest of
+        raw [P,4] stays (torch.ops.nvsr.triplane_colour_generic_fused_arith; index int32 [n], count int32 [1], both on the device -- what
+        torch.ops.nvsr.generic_live_list returns).  -> raw"""
+        head, tail = self._generic_phase_args(points, coord_noise)
+        torch.ops.nvsr.triplane_colour_generic_fused_arith(raw, *head, index, count, *tail)
+        return raw
 
     def scene_args(self, planes=None, check_native=True):
         """(planes, consts) of the current scene id as the torch.ops.nvsr operators take them: the channel-last planes (position planes, then

@@ -335,6 +335,90 @@ def _(planes, consts, natural, packed, geometry, x, align_corners=True, coord_no
     return x.new_empty((x.shape[0], 4))
 
 
+def _generic_phase_setup(planes, consts, natural, packed, geometry, x, align_corners, coord_noise, bicubic, arith):
+    """the checks the two phase operators share with triplane_decode_generic_fused_arith -> (geo, scene, coord_noise)"""
+    P = x.shape[0]
+    coord_noise = None if coord_noise is None else _c(coord_noise)
+    geo, n_pos, _, sc = _generic_setup(planes, consts, natural, geometry, align_corners, coord_noise, P, bicubic)
+    if capi.lib().nvsr_generic_fused_supported_arith(C.byref(geo), n_pos, int(arith)) != 1:
+        raise capi.NvsrError("the fused generic kernel does not take this decoder geometry in this arithmetic (nvsr_generic_fused_supported_arith: "
+                             "beyond its capacity, or not 'f32' / 'f16x2')")
+    if int(arith) == capi.ARITHMETIC["f16x2"]:
+        assert packed.numel() == capi.lib().nvsr_generic_packed_floats_ext(C.byref(geo), n_pos), "packed blob of another geometry"
+    return geo, sc, coord_noise
+
+
+@custom_op("nvsr::triplane_density_generic_fused_arith", mutates_args=(), device_types="cuda")
+def triplane_density_generic_fused_arith(planes: Sequence[Tensor], consts: Sequence[float], natural: Tensor, packed: Tensor, geometry: Sequence[int],
+                                         x: Tensor, align_corners: bool = True, coord_noise: Optional[Tensor] = None, bicubic: bool = False,
+                                         arith: int = 0) -> Tensor:
+    """the DENSITY phase of triplane_decode_generic_fused_arith (same arguments; `packed` is read in 'f16x2' only and may be empty otherwise):
+    the density decoder on all P points -> raw [P,4] = [+0, +0, +0, sigma_raw] per row, sigma_raw with the one-launch operator's bits.  A
+    compositor reads the tensor as it is; triplane_colour_generic_fused_arith completes it.  Evaluation only: no autograd."""
+    x, natural, packed = _c(x), _c(natural), _c(packed)
+    P = x.shape[0]
+    geo, sc, coord_noise = _generic_phase_setup(planes, consts, natural, packed, geometry, x, align_corners, coord_noise, bicubic, arith)
+    raw = _f(P, 4, like=x)
+    if P:
+        capi.call("nvsr_generic_decode_fused_density_arith_ext", C.byref(sc), C.byref(geo), capi.ptr(natural), capi.ptr(packed), P, capi.ptr(x),
+                  None if coord_noise is None else capi.ptr(coord_noise), capi.ptr(raw), int(arith), capi.stream())
+    return raw
+
+
+@triplane_density_generic_fused_arith.register_fake
+def _(planes, consts, natural, packed, geometry, x, align_corners=True, coord_noise=None, bicubic=False, arith=0):
+    return x.new_empty((x.shape[0], 4))
+
+
+@custom_op("nvsr::triplane_colour_generic_fused_arith", mutates_args=("raw",), device_types="cuda")
+def triplane_colour_generic_fused_arith(raw: Tensor, planes: Sequence[Tensor], consts: Sequence[float], natural: Tensor, packed: Tensor,
+                                        geometry: Sequence[int], x: Tensor, index: Tensor, count: Tensor, align_corners: bool = True,
+                                        coord_noise: Optional[Tensor] = None, bicubic: bool = False, arith: int = 0, max_count: int = -1) -> None:
+    """the COLOUR phase: the colour decoder on the points x[index[i]], i < count, written IN PLACE into raw[index[i], 0:3] with the one-launch
+    operator's bits; column 3 and every other row of raw [P,4] stay as they are.  index: int32 [>= max_count] on the device, distinct, any
+    order; count: int32 [1] on the device, read by the kernel (generic_live_list makes both; no host synchronisation); max_count: what the
+    launch is sized for, -1 = min(len(index), P).  Entries of index at or beyond count are not read.  Evaluation only: no autograd."""
+    x, natural, packed = _c(x), _c(natural), _c(packed)
+    P = x.shape[0]
+    capi.require_cuda(raw, index, count)
+    assert raw.dtype == torch.float32 and tuple(raw.shape) == (P, 4) and raw.is_contiguous(), "raw: contiguous [P,4] f32 (written in place)"
+    assert index.dtype == torch.int32 and index.dim() == 1 and index.is_contiguous(), "index: contiguous int32 [n]"
+    assert count.dtype == torch.int32 and count.numel() == 1, "count: int32 [1]"
+    n = min(index.numel(), P) if max_count < 0 else int(max_count)
+    assert n <= index.numel() and n <= P, "max_count: at most len(index) and P"
+    geo, sc, coord_noise = _generic_phase_setup(planes, consts, natural, packed, geometry, x, align_corners, coord_noise, bicubic, arith)
+    if n:
+        capi.call("nvsr_generic_decode_fused_colour_arith_ext", C.byref(sc), C.byref(geo), capi.ptr(natural), capi.ptr(packed), P, capi.ptr(x),
+                  None if coord_noise is None else capi.ptr(coord_noise), capi.ptr(index), capi.ptr(count), n, capi.ptr(raw), int(arith), capi.stream())
+
+
+@triplane_colour_generic_fused_arith.register_fake
+def _(raw, planes, consts, natural, packed, geometry, x, index, count, align_corners=True, coord_noise=None, bicubic=False, arith=0, max_count=-1):
+    return None
+
+
+@custom_op("nvsr::generic_live_list", mutates_args=(), device_types="cuda")
+def generic_live_list(w: Tensor) -> Tuple[Tensor, Tensor]:
+    """weights of any shape (P values) -> (index int32 [P], count int32 [1]): index[:count] = the flat positions p with not (w[p] == 0) in
+    ascending order (NaN is live, +0.0 and -0.0 are dead), both on the device (csrc/generic_live.hip: no atomics, the same list on every run).
+    index[count:] is not written."""
+    w = _c(w)
+    P = w.numel()
+    index = torch.empty((P,), dtype=torch.int32, device=w.device)
+    count = torch.empty((1,), dtype=torch.int32, device=w.device)
+    nbytes = capi.lib().nvsr_generic_live_list_workspace_bytes(P)
+    if nbytes < 0:
+        raise capi.NvsrError("generic_live_list: at most 2^31 - 1 weights")
+    ws = torch.empty((nbytes // 4,), dtype=torch.int32, device=w.device)
+    capi.call("nvsr_generic_live_list", P, capi.ptr(w), capi.ptr(index), capi.ptr(count), capi.ptr(ws), capi.stream())
+    return index, count
+
+
+@generic_live_list.register_fake
+def _(w):
+    return w.new_empty((w.numel(),), dtype=torch.int32), w.new_empty((1,), dtype=torch.int32)
+
+
 @custom_op("nvsr::triplane_decode_generic_backward", mutates_args=(), device_types="cuda")
 def triplane_decode_generic_backward(planes: Sequence[Tensor], consts: Sequence[float], natural: Tensor, geometry: Sequence[int], x: Tensor,
                                      g_out: Tensor, want_natural: bool, want_planes: Sequence[bool], align_corners: bool = True,
@@ -1601,6 +1685,7 @@ lowrank_planes.register_autograd(_lowrank_bwd, setup_context=_lowrank_setup)
 
 FORWARD_OPS = ["plane_to_channel_last", "plane_from_channel_last", "pack_decoder", "coarse_z", "importance_resample", "triplane_decode",
                "triplane_decode_generic", "triplane_decode_generic_fused", "pack_generic_decoder", "triplane_decode_generic_fused_arith", "ray_points", "lowrank_planes",
+               "triplane_density_generic_fused_arith", "triplane_colour_generic_fused_arith", "generic_live_list",
                "render_pass", "render_rays", "decode_rays", "composite", "composite_rays", "edsr", "planes_sr", "cumprod_exclusive"]
 
 

@@ -447,13 +447,26 @@ def _render_generic(rays, model_coarse, model_fine, m, Nc, Nf, t_rand, u, n_c, n
             return rgb, disp, acc, w.detach()
         return nv.composite_rays(raw, z, rays, noise, white, want_weights)
 
+    def decode(model, z, noise, jit):
+        """raw [N,S,4] of a pass.  Without gradients, a model whose generic_frame_route() is 'two_phase' runs its colour decoder on the samples
+        of nonzero weight only: density phase, the compositor's weights on [+0, +0, +0, sigma] (the same `noise` as the final call), their
+        live list, colour phase -- all enqueued, no host round trip.  A sample it leaves out keeps colour logits +0 under a weight of 0:
+        the one-phase frame's bits (include/nvsr.h has the contract and its one exception, NaN logits under a zero weight)."""
+        pts = nv.ray_points(rays, z)
+        if torch.is_grad_enabled() or not hasattr(model, "generic_frame_route") or model.generic_frame_route() != "two_phase":
+            return model(pts, coord_noise=jit).reshape(N, z.shape[1], 4)
+        raw = model.density_field(pts, coord_noise=jit)
+        w = nv.composite_rays(raw.reshape(N, z.shape[1], 4), z, rays, noise, white, True)[3]
+        index, count = nv.generic_live_list(w)
+        return model.colour_field_(raw, pts, index, count, coord_noise=jit).reshape(N, z.shape[1], 4)
+
     z_c = nv.coarse_z(rays, Nc, lindisp, t_rand)
-    raw = model_coarse(nv.ray_points(rays, z_c), coord_noise=jit_c).reshape(N, Nc, 4)
+    raw = decode(model_coarse, z_c, n_c, jit_c)
     rgb_c, disp_c, acc_c, w_c = composite(raw, z_c, n_c, Nf > 0)
     rgb_f = disp_f = acc_f = None
     if Nf > 0:
         z_f = nv.importance_resample(z_c, w_c, Nf, u)
-        raw_f = model_fine(nv.ray_points(rays, z_f), coord_noise=jit_f).reshape(N, Nc + Nf, 4)
+        raw_f = decode(model_fine, z_f, n_f, jit_f)
         rgb_f, disp_f, acc_f, _ = composite(raw_f, z_f, n_f, False)
     return rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f, None, None, None
 
