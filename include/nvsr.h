@@ -856,6 +856,34 @@ int nvsr_generic_decode_fused_colour_arith_ext(const nvsr_scene_ext* scene, cons
  * P >= 2^31, which nvsr_generic_live_list refuses with NVSR_ERR_SHAPE).  P == 0: *count_dev = 0. */
 int64_t nvsr_generic_live_list_workspace_bytes(int64_t P);
 int nvsr_generic_live_list(int64_t P, const float* w, int32_t* index_out, int32_t* count_dev, void* workspace, nvsr_stream_t stream);
+/* ---- generic decoder, occupancy grid (csrc/occupancy.hip, csrc/generic_fused*.hip; opt-in: without a grid nothing above changes) ------------
+ * The grid of "Occupancy grid" above -- the same layout, the same probe positions, the same rule for a bit (sigma_raw > threshold or NaN), the
+ * same dilation, the same slabs and nvsr_occupancy_workspace_floats(G, K) floats of workspace, out of the same kernels -- for a generic
+ * geometry, and a density phase that runs on the KEPT samples only.
+ * Contract of a frame: a CULLED sample behaves as if the density decoder had answered NVSR_CULLED_SIGMA (-1e30f, the value the native route's
+ * contract uses): relu makes it 0, so alpha = 0, w = +0.0, T unchanged, and the live list leaves the sample out.  A KEPT sample carries the
+ * bits of nvsr_generic_decode_fused_arith_ext at the same point.  A point with a NaN coordinate is kept, and so is a point OUTSIDE the box
+ * (a normalised coordinate with |n| > 1; n = +-1 exactly is inside and goes by its cell): a generic geometry may sample its planes through
+ * rotated frames, where border padding clamps the projected coordinates, not n, so such a point does not have its clamped cell's features.
+ * The one documented difference is the native route's: a NaN sigma inside a culled cell no longer reaches the pixel.
+ * nvsr_generic_occupancy_build_ext: nvsr_occupancy_build with nvsr_generic_decode_fused_density_arith_ext (NVSR_ARITH_F32 / _F16X2; `packed`
+ * is read in F16X2 only) as the decode in the middle.  A geometry or arithmetic beyond nvsr_generic_fused_supported_arith, G outside 1..512, K
+ * outside 1..4, dilate < 0: NVSR_ERR_SHAPE with nothing launched.
+ * nvsr_generic_occupancy_keep: for x [P,6], n = 2 (x - lo) / range - 1 as the decode kernels form it (no jitter); keep[p] = 1.0f if the point is
+ * kept by the rules above, else 0.0f, and a culled point's row raw[p] = [+0, +0, +0, NVSR_CULLED_SIGMA]; kept rows of raw [P,4] are not
+ * touched.  Only lo, range and num_position_planes of the scene are read.  nvsr_generic_live_list on `keep` gives the ascending kept list.
+ * nvsr_generic_decode_fused_density_list_arith_ext: the density phase on the points index[i], i < min(*count_dev, max_count), listed exactly as
+ * for the colour phase (entries at or beyond the count are not read, an index outside [0, P) is skipped, workgroups beyond the count return at
+ * once; 0 <= max_count <= P < 2^31): writes the 16-byte row [+0, +0, +0, sigma_raw] at raw_inout[index[i]] and no other row.  F16X2: a
+ * non-finite sigma of a listed point raises bit 1 of the range flag. */
+#define NVSR_CULLED_SIGMA (-1e30f)
+int nvsr_generic_occupancy_build_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural, const float* packed,
+                                     int G, int K, float threshold, int dilate, int arith, uint32_t* grid, float* workspace, nvsr_stream_t stream);
+int nvsr_generic_occupancy_keep(const nvsr_scene_ext* scene, int64_t P, const float* x, const uint32_t* grid, int G, float* keep, float* raw,
+                                nvsr_stream_t stream);
+int nvsr_generic_decode_fused_density_list_arith_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural,
+                                                     const float* packed, int64_t P, const float* x, const float* coord_noise, const int32_t* index,
+                                                     const int32_t* count_dev, int64_t max_count, float* raw_inout, int arith, nvsr_stream_t stream);
 
 /* run_network's model input for a pass (train_utils.py:15-64,111): x [N*S,6] = [ro + rd * z, viewdir] from packed rays [N,11], z [N,S] */
 int nvsr_ray_points(int64_t N, int S, const float* rays, const float* z, float* x, nvsr_stream_t stream);

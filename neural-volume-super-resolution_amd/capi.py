@@ -42,6 +42,8 @@ class Scene(C.Structure):
 
 
 MAX_POSITION_PLANES = 15
+# NVSR_CULLED_SIGMA (include/nvsr.h): the sigma_raw a sample culled by an occupancy grid of a generic geometry is given (relu makes it 0)
+CULLED_SIGMA = -1e30
 
 
 class SceneExt(C.Structure):
@@ -179,6 +181,11 @@ _PROTOS_OPTIONAL = {   # feature-plane super-resolution (csrc/sr.hip)
                                                     _vp], _i),
     "nvsr_generic_live_list_workspace_bytes": ([_i64], _i64),
     "nvsr_generic_live_list": ([_i64, _vp, _vp, _vp, _vp, _vp], _i),
+    # ... and with an occupancy grid: the grid of a generic geometry, the keep mask of a point list, the density phase over the kept list
+    "nvsr_generic_occupancy_build_ext": ([C.POINTER(SceneExt), C.POINTER(DecoderGeometry), _vp, _vp, _i, _i, C.c_float, _i, _i, _vp, _vp, _vp], _i),
+    "nvsr_generic_occupancy_keep": ([C.POINTER(SceneExt), _i64, _vp, _vp, _i, _vp, _vp, _vp], _i),
+    "nvsr_generic_decode_fused_density_list_arith_ext": ([C.POINTER(SceneExt), C.POINTER(DecoderGeometry), _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp,
+                                                          _i, _vp], _i),
     "nvsr_generic_decode_backward_ext": ([C.POINTER(SceneExt), C.POINTER(DecoderGeometry), _vp, _i64, _vp, _vp, _vp, _vp, C.POINTER(C.c_void_p),
                                           _vp, _vp], _i),
     "nvsr_ray_points": ([_i64, _i, _vp, _vp, _vp, _vp], _i),

@@ -30,7 +30,7 @@ namespace nvsr {
 
 // PHASE (generic_fused_core.h): GF_FULL is the kernel above; GF_DENSITY / GF_COLOUR are its two halves for a frame in two phases -- the density
 // decoder on every point, then the colour decoder on the listed points (`list`, not read by the other phases) -- out of the same code: the same
-// rows, the same chains, the same bits.
+// rows, the same chains, the same bits.  GF_DENSITY_LIST is GF_DENSITY on the listed points: the kept samples of an occupancy grid.
 template <int NT, int LDSF, int PHASE>
 __global__ __launch_bounds__(64 * GF_MAX_WAVES) void generic_decode_fused_kernel(SceneDevN sc, GenGeom g, GenFusedPlan L, long P, long block0,
                                                                                   const float* __restrict__ x, const float* __restrict__ noise,
@@ -55,7 +55,7 @@ __global__ __launch_bounds__(64 * GF_MAX_WAVES) void generic_decode_fused_kernel
     // ---- the two decoders (one of them in a phase) ----
     const float* w = natural;
     if (PHASE == GF_COLOUR) w += gf_density_floats(g);
-    for (int dec = PHASE == GF_COLOUR ? 1 : 0; dec < (PHASE == GF_DENSITY ? 1 : 2); ++dec) {
+    for (int dec = PHASE == GF_COLOUR ? 1 : 0; dec < (gf_density_only(PHASE) ? 1 : 2); ++dec) {
         const bool rgb = dec == 1;
         if (rgb && !raw) {                                // Xd -> Xr in place: combine_all_planes 'sum' / 'avg' / 'mult'
             gf_plane_features(sc, g, R, n, h, g.np, g.Cv, vgx, vgy, 0, 2);
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(64 * GF_MAX_WAVES) void generic_decode_fused_kernel
         gf_layer<1>(acc, row, cur_k, cur, 0, cur, w, M, n, h);
         const float* b = w + (long)M * g.hidden;
         if (live && h == 0) {
-            if (PHASE == GF_DENSITY) {                    // the whole row: the colour logits of a sample the colour phase leaves out are +0
+            if (gf_density_only(PHASE)) {                 // the whole row: the colour logits of a sample the colour phase leaves out are +0
                 f32x4 o = {0.0f, 0.0f, 0.0f, __fadd_rn(acc[0][0], b[0])};
                 *reinterpret_cast<f32x4*>(out + p * 4) = o;
             } else {
@@ -105,11 +105,11 @@ __global__ __launch_bounds__(64 * GF_MAX_WAVES) void generic_decode_fused_kernel
     }
 }
 
-// the launch covers P points (GF_FULL, GF_DENSITY) or list.max_count slots of the list (GF_COLOUR: workgroups beyond the count return at once)
+// the launch covers P points (GF_FULL, GF_DENSITY) or list.max_count slots of the list (GF_COLOUR, GF_DENSITY_LIST: workgroups beyond the count return at once)
 template <int NT, int CLS, int PHASE>
 static int gen_fused_launch(const SceneDevN& sc, const GenGeom& g, const GenFusedPlan& pl, long P, const float* x, const float* noise, const float* natural,
                             float* out, const GenFusedList& list, hipStream_t stream) {
-    const long slots = PHASE == GF_COLOUR ? list.max_count : P;
+    const long slots = gf_listed(PHASE) ? list.max_count : P;
     const long pts = 32L * pl.waves, blocks = (slots + pts - 1) / pts, piece = 1L << 30;       // (grid limit: pieces of whole point blocks)
     for (long b0 = 0; b0 < blocks; b0 += piece) {
         const long nb = blocks - b0 < piece ? blocks - b0 : piece;
@@ -136,6 +136,7 @@ int gen_fused_f32_phase(int phase, const SceneDevN& sc, const GenGeom& g, const 
                         const float* natural, float* out, const GenFusedList& list, hipStream_t stream) {
     if (phase == GF_DENSITY) return gen_fused_dispatch<GF_DENSITY>(sc, g, pl, P, x, noise, natural, out, list, stream);
     if (phase == GF_COLOUR) return gen_fused_dispatch<GF_COLOUR>(sc, g, pl, P, x, noise, natural, out, list, stream);
+    if (phase == GF_DENSITY_LIST) return gen_fused_dispatch<GF_DENSITY_LIST>(sc, g, pl, P, x, noise, natural, out, list, stream);
     return gen_fused_dispatch<GF_FULL>(sc, g, pl, P, x, noise, natural, out, list, stream);
 }
 

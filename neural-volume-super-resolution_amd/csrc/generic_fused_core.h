@@ -17,10 +17,14 @@ constexpr int GF_MAX_HIDDEN = 256, GF_MAX_K0 = 512;
 //               writes the 16-byte row [+0, +0, +0, sigma]
 //   GF_COLOUR   the points index[i], i < min(*count, max_count): stage 0 as far as Xr needs it, the colour layers, fc_rgb; writes the 12 bytes
 //               out[index[i]][0:3] and nothing else; entries at or beyond the count are not read
-// Both keep the full kernel's rows (gen_fused_plan), operand pairs and order: the same bits as GF_FULL at the same points.
-constexpr int GF_FULL = 0, GF_DENSITY = 1, GF_COLOUR = 2;
+//   GF_DENSITY_LIST  GF_DENSITY on the points index[i], i < min(*count, max_count), listed as for GF_COLOUR (the kept samples of an occupancy
+//               grid): writes the 16-byte row [+0, +0, +0, sigma] at out[index[i]] and no other row
+// All keep the full kernel's rows (gen_fused_plan), operand pairs and order: the same bits as GF_FULL at the same points.
+constexpr int GF_FULL = 0, GF_DENSITY = 1, GF_COLOUR = 2, GF_DENSITY_LIST = 3;
+constexpr bool gf_density_only(int phase) { return phase == GF_DENSITY || phase == GF_DENSITY_LIST; }      // the density decoder alone
+constexpr bool gf_listed(int phase) { return phase == GF_COLOUR || phase == GF_DENSITY_LIST; }             // the points come from a list
 struct GenFusedList {
-    const int* index;    // GF_COLOUR: the points to evaluate (device)
+    const int* index;    // GF_COLOUR / GF_DENSITY_LIST: the points to evaluate (device)
     const int* count;    // how many of them (device, read by the kernel)
     long max_count;      // what the launch is sized for
 };
@@ -100,7 +104,7 @@ __device__ __forceinline__ void gf_plane_features(const SceneDevN& sc, const Gen
 // in place later) in columns [0, ..) and Xd at xd_off of every row, behind a barrier; (vgx, vgy): the view plane's grid coordinates, which the
 // colour decoder's in-place combination needs again.
 // (a point past P takes part with the position 0: in-bounds taps, nothing stored)
-// GF_DENSITY leaves out the view direction (vgx = vgy = 0, its columns of a 'concat' / 'concat_pos' row are not written); GF_COLOUR leaves out
+// GF_DENSITY / GF_DENSITY_LIST leave out the view direction (vgx = vgy = 0, its columns of a 'concat' / 'concat_pos' row are not written); GF_COLOUR leaves out
 // the combined position features where only the density decoder reads them ('sum' / 'avg' under 'concat_pos').
 template <int PHASE = GF_FULL>
 __device__ __forceinline__ void gf_stage0(const SceneDevN& sc, const GenGeom& g, const GenFusedRows& R, int n, int h, bool live, long p,
@@ -109,7 +113,7 @@ __device__ __forceinline__ void gf_stage0(const SceneDevN& sc, const GenGeom& g,
     vgx = 0.0f; vgy = 0.0f;
     if (live) {
         gen_position(sc, x + p * 6, noise, p, n0, n1, n2);
-        if (PHASE != GF_DENSITY) gen_view_grid(sc, x + p * 6, vgx, vgy);
+        if (!gf_density_only(PHASE)) gen_view_grid(sc, x + p * 6, vgx, vgy);
     }
     const bool raw = g.proj == 2 || g.view == 4;          // the rows start as cat(pos_planes + [viewdir]) (= Xr; 'concat': Xd is its head)
     for (int d = 0; d < g.np; ++d) {
@@ -117,7 +121,7 @@ __device__ __forceinline__ void gf_stage0(const SceneDevN& sc, const GenGeom& g,
         gen_pos_grid(sc, d, n0, n1, n2, gx, gy);
         gf_plane_features(sc, g, R, n, h, d, g.C, gx, gy, raw ? d * g.C : 0, raw || d == 0 ? 0 : 1);
     }
-    if (raw && PHASE != GF_DENSITY) gf_plane_features(sc, g, R, n, h, g.np, g.Cv, vgx, vgy, g.np * g.C, 0);
+    if (raw && !gf_density_only(PHASE)) gf_plane_features(sc, g, R, n, h, g.np, g.Cv, vgx, vgy, g.np * g.C, 0);
     __syncthreads();
     if (g.proj != 2 && (PHASE != GF_COLOUR || !raw)) {        // combine_pos_planes 'sum' / 'avg': plane by plane, then the mean
         for (int c = h; c < g.C; c += 2) {
@@ -140,13 +144,13 @@ __host__ __device__ inline long gf_density_floats(const GenGeom& g) {
     return n + g.hidden + 1;
 }
 
-// the point of this lane's slot: GF_FULL / GF_DENSITY: the slot itself; GF_COLOUR: index[slot] while slot < the count (an index outside [0, P) is
+// the point of this lane's slot: GF_FULL / GF_DENSITY: the slot itself; GF_COLOUR / GF_DENSITY_LIST: index[slot] while slot < the count (an index outside [0, P) is
 // left out).  false: the whole workgroup lies beyond the list and returns (before any barrier).
 template <int PHASE>
 __device__ __forceinline__ bool gf_point(const GenFusedList& list, long P, long slot0, long slot, long& p, bool& live) {
     p = slot;
     live = slot < P;
-    if (PHASE == GF_COLOUR) {
+    if (gf_listed(PHASE)) {
         long cnt = *list.count;
         if (cnt > list.max_count) cnt = list.max_count;
         if (slot0 >= cnt) return false;

@@ -151,7 +151,8 @@ __device__ __forceinline__ void gfl_layer(f32x16 (&acc)[NT], const float* row, i
 
 // PHASE (generic_fused_core.h): GF_FULL, or one decoder of a frame in two phases -- GF_DENSITY on every point, GF_COLOUR on the listed points --
 // from the same packed blob (the colour decoder's fragments start behind the density layers').  The range flag: GF_DENSITY raises it for a
-// non-finite sigma, GF_COLOUR for non-finite colour logits of the listed points only.
+// non-finite sigma, GF_COLOUR for non-finite colour logits of the listed points only.  GF_DENSITY_LIST: GF_DENSITY on the listed points (the kept
+// samples of an occupancy grid); the flag is raised for a non-finite sigma of a listed point only.
 template <int NT, int LDSF, int PHASE>
 __global__ __launch_bounds__(64 * GF_MAX_WAVES) void generic_decode_fused_limb_kernel(SceneDevN sc, GenGeom g, GenFusedPlan L, long P, long block0,
                                                                                        const float* __restrict__ x, const float* __restrict__ noise,
@@ -183,7 +184,7 @@ __global__ __launch_bounds__(64 * GF_MAX_WAVES) void generic_decode_fused_limb_k
         w += gf_density_floats(g);
         for (int l = 0; l < g.nd; ++l) wp += (long)gfl_kb(gfl_layer_in(g, false, l)) * TT * 128;
     }
-    for (int dec = PHASE == GF_COLOUR ? 1 : 0; dec < (PHASE == GF_DENSITY ? 1 : 2); ++dec) {
+    for (int dec = PHASE == GF_COLOUR ? 1 : 0; dec < (gf_density_only(PHASE) ? 1 : 2); ++dec) {
         const bool rgb = dec == 1;
         if (rgb && !raw) {                                // Xd -> Xr in place: combine_all_planes 'sum' / 'avg' / 'mult'
             gf_plane_features(sc, g, R, n, h, g.np, g.Cv, vgx, vgy, 0, 2);
@@ -226,7 +227,7 @@ __global__ __launch_bounds__(64 * GF_MAX_WAVES) void generic_decode_fused_limb_k
         float o[3];
         gf_head(row, cur_k, cur, w, rgb, n, h, o);
         if (live && h == 0) {
-            if (PHASE == GF_DENSITY) {                    // the whole row: the colour logits of a sample the colour phase leaves out are +0
+            if (gf_density_only(PHASE)) {                 // the whole row: the colour logits of a sample the colour phase leaves out are +0
                 f32x4 row4 = {0.0f, 0.0f, 0.0f, o[0]};
                 *reinterpret_cast<f32x4*>(out + p * 4) = row4;
                 bad = bad || !(fabsf(o[0]) <= 3.0e38f);
@@ -248,7 +249,7 @@ __global__ __launch_bounds__(64 * GF_MAX_WAVES) void generic_decode_fused_limb_k
 template <int NT, int CLS, int PHASE>
 static int gen_fused_limb_launch(const SceneDevN& sc, const GenGeom& g, const GenFusedPlan& pl, long P, const float* x, const float* noise,
                                  const float* natural, const float* packed, float* out, const GenFusedList& list, hipStream_t stream) {
-    const long slots = PHASE == GF_COLOUR ? list.max_count : P;      // (GF_COLOUR: workgroups beyond the count return at once)
+    const long slots = gf_listed(PHASE) ? list.max_count : P;      // (GF_COLOUR: workgroups beyond the count return at once)
     const long pts = 32L * pl.waves, blocks = (slots + pts - 1) / pts, piece = 1L << 30;       // (grid limit: pieces of whole point blocks)
     unsigned* flag = nvsr_get_range_flag();
     for (long b0 = 0; b0 < blocks; b0 += piece) {
@@ -284,16 +285,18 @@ static int gen_fused_arith_phase(int phase, const nvsr_scene_ext* scene, const n
     GenFusedPlan pl;
     if (!gen_fused_plan(g, &pl, limb)) return NVSR_ERR_SHAPE;
     if (!natural || (limb && !packed) || !x || !out) return NVSR_ERR_NULL;
-    if (phase == GF_COLOUR && (!list.index || !list.count)) return NVSR_ERR_NULL;
+    const bool listed = gf_listed(phase);
+    if (listed && (!list.index || !list.count)) return NVSR_ERR_NULL;
     const SceneDevN sc = gen_scene(scene);
     if (int e = gen_check_scene(sc, g)) return e;
     if (P < 0) return NVSR_ERR_SHAPE;
-    if (phase == GF_COLOUR && (list.max_count < 0 || list.max_count > P || P > 0x7fffffffL)) return NVSR_ERR_SHAPE;      // (int32 indices)
-    if (P == 0 || (phase == GF_COLOUR && list.max_count == 0)) return NVSR_OK;
+    if (listed && (list.max_count < 0 || list.max_count > P || P > 0x7fffffffL)) return NVSR_ERR_SHAPE;      // (int32 indices)
+    if (P == 0 || (listed && list.max_count == 0)) return NVSR_OK;
     hipStream_t s = (hipStream_t)stream;
     if (!limb) return gen_fused_f32_phase(phase, sc, g, pl, (long)P, x, coord_noise, natural, out, list, s);
     if (phase == GF_DENSITY) return gen_fused_limb_dispatch<GF_DENSITY>(sc, g, pl, (long)P, x, coord_noise, natural, packed, out, list, s);
     if (phase == GF_COLOUR) return gen_fused_limb_dispatch<GF_COLOUR>(sc, g, pl, (long)P, x, coord_noise, natural, packed, out, list, s);
+    if (phase == GF_DENSITY_LIST) return gen_fused_limb_dispatch<GF_DENSITY_LIST>(sc, g, pl, (long)P, x, coord_noise, natural, packed, out, list, s);
     return gen_fused_limb_dispatch<GF_FULL>(sc, g, pl, (long)P, x, coord_noise, natural, packed, out, list, s);
 }
 
@@ -348,6 +351,13 @@ int nvsr_generic_decode_fused_colour_arith_ext(const nvsr_scene_ext* scene, cons
                                                const int32_t* count_dev, int64_t max_count, float* raw_inout, int arith, nvsr_stream_t stream) {
     return gen_fused_arith_phase(GF_COLOUR, scene, geometry, natural, packed, P, x, coord_noise, raw_inout, GenFusedList{index, count_dev, (long)max_count},
                                  arith, stream);
+}
+
+int nvsr_generic_decode_fused_density_list_arith_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural,
+                                                     const float* packed, int64_t P, const float* x, const float* coord_noise, const int32_t* index,
+                                                     const int32_t* count_dev, int64_t max_count, float* raw_inout, int arith, nvsr_stream_t stream) {
+    return gen_fused_arith_phase(GF_DENSITY_LIST, scene, geometry, natural, packed, P, x, coord_noise, raw_inout,
+                                 GenFusedList{index, count_dev, (long)max_count}, arith, stream);
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 // The grid is APPROXIMATE by nature: no finite set of probes bounds an MLP over a cell.  K (probes per axis and cell), the threshold and the
 // rounds of dilation are the caller's knobs.
 #include "occupancy.h"
+#include "generic_core.h"
 #include "nvsr_internal.h"
 
 namespace nvsr {
@@ -156,13 +157,13 @@ extern "C" int64_t nvsr_occupancy_workspace_floats(int G, int K) {
     return 10 * P + round4(grid_words(G));
 }
 
-extern "C" int nvsr_occupancy_build(const nvsr_scene* scene, const float* packed_decoder, int G, int K, float threshold, int dilate, int arithmetic, uint32_t* grid,
-                                    float* workspace, nvsr_stream_t stream) {
-    if (!build_shape_ok(G, K) || dilate < 0 || nvsr_internal_resolve_decoder_arith(arithmetic) < 0) return NVSR_ERR_SHAPE;
-    if (int e = check_scene(scene)) return e;
-    if (!packed_decoder || !grid || !workspace) return NVSR_ERR_NULL;
-    if (!aligned16(packed_decoder) || !aligned16(workspace)) return NVSR_ERR_ALIGN;
-    const hipStream_t st = (hipStream_t)stream;
+namespace nvsr {
+namespace {
+// the build both entries share: per slab the probes, `decode(P, x, out)` -- the density decoder of the caller's geometry on the slab's probes --
+// and the marks; then the dilation.  Everything has been checked by the caller.
+template <typename Decode>
+int occupancy_build_slabs(const float* lo, const float* range, int G, int K, float threshold, int dilate, uint32_t* grid, float* workspace, hipStream_t st,
+                          Decode decode) {
     const int K3 = K * K * K;
     const int64_t G3 = (int64_t)G * G * G, words = grid_words(G), sw = slab_words(G, K);
     float* out = workspace;
@@ -170,10 +171,10 @@ extern "C" int nvsr_occupancy_build(const nvsr_scene* scene, const float* packed
     uint32_t* other = reinterpret_cast<uint32_t*>(x + 6 * sw * 32 * K3);
     for (int64_t w0 = 0; w0 < words; w0 += sw) {
         const int64_t nw = words - w0 < sw ? words - w0 : sw, P = nw * 32 * K3;
-        hipLaunchKernelGGL(occupancy_probe_kernel, dim3(blocks256(P)), dim3(256), 0, st, scene->lo[0], scene->lo[1], scene->lo[2], scene->range[0], scene->range[1],
-                           scene->range[2], G, K, (long)(w0 * 32), (long)(nw * 32), x);
+        hipLaunchKernelGGL(occupancy_probe_kernel, dim3(blocks256(P)), dim3(256), 0, st, lo[0], lo[1], lo[2], range[0], range[1], range[2], G, K, (long)(w0 * 32),
+                           (long)(nw * 32), x);
         if (hipGetLastError() != hipSuccess) return NVSR_ERR_LAUNCH;
-        if (int e = nvsr_triplane_decode_arith(scene, packed_decoder, P, x, out, arithmetic, stream)) return e;
+        if (int e = decode(P, x, out)) return e;
         hipLaunchKernelGGL(occupancy_mark_kernel, dim3(blocks256(nw * 32)), dim3(256), 0, st, out, K3, (long)G3, (long)(w0 * 32), (long)nw, threshold, grid);
         if (hipGetLastError() != hipSuccess) return NVSR_ERR_LAUNCH;
     }
@@ -185,6 +186,70 @@ extern "C" int nvsr_occupancy_build(const nvsr_scene* scene, const float* packed
         uint32_t* t = src; src = dst; dst = t;
     }
     if (src != grid && hipMemcpyAsync(grid, src, (size_t)words * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return NVSR_ERR_LAUNCH;
+    return NVSR_CHECK_LAUNCH();
+}
+}  // namespace
+
+// ---- generic decoder geometries: the keep mask of a point list -----------------------------------------------------------------------------
+// A thread per point of x [P, 6].  n = the normalised position exactly as gen_position forms it (no jitter).  KEPT iff a coordinate of n is NaN,
+// or lies outside the box (|n[a]| > 1: a generic geometry may sample its planes through rotated frames, where border padding clamps the
+// PROJECTED coordinates -- a point outside the box does not have its clamped cell's features), or the cell's bit is set.  keep[p] = 1.0f / 0.0f
+// (the live list builder reads it as weights); a culled point gets the raw row [+0, +0, +0, NVSR_CULLED_SIGMA], a kept row is left alone.
+__global__ __launch_bounds__(256) void generic_occupancy_keep_kernel(SceneDevN sc, long P, const float* __restrict__ x, const uint32_t* __restrict__ grid, int G,
+                                                                     float* __restrict__ keep, float* __restrict__ raw) {
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= P) return;
+    float n0, n1, n2;
+    gen_position(sc, x + p * 6, nullptr, p, n0, n1, n2);
+    bool k = n0 != n0 || n1 != n1 || n2 != n2 || fabsf(n0) > 1.0f || fabsf(n1) > 1.0f || fabsf(n2) > 1.0f;
+    if (!k) {
+        const int i = (occupancy_cell(n2, G) * G + occupancy_cell(n1, G)) * G + occupancy_cell(n0, G);      // < 2^27
+        k = (grid[i >> 5] >> (i & 31)) & 1u;
+    }
+    keep[p] = k ? 1.0f : 0.0f;
+    if (!k) {
+        const f32x4 row = {0.0f, 0.0f, 0.0f, NVSR_CULLED_SIGMA};
+        *reinterpret_cast<f32x4*>(raw + p * 4) = row;
+    }
+}
+
+}  // namespace nvsr
+
+extern "C" int nvsr_occupancy_build(const nvsr_scene* scene, const float* packed_decoder, int G, int K, float threshold, int dilate, int arithmetic, uint32_t* grid,
+                                    float* workspace, nvsr_stream_t stream) {
+    if (!build_shape_ok(G, K) || dilate < 0 || nvsr_internal_resolve_decoder_arith(arithmetic) < 0) return NVSR_ERR_SHAPE;
+    if (int e = check_scene(scene)) return e;
+    if (!packed_decoder || !grid || !workspace) return NVSR_ERR_NULL;
+    if (!aligned16(packed_decoder) || !aligned16(workspace)) return NVSR_ERR_ALIGN;
+    return occupancy_build_slabs(scene->lo, scene->range, G, K, threshold, dilate, grid, workspace, (hipStream_t)stream,
+                                 [&](int64_t P, const float* x, float* out) { return nvsr_triplane_decode_arith(scene, packed_decoder, P, x, out, arithmetic, stream); });
+}
+
+// the same build for a generic decoder geometry: the decode in the middle is the fused kernel's density phase (GF_DENSITY) in `arith`
+extern "C" int nvsr_generic_occupancy_build_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural, const float* packed,
+                                                int G, int K, float threshold, int dilate, int arith, uint32_t* grid, float* workspace, nvsr_stream_t stream) {
+    if (!build_shape_ok(G, K) || dilate < 0) return NVSR_ERR_SHAPE;
+    if (int e = gen_check_ext(scene)) return e;
+    if (!geometry) return NVSR_ERR_NULL;
+    if (nvsr_generic_fused_supported_arith(geometry, scene->num_position_planes, arith) != 1) return NVSR_ERR_SHAPE;      // (nothing launched)
+    if (!natural || (arith == NVSR_ARITH_F16X2 && !packed) || !grid || !workspace) return NVSR_ERR_NULL;
+    if (!aligned16(workspace)) return NVSR_ERR_ALIGN;
+    return occupancy_build_slabs(scene->lo, scene->range, G, K, threshold, dilate, grid, workspace, (hipStream_t)stream, [&](int64_t P, const float* x, float* out) {
+        return nvsr_generic_decode_fused_density_arith_ext(scene, geometry, natural, packed, P, x, nullptr, out, arith, stream);
+    });
+}
+
+extern "C" int nvsr_generic_occupancy_keep(const nvsr_scene_ext* scene, int64_t P, const float* x, const uint32_t* grid, int G, float* keep, float* raw,
+                                           nvsr_stream_t stream) {
+    if (int e = gen_check_ext(scene)) return e;
+    if (G < 1 || G > OCC_MAX_G || P < 0 || (P + 255) / 256 > 0x7fffffff) return NVSR_ERR_SHAPE;
+    if (P == 0) return NVSR_OK;
+    if (!x || !grid || !keep || !raw) return NVSR_ERR_NULL;
+    if (!aligned16(raw)) return NVSR_ERR_ALIGN;
+    // (the kernel reads lo and range only: the planes of the scene need not be set)
+    SceneDevN sc = {};
+    for (int i = 0; i < 5; ++i) { sc.lo[i] = scene->lo[i]; sc.range[i] = scene->range[i]; }
+    hipLaunchKernelGGL(generic_occupancy_keep_kernel, dim3(blocks256(P)), dim3(256), 0, (hipStream_t)stream, sc, (long)P, x, grid, G, keep, raw);
     return NVSR_CHECK_LAUNCH();
 }
 

@@ -319,7 +319,7 @@ class TwoDimPlanesModel(nn.Module):
         sources -- the raw or generated planes; for a super-resolved plane what it is made from, the SR network's parameters and its LR
         planes, not the SR output itself: that tensor is remade (the f16 range re-render in 'bf16x3' drops it) without the scene changing --
         and the decoder"""
-        self.scene_args()                          # (super-resolves / generates what is missing, so that the sources below are the cached ones)
+        self.scene_args(check_native=False)        # (super-resolves / generates what is missing, so that the sources below are the cached ones)
         srcs = [self._plane_source(d) for d in range(self.num_density_planes + 1)]
         ts = [t for name, t in srcs if not name.endswith("/SR")] + list(self.decoder_parameters())
         if hasattr(self, "SR_model") and not self.skip_SR_:
@@ -338,13 +338,39 @@ class TwoDimPlanesModel(nn.Module):
         a limb arithmetic) then skip the density decoder in empty cells.  The grid is APPROXIMATE by nature -- no finite set of probes bounds
         an MLP over a cell -- and resolution, probes, threshold and dilate are the caller's knobs.  It is built from what scene_args()
         returns now (super-resolved planes where the model super-resolves, generated planes of low-rank scenes) and is dropped, never
-        used, once a plane or a decoder parameter has changed (occupancy()).  -> the grid, int32 [ceil(resolution^3 / 32)]"""
-        self._check_native_geometry()
+        used, once a plane or a decoder parameter has changed (occupancy()).  -> the grid, int32 [ceil(resolution^3 / 32)]
+        A generic geometry (any other decoder the fused generic kernel holds) builds the same grid with its own density phase
+        (torch.ops.nvsr.generic_occupancy_build on _generic_eval_args() in generic_arithmetic()); its evaluation frames then run the
+        density decoder on the kept samples only (density_field_kept; include/nvsr.h has the contract: samples outside the box are kept).
+        NotImplementedError where the fused kernel has no capacity for the geometry.  A frame uses the grid only where generic_route() is
+        'fused' when it is rendered: at a width the fused route does not take by default (dec_channels above GENERIC_FUSED_DEFAULT_MAX_HIDDEN
+        without NVSR_GENERIC_FUSED=1) the grid is built and kept, and the frames stay grid-less."""
+        if not self.is_native_geometry():
+            return self._build_generic_occupancy(scene_id, resolution, probes, threshold, dilate)
         self.set_cur_scene_id(scene_id)
         with torch.no_grad():
             planes, consts = self.scene_args()
             grid = torch.ops.nvsr.occupancy_build(planes, consts, self.packed_decoder(), int(resolution), int(probes), float(threshold), int(dilate),
                                                   self.arith())
+        self.__dict__.setdefault("_occupancy", {})[scene_id] = (self._occupancy_key(), grid, int(resolution))
+        return grid
+
+    def _build_generic_occupancy(self, scene_id, resolution, probes, threshold, dilate):
+        """build_occupancy for a generic geometry; the capacity is asked of the host (nvsr_generic_fused_supported_arith) before any GPU work"""
+        with torch.no_grad():                      # (the arithmetic of an evaluation: what the frames that use the grid run in)
+            limb = self.generic_arithmetic() == "f16x2"
+        arith = capi.ARITHMETIC["f16x2" if limb else "f32"]
+        geo = capi.DecoderGeometry(*[int(v) for v in self.generic_geometry()])
+        if capi.lib().nvsr_generic_fused_supported_arith(C.byref(geo), int(self.num_density_planes), arith) != 1:
+            raise NotImplementedError("an occupancy grid of a generic decoder geometry is probed with the fused generic kernel's density phase, which "
+                                      "does not hold this geometry (nvsr_generic_fused_supported_arith: hidden <= 256, first-layer inputs <= 512 "
+                                      "columns, 32 points' rows in 160 KB of LDS)")
+        self.set_cur_scene_id(scene_id)
+        with torch.no_grad():
+            planes, consts, nat = self._generic_eval_args()
+            packed = self.packed_generic_decoder() if limb else nat.new_empty(0)
+            grid = torch.ops.nvsr.generic_occupancy_build(planes, consts, nat, packed, self.generic_geometry(), int(resolution), int(probes),
+                                                          float(threshold), int(dilate), bool(self.align_corners), self.plane_interp == "bicubic", arith)
         self.__dict__.setdefault("_occupancy", {})[scene_id] = (self._occupancy_key(), grid, int(resolution))
         return grid
 
@@ -800,6 +826,18 @@ class TwoDimPlanesModel(nn.Module):
         raises for a geometry beyond the fused kernel's capacity."""
         head, tail = self._generic_phase_args(points, coord_noise)
         return torch.ops.nvsr.triplane_density_generic_fused_arith(*head, *tail)
+
+    def density_field_kept(self, points, grid, G):
+        """density_field on the points an occupancy grid (G^3 bits, build_occupancy) keeps: the keep mask of the point list
+        (torch.ops.nvsr.generic_occupancy_keep), its ascending list (generic_live_list), the density phase over the list
+        (triplane_density_list_generic_fused_arith) -- all enqueued, nothing read back.  -> (raw [P,4], index int32 [P], count int32 [1]): a
+        kept row is [+0, +0, +0, sigma_raw] with the bits of forward(), a culled row [+0, +0, +0, capi.CULLED_SIGMA]; index[:count] are the kept
+        points.  Points with a NaN coordinate or outside the box are kept.  No jitter of the sample positions: evaluation only."""
+        head, tail = self._generic_phase_args(points, None)
+        keep, raw = torch.ops.nvsr.generic_occupancy_keep(head[1], points, grid, int(G))
+        index, count = torch.ops.nvsr.generic_live_list(keep)
+        torch.ops.nvsr.triplane_density_list_generic_fused_arith(raw, *head, index, count, *tail)
+        return raw, index, count
 
     def colour_field_(self, raw, points, index, count, coord_noise=None):
         """the colour decoder on points[index[:count]], written in place into raw[index[:count], 0:3] with the bits of forward(); the rest of

@@ -419,6 +419,94 @@ def _(w):
     return w.new_empty((w.numel(),), dtype=torch.int32), w.new_empty((1,), dtype=torch.int32)
 
 
+# ---- occupancy grid of a generic geometry (include/nvsr.h, "generic decoder, occupancy grid"): opt-in, evaluation only ---------------------
+@custom_op("nvsr::generic_occupancy_build", mutates_args=(), device_types="cuda")
+def generic_occupancy_build(planes: Sequence[Tensor], consts: Sequence[float], natural: Tensor, packed: Tensor, geometry: Sequence[int], G: int,
+                            K: int, threshold: float, dilate: int, align_corners: bool = True, bicubic: bool = False, arith: int = 0) -> Tensor:
+    """occupancy_build for ANY decoder geometry the fused generic kernel holds: the same grid layout, probes, marks and dilation, with the
+    density phase (triplane_density_generic_fused_arith, `arith` = 'f32' or 'f16x2'; `packed` is read in 'f16x2' only) as the decoder.
+    -> int32 [ceil(G^3 / 32)]"""
+    natural, packed = _c(natural), _c(packed)
+    geo, n_pos, _, sc = _generic_setup(planes, consts, natural, geometry, align_corners, None, 0, bicubic)
+    if capi.lib().nvsr_generic_fused_supported_arith(C.byref(geo), n_pos, int(arith)) != 1:
+        raise capi.NvsrError("the fused generic kernel does not take this decoder geometry in this arithmetic (nvsr_generic_fused_supported_arith: "
+                             "beyond its capacity, or not 'f32' / 'f16x2'): no occupancy grid for it")
+    if int(arith) == capi.ARITHMETIC["f16x2"]:
+        assert packed.numel() == capi.lib().nvsr_generic_packed_floats_ext(C.byref(geo), n_pos), "packed blob of another geometry"
+    words = capi.lib().nvsr_occupancy_words(int(G))
+    if words <= 0:
+        raise capi.NvsrError("nvsr_generic_occupancy_build_ext failed: %s" % capi._STATUS[1])
+    grid = torch.empty(words, dtype=torch.int32, device=natural.device)
+    ws = _f(max(int(capi.lib().nvsr_occupancy_workspace_floats(int(G), int(K))), 4), like=natural)
+    capi.call("nvsr_generic_occupancy_build_ext", C.byref(sc), C.byref(geo), capi.ptr(natural), capi.ptr(packed), int(G), int(K), float(threshold),
+              int(dilate), int(arith), capi.ptr(grid), capi.ptr(ws), capi.stream())
+    return grid
+
+
+@generic_occupancy_build.register_fake
+def _(planes, consts, natural, packed, geometry, G, K, threshold, dilate, align_corners=True, bicubic=False, arith=0):
+    return natural.new_empty(((G ** 3 + 31) // 32,), dtype=torch.int32)
+
+
+@custom_op("nvsr::generic_occupancy_keep", mutates_args=(), device_types="cuda")
+def generic_occupancy_keep(consts: Sequence[float], x: Tensor, grid: Tensor, G: int, raw: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """the keep mask of points x [P,6] under `grid` (G^3 bits) in the box of `consts` (lo[5], range[5], then the projections, which are not
+    read) -> (keep f32 [P], raw f32 [P,4]).  keep[p] = 1.0 iff a normalised coordinate of the point is NaN or lies outside the box (|n| > 1),
+    or the bit of its cell is set; else 0.0, and the row of raw is [+0, +0, +0, capi.CULLED_SIGMA].  Kept rows are not written: they are
+    those of a copy of the `raw` handed in, or uninitialised without one -- triplane_density_list_generic_fused_arith fills them.
+    generic_live_list(keep) gives the ascending kept list."""
+    x = _c(x)
+    P = x.shape[0]
+    assert x.dim() == 2 and x.shape[1] == 6, "x: [P,6]"
+    assert len(consts) >= 10 and (len(consts) - 10) % 6 == 0, "scene constants: lo[5], range[5] (and the projections)"
+    grid = _grid(grid, int(G))
+    if raw is None:
+        out = _f(P, 4, like=x)
+    else:
+        assert raw.dtype == torch.float32 and tuple(raw.shape) == (P, 4), "raw: [P,4] f32"
+        out = raw.contiguous().clone()
+    keep = _f(P, like=x)
+    sc = capi.SceneExt()
+    sc.num_position_planes = max((len(consts) - 10) // 6, 1)
+    for i in range(5):
+        sc.lo[i] = consts[i]
+        sc.range[i] = consts[5 + i]
+    if P:
+        capi.call("nvsr_generic_occupancy_keep", C.byref(sc), P, capi.ptr(x), capi.ptr(grid), int(G), capi.ptr(keep), capi.ptr(out), capi.stream())
+    return keep, out
+
+
+@generic_occupancy_keep.register_fake
+def _(consts, x, grid, G, raw=None):
+    return x.new_empty((x.shape[0],)), x.new_empty((x.shape[0], 4))
+
+
+@custom_op("nvsr::triplane_density_list_generic_fused_arith", mutates_args=("raw",), device_types="cuda")
+def triplane_density_list_generic_fused_arith(raw: Tensor, planes: Sequence[Tensor], consts: Sequence[float], natural: Tensor, packed: Tensor,
+                                              geometry: Sequence[int], x: Tensor, index: Tensor, count: Tensor, align_corners: bool = True,
+                                              coord_noise: Optional[Tensor] = None, bicubic: bool = False, arith: int = 0, max_count: int = -1) -> None:
+    """the DENSITY phase on the points x[index[i]], i < count: the row [+0, +0, +0, sigma_raw] written IN PLACE into raw[index[i]], sigma_raw
+    with the one-launch operator's bits; every other row of raw [P,4] stays as it is.  index, count, max_count: as for
+    triplane_colour_generic_fused_arith (the kept list of generic_occupancy_keep through generic_live_list).  Evaluation only: no autograd."""
+    x, natural, packed = _c(x), _c(natural), _c(packed)
+    P = x.shape[0]
+    capi.require_cuda(raw, index, count)
+    assert raw.dtype == torch.float32 and tuple(raw.shape) == (P, 4) and raw.is_contiguous(), "raw: contiguous [P,4] f32 (written in place)"
+    assert index.dtype == torch.int32 and index.dim() == 1 and index.is_contiguous(), "index: contiguous int32 [n]"
+    assert count.dtype == torch.int32 and count.numel() == 1, "count: int32 [1]"
+    n = min(index.numel(), P) if max_count < 0 else int(max_count)
+    assert n <= index.numel() and n <= P, "max_count: at most len(index) and P"
+    geo, sc, coord_noise = _generic_phase_setup(planes, consts, natural, packed, geometry, x, align_corners, coord_noise, bicubic, arith)
+    if n:
+        capi.call("nvsr_generic_decode_fused_density_list_arith_ext", C.byref(sc), C.byref(geo), capi.ptr(natural), capi.ptr(packed), P, capi.ptr(x),
+                  None if coord_noise is None else capi.ptr(coord_noise), capi.ptr(index), capi.ptr(count), n, capi.ptr(raw), int(arith), capi.stream())
+
+
+@triplane_density_list_generic_fused_arith.register_fake
+def _(raw, planes, consts, natural, packed, geometry, x, index, count, align_corners=True, coord_noise=None, bicubic=False, arith=0, max_count=-1):
+    return None
+
+
 @custom_op("nvsr::triplane_decode_generic_backward", mutates_args=(), device_types="cuda")
 def triplane_decode_generic_backward(planes: Sequence[Tensor], consts: Sequence[float], natural: Tensor, geometry: Sequence[int], x: Tensor,
                                      g_out: Tensor, want_natural: bool, want_planes: Sequence[bool], align_corners: bool = True,
@@ -1686,6 +1774,7 @@ lowrank_planes.register_autograd(_lowrank_bwd, setup_context=_lowrank_setup)
 FORWARD_OPS = ["plane_to_channel_last", "plane_from_channel_last", "pack_decoder", "coarse_z", "importance_resample", "triplane_decode",
                "triplane_decode_generic", "triplane_decode_generic_fused", "pack_generic_decoder", "triplane_decode_generic_fused_arith", "ray_points", "lowrank_planes",
                "triplane_density_generic_fused_arith", "triplane_colour_generic_fused_arith", "generic_live_list",
+               "generic_occupancy_build", "generic_occupancy_keep", "triplane_density_list_generic_fused_arith",
                "render_pass", "render_rays", "decode_rays", "composite", "composite_rays", "edsr", "planes_sr", "cumprod_exclusive"]
 
 

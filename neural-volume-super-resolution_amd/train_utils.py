@@ -430,6 +430,17 @@ def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, sc
     return rgb_c, disp_c, acc_c, rgb_f, disp_f, acc_f, None, None, None
 
 
+def _generic_occupancy(model, noise, jit):
+    """(grid, resolution) if a pass of `model` through _render_generic takes the occupancy route now, else None: a generic geometry, no
+    gradients, no density noise and no jitter of the sample positions, generic_route() == 'fused', NVSR_GENERIC_TWO_PHASE not 0, and a grid of
+    the current scene that is not stale (model.occupancy_entry).  A model for which nobody built a grid is asked nothing else."""
+    if torch.is_grad_enabled() or noise is not None or jit is not None or not model.__dict__.get("_occupancy"):
+        return None
+    if os.environ.get("NVSR_GENERIC_TWO_PHASE", "") == "0" or model.is_native_geometry() or model.jitter_std() or model.generic_route() != "fused":
+        return None
+    return model.occupancy_entry(model.cur_id)
+
+
 def _render_generic(rays, model_coarse, model_fine, m, Nc, Nf, t_rand, u, n_c, n_f, jit_c=None, jit_f=None):
     """predict_and_render_radiance for decoder geometries other than the shipped one, pass by pass like the reference (train_utils.py:95-180):
     depths -> run_network (the model's generic kernels on the [N*S,6] point list) -> compositing -> importance resampling -> again.
@@ -453,6 +464,14 @@ def _render_generic(rays, model_coarse, model_fine, m, Nc, Nf, t_rand, u, n_c, n
         live list, colour phase -- all enqueued, no host round trip.  A sample it leaves out keeps colour logits +0 under a weight of 0:
         the one-phase frame's bits (include/nvsr.h has the contract and its one exception, NaN logits under a zero weight)."""
         pts = nv.ray_points(rays, z)
+        occ = _generic_occupancy(model, noise, jit)
+        if occ is not None:
+            # the model's occupancy grid (models.build_occupancy: the user opted in, whatever generic_frame_route() says): the density decoder on the
+            # kept samples only, a culled one being [+0, +0, +0, capi.CULLED_SIGMA] -- weight +0.0, absent from the live list; then as below
+            raw, _, _ = model.density_field_kept(pts, occ[0], occ[1])
+            w = nv.composite_rays(raw.reshape(N, z.shape[1], 4), z, rays, None, white, True)[3]
+            index, count = nv.generic_live_list(w)
+            return model.colour_field_(raw, pts, index, count).reshape(N, z.shape[1], 4)
         if torch.is_grad_enabled() or not hasattr(model, "generic_frame_route") or model.generic_frame_route() != "two_phase":
             return model(pts, coord_noise=jit).reshape(N, z.shape[1], 4)
         raw = model.density_field(pts, coord_noise=jit)

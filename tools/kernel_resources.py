@@ -37,8 +37,11 @@ BENCHMARKED = [
     "render_pass3_density_kernel", "render_pass3_density_z_kernel", "render_pass3_colour_kernel", "render_pass3_colour_z_kernel",
     "render_pass3_points_kernel", "render_pass3_points_z_kernel",
     # the generic decoder geometries' evaluation (tools/generic_fused_time.py, generic_limb_time.py, generic_two_phase_time.py time it): the fused
-    # kernels in every phase -- <NT, LDS floats, 0 one launch | 1 density | 2 colour> -- and the live list between the phases
+    # kernels in every phase -- <NT, LDS floats, 0 one launch | 1 density | 2 colour | 3 density over a list> -- and the live list between the phases
     "generic_decode_fused_kernel", "generic_decode_fused_limb_kernel", "generic_live_count_kernel", "generic_live_list_kernel",
+    # ... with an occupancy grid (tools/generic_occupancy_time.py times it): phase 3 of the two kernels above, all 36 instantiations matched by
+    # those names, and the keep mask of the point list
+    "generic_occupancy_keep_kernel",
 ]
 # The gate covers EVERY kernel of the library (round 4; round 3 covered the benchmarked ones): no scratch memory, no spilled VGPRs -- except:
 #   ALLOW  name substring -> spilled VGPRs tolerated.  What is listed is debt, with the round that recorded it:
