@@ -62,6 +62,10 @@ namespace nvsr {
 // for the whole launch.  Those are the blocks that issue the plane gathers: weight copies issued beside the gathers go through the same
 // texture path and cost the step ~9 k of its 94 k cycles (stamps with -DR3_ABLATE=32); resident, the gather blocks issue no copy at all and the
 // step streams 432 instead of 504 KB.  (3 bf16 limbs: 108 KB would not fit beside the 96 KB ring.)
+// The density kernels of the two-phase route (two f16 limbs) use the same region for the first 9 K-blocks of the DENSITY decoder (DEN_RES_KB
+// below): a density step streams 144 instead of 216 KB in 5 chunks instead of 7.  Measured on the benchmark frame (profiles/
+// density_resident_ab.txt, one job, one box): L2 requests of the fine density launch 2081 M -> 1839 M, of the coarse one 441 M -> 350 M;
+// fine density kernel 40.92 -> 40.05 ms, coarse 13.37 -> 13.23 ms; frame 81.1-81.3 -> 80.3-80.7 ms, identical bits.
 template <int LIMBS>
 struct Lds3 {
     static constexpr bool F16 = limb_f16(LIMBS);                     // one or two f16 limbs: the same layout, a ring and a resident region of half the size
@@ -76,6 +80,17 @@ struct Lds3 {
     static constexpr int FAR = F16 ? VTAPS + RAYS2 * TAP_FLOATS : -1;
     static constexpr int RES = VTAPS + RAYS2 * TAP_FLOATS + (F16 ? RAYS2 : 0);
     static constexpr int RES_KB = F16 ? 9 : 0;
+    // The density kernels' view (render3.hip, PHASE 1 and PHASE 4; two f16 limbs only): the same array, the same ring of two slots of
+    // DEN_CHUNK_KB K-blocks, and in RES -- which belongs to the colour and fused kernels and was allocated and never touched here -- the first
+    // DEN_RES_KB K-blocks of the density decoder from KB_DEN0 on: density layer 0 (3), layer 1 chunk a (4) and the first 2 K-blocks of
+    // layer 1 chunk b, loaded once per launch (ring3_load_resident; the coarse and the fine decoder alternate on one stream).  A step streams
+    // the other 18 K-blocks in 5 chunks -- 2 + 4 + 4 + 4 + 4, 144 KB -- where it streamed 27 in 7 (216 KB); the blocks that multiply
+    // resident K-blocks issue no copy and stand behind no ring wait.  (The tap region VTAPS, dead in these phases too, is one more K-block
+    // but FAR lies between it and RES: it is not joined.  One limb: the ring's schedule has no room for a 4-K-block copy in half a block's
+    // 8 slots; three limbs: no RES.  Both keep the streamed plan.)
+    static constexpr int DEN_RES_KB = LIMBS == 2 ? RES_KB : 0;
+    static constexpr int DEN_CHUNK_KB = 4;
+    static_assert(DEN_CHUNK_KB * kb_words(LIMBS) == SLOT, "the density ring is the ring");
     // the point-major colour pass's exchange (render3.hip, PHASE 3): the rays' colour sums and a step's terms, 3 RAYS2 floats each, the step's
     // slots and the slots' rays, RAYS2 ints each -- 8 KB.  Two f16 limbs have under 1 KB to spare: the region is the taps' (dead after the prologue
     // while R3_BOUNCE is off), so neither the ring nor the resident weights pay for it; 3 bf16 limbs have the room behind the ring.

@@ -330,11 +330,20 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
     float stamp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long tprev = __builtin_amdgcn_s_memtime();
 #endif
-    constexpr bool RESIDENT = L::RES_KB > 0 && !DENSITY;             // (the density pass streams KB_DEN0 .. through the ring and keeps nothing resident)
-    constexpr int KB_FIRST = DENSITY ? KB_DEN0 : RESIDENT ? KB_RGB0 + 9 : KB_RGB0;      // the first chunk of a step that goes through the ring
+    constexpr bool RESIDENT = L::RES_KB > 0 && !DENSITY;
+    // density pass, two f16 limbs (Lds3, "the density kernels' view"): K-blocks KB_DEN0 .. KB_DEN0 + 8 resident, the step's first ring chunk is
+    // the last 2 K-blocks of layer 1; otherwise the density pass streams KB_DEN0 .. through the ring and keeps nothing resident
+    constexpr bool DRES = DENSITY && L::DEN_RES_KB > 0;
+    static_assert(!DRES || L::DEN_RES_KB == 9, "the split of layer 1 chunk b below is written for 3 + 4 + 2 resident K-blocks");
+    constexpr int KB_FIRST = DRES ? KB_DEN0 + L::DEN_RES_KB : DENSITY ? KB_DEN0 : RESIDENT ? KB_RGB0 + 9 : KB_RGB0;      // the first chunk of a step that goes through the ring
+    constexpr int NKB_FIRST = DRES ? KB_DEN1 + 8 - KB_FIRST : 3;
     unsigned* const res = lds + L::RES;
     if constexpr (RESIDENT) ring3_load_resident<LIMBS, L::RES_KB>(rs, res, KB_RGB0);
-    unsigned* cw = const_cast<unsigned*>(ring3_issue<LIMBS, 3>(rs, KB_FIRST));     // first ring chunk of sample 0; every later one is issued during the previous sample
+    if constexpr (DRES) ring3_load_resident<LIMBS, L::DEN_RES_KB>(rs, res, KB_DEN0);
+    unsigned* cw = const_cast<unsigned*>(ring3_issue<LIMBS, NKB_FIRST>(rs, KB_FIRST));     // first ring chunk of sample 0; every later one is issued during the previous sample
+    // DRES: the first blocks of a step read the resident region and stand behind no ring wait, so the launch's first wait is here -- younger
+    // than the region's last piece: the NKB_FIRST * LIMBS = 4 pieces per wave of the chunk just issued, which stay in flight
+    if constexpr (DRES) ring3_sync<NKB_FIRST * LIMBS>();
     const int steps = COLOUR || KEPT ? trip : S;
     for (int s = 0; s < steps; ++s) {
         asm volatile("" : "+v"(rs.voff), "+v"(rs.lane));
@@ -382,7 +391,9 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
         // multiplies plane p - 1 of a tile loads plane p of the same tile, the next block blends it.
         GatherJob ja, jb;
         R3_MARK(0)      // loop top
-        ring3_sync<(ZCOMP || COLOUR || KEPT) ? 0 : 2>();         // the step's first ring chunk (issued during the previous sample) -- younger: the two z loads above
+        // the step's first ring chunk (issued during the previous sample) -- younger: the two z loads above.  DRES: no wait here -- density
+        // layer 0 and layer 1 chunk a multiply out of the resident region; the step's first chunk is waited for inside layer 1
+        if constexpr (!DRES) ring3_sync<(ZCOMP || COLOUR || KEPT) ? 0 : 2>();
         int eX2 = POINT_NONE, eY2 = POINT_NONE;
         if constexpr (POINTS) {
             // the entries of the step after the next, and the next step's point: both a whole step ahead of their use
@@ -577,23 +588,31 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
         // there, in the order (F0 + F1) + F2, then div3.  A ring chunk is issued in the first half of an X block and waited for behind the Y
         // block that follows it, whose 12 gather loads are younger than the chunk's last piece (ring3_sync<12>; the X block's own loads are
         // blended by then).
+        // DRES (two f16 limbs): layer 0, layer 1 chunk a and half of chunk b read the resident region -- no copy, no slot, no wait; the
+        // step's ring chunks are layer 1 K-blocks 6, 7 | 2 a | 2 b | 3 a | 3 b, five per step, so the two slots swap roles every step as
+        // they did with seven.
         float (&Fg)[HALF_C] = X.F;
 #define NVSR_HALF(JL, HL, JB, HB, LOADS, BLENDS, NS_) gather_half<NS_, LOADS, HL, BLENDS, HB>(slot, JL, JB, Fg, h, r2)
 #define NVSR_JOB(J, P, N0, N1, N2) J.plane = sc.plane[P]; J.t = pos_taps2(sc, P, N0, N1, N2); scale_taps(J.t);
-        // density layer 0
-        nw = ring3_take(rs);
+        // density layer 0 (DRES: out of the resident region -- no ring slot, no copy)
+        const unsigned* const w_d0 = DRES ? res : cw;
+        if constexpr (!DRES) nw = ring3_take(rs);
         NVSR_JOB(ja, 0, xn0, xn1, xn2)
         split_feat(X.D);
-        limb_block<LIMBS, 3, true, true>(cw, lane, X.acc, cur, fa, feat(X.D),
-                                         [&](int slot) NVSR_INL { NVSR_HALF(ja, 0, ja, 0, true, false, NSF); dma_side<LIMBS, 4>(slot, rs, nw, KB_DEN1); }, NoTail{});
+        limb_block<LIMBS, 3, true, true>(w_d0, lane, X.acc, cur, fa, feat(X.D),
+                                         [&](int slot) NVSR_INL {
+                                             NVSR_HALF(ja, 0, ja, 0, true, false, NSF);
+                                             if constexpr (!DRES) dma_side<LIMBS, 4>(slot, rs, nw, KB_DEN1);
+                                         },
+                                         NoTail{});
         split_feat(Y.D);
-        limb_block<LIMBS, 3, true, false>(cw, lane, Y.acc, cur, fa, feat(Y.D),
+        limb_block<LIMBS, 3, true, false>(w_d0, lane, Y.acc, cur, fa, feat(Y.D),
                                           [&](int slot) NVSR_INL {
                                               spread<RELU_STEPS, 0, NSF>(slot, [&](int k) NVSR_INL { relu_bias_step<LIMBS>(k, small + S_BIAS + 0 * HID, h, X.acc, X.act, bp, nsc); });
                                               NVSR_HALF(ja, 1, ja, 0, true, true, NSF);
                                           },
                                           tail_of(X.act, 0));
-        cw = nw;
+        if constexpr (!DRES) cw = nw;
         // one hidden layer: X a | Y a | X b | Y b, each with the gather halves (JL, HL) it loads and (JB, HB) it blends, and the statements
         // (D updates, the next job's taps) that go in front of it
 #define NVSR_DEN_LAYER(VPREV, KB_NEXT_A, KB_NEXT_B, NKB_B, PRE_XA, G_XA, PRE_YA, G_YA, PRE_XB, G_XB, PRE_YB, YB_SIDE, YB_TAIL)                      \
@@ -619,11 +638,56 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
 #define NVSR_D_ADD(T) _Pragma("unroll") for (int c = 0; c < HALF_C; ++c) { T.D[c] = __fadd_rn(T.D[c], Fg[c]); asm volatile("" : "+v"(T.D[c])); }
 #define NVSR_D_AVG(T) _Pragma("unroll") for (int c = 0; c < HALF_C; ++c) { T.D[c] = div3(__fadd_rn(T.D[c], Fg[c])); asm volatile("" : "+v"(T.D[c])); }
         // density layer 1: X p0 -> D, X p1, X p2 (first half)
+        if constexpr (DRES) {
+            // The same blocks, products and side work in the same order; only where the fragments are read from changes.  Chunk a is
+            // resident.  Chunk b is cut behind its second K-block: X b = [K-blocks 4, 5: resident | 6, 7: the ring chunk], then Y b
+            // likewise -- two limb_blocks of 2 K-blocks each, the side work of slots 0 .. NSH/2 - 1 in the first and NSH/2 .. NSH - 1
+            // in the second, the tail of the first splitting the second's first K-block (what the undivided block did in its own
+            // K-block 1).  Every accumulator sees K-blocks 0 .. 7 in order, as before.
+            const unsigned* const w_1a = res + 3 * kb_words(LIMBS);
+            const unsigned* const w_1b = res + 7 * kb_words(LIMBS);
+            NVSR_JOB(jb, 1, xn0, xn1, xn2)
+            limb_block<LIMBS, 4, true, true>(w_1a, lane, X.acc, cur, fa, hid(X.act, 0),
+                                             [&](int slot) NVSR_INL { relu_side(Y, 0)(slot); NVSR_HALF(jb, 0, ja, 1, true, true, NSH); }, tail_of(Y.act, 0));
+            NVSR_D_SET(X)
+            limb_block<LIMBS, 4, true, false>(w_1a, lane, Y.acc, cur, fa, hid(Y.act, 0), [&](int slot) NVSR_INL { NVSR_HALF(jb, 1, jb, 0, true, true, NSH); },
+                                              tail_of(X.act, 4));
+            NVSR_JOB(ja, 2, xn0, xn1, xn2)
+            limb_block<LIMBS, 2, false, true>(w_1b, lane, X.acc, cur, fa, hid(X.act, 4), [&](int slot) NVSR_INL { NVSR_HALF(ja, 0, jb, 1, true, true, NSH); },
+                                              tail_of(X.act, 6));
+            // The step's first ring chunk (layer 1, K-blocks 6 and 7), issued in X b of layer 3 of the previous sample (before the loop for
+            // sample 0).  Vector-memory operations issued behind its last piece and certain to exist: the 12 gather loads each of X and Y
+            // density layer 0 and of X a and Y a above = 48 (the half-block just done blends and loads nothing).  Older than those 48 and
+            // not counted: the previous epilogue's loads and stores and this step's depth and noise loads, whose number varies with the
+            // launch -- all consumed or drained by the time the first of the 48 is waited for, so leaving them out costs no stall.
+            ring3_sync<48>();
+            nw = ring3_take(rs);
+            limb_block<LIMBS, 2, false, true>(cw, lane, X.acc, cur, fa, hid(X.act, 6),
+                                              [&](int sl) NVSR_INL {
+                                                  const int slot = sl + NSH / 2;
+                                                  NVSR_HALF(ja, 0, jb, 1, true, true, NSH);
+                                                  dma_side<LIMBS, 4>(sl, rs, nw, KB_DEN1 + 8);       // 8 pieces per wave: slots 2, 5 .. 23 of the 24
+                                              },
+                                              tail_of(Y.act, 4));
+            NVSR_D_ADD(X)
+            limb_block<LIMBS, 2, false, true>(w_1b, lane, Y.acc, cur, fa, hid(Y.act, 4),
+                                              [&](int slot) NVSR_INL { relu_side(X, 1)(slot); NVSR_HALF(ja, 1, ja, 0, true, true, NSH); }, tail_of(Y.act, 6));
+            // (the wait in front of layer 2 keeps its 12: the copy's last piece goes out in the last slot of X b's second half, behind that
+            //  half's own loads; Y b's first half loads nothing, its second half issues the 12 loads that are younger)
+            limb_block<LIMBS, 2, false, true>(cw, lane, Y.acc, cur, fa, hid(Y.act, 6),
+                                              [&](int sl) NVSR_INL {
+                                                  const int slot = sl + NSH / 2;
+                                                  relu_side(X, 1)(slot); NVSR_HALF(ja, 1, ja, 0, true, true, NSH);
+                                              },
+                                              tail_of(X.act, 0));
+            cw = nw;
+        } else {
         NVSR_DEN_LAYER(0, KB_DEN1 + 4, KB_DEN1 + 8, 4,
                        NVSR_JOB(jb, 1, xn0, xn1, xn2), NVSR_HALF(jb, 0, ja, 1, true, true, NSH),
                        NVSR_D_SET(X), NVSR_HALF(jb, 1, jb, 0, true, true, NSH),
                        NVSR_JOB(ja, 2, xn0, xn1, xn2), NVSR_HALF(ja, 0, jb, 1, true, true, NSH),
                        NVSR_D_ADD(X), relu_side(X, 1)(slot); NVSR_HALF(ja, 1, ja, 0, true, true, NSH), tail_of(X.act, 0))
+        }
         // density layer 2: X p2 -> D done; Y p0, Y p1
         NVSR_DEN_LAYER(1, KB_DEN1 + 12, KB_DEN1 + 16, 4,
                        NVSR_JOB(jb, 0, yn0, yn1, yn2), NVSR_HALF(jb, 0, ja, 1, true, true, NSH),
@@ -637,7 +701,7 @@ __device__ __forceinline__ void render_pass3_body(const SceneDev& sc, const floa
             spread<RELU_STEPS, 0, NSH / 2>(slot, [&](int k) NVSR_INL { relu_bias_step<LIMBS>(k, small + S_BIAS + 3 * HID, h, X.acc, X.act, bp, nsc); });
             spread<64, NSH / 2, NSH>(slot, [&](int k) NVSR_INL { heads_side<1>(k >> 2, k & 3, small + S_ALPHA_W, h, X.act, sx, hp1); });
         };
-        NVSR_DEN_LAYER(2, KB_DEN1 + 20, KB_FIRST, 3,
+        NVSR_DEN_LAYER(2, KB_DEN1 + 20, KB_FIRST, NKB_FIRST,
                        NVSR_JOB(jb, 2, yn0, yn1, yn2), NVSR_HALF(jb, 0, ja, 1, true, true, NSH),
                        NVSR_D_ADD(Y), NVSR_HALF(jb, 1, jb, 0, true, true, NSH),
                        , NVSR_HALF(jb, 1, jb, 1, false, true, NSH),
