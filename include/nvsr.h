@@ -782,7 +782,8 @@ int nvsr_generic_decode_backward_ext(const nvsr_scene_ext* scene, const nvsr_dec
 /* ---- generic decoder, fused evaluation ----------------------------------------------------------------------------------------
  * TwoDimPlanesModel.forward (models.py:381-421) of a generic geometry in ONE launch: the input features, every layer of both decoders and
  * both heads; the activations stay in LDS.  The result has the bits of nvsr_generic_decode_ext (the same v_mfma_f32_32x32x2_f32 chains over
- * the same operand pairs in the same order); there is no backward -- training keeps the layered route.
+ * the same operand pairs in the same order).  Its backward is the plane-gradient launch of "generic decoder, fused plane gradients" below;
+ * decoder-weight gradients keep the layered route.
  * Capacity: a point's row in LDS holds the decoder inputs and one hidden activation,
  *   row = Kr (+ Kd where the density decoder's input is not a prefix of the colour decoder's: 'sum' / 'avg' position features under
  *         'concat_pos') + hidden floats, rounded up to 2 x an odd number;
@@ -794,12 +795,37 @@ int nvsr_generic_fused_supported(const nvsr_decoder_geometry* geometry, int num_
  * limit forces them); NVSR_ERR_SHAPE for a geometry beyond the capacity above; P == 0: NVSR_OK without a launch. */
 int nvsr_generic_decode_fused_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural, int64_t P,
                                   const float* x, const float* coord_noise, float* out, nvsr_stream_t stream);
+/* ---- generic decoder, fused plane gradients (csrc/generic_fused_bwd.hip) -----------------------------------------------------------------
+ * The backward of TwoDimPlanesModel.forward (the reference: torch.autograd through models.py:381-421) of a generic geometry for an iteration
+ * in which the decoder's parameters take NO gradient, in ONE launch and exact f32: d_out [P,4] -> the gradients of the planes.  The kernel
+ * recomputes the forward in LDS as nvsr_generic_decode_fused_ext does, keeps one gate bit per hidden unit (its output is > 0; NaN and 0 are
+ * closed), runs the transposed chain of both decoders and scatters through the combination rule and the taps (bilinear or bicubic, either
+ * align_corners, coord_noise).  Up to the scatter every value carries the bits of nvsr_generic_decode_backward_ext: dX[p][k] is one
+ * v_mfma_f32_32x32x2_f32 chain from +0.0 over the pairs (2s, 2s + 1) of the output index in ascending order, the gradient of a decoder's
+ * input starts at +0.0 and takes, layers descending, a skip layer's part and last layer 0's part with one rounded addition each.  The scatter
+ * adds the density decoder's and the colour decoder's product of a (texel, channel) with one rounded addition in front of ONE atomic (the
+ * layered route issues two): where no two points share a texel the result is the layered route's bit for bit, elsewhere the two differ by
+ * the order of their float atomics only.  The lanes of an atomic instruction run over the channels of one texel.
+ * Capacity: a point's row in LDS holds both decoders' inputs apart, one hidden activation, the cotangent and the gate words,
+ *   row = Kr + Kd + hidden + 4 + (density_layers + rgb_layers) x ceil(hidden / 32) floats, rounded up to 2 x an odd number;
+ * supported = nvsr_generic_fused_supported's limits (hidden <= 256, max(Kd, Kr) <= 512) and 32 such rows fit in 160 KB (row <= 1280).
+ * nvsr_generic_backward_fused_supported (models.py:381-421; host only, no device needed): 1 / 0, or the negated status for a geometry that
+ * nvsr_generic_decoder_natural_floats_ext refuses; never 1 where nvsr_generic_fused_supported answers 0. */
+int nvsr_generic_backward_fused_supported(const nvsr_decoder_geometry* geometry, int num_position_planes);
+/* The plane gradients of nvsr_generic_decode_ext (models.py:381-421 under torch.autograd) without a workspace and without d_natural:
+ * ACCUMULATED into d_planes like nvsr_generic_decode_backward_ext (num_position_planes + 1 device pointers in a host array; a NULL entry is
+ * not wanted and costs no atomics; a NULL array or no wanted plane: NVSR_OK without a launch).  One launch for any P (pieces of whole point
+ * blocks only where the grid limit forces them); P == 0: NVSR_OK without a launch; NVSR_ERR_SHAPE for a geometry beyond the capacity above;
+ * NVSR_ERR_NULL without natural, x or d_out.  Never allocates or synchronises. */
+int nvsr_generic_decode_backward_fused_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural, int64_t P,
+                                           const float* x, const float* coord_noise, const float* d_out, float* const* d_planes,
+                                           nvsr_stream_t stream);
 /* ---- generic decoder, fused evaluation in NVSR_ARITH_F16X2 (csrc/generic_fused_limb.hip) ---------------------------------------------
  * The launch above with the HIDDEN layers of both decoders in two f16 limbs: per layer w^ = limbs of 2^8 W, x^ = limbs of 2^4 x (hi = RN_f16(v),
  * lo = RN_f16(v - hi)), the products Wh xl, Wh xh, Wl xh on v_mfma_f32_32x32x16_f16 per 16-column K-block of [X1 | X2] in ascending order, f32
  * accumulation, act = relu(fma(acc, 2^-12, b)) with a ReLU that keeps NaN.  The input features, the biases, both heads (on the f32 activations,
  * from the natural blob) and the outputs are f32 and computed exactly as by nvsr_generic_decode_fused_ext.  BY NAME only: there is no process
- * default here, and no backward (training keeps the layered route).
+ * default here, and no backward in this arithmetic (training runs in exact f32: the layered route, or the fused plane gradients below).
  * Range contract: F16X2's -- |W| < 255 for the hidden matrices, |feature / activation| < 4094; beyond them the outputs that depend on the
  * operand are NaN, never a finite wrong number, and a NaN in the planes, the points or the weights comes out as NaN.  A launch that writes a
  * non-finite out row ORs 1 into the range flag (nvsr_set_range_flag), wherever the NaN came from.

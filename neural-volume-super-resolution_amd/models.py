@@ -697,6 +697,37 @@ class TwoDimPlanesModel(nn.Module):
         return "fused" if capi.lib().nvsr_generic_fused_supported(C.byref(geo), int(self.num_density_planes)) == 1 else "layered"
 
     GENERIC_FUSED_DEFAULT_MAX_HIDDEN = 128
+
+    # dec_channels (lowest, highest) at which the fused TRAINING route (generic_train_route) is taken without NVSR_GENERIC_TRAIN_FUSED=1: the
+    # widths at which it was measured faster than the layered route -- this tree's and the parent commit's -- by more than the spread of the
+    # alternations in both timed shapes (tools/generic_train_time.py -> profiles/generic_train_ab.txt).  None: nowhere, the route is opt-in.
+    # Measured: 128 ('sum': 1.09 x on 2^19 points forward + backward, 1.03 x per planes-only iteration of 4 096 rays).  At 64 the iteration
+    # ties inside the spread (17.88 against 17.98 ms) although forward + backward wins 1.10 x, at 256 the route loses (0.36 x: one wave per
+    # workgroup): both stay opt-in, and so does every width that was not measured.
+    GENERIC_TRAIN_FUSED_DEFAULT_HIDDEN = (128, 128)
+
+    def generic_train_route(self):
+        """'fused' or 'layered': how a forward through the generic kernels that RECORDS A GRAPH trains if called now.  'fused' = the forward
+        in one launch (torch.ops.nvsr.triplane_decode_generic_fused: the layered forward's bits) and the planes' gradients in one launch
+        (csrc/generic_fused_bwd.hip, torch.ops.nvsr.triplane_decode_generic_fused_backward), exact f32.  It is taken when a graph is being
+        recorded, NO decoder parameter requires a gradient (planes-only iterations, refinement and SR training under a frozen decoder), the
+        deterministic mode is off (generic training is refused there, before any launch), both kernels hold the geometry
+        (nvsr_generic_fused_supported, nvsr_generic_backward_fused_supported) and NVSR_GENERIC_TRAIN_FUSED (read at every call) allows it: 0
+        never, 1 wherever the capacity allows, unset at the widths of GENERIC_TRAIN_FUSED_DEFAULT_HIDDEN.  'layered' = csrc/generic.hip layer by
+        layer: decoder-weight gradients and everything else.  The decision touches no GPU; generic_route() is not affected."""
+        handle = os.environ.get("NVSR_GENERIC_TRAIN_FUSED", "")
+        if handle == "0" or not torch.is_grad_enabled() or capi.deterministic():
+            return "layered"
+        dec, _, graph = self._generic_graph()
+        if dec or not graph:
+            return "layered"
+        span = self.GENERIC_TRAIN_FUSED_DEFAULT_HIDDEN
+        if handle != "1" and not (span is not None and span[0] <= self.dec_channels <= span[1]):
+            return "layered"
+        geo = capi.DecoderGeometry(*[int(v) for v in self.generic_geometry()])
+        n_pos = int(self.num_density_planes)
+        ok = capi.lib().nvsr_generic_fused_supported(C.byref(geo), n_pos) == 1 and capi.lib().nvsr_generic_backward_fused_supported(C.byref(geo), n_pos) == 1
+        return "fused" if ok else "layered"
     # dec_channels (lowest, highest) at which the fused route in 'f16x2' was measured faster, by more than the spread of the alternations, than
     # the better of the two f32 routes: 1.28 - 1.54 x on 2^22 points, 1.39 - 1.69 x on a 400 x 400 frame at 64, 128 and 256
     # (profiles/generic_limb_ab.txt).  Narrower decoders were not measured: there the arithmetic needs NVSR_GENERIC_FUSED=1.  None: nowhere.
@@ -758,6 +789,8 @@ class TwoDimPlanesModel(nn.Module):
                     planes = self.training_planes(None, normalized_points=n if coord_noise is None else n + coord_noise)
                 else:
                     planes = [self.raw_plane(n) for n in names]
+                if self.generic_train_route() == "fused":
+                    return _GenericFusedTrainFn.apply(self, x, coord_noise, *planes)
                 return _GenericDecodeFn.apply(self, x, self.natural_blob(differentiable=True) if dec else None, coord_noise, *planes)
         planes, consts, nat = self._generic_eval_args()
         if self.generic_arithmetic() == "f16x2":
@@ -1030,6 +1063,38 @@ class _GenericDecodeFn(torch.autograd.Function):
                                                             align, coord_noise, bicubic)
         return (None, None, g[0] if need[2] else None, None) + \
                tuple(from_channel_last(gp, like=p_) if n else None for gp, p_, n in zip(g[1:], ctx.plane_srcs, need_planes))
+
+
+class _GenericFusedTrainFn(torch.autograd.Function):
+    """_GenericDecodeFn for a decoder that takes no gradient, on the fused kernels (TwoDimPlanesModel.generic_train_route() == 'fused'): the
+    forward is torch.ops.nvsr.triplane_decode_generic_fused (the layered forward's bits), the backward
+    torch.ops.nvsr.triplane_decode_generic_fused_backward (csrc/generic_fused_bwd.hip: the planes' gradients in one launch, exact f32).
+    inputs: model, x, jitter (None = none), then the planes of the scene."""
+
+    @staticmethod
+    def forward(ctx, model, x, coord_noise, *plane_srcs):
+        if capi.deterministic():
+            capi.refuse_deterministic("training a generic decoder geometry (generic.hip)")
+        planes_cl = [to_channel_last(p.detach()) for p in plane_srcs]
+        planes_cl, consts = model.scene_args(planes=planes_cl, check_native=False)
+        natural = model.natural_blob()
+        capi.require_cuda(natural)
+        geometry = model.generic_geometry()
+        ctx.plane_srcs = plane_srcs
+        bicubic = model.plane_interp == "bicubic"
+        ctx.state = (planes_cl, consts, natural, geometry, x, bool(model.align_corners), coord_noise, bicubic)
+        return torch.ops.nvsr.triplane_decode_generic_fused(planes_cl, consts, natural, geometry, x, bool(model.align_corners), coord_noise, bicubic)
+
+    @staticmethod
+    def backward(ctx, g_out):
+        planes_cl, consts, natural, geometry, x, align, coord_noise, bicubic = ctx.state
+        need = ctx.needs_input_grad
+        need_planes = [bool(n) for n in need[3:]]
+        if not any(need_planes):
+            return (None,) * len(need)
+        g = torch.ops.nvsr.triplane_decode_generic_fused_backward(planes_cl, consts, natural, geometry, x, capi.f32c(g_out), need_planes, align,
+                                                                  coord_noise, bicubic)
+        return (None, None, None) + tuple(from_channel_last(gp, like=p_) if n else None for gp, p_, n in zip(g, ctx.plane_srcs, need_planes))
 
 
 # =======================================================================================================================

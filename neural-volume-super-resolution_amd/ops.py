@@ -263,8 +263,9 @@ def _(planes, consts, natural, geometry, x, align_corners=True, coord_noise=None
 def triplane_decode_generic_fused(planes: Sequence[Tensor], consts: Sequence[float], natural: Tensor, geometry: Sequence[int], x: Tensor,
                                   align_corners: bool = True, coord_noise: Optional[Tensor] = None, bicubic: bool = False) -> Tensor:
     """triplane_decode_generic in ONE launch, for evaluation (csrc/generic_fused.hip): the input features, every layer of both decoders and both
-    heads with the activations in LDS; same arguments, the same bits in the result, no workspace and no autograd (training keeps
-    triplane_decode_generic).  Raises for a geometry beyond the kernel's capacity (nvsr_generic_fused_supported, include/nvsr.h: hidden <= 256,
+    heads with the activations in LDS; same arguments, the same bits in the result, no workspace and no registered autograd (training with
+    decoder-weight gradients keeps triplane_decode_generic; planes-only training pairs this forward with
+    triplane_decode_generic_fused_backward, TwoDimPlanesModel.generic_train_route()).  Raises for a geometry beyond the kernel's capacity (nvsr_generic_fused_supported, include/nvsr.h: hidden <= 256,
     first-layer inputs <= 512 columns, 32 points' rows in 160 KB of LDS) -- TwoDimPlanesModel.generic_route() picks the operator."""
     x, natural = _c(x), _c(natural)
     P = x.shape[0]
@@ -534,6 +535,39 @@ def triplane_decode_generic_backward(planes: Sequence[Tensor], consts: Sequence[
 @triplane_decode_generic_backward.register_fake
 def _(planes, consts, natural, geometry, x, g_out, want_natural, want_planes, align_corners=True, coord_noise=None, bicubic=False):
     return [natural.new_empty(natural.numel() if want_natural else 0)] + [pl.new_empty(pl.shape if w else (0,)) for pl, w in zip(planes, want_planes)]
+
+
+@custom_op("nvsr::triplane_decode_generic_fused_backward", mutates_args=(), device_types="cuda")
+def triplane_decode_generic_fused_backward(planes: Sequence[Tensor], consts: Sequence[float], natural: Tensor, geometry: Sequence[int], x: Tensor,
+                                           d_out: Tensor, need_planes: Sequence[bool], align_corners: bool = True,
+                                           coord_noise: Optional[Tensor] = None, bicubic: bool = False) -> List[Tensor]:
+    """The PLANE gradients of triplane_decode_generic in ONE launch, exact f32, for a decoder whose parameters take no gradient
+    (csrc/generic_fused_bwd.hip; the reference: torch.autograd through models.py:381-421): d_out [P,4] -> [d_plane0 .. d_planeN], channel-last
+    like the planes; a gradient that is not wanted comes back as an empty tensor and costs no atomics.  No workspace.  Raises for a geometry
+    beyond the kernel's capacity (nvsr_generic_backward_fused_supported, include/nvsr.h) -- TwoDimPlanesModel.generic_train_route() picks the
+    operator; triplane_decode_generic_backward runs every geometry, and the decoder's gradients, layer by layer."""
+    x, natural, d_out = _c(x), _c(natural), _c(d_out)
+    P = x.shape[0]
+    coord_noise = None if coord_noise is None else _c(coord_noise)
+    geo, n_pos, _, sc = _generic_setup(planes, consts, natural, geometry, align_corners, coord_noise, P, bicubic)
+    if capi.lib().nvsr_generic_backward_fused_supported(C.byref(geo), n_pos) != 1:
+        raise capi.NvsrError("this decoder geometry is beyond the fused generic backward's capacity (nvsr_generic_backward_fused_supported); "
+                             "torch.ops.nvsr.triplane_decode_generic_backward runs it layer by layer")
+    assert tuple(d_out.shape) == (P, 4) and d_out.dtype == torch.float32
+    capi.require_cuda(d_out)
+    need_planes = [bool(w) for w in need_planes]
+    assert len(need_planes) == n_pos + 1
+    g_pl = [torch.zeros_like(pl) if w else _f(0, like=x) for pl, w in zip(planes, need_planes)]
+    if P and any(need_planes):
+        d_planes = (C.c_void_p * (n_pos + 1))(*[g.data_ptr() if w else None for g, w in zip(g_pl, need_planes)])
+        capi.call("nvsr_generic_decode_backward_fused_ext", C.byref(sc), C.byref(geo), capi.ptr(natural), P, capi.ptr(x),
+                  None if coord_noise is None else capi.ptr(coord_noise), capi.ptr(d_out), d_planes, capi.stream())
+    return g_pl
+
+
+@triplane_decode_generic_fused_backward.register_fake
+def _(planes, consts, natural, geometry, x, d_out, need_planes, align_corners=True, coord_noise=None, bicubic=False):
+    return [pl.new_empty(pl.shape if w else (0,)) for pl, w in zip(planes, need_planes)]
 
 
 @custom_op("nvsr::ray_points", mutates_args=(), device_types="cuda")

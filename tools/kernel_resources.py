@@ -42,6 +42,8 @@ BENCHMARKED = [
     # ... with an occupancy grid (tools/generic_occupancy_time.py times it): phase 3 of the two kernels above, all 36 instantiations matched by
     # those names, and the keep mask of the point list
     "generic_occupancy_keep_kernel",
+    # ... and their planes-only training (tools/generic_train_time.py times it): <NT, LDS floats>
+    "generic_backward_fused_kernel",
 ]
 # The gate covers EVERY kernel of the library (round 4; round 3 covered the benchmarked ones): no scratch memory, no spilled VGPRs -- except:
 #   ALLOW  name substring -> spilled VGPRs tolerated.  What is listed is debt, with the round that recorded it:
