@@ -105,39 +105,19 @@ __global__ __launch_bounds__(64 * GF_MAX_WAVES) void generic_decode_fused_kernel
     }
 }
 
-// the launch covers P points (GF_FULL, GF_DENSITY) or list.max_count slots of the list (GF_COLOUR, GF_DENSITY_LIST: workgroups beyond the count return at once)
-template <int NT, int CLS, int PHASE>
-static int gen_fused_launch(const SceneDevN& sc, const GenGeom& g, const GenFusedPlan& pl, long P, const float* x, const float* noise, const float* natural,
-                            float* out, const GenFusedList& list, hipStream_t stream) {
-    const long slots = gf_listed(PHASE) ? list.max_count : P;
-    const long pts = 32L * pl.waves, blocks = (slots + pts - 1) / pts, piece = 1L << 30;       // (grid limit: pieces of whole point blocks)
-    for (long b0 = 0; b0 < blocks; b0 += piece) {
-        const long nb = blocks - b0 < piece ? blocks - b0 : piece;
-        hipLaunchKernelGGL((generic_decode_fused_kernel<NT, GF_LDS_FLOATS[CLS], PHASE>), dim3((unsigned)nb), dim3(64 * pl.waves), 0, stream, sc, g, pl, P,
-                           b0, x, noise, natural, out, list);
-        if (int e = NVSR_CHECK_LAUNCH()) return e;
-    }
-    return NVSR_OK;
-}
-
-template <int PHASE>
-static int gen_fused_dispatch(const SceneDevN& sc, const GenGeom& g, const GenFusedPlan& pl, long P, const float* x, const float* noise,
-                              const float* natural, float* out, const GenFusedList& list, hipStream_t s) {
-#define GF_CASE(NT, CLS) \
-    if (pl.nt == NT && pl.cls == CLS) return gen_fused_launch<NT, CLS, PHASE>(sc, g, pl, P, x, noise, natural, out, list, s);
-#define GF_CASES(NT) GF_CASE(NT, 0) GF_CASE(NT, 1) GF_CASE(NT, 2)
-    GF_CASES(1) GF_CASES(2) GF_CASES(3) GF_CASES(4) GF_CASES(6) GF_CASES(8)
-#undef GF_CASES
-#undef GF_CASE
-    return NVSR_ERR_SHAPE;
-}
-
+// a phase's launch: it covers P points (GF_FULL, GF_DENSITY) or list.max_count slots of the list (GF_COLOUR, GF_DENSITY_LIST: workgroups beyond
+// the count return at once)
 int gen_fused_f32_phase(int phase, const SceneDevN& sc, const GenGeom& g, const GenFusedPlan& pl, long P, const float* x, const float* noise,
                         const float* natural, float* out, const GenFusedList& list, hipStream_t stream) {
-    if (phase == GF_DENSITY) return gen_fused_dispatch<GF_DENSITY>(sc, g, pl, P, x, noise, natural, out, list, stream);
-    if (phase == GF_COLOUR) return gen_fused_dispatch<GF_COLOUR>(sc, g, pl, P, x, noise, natural, out, list, stream);
-    if (phase == GF_DENSITY_LIST) return gen_fused_dispatch<GF_DENSITY_LIST>(sc, g, pl, P, x, noise, natural, out, list, stream);
-    return gen_fused_dispatch<GF_FULL>(sc, g, pl, P, x, noise, natural, out, list, stream);
+    return gf_for_phase(phase, [&](auto ph) {
+        return gf_for_plan(pl.nt, pl.cls, [&](auto nt, auto cls) {
+            constexpr int PHASE = decltype(ph)::value, NT = decltype(nt)::value, LDSF = GF_LDS_FLOATS[decltype(cls)::value];
+            return gf_launch_pieces(gf_listed(PHASE) ? list.max_count : P, pl.waves, [&](long b0, unsigned nb) {
+                hipLaunchKernelGGL((generic_decode_fused_kernel<NT, LDSF, PHASE>), dim3(nb), dim3(64 * pl.waves), 0, stream, sc, g, pl, P, b0, x, noise,
+                                   natural, out, list);
+            });
+        });
+    });
 }
 
 }  // namespace nvsr
@@ -147,25 +127,12 @@ using namespace nvsr;
 extern "C" {
 
 int nvsr_generic_fused_supported(const nvsr_decoder_geometry* geometry, int num_position_planes) {
-    GenGeom g;
-    if (int e = gen_resolve(geometry, &g, num_position_planes)) return -e;      // (the status codes are positive: 1 must stay "supported")
-    GenFusedPlan pl;
-    return gen_fused_plan(g, &pl);
+    return nvsr_generic_fused_supported_arith(geometry, num_position_planes, NVSR_ARITH_F32);
 }
 
 int nvsr_generic_decode_fused_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural, int64_t P, const float* x,
                                   const float* coord_noise, float* out, nvsr_stream_t stream) {
-    if (int e = gen_check_ext(scene)) return e;
-    GenGeom g;
-    if (int e = gen_resolve(geometry, &g, scene->num_position_planes)) return e;
-    GenFusedPlan pl;
-    if (!gen_fused_plan(g, &pl)) return NVSR_ERR_SHAPE;
-    if (!natural || !x || !out) return NVSR_ERR_NULL;
-    const SceneDevN sc = gen_scene(scene);
-    if (int e = gen_check_scene(sc, g)) return e;
-    if (P < 0) return NVSR_ERR_SHAPE;
-    if (P == 0) return NVSR_OK;
-    return gen_fused_f32_phase(GF_FULL, sc, g, pl, (long)P, x, coord_noise, natural, out, GenFusedList{nullptr, nullptr, 0}, (hipStream_t)stream);
+    return gen_fused_arith_phase(GF_FULL, scene, geometry, natural, nullptr, P, x, coord_noise, out, GenFusedList{nullptr, nullptr, 0}, NVSR_ARITH_F32, stream);
 }
 
 }  // extern "C"

@@ -349,30 +349,6 @@ __global__ __launch_bounds__(64 * GF_MAX_WAVES) void generic_backward_fused_kern
     }
 }
 
-template <int NT, int CLS>
-static int gen_fused_bwd_launch(const SceneDevN& sc, const GenGeom& g, const GenFusedBwdPlan& pl, long P, const float* x, const float* noise,
-                                const float* natural, const float* d_out, const GradPlanesN& gp, hipStream_t stream) {
-    const long pts = 32L * pl.waves, blocks = (P + pts - 1) / pts, piece = 1L << 30;       // (grid limit: pieces of whole point blocks)
-    for (long b0 = 0; b0 < blocks; b0 += piece) {
-        const long nb = blocks - b0 < piece ? blocks - b0 : piece;
-        hipLaunchKernelGGL((generic_backward_fused_kernel<NT, GF_LDS_FLOATS[CLS]>), dim3((unsigned)nb), dim3(64 * pl.waves), 0, stream, sc, g, pl, P, b0, x,
-                           noise, natural, d_out, gp);
-        if (int e = NVSR_CHECK_LAUNCH()) return e;
-    }
-    return NVSR_OK;
-}
-
-static int gen_fused_bwd_dispatch(const SceneDevN& sc, const GenGeom& g, const GenFusedBwdPlan& pl, long P, const float* x, const float* noise,
-                                  const float* natural, const float* d_out, const GradPlanesN& gp, hipStream_t s) {
-#define GF_CASE(NT, CLS) \
-    if (pl.nt == NT && pl.cls == CLS) return gen_fused_bwd_launch<NT, CLS>(sc, g, pl, P, x, noise, natural, d_out, gp, s);
-#define GF_CASES(NT) GF_CASE(NT, 0) GF_CASE(NT, 1) GF_CASE(NT, 2)
-    GF_CASES(1) GF_CASES(2) GF_CASES(3) GF_CASES(4) GF_CASES(6) GF_CASES(8)
-#undef GF_CASES
-#undef GF_CASE
-    return NVSR_ERR_SHAPE;
-}
-
 }  // namespace nvsr
 
 using namespace nvsr;
@@ -380,30 +356,33 @@ using namespace nvsr;
 extern "C" {
 
 int nvsr_generic_backward_fused_supported(const nvsr_decoder_geometry* geometry, int num_position_planes) {
-    GenGeom g;
-    if (int e = gen_resolve(geometry, &g, num_position_planes)) return -e;      // (the status codes are positive: 1 must stay "supported")
-    GenFusedBwdPlan pl;
-    return gen_fused_bwd_plan(g, &pl);
+    return gf_supported(geometry, num_position_planes, [](const GenGeom& g) {
+        GenFusedBwdPlan pl;
+        return gen_fused_bwd_plan(g, &pl);
+    });
 }
 
 int nvsr_generic_decode_backward_fused_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural, int64_t P,
                                            const float* x, const float* coord_noise, const float* d_out, float* const* d_planes,
                                            nvsr_stream_t stream) {
-    if (int e = gen_check_ext(scene)) return e;
     GenGeom g;
-    if (int e = gen_resolve(geometry, &g, scene->num_position_planes)) return e;
     GenFusedBwdPlan pl;
-    if (!gen_fused_bwd_plan(g, &pl)) return NVSR_ERR_SHAPE;
-    if (!natural || !x || !d_out) return NVSR_ERR_NULL;
-    const SceneDevN sc = gen_scene(scene);
-    if (int e = gen_check_scene(sc, g)) return e;
-    if (P < 0) return NVSR_ERR_SHAPE;
+    SceneDevN sc;
+    const int e = gf_check_entry(scene, geometry, [&](const GenGeom& gg) { return gen_fused_bwd_plan(gg, &pl); }, natural && x && d_out, GF_FULL,
+                                 GenFusedList{nullptr, nullptr, 0}, P, &g, &sc);
+    if (e != GF_LAUNCH) return e;
     GradPlanesN gp = {};
     bool want = false;
     if (d_planes)
         for (int d = 0; d <= g.np; ++d) { gp.g[d] = d_planes[d]; want = want || d_planes[d] != nullptr; }
-    if (P == 0 || !want) return NVSR_OK;
-    return gen_fused_bwd_dispatch(sc, g, pl, (long)P, x, coord_noise, natural, d_out, gp, (hipStream_t)stream);
+    if (!want) return NVSR_OK;
+    return gf_for_plan(pl.nt, pl.cls, [&](auto nt, auto cls) {
+        constexpr int NT = decltype(nt)::value, LDSF = GF_LDS_FLOATS[decltype(cls)::value];
+        return gf_launch_pieces((long)P, pl.waves, [&](long b0, unsigned nb) {
+            hipLaunchKernelGGL((generic_backward_fused_kernel<NT, LDSF>), dim3(nb), dim3(64 * pl.waves), 0, (hipStream_t)stream, sc, g, pl, (long)P, b0, x,
+                               coord_noise, natural, d_out, gp);
+        });
+    });
 }
 
 }  // extern "C"

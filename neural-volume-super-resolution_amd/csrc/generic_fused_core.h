@@ -3,6 +3,8 @@
 // both kernels run for the heads.  Both compile the SAME stage 0 out of this header: the limb kernel differs from the f32 one in the hidden layers
 // only.
 #pragma once
+#include <type_traits>
+
 #include "generic_core.h"
 
 namespace nvsr {
@@ -222,9 +224,81 @@ __device__ __forceinline__ void gf_head(const float* row, int K, int x0, const f
     for (int r = 0; r < 3; ++r) o[r] = r < M ? __fadd_rn(acc[0][r], b[r]) : 0.0f;
 }
 
-// generic_fused.hip: a phase of the exact-f32 kernel (the arithmetic entry points of generic_fused_limb.hip forward NVSR_ARITH_F32 to it);
-// everything has been checked by the caller, P > 0
+// ---- host side: what the entry points and launches of generic_fused.hip, generic_fused_limb.hip and generic_fused_bwd.hip share ----------
+
+// the launches of a kernel over `slots` point slots, 32 per wave: launch(b0, nb) starts the workgroups [b0, b0 + nb) (grid limit: pieces of
+// whole point blocks); every piece's launch is checked
+template <typename Launch>
+static inline int gf_launch_pieces(long slots, int waves, Launch launch) {
+    const long pts = 32L * waves, blocks = (slots + pts - 1) / pts, piece = 1L << 30;
+    for (long b0 = 0; b0 < blocks; b0 += piece) {
+        launch(b0, (unsigned)(blocks - b0 < piece ? blocks - b0 : piece));
+        if (int e = NVSR_CHECK_LAUNCH()) return e;
+    }
+    return NVSR_OK;
+}
+
+// the instantiations of a plan: f(NT, CLS) with the plan's tiles and LDS class as std::integral_constant, NVSR_ERR_SHAPE for any other plan
+template <typename F>
+static inline int gf_for_plan(int nt, int cls, F f) {
+#define GF_CASE(NT, CLS) \
+    if (nt == NT && cls == CLS) return f(std::integral_constant<int, NT>{}, std::integral_constant<int, CLS>{});
+#define GF_CASES(NT) GF_CASE(NT, 0) GF_CASE(NT, 1) GF_CASE(NT, 2)
+    GF_CASES(1) GF_CASES(2) GF_CASES(3) GF_CASES(4) GF_CASES(6) GF_CASES(8)
+#undef GF_CASES
+#undef GF_CASE
+    return NVSR_ERR_SHAPE;
+}
+// the run-time phase as the kernels' template argument: f(PHASE); what is no phase runs GF_FULL
+template <typename F>
+static inline int gf_for_phase(int phase, F f) {
+    if (phase == GF_DENSITY) return f(std::integral_constant<int, GF_DENSITY>{});
+    if (phase == GF_COLOUR) return f(std::integral_constant<int, GF_COLOUR>{});
+    if (phase == GF_DENSITY_LIST) return f(std::integral_constant<int, GF_DENSITY_LIST>{});
+    return f(std::integral_constant<int, GF_FULL>{});
+}
+
+// 1 / 0 / -status of a *_supported entry: the geometry resolved, then plan(g)
+template <typename Plan>
+static inline int gf_supported(const nvsr_decoder_geometry* geometry, int num_position_planes, Plan plan) {
+    GenGeom g;
+    if (int e = gen_resolve(geometry, &g, num_position_planes)) return -e;      // (the status codes are positive: 1 must stay "supported")
+    return plan(g);
+}
+// the forward kernels' plan by arithmetic; 0 for an arithmetic that is neither NVSR_ARITH_F32 nor NVSR_ARITH_F16X2
+static inline int gen_fused_plan_arith(const GenGeom& g, GenFusedPlan* pl, int arith) {
+    return arith == NVSR_ARITH_F32 || arith == NVSR_ARITH_F16X2 ? gen_fused_plan(g, pl, arith == NVSR_ARITH_F16X2) : 0;
+}
+
+// The checks of an entry point, in the order that fixes its status codes: scene, geometry, plan(g) (the capacity) -- gf_check_capacity, which
+// nvsr_generic_occupancy_build_ext asks alone -- then the caller's pointers (have_pointers), the list's pointers, the planes of the scene,
+// P < 0, the list's bounds and the int32 limit.  GF_LAUNCH: launch; NVSR_OK: nothing to do; else the status.
+template <typename Plan>
+static inline int gf_check_capacity(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, GenGeom* g, Plan plan) {
+    if (int e = gen_check_ext(scene)) return e;
+    if (int e = gen_resolve(geometry, g, scene->num_position_planes)) return e;
+    return plan(*g) ? NVSR_OK : NVSR_ERR_SHAPE;
+}
+constexpr int GF_LAUNCH = -1;
+template <typename Plan>
+static inline int gf_check_entry(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, Plan plan, bool have_pointers, int phase,
+                                 const GenFusedList& list, int64_t P, GenGeom* g, SceneDevN* sc) {
+    if (int e = gf_check_capacity(scene, geometry, g, plan)) return e;
+    if (!have_pointers) return NVSR_ERR_NULL;
+    const bool listed = gf_listed(phase);
+    if (listed && (!list.index || !list.count)) return NVSR_ERR_NULL;
+    *sc = gen_scene(scene);
+    if (int e = gen_check_scene(*sc, *g)) return e;
+    if (P < 0) return NVSR_ERR_SHAPE;
+    if (listed && (list.max_count < 0 || list.max_count > P || P > 0x7fffffffL)) return NVSR_ERR_SHAPE;      // (int32 indices)
+    return P == 0 || (listed && list.max_count == 0) ? NVSR_OK : GF_LAUNCH;
+}
+
+// generic_fused.hip: a phase of the exact-f32 kernel; everything has been checked by the caller, P > 0
 int gen_fused_f32_phase(int phase, const SceneDevN& sc, const GenGeom& g, const GenFusedPlan& pl, long P, const float* x, const float* noise,
                         const float* natural, float* out, const GenFusedList& list, hipStream_t stream);
+// generic_fused_limb.hip: a phase in either arithmetic behind gf_check_entry (NVSR_ARITH_F32: `packed` is not read and may be null)
+int gen_fused_arith_phase(int phase, const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural, const float* packed,
+                          int64_t P, const float* x, const float* coord_noise, float* out, const GenFusedList& list, int arith, nvsr_stream_t stream);
 
 }  // namespace nvsr

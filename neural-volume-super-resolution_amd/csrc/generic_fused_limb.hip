@@ -246,58 +246,30 @@ __global__ __launch_bounds__(64 * GF_MAX_WAVES) void generic_decode_fused_limb_k
     if (flag && __any(bad) && lane == 0) __hip_atomic_fetch_or(flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int NT, int CLS, int PHASE>
-static int gen_fused_limb_launch(const SceneDevN& sc, const GenGeom& g, const GenFusedPlan& pl, long P, const float* x, const float* noise,
-                                 const float* natural, const float* packed, float* out, const GenFusedList& list, hipStream_t stream) {
-    const long slots = gf_listed(PHASE) ? list.max_count : P;      // (GF_COLOUR: workgroups beyond the count return at once)
-    const long pts = 32L * pl.waves, blocks = (slots + pts - 1) / pts, piece = 1L << 30;       // (grid limit: pieces of whole point blocks)
-    unsigned* flag = nvsr_get_range_flag();
-    for (long b0 = 0; b0 < blocks; b0 += piece) {
-        const long nb = blocks - b0 < piece ? blocks - b0 : piece;
-        hipLaunchKernelGGL((generic_decode_fused_limb_kernel<NT, GF_LDS_FLOATS[CLS], PHASE>), dim3((unsigned)nb), dim3(64 * pl.waves), 0, stream, sc, g, pl,
-                           P, b0, x, noise, natural, reinterpret_cast<const unsigned*>(packed), out, flag, list);
-        if (int e = NVSR_CHECK_LAUNCH()) return e;
-    }
-    return NVSR_OK;
-}
-
-template <int PHASE>
-static int gen_fused_limb_dispatch(const SceneDevN& sc, const GenGeom& g, const GenFusedPlan& pl, long P, const float* x, const float* noise,
-                                   const float* natural, const float* packed, float* out, const GenFusedList& list, hipStream_t s) {
-#define GFL_CASE(NT, CLS) \
-    if (pl.nt == NT && pl.cls == CLS) return gen_fused_limb_launch<NT, CLS, PHASE>(sc, g, pl, P, x, noise, natural, packed, out, list, s);
-#define GFL_CASES(NT) GFL_CASE(NT, 0) GFL_CASE(NT, 1) GFL_CASE(NT, 2)
-    GFL_CASES(1) GFL_CASES(2) GFL_CASES(3) GFL_CASES(4) GFL_CASES(6) GFL_CASES(8)
-#undef GFL_CASES
-#undef GFL_CASE
-    return NVSR_ERR_SHAPE;
-}
-
-// one entry for the three phases, in either arithmetic: the checks of nvsr_generic_decode_fused_arith_ext, then the phase's launch
-static int gen_fused_arith_phase(int phase, const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural, const float* packed,
-                                 int64_t P, const float* x, const float* coord_noise, float* out, const GenFusedList& list, int arith,
-                                 nvsr_stream_t stream) {
+// one entry for the four phases, in either arithmetic: the checks (gf_check_entry), then the phase's launch -- over P points or over
+// list.max_count slots of the list, whose workgroups beyond the count return at once
+int gen_fused_arith_phase(int phase, const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural, const float* packed,
+                          int64_t P, const float* x, const float* coord_noise, float* out, const GenFusedList& list, int arith, nvsr_stream_t stream) {
     if (arith != NVSR_ARITH_F32 && arith != NVSR_ARITH_F16X2) return NVSR_ERR_SHAPE;      // by name only: no process default, no one-limb or bf16 mode here
     const bool limb = arith == NVSR_ARITH_F16X2;
-    if (int e = gen_check_ext(scene)) return e;
     GenGeom g;
-    if (int e = gen_resolve(geometry, &g, scene->num_position_planes)) return e;
     GenFusedPlan pl;
-    if (!gen_fused_plan(g, &pl, limb)) return NVSR_ERR_SHAPE;
-    if (!natural || (limb && !packed) || !x || !out) return NVSR_ERR_NULL;
-    const bool listed = gf_listed(phase);
-    if (listed && (!list.index || !list.count)) return NVSR_ERR_NULL;
-    const SceneDevN sc = gen_scene(scene);
-    if (int e = gen_check_scene(sc, g)) return e;
-    if (P < 0) return NVSR_ERR_SHAPE;
-    if (listed && (list.max_count < 0 || list.max_count > P || P > 0x7fffffffL)) return NVSR_ERR_SHAPE;      // (int32 indices)
-    if (P == 0 || (listed && list.max_count == 0)) return NVSR_OK;
+    SceneDevN sc;
+    const int e = gf_check_entry(scene, geometry, [&](const GenGeom& gg) { return gen_fused_plan(gg, &pl, limb); },
+                                 natural && (!limb || packed) && x && out, phase, list, P, &g, &sc);
+    if (e != GF_LAUNCH) return e;
     hipStream_t s = (hipStream_t)stream;
     if (!limb) return gen_fused_f32_phase(phase, sc, g, pl, (long)P, x, coord_noise, natural, out, list, s);
-    if (phase == GF_DENSITY) return gen_fused_limb_dispatch<GF_DENSITY>(sc, g, pl, (long)P, x, coord_noise, natural, packed, out, list, s);
-    if (phase == GF_COLOUR) return gen_fused_limb_dispatch<GF_COLOUR>(sc, g, pl, (long)P, x, coord_noise, natural, packed, out, list, s);
-    if (phase == GF_DENSITY_LIST) return gen_fused_limb_dispatch<GF_DENSITY_LIST>(sc, g, pl, (long)P, x, coord_noise, natural, packed, out, list, s);
-    return gen_fused_limb_dispatch<GF_FULL>(sc, g, pl, (long)P, x, coord_noise, natural, packed, out, list, s);
+    unsigned* flag = nvsr_get_range_flag();
+    return gf_for_phase(phase, [&](auto ph) {
+        return gf_for_plan(pl.nt, pl.cls, [&](auto nt, auto cls) {
+            constexpr int PHASE = decltype(ph)::value, NT = decltype(nt)::value, LDSF = GF_LDS_FLOATS[decltype(cls)::value];
+            return gf_launch_pieces(gf_listed(PHASE) ? list.max_count : (long)P, pl.waves, [&](long b0, unsigned nb) {
+                hipLaunchKernelGGL((generic_decode_fused_limb_kernel<NT, LDSF, PHASE>), dim3(nb), dim3(64 * pl.waves), 0, s, sc, g, pl, (long)P, b0, x,
+                                   coord_noise, natural, reinterpret_cast<const unsigned*>(packed), out, flag, list);
+            });
+        });
+    });
 }
 
 }  // namespace nvsr
@@ -324,18 +296,14 @@ int nvsr_pack_generic_decoder_ext(const nvsr_decoder_geometry* geometry, int num
 }
 
 int nvsr_generic_fused_supported_arith(const nvsr_decoder_geometry* geometry, int num_position_planes, int arith) {
-    if (arith == NVSR_ARITH_F32) return nvsr_generic_fused_supported(geometry, num_position_planes);
-    GenGeom g;
-    if (int e = gen_resolve(geometry, &g, num_position_planes)) return -e;      // (the status codes are positive: 1 must stay "supported")
-    if (arith != NVSR_ARITH_F16X2) return 0;
-    GenFusedPlan pl;
-    return gen_fused_plan(g, &pl, true);
+    return gf_supported(geometry, num_position_planes, [&](const GenGeom& g) {
+        GenFusedPlan pl;
+        return gen_fused_plan_arith(g, &pl, arith);
+    });
 }
 
 int nvsr_generic_decode_fused_arith_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural, const float* packed,
                                         int64_t P, const float* x, const float* coord_noise, float* out, int arith, nvsr_stream_t stream) {
-    if (arith == NVSR_ARITH_F32) return nvsr_generic_decode_fused_ext(scene, geometry, natural, P, x, coord_noise, out, stream);
-    if (arith != NVSR_ARITH_F16X2) return NVSR_ERR_SHAPE;            // by name only: no process default, no one-limb or bf16 mode here
     return gen_fused_arith_phase(GF_FULL, scene, geometry, natural, packed, P, x, coord_noise, out, GenFusedList{nullptr, nullptr, 0}, arith, stream);
 }
 

@@ -6,7 +6,7 @@
 // The grid is APPROXIMATE by nature: no finite set of probes bounds an MLP over a cell.  K (probes per axis and cell), the threshold and the
 // rounds of dilation are the caller's knobs.
 #include "occupancy.h"
-#include "generic_core.h"
+#include "generic_fused_core.h"
 #include "nvsr_internal.h"
 
 namespace nvsr {
@@ -229,9 +229,9 @@ extern "C" int nvsr_occupancy_build(const nvsr_scene* scene, const float* packed
 extern "C" int nvsr_generic_occupancy_build_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural, const float* packed,
                                                 int G, int K, float threshold, int dilate, int arith, uint32_t* grid, float* workspace, nvsr_stream_t stream) {
     if (!build_shape_ok(G, K) || dilate < 0) return NVSR_ERR_SHAPE;
-    if (int e = gen_check_ext(scene)) return e;
-    if (!geometry) return NVSR_ERR_NULL;
-    if (nvsr_generic_fused_supported_arith(geometry, scene->num_position_planes, arith) != 1) return NVSR_ERR_SHAPE;      // (nothing launched)
+    GenGeom g;
+    GenFusedPlan pl;
+    if (int e = gf_check_capacity(scene, geometry, &g, [&](const GenGeom& gg) { return gen_fused_plan_arith(gg, &pl, arith); })) return e;      // (nothing launched)
     if (!natural || (arith == NVSR_ARITH_F16X2 && !packed) || !grid || !workspace) return NVSR_ERR_NULL;
     if (!aligned16(workspace)) return NVSR_ERR_ALIGN;
     return occupancy_build_slabs(scene->lo, scene->range, G, K, threshold, dilate, grid, workspace, (hipStream_t)stream, [&](int64_t P, const float* x, float* out) {

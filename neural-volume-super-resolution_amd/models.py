@@ -360,8 +360,7 @@ class TwoDimPlanesModel(nn.Module):
         with torch.no_grad():                      # (the arithmetic of an evaluation: what the frames that use the grid run in)
             limb = self.generic_arithmetic() == "f16x2"
         arith = capi.ARITHMETIC["f16x2" if limb else "f32"]
-        geo = capi.DecoderGeometry(*[int(v) for v in self.generic_geometry()])
-        if capi.lib().nvsr_generic_fused_supported_arith(C.byref(geo), int(self.num_density_planes), arith) != 1:
+        if not self._generic_held("f16x2" if limb else "f32"):
             raise NotImplementedError("an occupancy grid of a generic decoder geometry is probed with the fused generic kernel's density phase, which "
                                       "does not hold this geometry (nvsr_generic_fused_supported_arith: hidden <= 256, first-layer inputs <= 512 "
                                       "columns, 32 points' rows in 160 KB of LDS)")
@@ -678,6 +677,26 @@ class TwoDimPlanesModel(nn.Module):
         sr_grad = sr_on and self.SR_model.training and self.SR_model.inner_model.wants_grad(*self.SR_model.LR_planes.values())
         return dec, sr_on, bool(dec or sr_grad or any(n in self.planes_ and self.planes_[n].requires_grad for n in names))
 
+    @staticmethod
+    def _generic_handle(name):
+        """an environment handle of the generic routes, read at every call: '0' (never), '1' (wherever the conditions hold), '' (anything else:
+        the measured default)"""
+        value = os.environ.get(name, "")
+        return value if value in ("0", "1") else ""
+
+    def _generic_width_in(self, span):
+        """is dec_channels within (lowest, highest)?  None: nowhere"""
+        return span is not None and span[0] <= self.dec_channels <= span[1]
+
+    def _generic_held(self, *kinds):
+        """do the fused kernels hold this geometry -- 'f32' (nvsr_generic_fused_supported), 'f16x2' (nvsr_generic_fused_supported_arith),
+        'backward' (nvsr_generic_backward_fused_supported), every one of `kinds`?  Host code: no GPU is touched."""
+        geo, n_pos, lib = C.byref(capi.DecoderGeometry(*[int(v) for v in self.generic_geometry()])), int(self.num_density_planes), capi.lib()
+        ask = {"f32": lambda: lib.nvsr_generic_fused_supported(geo, n_pos),
+               "f16x2": lambda: lib.nvsr_generic_fused_supported_arith(geo, n_pos, capi.ARITHMETIC["f16x2"]),
+               "backward": lambda: lib.nvsr_generic_backward_fused_supported(geo, n_pos)}
+        return all(ask[kind]() == 1 for kind in kinds)
+
     def generic_route(self):
         """'fused' or 'layered': what a forward through the generic kernels runs if called now.  'fused' = one launch, activations in LDS
         (csrc/generic_fused.hip, torch.ops.nvsr.triplane_decode_generic_fused); it is taken when no graph is being recorded (gradients off, or
@@ -686,15 +705,12 @@ class TwoDimPlanesModel(nn.Module):
         wave per workgroup and takes twice the layered route's time).  'layered' = a launch per layer (csrc/generic.hip): training and
         everything else.  NVSR_GENERIC_FUSED (read at every call): 0 forces 'layered', 1 takes 'fused' wherever the capacity allows.
         The two give the same bits.  The decision touches no GPU."""
-        handle = os.environ.get("NVSR_GENERIC_FUSED", "")
-        if handle == "0":
-            return "layered"
-        if torch.is_grad_enabled() and self._generic_graph()[2]:
+        handle = self._generic_handle("NVSR_GENERIC_FUSED")
+        if handle == "0" or (torch.is_grad_enabled() and self._generic_graph()[2]):
             return "layered"
         if handle != "1" and self.dec_channels > self.GENERIC_FUSED_DEFAULT_MAX_HIDDEN:
             return "layered"
-        geo = capi.DecoderGeometry(*[int(v) for v in self.generic_geometry()])
-        return "fused" if capi.lib().nvsr_generic_fused_supported(C.byref(geo), int(self.num_density_planes)) == 1 else "layered"
+        return "fused" if self._generic_held("f32") else "layered"
 
     GENERIC_FUSED_DEFAULT_MAX_HIDDEN = 128
 
@@ -715,19 +731,14 @@ class TwoDimPlanesModel(nn.Module):
         (nvsr_generic_fused_supported, nvsr_generic_backward_fused_supported) and NVSR_GENERIC_TRAIN_FUSED (read at every call) allows it: 0
         never, 1 wherever the capacity allows, unset at the widths of GENERIC_TRAIN_FUSED_DEFAULT_HIDDEN.  'layered' = csrc/generic.hip layer by
         layer: decoder-weight gradients and everything else.  The decision touches no GPU; generic_route() is not affected."""
-        handle = os.environ.get("NVSR_GENERIC_TRAIN_FUSED", "")
+        handle = self._generic_handle("NVSR_GENERIC_TRAIN_FUSED")
         if handle == "0" or not torch.is_grad_enabled() or capi.deterministic():
             return "layered"
         dec, _, graph = self._generic_graph()
-        if dec or not graph:
+        if dec or not graph or (handle != "1" and not self._generic_width_in(self.GENERIC_TRAIN_FUSED_DEFAULT_HIDDEN)):
             return "layered"
-        span = self.GENERIC_TRAIN_FUSED_DEFAULT_HIDDEN
-        if handle != "1" and not (span is not None and span[0] <= self.dec_channels <= span[1]):
-            return "layered"
-        geo = capi.DecoderGeometry(*[int(v) for v in self.generic_geometry()])
-        n_pos = int(self.num_density_planes)
-        ok = capi.lib().nvsr_generic_fused_supported(C.byref(geo), n_pos) == 1 and capi.lib().nvsr_generic_backward_fused_supported(C.byref(geo), n_pos) == 1
-        return "fused" if ok else "layered"
+        return "fused" if self._generic_held("f32", "backward") else "layered"
+
     # dec_channels (lowest, highest) at which the fused route in 'f16x2' was measured faster, by more than the spread of the alternations, than
     # the better of the two f32 routes: 1.28 - 1.54 x on 2^22 points, 1.39 - 1.69 x on a 400 x 400 frame at 64, 128 and 256
     # (profiles/generic_limb_ab.txt).  Narrower decoders were not measured: there the arithmetic needs NVSR_GENERIC_FUSED=1.  None: nowhere.
@@ -744,15 +755,12 @@ class TwoDimPlanesModel(nn.Module):
         which holds this answer at 'f32' while it does.  The decision touches no GPU."""
         if not (isinstance(self.arithmetic, str) and self.arithmetic == "f16x2") or self.__dict__.get("_generic_limb_off"):
             return "f32"
-        handle = os.environ.get("NVSR_GENERIC_FUSED", "")
+        handle = self._generic_handle("NVSR_GENERIC_FUSED")
         if handle == "0" or (torch.is_grad_enabled() and self._generic_graph()[2]):
             return "f32"
-        span = self.GENERIC_LIMB_DEFAULT_HIDDEN
-        if handle != "1" and not (span is not None and span[0] <= self.dec_channels <= span[1]):
+        if handle != "1" and not self._generic_width_in(self.GENERIC_LIMB_DEFAULT_HIDDEN):
             return "f32"
-        geo = capi.DecoderGeometry(*[int(v) for v in self.generic_geometry()])
-        ok = capi.lib().nvsr_generic_fused_supported_arith(C.byref(geo), int(self.num_density_planes), capi.ARITHMETIC["f16x2"]) == 1
-        return "f16x2" if ok else "f32"
+        return "f16x2" if self._generic_held("f16x2") else "f32"
 
     def packed_generic_decoder(self):
         """the hidden layers' f16-limb fragments for generic_arithmetic() == 'f16x2' (nvsr_pack_generic_decoder_ext), cached like packed_decoder()"""
@@ -833,14 +841,18 @@ class TwoDimPlanesModel(nn.Module):
         the sample positions drawn inside the forward (jitter_std() == 0).  NVSR_GENERIC_TWO_PHASE (read at every call): 0 forces 'one_phase',
         1 takes 'two_phase' wherever those conditions hold; unset: the measured default (GENERIC_TWO_PHASE_DEFAULT_HIDDEN).  The decision
         touches no GPU."""
-        handle = os.environ.get("NVSR_GENERIC_TWO_PHASE", "")
-        if handle == "0" or self.is_native_geometry() or self.jitter_std() or self.generic_route() != "fused":
+        if not self.generic_phases_allowed():
             return "one_phase"
-        if handle != "1":
-            span = self.GENERIC_TWO_PHASE_DEFAULT_HIDDEN.get(self.generic_arithmetic())
-            if not (span is not None and span[0] <= self.dec_channels <= span[1]):
-                return "one_phase"
+        if self._generic_handle("NVSR_GENERIC_TWO_PHASE") != "1" and not self._generic_width_in(
+                self.GENERIC_TWO_PHASE_DEFAULT_HIDDEN.get(self.generic_arithmetic())):
+            return "one_phase"
         return "two_phase"
+
+    def generic_phases_allowed(self):
+        """what a frame in two phases and a frame under an occupancy grid (train_utils._generic_occupancy) both need: NVSR_GENERIC_TWO_PHASE
+        is not 0, the geometry is a generic one, no jitter of the sample positions, and generic_route() == 'fused'"""
+        return not (self._generic_handle("NVSR_GENERIC_TWO_PHASE") == "0" or self.is_native_geometry() or self.jitter_std()
+                    or self.generic_route() != "fused")
 
     def _generic_phase_args(self, points, coord_noise):
         if torch.is_grad_enabled() and self._generic_graph()[2]:
@@ -1033,6 +1045,20 @@ class _DecodePointsFn(torch.autograd.Function):
         return (None, None) + tuple(from_channel_last(g, like=p_) if n else None for g, p_, n in zip(gplanes, ctx.plane_srcs, need_planes)) + (gnat,)
 
 
+def _generic_forward_state(ctx, model, x, nat, coord_noise, plane_srcs):
+    """what the forwards of the two generic autograd functions share: the refusal in the deterministic mode (before any launch), the
+    channel-last planes and the scene constants, the natural blob (nat, or the model's where the decoder does not train) -> the arguments of the
+    forward operator, kept as ctx.state for the backward"""
+    if capi.deterministic():
+        capi.refuse_deterministic("training a generic decoder geometry (generic.hip)")
+    planes_cl, consts = model.scene_args(planes=[to_channel_last(p.detach()) for p in plane_srcs], check_native=False)
+    natural = model.natural_blob() if nat is None else nat.detach()
+    capi.require_cuda(natural)
+    ctx.plane_srcs = plane_srcs
+    ctx.state = (planes_cl, consts, natural, model.generic_geometry(), x, bool(model.align_corners), coord_noise, model.plane_interp == "bicubic")
+    return ctx.state
+
+
 class _GenericDecodeFn(torch.autograd.Function):
     """TwoDimPlanesModel.forward for a decoder geometry / option set other than the shipped one, with gradients for the planes and the
     decoder (torch.ops.nvsr.triplane_decode_generic / _backward: csrc/generic.hip recomputes the forward in the backward).
@@ -1040,17 +1066,7 @@ class _GenericDecodeFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, x, nat, coord_noise, *plane_srcs):
-        if capi.deterministic():
-            capi.refuse_deterministic("training a generic decoder geometry (generic.hip)")
-        planes_cl = [to_channel_last(p.detach()) for p in plane_srcs]
-        planes_cl, consts = model.scene_args(planes=planes_cl, check_native=False)
-        natural = model.natural_blob() if nat is None else nat.detach()
-        capi.require_cuda(natural)
-        geometry = model.generic_geometry()
-        ctx.plane_srcs = plane_srcs
-        bicubic = model.plane_interp == "bicubic"
-        ctx.state = (planes_cl, consts, natural, geometry, x, bool(model.align_corners), coord_noise, bicubic)
-        return torch.ops.nvsr.triplane_decode_generic(planes_cl, consts, natural, geometry, x, bool(model.align_corners), coord_noise, bicubic)
+        return torch.ops.nvsr.triplane_decode_generic(*_generic_forward_state(ctx, model, x, nat, coord_noise, plane_srcs))
 
     @staticmethod
     def backward(ctx, g_out):
@@ -1073,17 +1089,7 @@ class _GenericFusedTrainFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, x, coord_noise, *plane_srcs):
-        if capi.deterministic():
-            capi.refuse_deterministic("training a generic decoder geometry (generic.hip)")
-        planes_cl = [to_channel_last(p.detach()) for p in plane_srcs]
-        planes_cl, consts = model.scene_args(planes=planes_cl, check_native=False)
-        natural = model.natural_blob()
-        capi.require_cuda(natural)
-        geometry = model.generic_geometry()
-        ctx.plane_srcs = plane_srcs
-        bicubic = model.plane_interp == "bicubic"
-        ctx.state = (planes_cl, consts, natural, geometry, x, bool(model.align_corners), coord_noise, bicubic)
-        return torch.ops.nvsr.triplane_decode_generic_fused(planes_cl, consts, natural, geometry, x, bool(model.align_corners), coord_noise, bicubic)
+        return torch.ops.nvsr.triplane_decode_generic_fused(*_generic_forward_state(ctx, model, x, None, coord_noise, plane_srcs))
 
     @staticmethod
     def backward(ctx, g_out):

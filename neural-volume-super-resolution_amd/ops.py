@@ -18,6 +18,7 @@ Reference functions behind the operators: models.py:381-421 (decoder), train_uti
 (compositing), nerf_helpers.py:668-702 (importance sampling), models.py:769-822,884-926 (EDSR / PlanesSR)."""
 import ctypes as C
 import os
+from types import SimpleNamespace
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -211,26 +212,76 @@ def _scene_ext(planes, consts, channels, align_corners, bicubic=False):
         assert p.dtype == torch.float32 and p.dim() == 3 and p.shape[2] == cc and p.is_contiguous(), "planes must be channel-last [H,W,%d] f32" % cc
         sc.planes[d] = p.data_ptr()
         sc.ph[d], sc.pw[d] = p.shape[0], p.shape[1]
-    for i in range(5):
-        sc.lo[i] = consts[i]
-        sc.range[i] = consts[5 + i]
+    _scene_box(sc, consts)
     for d in range(n_pos):
         for j in range(6):
             sc.proj[d][j] = consts[10 + 6 * d + j]
     return sc
 
 
-def _generic_setup(planes, consts, natural, geometry, align_corners, coord_noise, P, bicubic=False):
+def _scene_box(sc, consts):
+    """lo[5] and range[5] of a capi.SceneExt from the head of the scene constants"""
+    for i in range(5):
+        sc.lo[i] = consts[i]
+        sc.range[i] = consts[5 + i]
+    return sc
+
+
+def _generic_geometry(geometry, n_pos, natural=None):
+    """(struct nvsr_decoder_geometry, floats of its natural blob); raises for an inconsistent geometry and for a `natural` of another size"""
     geo = capi.DecoderGeometry(*[int(v) for v in geometry])
-    n_pos = len(planes) - 1
-    n = capi.lib().nvsr_generic_decoder_natural_floats_ext(C.byref(geo), n_pos)
+    n = capi.lib().nvsr_generic_decoder_natural_floats_ext(C.byref(geo), int(n_pos))
     if n < 0:
         raise capi.NvsrError("this decoder geometry is inconsistent (the reference's own layer sizes do not admit it)")
-    assert natural.numel() == n, "natural blob: %d floats, the geometry needs %d" % (natural.numel(), n)
+    assert natural is None or natural.numel() == n, "natural blob: %d floats, the geometry needs %d" % (natural.numel(), n)
+    return geo, n
+
+
+def _generic_setup(planes, consts, natural, geometry, align_corners, coord_noise, P, bicubic=False):
+    """the geometry with the natural blob's size checked, coord_noise [P,3] validated, the scene -> (geo, n_pos, floats of natural, scene)"""
+    n_pos = len(planes) - 1
+    geo, n = _generic_geometry(geometry, n_pos, natural)
     if coord_noise is not None:
         assert tuple(coord_noise.shape) == (P, 3) and coord_noise.dtype == torch.float32, "coord_noise: [P,3] f32"
         capi.require_cuda(coord_noise)
     return geo, n_pos, n, _scene_ext(planes, consts, (geo.plane_channels, geo.viewdir_channels), align_corners, bicubic)
+
+
+# what each capacity check of _generic_call asks and says: capacity -> (entry, takes `arith`, message)
+_ARITH_CAPACITY = ("the fused generic kernel does not take this decoder geometry in this arithmetic (nvsr_generic_fused_supported_arith: "
+                   "beyond its capacity, or not 'f32' / 'f16x2')")
+_GENERIC_CAPACITY = {
+    "fused": ("nvsr_generic_fused_supported", False, "this decoder geometry is beyond the fused generic kernel's capacity "
+              "(nvsr_generic_fused_supported); torch.ops.nvsr.triplane_decode_generic runs it layer by layer"),
+    "arith": ("nvsr_generic_fused_supported_arith", True, _ARITH_CAPACITY),
+    "occupancy": ("nvsr_generic_fused_supported_arith", True, _ARITH_CAPACITY + ": no occupancy grid for it"),
+    "backward": ("nvsr_generic_backward_fused_supported", False, "this decoder geometry is beyond the fused generic backward's capacity "
+                 "(nvsr_generic_backward_fused_supported); torch.ops.nvsr.triplane_decode_generic_backward runs it layer by layer"),
+}
+
+
+def _generic_call(planes, consts, natural, geometry, align_corners, bicubic, x=None, coord_noise=None, capacity=None, arith=0, packed=None,
+                  grad=None):
+    """The paragraph every generic operator opens with.  Makes natural, x [P,6], coord_noise [P,3], packed and grad (g_out / d_out [P,4]) f32 and
+    contiguous -- the kernels take dense row-major buffers, and a view must never reach them; _generic_setup; then the `capacity` the operator
+    needs (None: every geometry runs; 'fused': the f32 kernel; 'arith' / 'occupancy': the forward kernel in `arith`; 'backward': the fused
+    backward) and, in 'f16x2', the packed size.
+    -> a namespace that holds the contiguous tensors until the call is made: geo, n_pos, n (floats of natural), sc, P, grad, arith and head =
+    the arguments (scene, geometry, natural[, packed in the arith entries], P, x, coord_noise or NULL) every decode entry starts with."""
+    s = SimpleNamespace(natural=_c(natural), x=_c(x), packed=_c(packed), grad=_c(grad), coord_noise=_c(coord_noise), arith=int(arith))
+    s.P = 0 if x is None else s.x.shape[0]
+    s.geo, s.n_pos, s.n, s.sc = _generic_setup(planes, consts, s.natural, geometry, align_corners, s.coord_noise, s.P, bicubic)
+    assert s.grad is None or tuple(s.grad.shape) == (s.P, 4), "the output's gradient: [P,4]"
+    lib, geo = capi.lib(), C.byref(s.geo)
+    if capacity is not None:
+        entry, by_arith, message = _GENERIC_CAPACITY[capacity]
+        if getattr(lib, entry)(geo, s.n_pos, *([s.arith] if by_arith else [])) != 1:
+            raise capi.NvsrError(message)
+        if by_arith and s.arith == capi.ARITHMETIC["f16x2"]:
+            assert s.packed.numel() == lib.nvsr_generic_packed_floats_ext(geo, s.n_pos), "packed blob of another geometry"
+    s.head = (C.byref(s.sc), geo, capi.ptr(s.natural)) + ((capi.ptr(s.packed),) if packed is not None else ()) + (s.P, capi.ptr(s.x),
+                                                                                                                 capi.ptr(s.coord_noise))
+    return s
 
 
 @custom_op("nvsr::triplane_decode_generic", mutates_args=(), device_types="cuda")
@@ -242,15 +293,11 @@ def triplane_decode_generic(planes: Sequence[Tensor], consts: Sequence[float], n
     state-dict order; planes channel-last: N position planes [H,W,plane_channels], then [H,W,viewdir_channels]; consts = lo[5], range[5],
     N 3x2 projections; align_corners / bicubic: grid_sample's align_corners and mode; coord_noise [P,3]: added to the normalised positions
     (point_coords_noise, models.py:291-293)."""
-    x, natural = _c(x), _c(natural)
-    P = x.shape[0]
-    coord_noise = None if coord_noise is None else _c(coord_noise)
-    geo, n_pos, _, sc = _generic_setup(planes, consts, natural, geometry, align_corners, coord_noise, P, bicubic)
-    out = _f(P, 4, like=x)
-    if P:
-        ws = _f(capi.lib().nvsr_generic_decode_workspace_floats_ext(C.byref(geo), n_pos, P), like=x)
-        capi.call("nvsr_generic_decode_ext", C.byref(sc), C.byref(geo), capi.ptr(natural), P, capi.ptr(x),
-                  None if coord_noise is None else capi.ptr(coord_noise), capi.ptr(out), capi.ptr(ws), capi.stream())
+    s = _generic_call(planes, consts, natural, geometry, align_corners, bicubic, x, coord_noise)
+    out = _f(s.P, 4, like=x)
+    if s.P:
+        ws = _f(capi.lib().nvsr_generic_decode_workspace_floats_ext(C.byref(s.geo), s.n_pos, s.P), like=x)
+        capi.call("nvsr_generic_decode_ext", *s.head, capi.ptr(out), capi.ptr(ws), capi.stream())
     return out
 
 
@@ -267,17 +314,10 @@ def triplane_decode_generic_fused(planes: Sequence[Tensor], consts: Sequence[flo
     decoder-weight gradients keeps triplane_decode_generic; planes-only training pairs this forward with
     triplane_decode_generic_fused_backward, TwoDimPlanesModel.generic_train_route()).  Raises for a geometry beyond the kernel's capacity (nvsr_generic_fused_supported, include/nvsr.h: hidden <= 256,
     first-layer inputs <= 512 columns, 32 points' rows in 160 KB of LDS) -- TwoDimPlanesModel.generic_route() picks the operator."""
-    x, natural = _c(x), _c(natural)
-    P = x.shape[0]
-    coord_noise = None if coord_noise is None else _c(coord_noise)
-    geo, n_pos, _, sc = _generic_setup(planes, consts, natural, geometry, align_corners, coord_noise, P, bicubic)
-    if capi.lib().nvsr_generic_fused_supported(C.byref(geo), n_pos) != 1:
-        raise capi.NvsrError("this decoder geometry is beyond the fused generic kernel's capacity (nvsr_generic_fused_supported); "
-                             "torch.ops.nvsr.triplane_decode_generic runs it layer by layer")
-    out = _f(P, 4, like=x)
-    if P:
-        capi.call("nvsr_generic_decode_fused_ext", C.byref(sc), C.byref(geo), capi.ptr(natural), P, capi.ptr(x),
-                  None if coord_noise is None else capi.ptr(coord_noise), capi.ptr(out), capi.stream())
+    s = _generic_call(planes, consts, natural, geometry, align_corners, bicubic, x, coord_noise, "fused")
+    out = _f(s.P, 4, like=x)
+    if s.P:
+        capi.call("nvsr_generic_decode_fused_ext", *s.head, capi.ptr(out), capi.stream())
     return out
 
 
@@ -291,11 +331,7 @@ def pack_generic_decoder(natural: Tensor, geometry: Sequence[int], n_pos: int) -
     """the hidden layers of a generic geometry's natural blob -> the f16-limb fragments of the fused evaluation kernel in 'f16x2'
     (csrc/generic_fused_limb.hip; include/nvsr.h has the layout).  Evaluation only: no autograd."""
     nat = capi.f32c(natural)
-    geo = capi.DecoderGeometry(*[int(v) for v in geometry])
-    n = capi.lib().nvsr_generic_decoder_natural_floats_ext(C.byref(geo), int(n_pos))
-    if n < 0:
-        raise capi.NvsrError("this decoder geometry is inconsistent (the reference's own layer sizes do not admit it)")
-    assert nat.numel() == n, "natural blob: %d floats, the geometry needs %d" % (nat.numel(), n)
+    geo, _ = _generic_geometry(geometry, n_pos, nat)
     packed = _f(capi.lib().nvsr_generic_packed_floats_ext(C.byref(geo), int(n_pos)), like=nat)
     capi.call("nvsr_pack_generic_decoder_ext", C.byref(geo), int(n_pos), capi.ptr(nat), capi.ptr(packed), capi.stream())
     return packed
@@ -303,7 +339,7 @@ def pack_generic_decoder(natural: Tensor, geometry: Sequence[int], n_pos: int) -
 
 @pack_generic_decoder.register_fake
 def _(natural, geometry, n_pos):
-    geo = capi.DecoderGeometry(*[int(v) for v in geometry])
+    geo, _ = _generic_geometry(geometry, n_pos, natural)
     return natural.new_empty((capi.lib().nvsr_generic_packed_floats_ext(C.byref(geo), int(n_pos)),), dtype=torch.float32)
 
 
@@ -315,19 +351,10 @@ def triplane_decode_generic_fused_arith(planes: Sequence[Tensor], consts: Sequen
     limbs from `packed` (pack_generic_decoder of the same natural blob), capi.ARITHMETIC['f32'] is triplane_decode_generic_fused (`packed`
     is not read).  Every other code raises: the mode is chosen by name, never inherited.  Beyond f16x2's ranges the result is NaN and the
     range flag (capi.range_flag) is raised.  Evaluation only: no autograd."""
-    x, natural, packed = _c(x), _c(natural), _c(packed)
-    P = x.shape[0]
-    coord_noise = None if coord_noise is None else _c(coord_noise)
-    geo, n_pos, _, sc = _generic_setup(planes, consts, natural, geometry, align_corners, coord_noise, P, bicubic)
-    if capi.lib().nvsr_generic_fused_supported_arith(C.byref(geo), n_pos, int(arith)) != 1:
-        raise capi.NvsrError("the fused generic kernel does not take this decoder geometry in this arithmetic (nvsr_generic_fused_supported_arith: "
-                             "beyond its capacity, or not 'f32' / 'f16x2')")
-    if int(arith) == capi.ARITHMETIC["f16x2"]:
-        assert packed.numel() == capi.lib().nvsr_generic_packed_floats_ext(C.byref(geo), n_pos), "packed blob of another geometry"
-    out = _f(P, 4, like=x)
-    if P:
-        capi.call("nvsr_generic_decode_fused_arith_ext", C.byref(sc), C.byref(geo), capi.ptr(natural), capi.ptr(packed), P, capi.ptr(x),
-                  None if coord_noise is None else capi.ptr(coord_noise), capi.ptr(out), int(arith), capi.stream())
+    s = _generic_call(planes, consts, natural, geometry, align_corners, bicubic, x, coord_noise, "arith", arith, packed)
+    out = _f(s.P, 4, like=x)
+    if s.P:
+        capi.call("nvsr_generic_decode_fused_arith_ext", *s.head, capi.ptr(out), s.arith, capi.stream())
     return out
 
 
@@ -336,17 +363,19 @@ def _(planes, consts, natural, packed, geometry, x, align_corners=True, coord_no
     return x.new_empty((x.shape[0], 4))
 
 
-def _generic_phase_setup(planes, consts, natural, packed, geometry, x, align_corners, coord_noise, bicubic, arith):
-    """the checks the two phase operators share with triplane_decode_generic_fused_arith -> (geo, scene, coord_noise)"""
+def _generic_list_phase(entry, raw, planes, consts, natural, packed, geometry, x, index, count, align_corners, coord_noise, bicubic, arith, max_count):
+    """a phase of the fused kernel on the points x[index[i]], i < count, written IN PLACE into raw [P,4] (`entry`: the colour phase or the
+    listed density phase): the list's checks, the launch size n = max_count or min(len(index), P), the shared setup, the call"""
     P = x.shape[0]
-    coord_noise = None if coord_noise is None else _c(coord_noise)
-    geo, n_pos, _, sc = _generic_setup(planes, consts, natural, geometry, align_corners, coord_noise, P, bicubic)
-    if capi.lib().nvsr_generic_fused_supported_arith(C.byref(geo), n_pos, int(arith)) != 1:
-        raise capi.NvsrError("the fused generic kernel does not take this decoder geometry in this arithmetic (nvsr_generic_fused_supported_arith: "
-                             "beyond its capacity, or not 'f32' / 'f16x2')")
-    if int(arith) == capi.ARITHMETIC["f16x2"]:
-        assert packed.numel() == capi.lib().nvsr_generic_packed_floats_ext(C.byref(geo), n_pos), "packed blob of another geometry"
-    return geo, sc, coord_noise
+    capi.require_cuda(raw, index, count)
+    assert raw.dtype == torch.float32 and tuple(raw.shape) == (P, 4) and raw.is_contiguous(), "raw: contiguous [P,4] f32 (written in place)"
+    assert index.dtype == torch.int32 and index.dim() == 1 and index.is_contiguous(), "index: contiguous int32 [n]"
+    assert count.dtype == torch.int32 and count.numel() == 1, "count: int32 [1]"
+    n = min(index.numel(), P) if max_count < 0 else int(max_count)
+    assert n <= index.numel() and n <= P, "max_count: at most len(index) and P"
+    s = _generic_call(planes, consts, natural, geometry, align_corners, bicubic, x, coord_noise, "arith", arith, packed)
+    if n:
+        capi.call(entry, *s.head, capi.ptr(index), capi.ptr(count), n, capi.ptr(raw), s.arith, capi.stream())
 
 
 @custom_op("nvsr::triplane_density_generic_fused_arith", mutates_args=(), device_types="cuda")
@@ -356,13 +385,10 @@ def triplane_density_generic_fused_arith(planes: Sequence[Tensor], consts: Seque
     """the DENSITY phase of triplane_decode_generic_fused_arith (same arguments; `packed` is read in 'f16x2' only and may be empty otherwise):
     the density decoder on all P points -> raw [P,4] = [+0, +0, +0, sigma_raw] per row, sigma_raw with the one-launch operator's bits.  A
     compositor reads the tensor as it is; triplane_colour_generic_fused_arith completes it.  Evaluation only: no autograd."""
-    x, natural, packed = _c(x), _c(natural), _c(packed)
-    P = x.shape[0]
-    geo, sc, coord_noise = _generic_phase_setup(planes, consts, natural, packed, geometry, x, align_corners, coord_noise, bicubic, arith)
-    raw = _f(P, 4, like=x)
-    if P:
-        capi.call("nvsr_generic_decode_fused_density_arith_ext", C.byref(sc), C.byref(geo), capi.ptr(natural), capi.ptr(packed), P, capi.ptr(x),
-                  None if coord_noise is None else capi.ptr(coord_noise), capi.ptr(raw), int(arith), capi.stream())
+    s = _generic_call(planes, consts, natural, geometry, align_corners, bicubic, x, coord_noise, "arith", arith, packed)
+    raw = _f(s.P, 4, like=x)
+    if s.P:
+        capi.call("nvsr_generic_decode_fused_density_arith_ext", *s.head, capi.ptr(raw), s.arith, capi.stream())
     return raw
 
 
@@ -379,18 +405,8 @@ def triplane_colour_generic_fused_arith(raw: Tensor, planes: Sequence[Tensor], c
     operator's bits; column 3 and every other row of raw [P,4] stay as they are.  index: int32 [>= max_count] on the device, distinct, any
     order; count: int32 [1] on the device, read by the kernel (generic_live_list makes both; no host synchronisation); max_count: what the
     launch is sized for, -1 = min(len(index), P).  Entries of index at or beyond count are not read.  Evaluation only: no autograd."""
-    x, natural, packed = _c(x), _c(natural), _c(packed)
-    P = x.shape[0]
-    capi.require_cuda(raw, index, count)
-    assert raw.dtype == torch.float32 and tuple(raw.shape) == (P, 4) and raw.is_contiguous(), "raw: contiguous [P,4] f32 (written in place)"
-    assert index.dtype == torch.int32 and index.dim() == 1 and index.is_contiguous(), "index: contiguous int32 [n]"
-    assert count.dtype == torch.int32 and count.numel() == 1, "count: int32 [1]"
-    n = min(index.numel(), P) if max_count < 0 else int(max_count)
-    assert n <= index.numel() and n <= P, "max_count: at most len(index) and P"
-    geo, sc, coord_noise = _generic_phase_setup(planes, consts, natural, packed, geometry, x, align_corners, coord_noise, bicubic, arith)
-    if n:
-        capi.call("nvsr_generic_decode_fused_colour_arith_ext", C.byref(sc), C.byref(geo), capi.ptr(natural), capi.ptr(packed), P, capi.ptr(x),
-                  None if coord_noise is None else capi.ptr(coord_noise), capi.ptr(index), capi.ptr(count), n, capi.ptr(raw), int(arith), capi.stream())
+    _generic_list_phase("nvsr_generic_decode_fused_colour_arith_ext", raw, planes, consts, natural, packed, geometry, x, index, count, align_corners,
+                        coord_noise, bicubic, arith, max_count)
 
 
 @triplane_colour_generic_fused_arith.register_fake
@@ -427,20 +443,14 @@ def generic_occupancy_build(planes: Sequence[Tensor], consts: Sequence[float], n
     """occupancy_build for ANY decoder geometry the fused generic kernel holds: the same grid layout, probes, marks and dilation, with the
     density phase (triplane_density_generic_fused_arith, `arith` = 'f32' or 'f16x2'; `packed` is read in 'f16x2' only) as the decoder.
     -> int32 [ceil(G^3 / 32)]"""
-    natural, packed = _c(natural), _c(packed)
-    geo, n_pos, _, sc = _generic_setup(planes, consts, natural, geometry, align_corners, None, 0, bicubic)
-    if capi.lib().nvsr_generic_fused_supported_arith(C.byref(geo), n_pos, int(arith)) != 1:
-        raise capi.NvsrError("the fused generic kernel does not take this decoder geometry in this arithmetic (nvsr_generic_fused_supported_arith: "
-                             "beyond its capacity, or not 'f32' / 'f16x2'): no occupancy grid for it")
-    if int(arith) == capi.ARITHMETIC["f16x2"]:
-        assert packed.numel() == capi.lib().nvsr_generic_packed_floats_ext(C.byref(geo), n_pos), "packed blob of another geometry"
+    s = _generic_call(planes, consts, natural, geometry, align_corners, bicubic, capacity="occupancy", arith=arith, packed=packed)
     words = capi.lib().nvsr_occupancy_words(int(G))
     if words <= 0:
         raise capi.NvsrError("nvsr_generic_occupancy_build_ext failed: %s" % capi._STATUS[1])
     grid = torch.empty(words, dtype=torch.int32, device=natural.device)
     ws = _f(max(int(capi.lib().nvsr_occupancy_workspace_floats(int(G), int(K))), 4), like=natural)
-    capi.call("nvsr_generic_occupancy_build_ext", C.byref(sc), C.byref(geo), capi.ptr(natural), capi.ptr(packed), int(G), int(K), float(threshold),
-              int(dilate), int(arith), capi.ptr(grid), capi.ptr(ws), capi.stream())
+    capi.call("nvsr_generic_occupancy_build_ext", *s.head[:4], int(G), int(K), float(threshold), int(dilate), s.arith, capi.ptr(grid), capi.ptr(ws),
+              capi.stream())
     return grid
 
 
@@ -467,11 +477,8 @@ def generic_occupancy_keep(consts: Sequence[float], x: Tensor, grid: Tensor, G: 
         assert raw.dtype == torch.float32 and tuple(raw.shape) == (P, 4), "raw: [P,4] f32"
         out = raw.contiguous().clone()
     keep = _f(P, like=x)
-    sc = capi.SceneExt()
+    sc = _scene_box(capi.SceneExt(), consts)
     sc.num_position_planes = max((len(consts) - 10) // 6, 1)
-    for i in range(5):
-        sc.lo[i] = consts[i]
-        sc.range[i] = consts[5 + i]
     if P:
         capi.call("nvsr_generic_occupancy_keep", C.byref(sc), P, capi.ptr(x), capi.ptr(grid), int(G), capi.ptr(keep), capi.ptr(out), capi.stream())
     return keep, out
@@ -489,23 +496,22 @@ def triplane_density_list_generic_fused_arith(raw: Tensor, planes: Sequence[Tens
     """the DENSITY phase on the points x[index[i]], i < count: the row [+0, +0, +0, sigma_raw] written IN PLACE into raw[index[i]], sigma_raw
     with the one-launch operator's bits; every other row of raw [P,4] stays as it is.  index, count, max_count: as for
     triplane_colour_generic_fused_arith (the kept list of generic_occupancy_keep through generic_live_list).  Evaluation only: no autograd."""
-    x, natural, packed = _c(x), _c(natural), _c(packed)
-    P = x.shape[0]
-    capi.require_cuda(raw, index, count)
-    assert raw.dtype == torch.float32 and tuple(raw.shape) == (P, 4) and raw.is_contiguous(), "raw: contiguous [P,4] f32 (written in place)"
-    assert index.dtype == torch.int32 and index.dim() == 1 and index.is_contiguous(), "index: contiguous int32 [n]"
-    assert count.dtype == torch.int32 and count.numel() == 1, "count: int32 [1]"
-    n = min(index.numel(), P) if max_count < 0 else int(max_count)
-    assert n <= index.numel() and n <= P, "max_count: at most len(index) and P"
-    geo, sc, coord_noise = _generic_phase_setup(planes, consts, natural, packed, geometry, x, align_corners, coord_noise, bicubic, arith)
-    if n:
-        capi.call("nvsr_generic_decode_fused_density_list_arith_ext", C.byref(sc), C.byref(geo), capi.ptr(natural), capi.ptr(packed), P, capi.ptr(x),
-                  None if coord_noise is None else capi.ptr(coord_noise), capi.ptr(index), capi.ptr(count), n, capi.ptr(raw), int(arith), capi.stream())
+    _generic_list_phase("nvsr_generic_decode_fused_density_list_arith_ext", raw, planes, consts, natural, packed, geometry, x, index, count,
+                        align_corners, coord_noise, bicubic, arith, max_count)
 
 
 @triplane_density_list_generic_fused_arith.register_fake
 def _(raw, planes, consts, natural, packed, geometry, x, index, count, align_corners=True, coord_noise=None, bicubic=False, arith=0, max_count=-1):
     return None
+
+
+def _gradient_planes(planes, want):
+    """the plane gradients of a generic backward: zeros like the plane where wanted, an empty tensor where not -> (the tensors, their pointers
+    as the C entry's float* const* with NULL for a plane that is not wanted, whether any is wanted)"""
+    want = [bool(w) for w in want]
+    assert len(want) == len(planes)
+    g_pl = [torch.zeros_like(pl) if w else _f(0, like=pl) for pl, w in zip(planes, want)]
+    return g_pl, (C.c_void_p * len(planes))(*[g.data_ptr() if w else None for g, w in zip(g_pl, want)]), any(want)
 
 
 @custom_op("nvsr::triplane_decode_generic_backward", mutates_args=(), device_types="cuda")
@@ -514,21 +520,13 @@ def triplane_decode_generic_backward(planes: Sequence[Tensor], consts: Sequence[
                                      coord_noise: Optional[Tensor] = None, bicubic: bool = False) -> List[Tensor]:
     """Backward of triplane_decode_generic (csrc/generic.hip; the reference: torch.autograd through models.py:381-421): g_out [P,4] ->
     [d_natural, d_plane0 .. d_planeN] (channel-last like the planes; a gradient that is not wanted comes back as an empty tensor)."""
-    x, natural, g_out = _c(x), _c(natural), _c(g_out)
-    P = x.shape[0]
-    coord_noise = None if coord_noise is None else _c(coord_noise)
-    geo, n_pos, n, sc = _generic_setup(planes, consts, natural, geometry, align_corners, coord_noise, P, bicubic)
-    assert tuple(g_out.shape) == (P, 4)
-    want_planes = [bool(w) for w in want_planes]
-    assert len(want_planes) == n_pos + 1
-    g_nat = torch.zeros(n if want_natural else 0, dtype=torch.float32, device=x.device)
-    g_pl = [torch.zeros_like(pl) if w else _f(0, like=x) for pl, w in zip(planes, want_planes)]
-    if P and (want_natural or any(want_planes)):
-        ws = _f(capi.lib().nvsr_generic_decode_backward_workspace_floats_ext(C.byref(geo), n_pos, P), like=x)
-        d_planes = (C.c_void_p * (n_pos + 1))(*[g.data_ptr() if w else None for g, w in zip(g_pl, want_planes)])
-        capi.call("nvsr_generic_decode_backward_ext", C.byref(sc), C.byref(geo), capi.ptr(natural), P, capi.ptr(x),
-                  None if coord_noise is None else capi.ptr(coord_noise), capi.ptr(g_out), capi.ptr(g_nat) if want_natural else None, d_planes,
-                  capi.ptr(ws), capi.stream())
+    s = _generic_call(planes, consts, natural, geometry, align_corners, bicubic, x, coord_noise, grad=g_out)
+    g_pl, d_planes, any_plane = _gradient_planes(planes, want_planes)
+    g_nat = torch.zeros(s.n if want_natural else 0, dtype=torch.float32, device=x.device)
+    if s.P and (want_natural or any_plane):
+        ws = _f(capi.lib().nvsr_generic_decode_backward_workspace_floats_ext(C.byref(s.geo), s.n_pos, s.P), like=x)
+        capi.call("nvsr_generic_decode_backward_ext", *s.head, capi.ptr(s.grad), capi.ptr(g_nat) if want_natural else None, d_planes, capi.ptr(ws),
+                  capi.stream())
     return [g_nat] + g_pl
 
 
@@ -546,22 +544,10 @@ def triplane_decode_generic_fused_backward(planes: Sequence[Tensor], consts: Seq
     like the planes; a gradient that is not wanted comes back as an empty tensor and costs no atomics.  No workspace.  Raises for a geometry
     beyond the kernel's capacity (nvsr_generic_backward_fused_supported, include/nvsr.h) -- TwoDimPlanesModel.generic_train_route() picks the
     operator; triplane_decode_generic_backward runs every geometry, and the decoder's gradients, layer by layer."""
-    x, natural, d_out = _c(x), _c(natural), _c(d_out)
-    P = x.shape[0]
-    coord_noise = None if coord_noise is None else _c(coord_noise)
-    geo, n_pos, _, sc = _generic_setup(planes, consts, natural, geometry, align_corners, coord_noise, P, bicubic)
-    if capi.lib().nvsr_generic_backward_fused_supported(C.byref(geo), n_pos) != 1:
-        raise capi.NvsrError("this decoder geometry is beyond the fused generic backward's capacity (nvsr_generic_backward_fused_supported); "
-                             "torch.ops.nvsr.triplane_decode_generic_backward runs it layer by layer")
-    assert tuple(d_out.shape) == (P, 4) and d_out.dtype == torch.float32
-    capi.require_cuda(d_out)
-    need_planes = [bool(w) for w in need_planes]
-    assert len(need_planes) == n_pos + 1
-    g_pl = [torch.zeros_like(pl) if w else _f(0, like=x) for pl, w in zip(planes, need_planes)]
-    if P and any(need_planes):
-        d_planes = (C.c_void_p * (n_pos + 1))(*[g.data_ptr() if w else None for g, w in zip(g_pl, need_planes)])
-        capi.call("nvsr_generic_decode_backward_fused_ext", C.byref(sc), C.byref(geo), capi.ptr(natural), P, capi.ptr(x),
-                  None if coord_noise is None else capi.ptr(coord_noise), capi.ptr(d_out), d_planes, capi.stream())
+    s = _generic_call(planes, consts, natural, geometry, align_corners, bicubic, x, coord_noise, "backward", grad=d_out)
+    g_pl, d_planes, any_plane = _gradient_planes(planes, need_planes)
+    if s.P and any_plane:
+        capi.call("nvsr_generic_decode_backward_fused_ext", *s.head, capi.ptr(s.grad), d_planes, capi.stream())
     return g_pl
 
 

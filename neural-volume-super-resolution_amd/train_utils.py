@@ -436,7 +436,7 @@ def _generic_occupancy(model, noise, jit):
     the current scene that is not stale (model.occupancy_entry).  A model for which nobody built a grid is asked nothing else."""
     if torch.is_grad_enabled() or noise is not None or jit is not None or not model.__dict__.get("_occupancy"):
         return None
-    if os.environ.get("NVSR_GENERIC_TWO_PHASE", "") == "0" or model.is_native_geometry() or model.jitter_std() or model.generic_route() != "fused":
+    if not model.generic_phases_allowed():
         return None
     return model.occupancy_entry(model.cur_id)
 
