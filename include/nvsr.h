@@ -825,7 +825,7 @@ int nvsr_generic_decode_backward_fused_ext(const nvsr_scene_ext* scene, const nv
  * lo = RN_f16(v - hi)), the products Wh xl, Wh xh, Wl xh on v_mfma_f32_32x32x16_f16 per 16-column K-block of [X1 | X2] in ascending order, f32
  * accumulation, act = relu(fma(acc, 2^-12, b)) with a ReLU that keeps NaN.  The input features, the biases, both heads (on the f32 activations,
  * from the natural blob) and the outputs are f32 and computed exactly as by nvsr_generic_decode_fused_ext.  BY NAME only: there is no process
- * default here, and no backward in this arithmetic (training runs in exact f32: the layered route, or the fused plane gradients below).
+ * default here.  Its backward for a frozen decoder is nvsr_generic_decode_backward_fused_arith_ext below; decoder-weight gradients stay exact f32.
  * Range contract: F16X2's -- |W| < 255 for the hidden matrices, |feature / activation| < 4094; beyond them the outputs that depend on the
  * operand are NaN, never a finite wrong number, and a NaN in the planes, the points or the weights comes out as NaN.  A launch that writes a
  * non-finite out row ORs 1 into the range flag (nvsr_set_range_flag), wherever the NaN came from.
@@ -850,6 +850,42 @@ int nvsr_generic_fused_supported_arith(const nvsr_decoder_geometry* geometry, in
 int nvsr_generic_decode_fused_arith_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural,
                                         const float* packed, int64_t P, const float* x, const float* coord_noise, float* out, int arith,
                                         nvsr_stream_t stream);
+/* ---- generic decoder, fused plane gradients in NVSR_ARITH_F16X2 (csrc/generic_fused_bwd_limb.hip) ------------------------------------------
+ * nvsr_generic_decode_backward_fused_ext with the HIDDEN layers in two f16 limbs, forward and transposed, in ONE launch: the backward of
+ * nvsr_generic_decode_fused_arith_ext(NVSR_ARITH_F16X2) for an iteration in which the decoder's parameters take NO gradient.  BY NAME only.
+ * The kernel recomputes the forward exactly as that launch does (the same packed blob, the same operand order): the gate bits (output > 0; NaN
+ * and 0 closed) belong to the activations the forward produced.  The heads' data gradients from d_out are exact f32 from the natural blob.
+ * A transposed hidden layer: dX[p][k] = sum_m dZ[p][m] W[m][k] over the 16-row blocks of the output index m in ascending order on
+ * v_mfma_f32_32x32x16_f16, f32 accumulation, per block the products Wh zl, Wh zh, Wl zh.  w^ = limbs of 2^8 W (the transposed blob below);
+ * z^ = limbs of 2^e dZ[p][.] with ONE exact power of two per point and layer: e puts the largest |dZ[p][m]| of the gated row into [2^14, 2^15)
+ * (a zero row: e = 0 and exact zeros); dX = acc 2^(-8 - e).  Multiplying a point's cotangent by 2^k multiplies its gradients by 2^k bit for bit
+ * (but for underflow).  The additions of a skip layer's part and layer 0's part into the decoder inputs' gradients, the view plane, the
+ * combination rules, the taps and the one atomic per (tap, channel) are nvsr_generic_decode_backward_fused_ext's own code.
+ * Range contract: |W| < 255 for the hidden matrices and the forward's |feature / activation| < 4094; a row of dZ that holds an inf or a NaN, or
+ * a weight beyond the range, gives NaN gradients -- never a finite wrong number -- and the launch ORs 1 into the range flag
+ * (nvsr_set_range_flag).  The cotangent's magnitude is free: 1e30 and 1e-30 are scaled exactly.
+ * Transposed blob (nvsr_pack_generic_decoder_bwd_ext, one kernel, one thread per word; nvsr_generic_packed_bwd_floats_ext 32-bit words, or the
+ * negated status for a geometry that nvsr_generic_decoder_natural_floats_ext refuses): every hidden layer in state-dict order -- the density
+ * layers, then the rgb layers.  A layer holds its column part [0, K1) (K1 = the decoder's input width for layer 0, hidden otherwise) and, if a
+ * skip layer, the part [K1, K1 + K2) behind it; a part of `cols` columns starting at column c0 holds MB = ceil(hidden / 16) x TT = ceil(cols / 32)
+ * x 2 fragments of 256 words, ordered [mb][t][limb].  Word 4 lane + j (j = 0 .. 3) of lane (k = lane & 31, h = lane >> 5) holds the f16
+ * W~[16 mb + 8 h + 2 j][c0 + 32 t + k] in its low half and W~[16 mb + 8 h + 2 j + 1][c0 + 32 t + k] in its high half, W~ = 2^8 W and +0 beyond
+ * row hidden and beyond the part's columns; limb 0 = RN_f16(W~), limb 1 = RN_f16(W~ - limb 0).  A lane's A operand of one MFMA is 16 contiguous
+ * bytes.  tests/generic_train_limb_ref.py restates the layout and the arithmetic in numpy.
+ * Capacity: nvsr_generic_fused_supported_arith(NVSR_ARITH_F16X2)'s limits and the row = Kr + Kd (each rounded up to 4 floats) + hidden (rounded
+ * up to 16) + 4 + (density_layers + rgb_layers) x ceil(hidden / 32), rounded up to 4 x an odd number, 32 of which fit in 160 KB.
+ * nvsr_generic_backward_fused_supported_arith (host only): NVSR_ARITH_F32 answers nvsr_generic_backward_fused_supported, NVSR_ARITH_F16X2 this
+ * capacity (1 / 0), any other arithmetic 0; the negated status for an inconsistent geometry.
+ * nvsr_generic_decode_backward_fused_arith_ext: NVSR_ARITH_F32 forwards to nvsr_generic_decode_backward_fused_ext (`packed`, `packed_bwd` may be
+ * NULL); NVSR_ARITH_F16X2 launches the limb kernel (NVSR_ERR_NULL without natural, packed, packed_bwd, x or d_out; NVSR_ERR_SHAPE beyond the
+ * capacity); every other arithmetic: NVSR_ERR_SHAPE.  d_planes, P == 0 and "no plane wanted" as nvsr_generic_decode_backward_fused_ext. */
+int nvsr_generic_backward_fused_supported_arith(const nvsr_decoder_geometry* geometry, int num_position_planes, int arith);
+int64_t nvsr_generic_packed_bwd_floats_ext(const nvsr_decoder_geometry* geometry, int num_position_planes);
+int nvsr_pack_generic_decoder_bwd_ext(const nvsr_decoder_geometry* geometry, int num_position_planes, const float* natural, float* packed_bwd,
+                                      nvsr_stream_t stream);
+int nvsr_generic_decode_backward_fused_arith_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural,
+                                                 const float* packed, const float* packed_bwd, int64_t P, const float* x, const float* coord_noise,
+                                                 const float* d_out, float* const* d_planes, int arith, nvsr_stream_t stream);
 /* ---- generic decoder, fused evaluation in two phases (csrc/generic_fused.hip, csrc/generic_fused_limb.hip, csrc/generic_live.hip) --------
  * The launch above split at the decoders, for a frame that runs the colour decoder on the samples of nonzero weight only: the density
  * phase on every point, the compositing weights, their live list, the colour phase on the listed points.  Both phases are the one-launch

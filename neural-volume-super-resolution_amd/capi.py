@@ -192,6 +192,12 @@ _PROTOS_OPTIONAL = {   # feature-plane super-resolution (csrc/sr.hip)
     "nvsr_generic_backward_fused_supported": ([C.POINTER(DecoderGeometry), _i], _i),
     "nvsr_generic_decode_backward_fused_ext": ([C.POINTER(SceneExt), C.POINTER(DecoderGeometry), _vp, _i64, _vp, _vp, _vp, C.POINTER(C.c_void_p),
                                                 _vp], _i),
+    # ... and that launch with the hidden layers in two f16 limbs, from a second, transposed blob (csrc/generic_fused_bwd_limb.hip)
+    "nvsr_generic_backward_fused_supported_arith": ([C.POINTER(DecoderGeometry), _i, _i], _i),
+    "nvsr_generic_packed_bwd_floats_ext": ([C.POINTER(DecoderGeometry), _i], _i64),
+    "nvsr_pack_generic_decoder_bwd_ext": ([C.POINTER(DecoderGeometry), _i, _vp, _vp, _vp], _i),
+    "nvsr_generic_decode_backward_fused_arith_ext": ([C.POINTER(SceneExt), C.POINTER(DecoderGeometry), _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                                      C.POINTER(C.c_void_p), _i, _vp], _i),
     "nvsr_ray_points": ([_i64, _i, _vp, _vp, _vp, _vp], _i),
     "nvsr_render_shared_workspace_floats": ([_i64, _i, _i], _i64),
     "nvsr_render_rays_shared_arith": ([C.POINTER(Scene), _vp, _i64, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp], _i),

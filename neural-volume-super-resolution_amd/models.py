@@ -263,6 +263,8 @@ class TwoDimPlanesModel(nn.Module):
         # (capi.set_decoder_arithmetic / NVSR_DECODER_ARITHMETIC).  Passed to every kernel launch explicitly; a training forward stores
         # the mode it ran in and its backward uses that one.
         self.arithmetic = None
+        # arithmetic of a generic geometry's planes-only TRAINING: 'f16x2' BY NAME (generic_train_arithmetic()); None and anything else: exact f32
+        self.train_arithmetic = None
 
     # ---- reference protocol ------------------------------------------------------------------------------------------
     def is_skip_layer(self, layer_num):
@@ -690,11 +692,13 @@ class TwoDimPlanesModel(nn.Module):
 
     def _generic_held(self, *kinds):
         """do the fused kernels hold this geometry -- 'f32' (nvsr_generic_fused_supported), 'f16x2' (nvsr_generic_fused_supported_arith),
-        'backward' (nvsr_generic_backward_fused_supported), every one of `kinds`?  Host code: no GPU is touched."""
+        'backward' (nvsr_generic_backward_fused_supported), 'backward_f16x2' (nvsr_generic_backward_fused_supported_arith), every one of
+        `kinds`?  Host code: no GPU is touched."""
         geo, n_pos, lib = C.byref(capi.DecoderGeometry(*[int(v) for v in self.generic_geometry()])), int(self.num_density_planes), capi.lib()
         ask = {"f32": lambda: lib.nvsr_generic_fused_supported(geo, n_pos),
                "f16x2": lambda: lib.nvsr_generic_fused_supported_arith(geo, n_pos, capi.ARITHMETIC["f16x2"]),
-               "backward": lambda: lib.nvsr_generic_backward_fused_supported(geo, n_pos)}
+               "backward": lambda: lib.nvsr_generic_backward_fused_supported(geo, n_pos),
+               "backward_f16x2": lambda: lib.nvsr_generic_backward_fused_supported_arith(geo, n_pos, capi.ARITHMETIC["f16x2"])}
         return all(ask[kind]() == 1 for kind in kinds)
 
     def generic_route(self):
@@ -739,6 +743,33 @@ class TwoDimPlanesModel(nn.Module):
             return "layered"
         return "fused" if self._generic_held("f32", "backward") else "layered"
 
+    # dec_channels (lowest, highest) at which planes-only training in 'f16x2' (generic_train_arithmetic) is taken without
+    # NVSR_GENERIC_TRAIN_FUSED=1 once train_arithmetic names it: the widths at which it was measured faster than the better f32 route of the
+    # parent commit by more than the larger spread, in both timed shapes (tools/generic_train_limb_time.py -> profiles/generic_train_limb_ab.txt;
+    # DESIGN 3.10 has the table).  None: nowhere, the route needs the handle.  Measured at 64 ('avg' / 'concat_pos'), 128 ('sum') and 256
+    # ('concat' over 4 planes): 1.52 / 1.92 / 1.09 x per forward + backward of 2^19 points, 1.40 / 1.32 / 1.12 x per iteration of 4 096 rays,
+    # every difference (3.4 ... 9.1 ms) above the spread (<= 0.19 ms).  Narrower and wider decoders were not measured: there the route needs the handle.
+    GENERIC_TRAIN_LIMB_DEFAULT_HIDDEN = (64, 256)
+
+    def generic_train_arithmetic(self):
+        """'f16x2' or 'f32': the arithmetic in which a forward through the generic kernels that RECORDS A GRAPH trains if called now.  'f16x2' =
+        the forward launch on two f16 limbs (torch.ops.nvsr.triplane_decode_generic_fused_arith) and the planes' gradients in one launch on two
+        f16 limbs (csrc/generic_fused_bwd_limb.hip, torch.ops.nvsr.triplane_decode_generic_fused_backward_arith).  It is taken exactly when
+        model.train_arithmetic is 'f16x2' BY NAME (model.arithmetic, the process default and NVSR_DECODER_ARITHMETIC never select it), a graph is
+        being recorded, NO decoder parameter requires a gradient, the deterministic mode is off, NVSR_GENERIC_TRAIN_FUSED is not 0, both limb
+        kernels hold the geometry (nvsr_generic_fused_supported_arith, nvsr_generic_backward_fused_supported_arith) and
+        NVSR_GENERIC_TRAIN_FUSED is 1 or dec_channels lies in GENERIC_TRAIN_LIMB_DEFAULT_HIDDEN.  'f32': what generic_train_route() says --
+        training with decoder gradients stays exact f32 on the layered route.  The decision touches no GPU and changes no other predicate."""
+        if not (isinstance(self.train_arithmetic, str) and self.train_arithmetic == "f16x2"):
+            return "f32"
+        handle = self._generic_handle("NVSR_GENERIC_TRAIN_FUSED")
+        if handle == "0" or not torch.is_grad_enabled() or capi.deterministic():
+            return "f32"
+        dec, _, graph = self._generic_graph()
+        if dec or not graph or (handle != "1" and not self._generic_width_in(self.GENERIC_TRAIN_LIMB_DEFAULT_HIDDEN)):
+            return "f32"
+        return "f16x2" if self._generic_held("f16x2", "backward_f16x2") else "f32"
+
     # dec_channels (lowest, highest) at which the fused route in 'f16x2' was measured faster, by more than the spread of the alternations, than
     # the better of the two f32 routes: 1.28 - 1.54 x on 2^22 points, 1.39 - 1.69 x on a 400 x 400 frame at 64, 128 and 256
     # (profiles/generic_limb_ab.txt).  Narrower decoders were not measured: there the arithmetic needs NVSR_GENERIC_FUSED=1.  None: nowhere.
@@ -774,6 +805,19 @@ class TwoDimPlanesModel(nn.Module):
             self.__dict__["_packed_generic_cache"] = cache
         return cache[1]
 
+    def packed_generic_decoder_bwd(self):
+        """the hidden layers' TRANSPOSED f16-limb fragments for generic_train_arithmetic() == 'f16x2' (nvsr_pack_generic_decoder_bwd_ext), cached
+        like packed_generic_decoder()"""
+        params = self.decoder_parameters()
+        key = tuple((p.data_ptr(), p._version) for p in params)
+        cache = self.__dict__.get("_packed_generic_bwd_cache")
+        if cache is None or cache[0] != key:
+            nat = self.natural_blob()
+            capi.require_cuda(nat)
+            cache = (key, torch.ops.nvsr.pack_generic_decoder_bwd(nat, self.generic_geometry(), int(self.num_density_planes)))
+            self.__dict__["_packed_generic_bwd_cache"] = cache
+        return cache[1]
+
     def _generic_forward(self, x, coord_noise=None):
         """forward through the generic kernels (any geometry); in training mode with gradients for the planes and the decoder.
         coord_noise [P,3]: the jitter of the normalised sample positions (models.py:291-293) when the caller has drawn it (run_one_iter_of_nerf
@@ -797,6 +841,8 @@ class TwoDimPlanesModel(nn.Module):
                     planes = self.training_planes(None, normalized_points=n if coord_noise is None else n + coord_noise)
                 else:
                     planes = [self.raw_plane(n) for n in names]
+                if self.generic_train_arithmetic() == "f16x2":
+                    return _GenericFusedLimbTrainFn.apply(self, x, coord_noise, *planes)
                 if self.generic_train_route() == "fused":
                     return _GenericFusedTrainFn.apply(self, x, coord_noise, *planes)
                 return _GenericDecodeFn.apply(self, x, self.natural_blob(differentiable=True) if dec else None, coord_noise, *planes)
@@ -1046,7 +1092,7 @@ class _DecodePointsFn(torch.autograd.Function):
 
 
 def _generic_forward_state(ctx, model, x, nat, coord_noise, plane_srcs):
-    """what the forwards of the two generic autograd functions share: the refusal in the deterministic mode (before any launch), the
+    """what the forwards of the three generic autograd functions share: the refusal in the deterministic mode (before any launch), the
     channel-last planes and the scene constants, the natural blob (nat, or the model's where the decoder does not train) -> the arguments of the
     forward operator, kept as ctx.state for the backward"""
     if capi.deterministic():
@@ -1100,6 +1146,33 @@ class _GenericFusedTrainFn(torch.autograd.Function):
             return (None,) * len(need)
         g = torch.ops.nvsr.triplane_decode_generic_fused_backward(planes_cl, consts, natural, geometry, x, capi.f32c(g_out), need_planes, align,
                                                                   coord_noise, bicubic)
+        return (None, None, None) + tuple(from_channel_last(gp, like=p_) if n else None for gp, p_, n in zip(g, ctx.plane_srcs, need_planes))
+
+
+class _GenericFusedLimbTrainFn(torch.autograd.Function):
+    """_GenericFusedTrainFn in 'f16x2' (TwoDimPlanesModel.generic_train_arithmetic() == 'f16x2'): the forward is
+    torch.ops.nvsr.triplane_decode_generic_fused_arith on the packed blob -- the limb evaluation kernel's bits, under its range contract: nothing
+    is rendered again, the range flag reaches the iteration's metrics (TrainStep._range_word) -- and the backward
+    torch.ops.nvsr.triplane_decode_generic_fused_backward_arith (csrc/generic_fused_bwd_limb.hip: the planes' gradients in one launch on two f16
+    limbs).  inputs: model, x, jitter (None = none), then the planes of the scene."""
+
+    @staticmethod
+    def forward(ctx, model, x, coord_noise, *plane_srcs):
+        planes_cl, consts, natural, geometry, x, align, coord_noise, bicubic = _generic_forward_state(ctx, model, x, None, coord_noise, plane_srcs)
+        ctx.blobs = (model.packed_generic_decoder(), model.packed_generic_decoder_bwd())
+        return torch.ops.nvsr.triplane_decode_generic_fused_arith(planes_cl, consts, natural, ctx.blobs[0], geometry, x, align, coord_noise, bicubic,
+                                                                  capi.ARITHMETIC["f16x2"])
+
+    @staticmethod
+    def backward(ctx, g_out):
+        planes_cl, consts, natural, geometry, x, align, coord_noise, bicubic = ctx.state
+        need = ctx.needs_input_grad
+        need_planes = [bool(n) for n in need[3:]]
+        if not any(need_planes):
+            return (None,) * len(need)
+        g = torch.ops.nvsr.triplane_decode_generic_fused_backward_arith(planes_cl, consts, natural, ctx.blobs[0], ctx.blobs[1], geometry, x,
+                                                                        capi.f32c(g_out), need_planes, align, coord_noise, bicubic,
+                                                                        capi.ARITHMETIC["f16x2"])
         return (None, None, None) + tuple(from_channel_last(gp, like=p_) if n else None for gp, p_, n in zip(g, ctx.plane_srcs, need_planes))
 
 

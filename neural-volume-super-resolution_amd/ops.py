@@ -257,18 +257,22 @@ _GENERIC_CAPACITY = {
     "occupancy": ("nvsr_generic_fused_supported_arith", True, _ARITH_CAPACITY + ": no occupancy grid for it"),
     "backward": ("nvsr_generic_backward_fused_supported", False, "this decoder geometry is beyond the fused generic backward's capacity "
                  "(nvsr_generic_backward_fused_supported); torch.ops.nvsr.triplane_decode_generic_backward runs it layer by layer"),
+    "backward_arith": ("nvsr_generic_backward_fused_supported_arith", True, "the fused generic backward does not take this decoder geometry in this "
+                       "arithmetic (nvsr_generic_backward_fused_supported_arith: beyond its capacity, or not 'f32' / 'f16x2'); "
+                       "torch.ops.nvsr.triplane_decode_generic_backward runs every geometry layer by layer"),
 }
 
 
 def _generic_call(planes, consts, natural, geometry, align_corners, bicubic, x=None, coord_noise=None, capacity=None, arith=0, packed=None,
-                  grad=None):
+                  grad=None, packed_bwd=None):
     """The paragraph every generic operator opens with.  Makes natural, x [P,6], coord_noise [P,3], packed and grad (g_out / d_out [P,4]) f32 and
     contiguous -- the kernels take dense row-major buffers, and a view must never reach them; _generic_setup; then the `capacity` the operator
     needs (None: every geometry runs; 'fused': the f32 kernel; 'arith' / 'occupancy': the forward kernel in `arith`; 'backward': the fused
-    backward) and, in 'f16x2', the packed size.
+    backward; 'backward_arith': the fused backward in `arith`) and, in 'f16x2', the packed size (and the transposed blob's, packed_bwd).
     -> a namespace that holds the contiguous tensors until the call is made: geo, n_pos, n (floats of natural), sc, P, grad, arith and head =
-    the arguments (scene, geometry, natural[, packed in the arith entries], P, x, coord_noise or NULL) every decode entry starts with."""
-    s = SimpleNamespace(natural=_c(natural), x=_c(x), packed=_c(packed), grad=_c(grad), coord_noise=_c(coord_noise), arith=int(arith))
+    the arguments (scene, geometry, natural[, packed in the arith entries][, packed_bwd], P, x, coord_noise or NULL) every decode entry starts with."""
+    s = SimpleNamespace(natural=_c(natural), x=_c(x), packed=_c(packed), grad=_c(grad), coord_noise=_c(coord_noise), arith=int(arith),
+                        packed_bwd=_c(packed_bwd))
     s.P = 0 if x is None else s.x.shape[0]
     s.geo, s.n_pos, s.n, s.sc = _generic_setup(planes, consts, s.natural, geometry, align_corners, s.coord_noise, s.P, bicubic)
     assert s.grad is None or tuple(s.grad.shape) == (s.P, 4), "the output's gradient: [P,4]"
@@ -279,8 +283,10 @@ def _generic_call(planes, consts, natural, geometry, align_corners, bicubic, x=N
             raise capi.NvsrError(message)
         if by_arith and s.arith == capi.ARITHMETIC["f16x2"]:
             assert s.packed.numel() == lib.nvsr_generic_packed_floats_ext(geo, s.n_pos), "packed blob of another geometry"
-    s.head = (C.byref(s.sc), geo, capi.ptr(s.natural)) + ((capi.ptr(s.packed),) if packed is not None else ()) + (s.P, capi.ptr(s.x),
-                                                                                                                 capi.ptr(s.coord_noise))
+            assert packed_bwd is None or s.packed_bwd.numel() == lib.nvsr_generic_packed_bwd_floats_ext(geo, s.n_pos), \
+                "transposed packed blob of another geometry"
+    s.head = (C.byref(s.sc), geo, capi.ptr(s.natural)) + ((capi.ptr(s.packed),) if packed is not None else ()) + \
+             ((capi.ptr(s.packed_bwd),) if packed_bwd is not None else ()) + (s.P, capi.ptr(s.x), capi.ptr(s.coord_noise))
     return s
 
 
@@ -553,6 +559,46 @@ def triplane_decode_generic_fused_backward(planes: Sequence[Tensor], consts: Seq
 
 @triplane_decode_generic_fused_backward.register_fake
 def _(planes, consts, natural, geometry, x, d_out, need_planes, align_corners=True, coord_noise=None, bicubic=False):
+    return [pl.new_empty(pl.shape if w else (0,)) for pl, w in zip(planes, need_planes)]
+
+
+@custom_op("nvsr::pack_generic_decoder_bwd", mutates_args=(), device_types="cuda")
+def pack_generic_decoder_bwd(natural: Tensor, geometry: Sequence[int], n_pos: int) -> Tensor:
+    """the hidden layers of a generic geometry's natural blob -> the TRANSPOSED f16-limb fragments of the fused backward in 'f16x2'
+    (csrc/generic_fused_bwd_limb.hip; include/nvsr.h has the layout).  No autograd: the decoder is frozen where this blob is read."""
+    nat = capi.f32c(natural)
+    geo, _ = _generic_geometry(geometry, n_pos, nat)
+    packed = _f(capi.lib().nvsr_generic_packed_bwd_floats_ext(C.byref(geo), int(n_pos)), like=nat)
+    capi.call("nvsr_pack_generic_decoder_bwd_ext", C.byref(geo), int(n_pos), capi.ptr(nat), capi.ptr(packed), capi.stream())
+    return packed
+
+
+@pack_generic_decoder_bwd.register_fake
+def _(natural, geometry, n_pos):
+    geo, _ = _generic_geometry(geometry, n_pos, natural)
+    return natural.new_empty((capi.lib().nvsr_generic_packed_bwd_floats_ext(C.byref(geo), int(n_pos)),), dtype=torch.float32)
+
+
+@custom_op("nvsr::triplane_decode_generic_fused_backward_arith", mutates_args=(), device_types="cuda")
+def triplane_decode_generic_fused_backward_arith(planes: Sequence[Tensor], consts: Sequence[float], natural: Tensor, packed: Tensor, packed_bwd: Tensor,
+                                                 geometry: Sequence[int], x: Tensor, d_out: Tensor, need_planes: Sequence[bool],
+                                                 align_corners: bool = True, coord_noise: Optional[Tensor] = None, bicubic: bool = False,
+                                                 arith: int = 2) -> List[Tensor]:
+    """triplane_decode_generic_fused_backward with the arithmetic of the hidden layers as an argument: capi.ARITHMETIC['f16x2'] is the backward of
+    triplane_decode_generic_fused_arith in 'f16x2' -- the forward recomputed in two f16 limbs from `packed`, the transposed layers in two f16
+    limbs from `packed_bwd` (pack_generic_decoder_bwd of the same natural blob) under one exact power-of-two scale per point and layer
+    (csrc/generic_fused_bwd_limb.hip); capi.ARITHMETIC['f32'] is triplane_decode_generic_fused_backward (the blobs are not read).  Every other
+    code raises: the mode is chosen by name.  Beyond f16x2's ranges, or with a non-finite cotangent, the gradients are NaN and the range flag
+    (capi.range_flag) is raised."""
+    s = _generic_call(planes, consts, natural, geometry, align_corners, bicubic, x, coord_noise, "backward_arith", arith, packed, d_out, packed_bwd)
+    g_pl, d_planes, any_plane = _gradient_planes(planes, need_planes)
+    if s.P and any_plane:
+        capi.call("nvsr_generic_decode_backward_fused_arith_ext", *s.head, capi.ptr(s.grad), d_planes, s.arith, capi.stream())
+    return g_pl
+
+
+@triplane_decode_generic_fused_backward_arith.register_fake
+def _(planes, consts, natural, packed, packed_bwd, geometry, x, d_out, need_planes, align_corners=True, coord_noise=None, bicubic=False, arith=2):
     return [pl.new_empty(pl.shape if w else (0,)) for pl, w in zip(planes, need_planes)]
 
 
@@ -1792,7 +1838,8 @@ lowrank_planes.register_autograd(_lowrank_bwd, setup_context=_lowrank_setup)
 
 
 FORWARD_OPS = ["plane_to_channel_last", "plane_from_channel_last", "pack_decoder", "coarse_z", "importance_resample", "triplane_decode",
-               "triplane_decode_generic", "triplane_decode_generic_fused", "pack_generic_decoder", "triplane_decode_generic_fused_arith", "ray_points", "lowrank_planes",
+               "triplane_decode_generic", "triplane_decode_generic_fused", "pack_generic_decoder", "triplane_decode_generic_fused_arith",
+               "pack_generic_decoder_bwd", "ray_points", "lowrank_planes",
                "triplane_density_generic_fused_arith", "triplane_colour_generic_fused_arith", "generic_live_list",
                "generic_occupancy_build", "generic_occupancy_keep", "triplane_density_list_generic_fused_arith",
                "render_pass", "render_rays", "decode_rays", "composite", "composite_rays", "edsr", "planes_sr", "cumprod_exclusive"]

@@ -44,6 +44,8 @@ BENCHMARKED = [
     "generic_occupancy_keep_kernel",
     # ... and their planes-only training (tools/generic_train_time.py times it): <NT, LDS floats>
     "generic_backward_fused_kernel",
+    # ... and that training in 'f16x2' by name (tools/generic_train_limb_time.py times it): <NT, LDS floats>, and the transposed blob's pack kernel
+    "generic_backward_fused_limb_kernel", "generic_pack_limb_bwd_kernel",
 ]
 # The gate covers EVERY kernel of the library (round 4; round 3 covered the benchmarked ones): no scratch memory, no spilled VGPRs -- except:
 #   ALLOW  name substring -> spilled VGPRs tolerated.  What is listed is debt, with the round that recorded it:
