@@ -783,7 +783,7 @@ int nvsr_generic_decode_backward_ext(const nvsr_scene_ext* scene, const nvsr_dec
  * TwoDimPlanesModel.forward (models.py:381-421) of a generic geometry in ONE launch: the input features, every layer of both decoders and
  * both heads; the activations stay in LDS.  The result has the bits of nvsr_generic_decode_ext (the same v_mfma_f32_32x32x2_f32 chains over
  * the same operand pairs in the same order).  Its backward is the plane-gradient launch of "generic decoder, fused plane gradients" below;
- * decoder-weight gradients keep the layered route.
+ * decoder-weight gradients keep the layered route unless the caller takes nvsr_generic_decode_backward_fused_record_ext (below).
  * Capacity: a point's row in LDS holds the decoder inputs and one hidden activation,
  *   row = Kr (+ Kd where the density decoder's input is not a prefix of the colour decoder's: 'sum' / 'avg' position features under
  *         'concat_pos') + hidden floats, rounded up to 2 x an odd number;
@@ -820,6 +820,30 @@ int nvsr_generic_backward_fused_supported(const nvsr_decoder_geometry* geometry,
 int nvsr_generic_decode_backward_fused_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural, int64_t P,
                                            const float* x, const float* coord_noise, const float* d_out, float* const* d_planes,
                                            nvsr_stream_t stream);
+/* ---- generic decoder, fused plane gradients with the decoder's weight gradients (csrc/generic_fused_bwd.hip) -------------------------------
+ * nvsr_generic_decode_backward_ext (the reference: torch.autograd through models.py:381-421) for a geometry the fused backward holds, exact f32:
+ * per chunk of nvsr_generic_backward_chunk() points ONE launch of the kernel above compiled to RECORD what the weight-gradient contraction needs
+ * as it forms it in LDS -- both decoders' inputs Xd [n][Kd] and Xr [n][Kr], every hidden layer's output H [layer][n][hidden] and every hidden
+ * layer's gated output gradient dZ [layer][n][hidden], the layered workspace's shapes, whole 16-byte stores wherever hidden / K is a multiple
+ * of 4 -- and then the layered route's own contraction launches (generic_wgrad_kernel per layer and head) on that record, in the same slabs
+ * of 2 048 points, onto the same offsets of d_natural.  When no plane gradient is wanted the launch leaves out the decoder inputs' gradients
+ * and both scatters.
+ * Bit contract: every recorded value has the bits the layered route computes for it, so each slab's accumulator is the layered route's and
+ * d_natural equals nvsr_generic_decode_backward_ext's up to the arrival order of the slabs' and waves' float atomics; for P <= 512 only one wave of
+ * one slab has points, the others add +0, and d_natural is the layered route's bit for bit.  The plane gradients keep the contract of
+ * nvsr_generic_decode_backward_fused_ext.  Everything is ACCUMULATED into what is there.
+ * nvsr_generic_backward_fused_record_workspace_floats_ext: (Kd + Kr + 2 (density_layers + rgb_layers) hidden) x min(P, chunk) floats of record
+ * + 16 floats with which the entry starts each of the four arrays at a multiple of 16 bytes in ANY workspace; -1 for a geometry that
+ * nvsr_generic_decoder_natural_floats_ext refuses or P < 0.  Capacity: nvsr_generic_backward_fused_supported -- the row does not grow.
+ * nvsr_generic_decode_backward_fused_record_ext: status codes in the order of nvsr_generic_decode_backward_fused_ext -- scene, geometry,
+ * NVSR_ERR_SHAPE beyond the capacity, NVSR_ERR_NULL without natural, x or d_out or with d_natural but no workspace, the scene's planes,
+ * NVSR_ERR_SHAPE for P < 0; P == 0: NVSR_OK without a launch.  d_natural == NULL: nvsr_generic_decode_backward_fused_ext (workspace is not
+ * read); neither d_natural nor a plane wanted: NVSR_OK without a launch.  Never allocates or synchronises. */
+int64_t nvsr_generic_backward_chunk(void);
+int64_t nvsr_generic_backward_fused_record_workspace_floats_ext(const nvsr_decoder_geometry* geometry, int num_position_planes, int64_t P);
+int nvsr_generic_decode_backward_fused_record_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural, int64_t P,
+                                                  const float* x, const float* coord_noise, const float* d_out, float* d_natural,
+                                                  float* const* d_planes, float* workspace, nvsr_stream_t stream);
 /* ---- generic decoder, fused evaluation in NVSR_ARITH_F16X2 (csrc/generic_fused_limb.hip) ---------------------------------------------
  * The launch above with the HIDDEN layers of both decoders in two f16 limbs: per layer w^ = limbs of 2^8 W, x^ = limbs of 2^4 x (hi = RN_f16(v),
  * lo = RN_f16(v - hi)), the products Wh xl, Wh xh, Wl xh on v_mfma_f32_32x32x16_f16 per 16-column K-block of [X1 | X2] in ascending order, f32

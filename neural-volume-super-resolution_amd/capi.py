@@ -192,6 +192,11 @@ _PROTOS_OPTIONAL = {   # feature-plane super-resolution (csrc/sr.hip)
     "nvsr_generic_backward_fused_supported": ([C.POINTER(DecoderGeometry), _i], _i),
     "nvsr_generic_decode_backward_fused_ext": ([C.POINTER(SceneExt), C.POINTER(DecoderGeometry), _vp, _i64, _vp, _vp, _vp, C.POINTER(C.c_void_p),
                                                 _vp], _i),
+    # ... and that launch recording what the decoder's weight gradients contract, then the layered contractions on the record (same file)
+    "nvsr_generic_backward_chunk": ([], _i64),
+    "nvsr_generic_backward_fused_record_workspace_floats_ext": ([C.POINTER(DecoderGeometry), _i, _i64], _i64),
+    "nvsr_generic_decode_backward_fused_record_ext": ([C.POINTER(SceneExt), C.POINTER(DecoderGeometry), _vp, _i64, _vp, _vp, _vp, _vp,
+                                                       C.POINTER(C.c_void_p), _vp, _vp], _i),
     # ... and that launch with the hidden layers in two f16 limbs, from a second, transposed blob (csrc/generic_fused_bwd_limb.hip)
     "nvsr_generic_backward_fused_supported_arith": ([C.POINTER(DecoderGeometry), _i, _i], _i),
     "nvsr_generic_packed_bwd_floats_ext": ([C.POINTER(DecoderGeometry), _i], _i64),
@@ -504,6 +509,12 @@ def fused_min_rays():
     if _fused_min_rays is None:
         _fused_min_rays = int(lib().nvsr_fused_min_rays())
     return _fused_min_rays
+
+
+def generic_backward_chunk():
+    """points per pass of the generic geometries' backwards that keep a chunk's activations (csrc/generic_core.h GEN_BWD_CHUNK), as the loaded
+    library was built with: the layered route's and the recording fused route's"""
+    return int(lib().nvsr_generic_backward_chunk())
 
 
 def call(name, *args):

@@ -187,8 +187,7 @@ __global__ __launch_bounds__(256) void generic_dgrad_kernel(long P, int M, int K
 }
 
 // dW[m][k] += sum_p dZ[p][m] Xc[p][k] for k < K = K1 + K2 (Xc = [X1 | X2]),  db[m] += sum_p dZ[p][m] (the column k == K of the tile grid,
-// whose operand is 1).  Workgroup = one 32 x 32 tile of (m, k) x a slab of GW_PTS points, a quarter of the slab per wave.
-constexpr int GW_PTS = 2048;
+// whose operand is 1).  Workgroup = one 32 x 32 tile of (m, k) x a slab of GW_PTS points (generic_core.h), a quarter of the slab per wave.
 __global__ __launch_bounds__(256) void generic_wgrad_kernel(long P, int M, int K1, int K2, const float* __restrict__ dY, int ldd, int doff,
                                                            const float* __restrict__ Hmask, const float* __restrict__ X1, const float* __restrict__ X2,
                                                            float* __restrict__ dW, float* __restrict__ db) {
@@ -281,7 +280,15 @@ __global__ void generic_inputs_backward_kernel(SceneDevN sc, GenGeom g, long P, 
 }
 
 constexpr long GEN_CHUNK = 1L << 20;       // points per pass of the layer stack (bounds the activation workspace)
-constexpr long GEN_BWD_CHUNK = 1L << 17;   // the backward keeps every layer's output of a chunk
+// (the backward keeps every layer's output of a chunk of GEN_BWD_CHUNK points: generic_core.h)
+
+int gen_wgrad_launch(long n, int M, int K1, int K2, const float* dY, int ldd, int doff, const float* Hmask, const float* X1, const float* X2,
+                     float* dW, float* db, hipStream_t stream) {
+    const unsigned slabs = (unsigned)((n + GW_PTS - 1) / GW_PTS);
+    hipLaunchKernelGGL(generic_wgrad_kernel, dim3((M + 31) / 32, (K1 + K2 + 1 + 31) / 32, slabs), dim3(256), 0, stream, n, M, K1, K2, dY, ldd, doff, Hmask,
+                       X1, X2, dW, db);
+    return NVSR_CHECK_LAUNCH();
+}
 
 }  // namespace nvsr
 
@@ -388,17 +395,8 @@ static int gen_decode_backward(const SceneDevN& sc, const GenGeom& g, const floa
     if (P < 0 || g.nd + g.nr > 128) return NVSR_ERR_SHAPE;
     bool want_planes = false;
     for (int d = 0; d <= g.np; ++d) want_planes = want_planes || gp.g[d] != nullptr;
-    // offsets of the layers in the natural blob (state-dict order: density layers, fc_alpha, rgb layers, fc_rgb; weight then bias)
     long woff[2][65];
-    {
-        long o = 0;
-        for (int dec = 0; dec < 2; ++dec) {
-            const int nl = dec ? g.nr : g.nd;
-            for (int l = 0; l < nl; ++l) { woff[dec][l] = o; o += (long)g.hidden * gen_layer_in(g, dec, l) + g.hidden; }
-            woff[dec][nl] = o;
-            o += (long)(dec ? 3 : 1) * g.hidden + (dec ? 3 : 1);
-        }
-    }
+    gen_blob_offsets(g, woff);
     for (int64_t a = 0; a < P; a += GEN_BWD_CHUNK) {
         const long n = (long)((P - a) < GEN_BWD_CHUNK ? (P - a) : GEN_BWD_CHUNK);
         float* Xin[2] = {workspace, workspace + n * g.Kd};
@@ -412,7 +410,6 @@ static int gen_decode_backward(const SceneDevN& sc, const GenGeom& g, const floa
         hipLaunchKernelGGL(generic_inputs_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, sc, g, n, xa, na, Xin[0], Xin[1]);
         if (int e = NVSR_CHECK_LAUNCH()) return e;
         const dim3 pts((unsigned)((n + GL_PTS - 1) / GL_PTS));
-        const unsigned slabs = (unsigned)((n + GW_PTS - 1) / GW_PTS);
         if (hipMemsetAsync(dXin[0], 0, sizeof(float) * n * (g.Kd + g.Kr), stream) != hipSuccess) return NVSR_ERR_LAUNCH;
         for (int dec = 0; dec < 2; ++dec) {
             const float* in0 = Xin[dec];
@@ -434,9 +431,7 @@ static int gen_decode_backward(const SceneDevN& sc, const GenGeom& g, const floa
             const float* wh = natural + woff[dec][nl];
             if (d_natural) {
                 float* gw = d_natural + woff[dec][nl];
-                hipLaunchKernelGGL(generic_wgrad_kernel, dim3(1, (g.hidden + 1 + 31) / 32, slabs), dim3(256), 0, stream, n, Mh, g.hidden, 0, da, 4, hoff,
-                                   (const float*)nullptr, cur, cur, gw, gw + (long)Mh * g.hidden);
-                if (int e = NVSR_CHECK_LAUNCH()) return e;
+                if (int e = gen_wgrad_launch(n, Mh, g.hidden, 0, da, 4, hoff, nullptr, cur, cur, gw, gw + (long)Mh * g.hidden, stream)) return e;
             }
             hipLaunchKernelGGL(generic_dgrad_kernel<false>, dim3(pts.x, (g.hidden + GL_OUT - 1) / GL_OUT), dim3(256), 0, stream, n, Mh, g.hidden, 0, g.hidden,
                                da, 4, hoff, (const float*)nullptr, wh, dH[0], g.hidden, 0);
@@ -450,9 +445,7 @@ static int gen_decode_backward(const SceneDevN& sc, const GenGeom& g, const floa
                 const float* w = natural + woff[dec][l];
                 if (d_natural) {
                     float* gw = d_natural + woff[dec][l];
-                    hipLaunchKernelGGL(generic_wgrad_kernel, dim3((g.hidden + 31) / 32, (K + 1 + 31) / 32, slabs), dim3(256), 0, stream, n, g.hidden, K1, K2,
-                                       dH[cb], g.hidden, 0, Hl, X1, in0, gw, gw + (long)g.hidden * K);
-                    if (int e = NVSR_CHECK_LAUNCH()) return e;
+                    if (int e = gen_wgrad_launch(n, g.hidden, K1, K2, dH[cb], g.hidden, 0, Hl, X1, in0, gw, gw + (long)g.hidden * K, stream)) return e;
                 }
                 if (l > 0) {
                     hipLaunchKernelGGL(generic_dgrad_kernel<false>, dim3(pts.x, (K1 + GL_OUT - 1) / GL_OUT), dim3(256), 0, stream, n, g.hidden, K, 0, K1,

@@ -72,6 +72,24 @@ static inline int gen_layer_in(const GenGeom& g, bool rgb, int l) {
     return g.hidden + (gen_skip_layer(l - 1, g.skip) ? k0 : 0);
 }
 
+// ---- what the two routes of the decoder-weight gradients share (generic.hip: layered; generic_fused_bwd.hip: on the fused launch's record) ----
+constexpr long GEN_BWD_CHUNK = 1L << 17;   // points per pass of a backward that keeps every layer's output of the chunk
+constexpr int GW_PTS = 2048;               // points per slab of generic_wgrad_kernel, a quarter of the slab per wave
+// offsets of the layers in the natural blob (state-dict order: density layers, fc_alpha, rgb layers, fc_rgb; weight then bias):
+// woff[dec][l] = layer l of decoder dec, woff[dec][layers of dec] = its head
+static inline void gen_blob_offsets(const GenGeom& g, long (&woff)[2][65]) {
+    long o = 0;
+    for (int dec = 0; dec < 2; ++dec) {
+        const int nl = dec ? g.nr : g.nd;
+        for (int l = 0; l < nl; ++l) { woff[dec][l] = o; o += (long)g.hidden * gen_layer_in(g, dec, l) + g.hidden; }
+        woff[dec][nl] = o;
+        o += (long)(dec ? 3 : 1) * g.hidden + (dec ? 3 : 1);
+    }
+}
+// generic.hip: one generic_wgrad_kernel launch over the n points of a chunk in slabs of GW_PTS (the kernel's own arguments); the launch's status
+int gen_wgrad_launch(long n, int M, int K1, int K2, const float* dY, int ldd, int doff, const float* Hmask, const float* X1, const float* X2,
+                     float* dW, float* db, hipStream_t stream);
+
 // what the entry points check of a scene before a launch: planes present, texel offsets within 31 bits
 static inline int gen_check_scene(const SceneDevN& sc, const GenGeom& g) {
     for (int d = 0; d <= g.np; ++d) {

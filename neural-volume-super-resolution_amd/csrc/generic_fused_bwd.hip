@@ -24,6 +24,12 @@
 //   density     head from d_out[:, 3], the layers descending; dXd replaces Xd
 //   planes      two points at a time, 32 lanes over the channels: one atomic per (tap, channel) of every wanted position plane
 // Capacity (gen_fused_bwd_plan, documented in include/nvsr.h): the forward kernel's, with the longer row in 160 KB.
+//
+// The kernel's text is generic_fused_bwd_kernel.h.  It is compiled a second time as generic_backward_fused_record_kernel, which also stores what
+// the decoder's WEIGHT gradients contract -- Xd, Xr, every hidden activation and every gated dZ, the layered workspace's arrays with the layered
+// route's bits -- as it forms them in LDS; nvsr_generic_decode_backward_fused_record_ext runs it per chunk of GEN_BWD_CHUNK points and then the
+// layered route's own generic_wgrad_kernel launches (gen_wgrad_launch, generic.hip) on that record.  A training iteration WITH decoder gradients
+// thereby keeps the layered route's values up to the order of the float atomics, without the recomputed layered forward and data gradients.
 #include "generic_fused_bwd_core.h"
 
 namespace nvsr {
@@ -53,117 +59,79 @@ static inline int gen_fused_bwd_plan(const GenGeom& g, GenFusedBwdPlan* pl) {
     return best ? 1 : 0;
 }
 
-template <int NT, int LDSF>
-__global__ __launch_bounds__(64 * GF_MAX_WAVES) void generic_backward_fused_kernel(SceneDevN sc, GenGeom g, GenFusedBwdPlan L, long P, long block0,
-                                                                                    const float* __restrict__ x, const float* __restrict__ noise,
-                                                                                    const float* __restrict__ natural,
-                                                                                    const float* __restrict__ d_out, GradPlanesN gp) {
-    __shared__ __attribute__((aligned(16))) float lds[LDSF];
-    NVSR_RACE_PROBE_DELAY(lds);      // (probe builds only, nvsr_common.h)
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n = lane & 31, h = lane >> 5;
-    const long slot0 = (block0 + blockIdx.x) * (long)(blockDim.x >> 6) * 32;
-    const long p = slot0 + wave * 32 + n;
-    const bool live = p < P;
-    float* rows = lds + wave * 32 * L.ld;
-    float* row = rows + n * L.ld;
-    unsigned* gate = reinterpret_cast<unsigned*>(row + L.gate_off);
-
-    // ---- forward: stage 0 and the hidden layers of both decoders; the gate bits stay ----
-    const GenFusedRows R = {rows, row, L.ld, L.xd_off};
-    float vgx, vgy;
-    gf_stage0<GF_FULL>(sc, g, R, n, h, live, p, x, noise, vgx, vgy);
-    const bool raw = g.proj == 2 || g.view == 4;
-    const int xd_in = g.proj == 2 ? 0 : L.xd_off;       // 'concat': Xd is the head of Xr
-    if (h == 0) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) row[L.dout_off + r] = live ? d_out[p * 4 + r] : 0.0f;
+// ---- the record of a launch that also serves the decoder's weight gradients (generic_backward_fused_record_kernel) ----
+// The operands of generic_wgrad_kernel for the P points of the launch (a chunk), in the layered workspace's shapes, with the layered route's
+// bits: what generic_inputs_kernel and the kept forward would have left there, and every hidden layer's dZ already gated.
+struct GenRecord {
+    float* Xd;       // [P][Kd]
+    float* Xr;       // [P][Kr]
+    float* H;        // [nd + nr][P][hidden]: every hidden layer's output, the density layers first
+    float* dZ;       // [nd + nr][P][hidden]: the gradient of every hidden layer's output, zeroed where the output is not > 0
+    int planes;      // 0: no plane gradient is wanted -- the gradients of the decoder inputs and both scatters are left out
+};
+// columns [col, col + K) of the wave's 32 rows -> dst[(base + pt) * K + c] for the points base + pt < P: one contiguous block of global memory,
+// read back from LDS behind a barrier.  K % 4 == 0: whole 16-byte stores (every array starts at a multiple of 16 bytes, so does a point's row);
+// else dword stores.  The lanes walk the block 64 vectors at a time: (pt, c) advance by the quotient and remainder of 64, no division per step.
+__device__ __forceinline__ void gfr_store_rows(const float* rows, int ld, int col, int K, float* __restrict__ dst, long base, long P, int lane) {
+    if (base >= P) return;
+    const int live = P - base < 32 ? (int)(P - base) : 32;
+    float* __restrict__ out = dst + base * K;
+    const bool vec = (K & 3) == 0;
+    const int per = vec ? K >> 2 : K, total = live * per, dq = 64 / per, dr = 64 % per;
+    int pt = lane / per, c = lane % per;
+    for (int e = lane; e < total; e += 64) {
+        if (vec) {
+            const float* r = rows + pt * ld + col + 4 * c;
+            *reinterpret_cast<float4*>(out + 4L * e) = make_float4(r[0], r[1], r[2], r[3]);
+        } else {
+            out[e] = rows[pt * ld + col + c];
+        }
+        pt += dq; c += dr;
+        if (c >= per) { c -= per; ++pt; }
     }
-    const float* const wcolour = natural + gf_density_floats(g);
-    for (int dec = 0; dec < 2; ++dec) {
-        const bool rgb = dec == 1;
-        if (rgb && !raw) {                                // Xd -> Xr: the combined position features, then combine_all_planes in place
-            for (int c = h; c < g.C; c += 2) row[c] = row[L.xd_off + c];
-            __syncthreads();
-            gf_plane_features(sc, g, R, n, h, g.np, g.Cv, vgx, vgy, 0, 2);
-            __syncthreads();
-        }
-        const int k0 = rgb ? g.Kr : g.Kd, nl = rgb ? g.nr : g.nd, in0 = rgb ? 0 : xd_in;
-        const float* w = rgb ? wcolour : natural;
-        int cur = in0, cur_k = k0;
-        for (int l = 0; l < nl; ++l) {
-            const bool skip = l > 0 && gen_skip_layer(l - 1, g.skip);
-            const int K1 = cur_k, K2 = skip ? k0 : 0;
-            f32x16 acc[NT];
-            gf_zero<NT>(acc);
-            gf_layer<NT>(acc, row, K1, cur, K2, in0, w, g.hidden, n, h);
-            const float* b = w + (long)g.hidden * (K1 + K2);
-            __syncthreads();
-            unsigned* gl = gate + (rgb ? g.nd + l : l) * L.gw;
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                unsigned bits = 0;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int j = (r & 3) + 8 * (r >> 2) + 4 * h, m = 32 * t + j;
-                    if (m < g.hidden) {
-                        const float v = fmaxf(__fadd_rn(acc[t][r], b[m]), 0.0f);
-                        row[L.h_off + m] = v;
-                        if (v > 0.0f) bits |= 1u << j;
-                    }
-                }
-                bits |= (unsigned)__shfl_xor((int)bits, 32);
-                if (h == 0 && t < L.gw) gl[t] = bits;
-            }
-            __syncthreads();
-            w += (long)g.hidden * (K1 + K2) + g.hidden;
-            cur = L.h_off; cur_k = g.hidden;
-        }
-    }
+}
 
-    // ---- the transposed chains: the colour decoder first (its inputs' room is free), the view plane, then the density decoder ----
-    float n0 = 0.0f, n1 = 0.0f, n2 = 0.0f;
-    if (live) gen_position(sc, x + p * 6, noise, p, n0, n1, n2);
-    for (int dec = 1; dec >= 0; --dec) {
-        const bool rgb = dec == 1;
-        const int k0 = rgb ? g.Kr : g.Kd, nl = rgb ? g.nr : g.nd, Mh = rgb ? 3 : 1, dx = rgb ? 0 : L.xd_off;
-        // the layers' offsets: the head follows the last layer
-        const float* wh = rgb ? wcolour : natural;
-        for (int l = 0; l < nl; ++l) wh += (long)g.hidden * ((l == 0 ? k0 : g.hidden + (gen_skip_layer(l - 1, g.skip) ? k0 : 0)) + 1);
-        for (int c = h; c < k0; c += 2) row[dx + c] = 0.0f;       // the gradient of the decoder's input starts at +0.0
-        // the head: d_out -> the gradient of the last layer's output, gated by that layer
-        {
-            f32x16 acc[NT];
-            gf_zero<NT>(acc);
-            gf_layer_t<NT>(acc, row, L.dout_off + (rgb ? 0 : 3), Mh, wh, g.hidden, 0, g.hidden, n, h);
-            __syncthreads();
-            gf_store_gated<NT>(acc, row + L.h_off, g.hidden, gate + (rgb ? g.nd + nl - 1 : nl - 1) * L.gw, L.gw, h);
-            __syncthreads();
-        }
-        const float* w = wh;
-        for (int l = nl - 1; l >= 0; --l) {
-            const bool skip = l > 0 && gen_skip_layer(l - 1, g.skip);
-            const int K1 = l == 0 ? k0 : g.hidden, K2 = skip ? k0 : 0, K = K1 + K2;
-            w -= (long)g.hidden * (K + 1);
-            if (l == 0) {
-                gf_input_grad<NT>(row, L.h_off, g.hidden, w, K, 0, K1, dx, n, h);
-                __syncthreads();
-                break;
-            }
-            if (skip) gf_input_grad<NT>(row, L.h_off, g.hidden, w, K, K1, K2, dx, n, h);
-            f32x16 acc[NT];
-            gf_zero<NT>(acc);
-            gf_layer_t<NT>(acc, row, L.h_off, g.hidden, w, K, 0, K1, n, h);
-            __syncthreads();                              // the layer's last read is done: its input gradient takes dZ's place, gated
-            gf_store_gated<NT>(acc, row + L.h_off, g.hidden, gate + (rgb ? g.nd + l - 1 : l - 1) * L.gw, L.gw, h);
-            __syncthreads();
-        }
+// generic_backward_fused_kernel<NT, LDS floats> and generic_backward_fused_record_kernel<NT, LDS floats>: one text, compiled twice
+#define GFB_KERNEL_NAME generic_backward_fused_kernel
+#define GFB_RECORD 0
+#include "generic_fused_bwd_kernel.h"
+#undef GFB_KERNEL_NAME
+#undef GFB_RECORD
+#define GFB_KERNEL_NAME generic_backward_fused_record_kernel
+#define GFB_RECORD 1
+#include "generic_fused_bwd_kernel.h"
+#undef GFB_KERNEL_NAME
+#undef GFB_RECORD
 
-        if (rgb) {
-            gfb_view_scatter(sc, g, rows, L.ld, L.xd_off, gp, vgx, vgy, slot0 + wave * 32, P, n, h);
-        }
-    }
+// the launches of either kernel over the P points at x: rec == nullptr: generic_backward_fused_kernel; else the recording kernel
+static int gfb_launch(const SceneDevN& sc, const GenGeom& g, const GenFusedBwdPlan& pl, long P, const float* x, const float* noise,
+                      const float* natural, const float* d_out, const GradPlanesN& gp, const GenRecord* rec, hipStream_t stream) {
+    return gf_for_plan(pl.nt, pl.cls, [&](auto nt, auto cls) {
+        constexpr int NT = decltype(nt)::value, LDSF = GF_LDS_FLOATS[decltype(cls)::value];
+        return gf_launch_pieces(P, pl.waves, [&](long b0, unsigned nb) {
+            if (rec)
+                hipLaunchKernelGGL((generic_backward_fused_record_kernel<NT, LDSF>), dim3(nb), dim3(64 * pl.waves), 0, stream, sc, g, pl, P, b0, x, noise,
+                                   natural, d_out, gp, *rec);
+            else
+                hipLaunchKernelGGL((generic_backward_fused_kernel<NT, LDSF>), dim3(nb), dim3(64 * pl.waves), 0, stream, sc, g, pl, P, b0, x, noise,
+                                   natural, d_out, gp);
+        });
+    });
+}
 
-    gfb_plane_scatter(sc, g, rows, L.ld, L.xd_off, gp, n0, n1, n2, slot0 + wave * 32, P, n, h);
+// floats of a point in the record, and the room that lets its four arrays start at multiples of 16 bytes in any workspace
+static inline int64_t gfr_floats_per_point(const GenGeom& g) { return (int64_t)g.Kd + g.Kr + 2 * (int64_t)(g.nd + g.nr) * g.hidden; }
+constexpr int GFR_ALIGN_FLOATS = 16;
+// the record of a chunk of n points in the workspace: Xd, Xr, H, dZ, each from the next multiple of 16 bytes on
+static inline GenRecord gfr_carve(float* workspace, const GenGeom& g, long n, bool planes) {
+    auto up4 = [](long v) { return (v + 3) & ~3L; };
+    GenRecord r;
+    r.Xd = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 15) & ~(uintptr_t)15);
+    r.Xr = r.Xd + up4(n * g.Kd);
+    r.H = r.Xr + up4(n * g.Kr);
+    r.dZ = r.H + up4((long)(g.nd + g.nr) * n * g.hidden);
+    r.planes = planes ? 1 : 0;
+    return r;
 }
 
 }  // namespace nvsr
@@ -190,13 +158,59 @@ int nvsr_generic_decode_backward_fused_ext(const nvsr_scene_ext* scene, const nv
     if (e != GF_LAUNCH) return e;
     GradPlanesN gp = {};
     if (!gfb_wanted(d_planes, g.np, &gp)) return NVSR_OK;
-    return gf_for_plan(pl.nt, pl.cls, [&](auto nt, auto cls) {
-        constexpr int NT = decltype(nt)::value, LDSF = GF_LDS_FLOATS[decltype(cls)::value];
-        return gf_launch_pieces((long)P, pl.waves, [&](long b0, unsigned nb) {
-            hipLaunchKernelGGL((generic_backward_fused_kernel<NT, LDSF>), dim3(nb), dim3(64 * pl.waves), 0, (hipStream_t)stream, sc, g, pl, (long)P, b0, x,
-                               coord_noise, natural, d_out, gp);
-        });
-    });
+    return gfb_launch(sc, g, pl, (long)P, x, coord_noise, natural, d_out, gp, nullptr, (hipStream_t)stream);
+}
+
+int64_t nvsr_generic_backward_chunk(void) { return GEN_BWD_CHUNK; }
+
+int64_t nvsr_generic_backward_fused_record_workspace_floats_ext(const nvsr_decoder_geometry* geometry, int num_position_planes, int64_t P) {
+    GenGeom g;
+    if (gen_resolve(geometry, &g, num_position_planes) || P < 0) return -1;
+    return (P < GEN_BWD_CHUNK ? P : GEN_BWD_CHUNK) * gfr_floats_per_point(g) + GFR_ALIGN_FLOATS;
+}
+
+int nvsr_generic_decode_backward_fused_record_ext(const nvsr_scene_ext* scene, const nvsr_decoder_geometry* geometry, const float* natural, int64_t P,
+                                                  const float* x, const float* coord_noise, const float* d_out, float* d_natural,
+                                                  float* const* d_planes, float* workspace, nvsr_stream_t stream) {
+    GenGeom g;
+    GenFusedBwdPlan pl;
+    SceneDevN sc;
+    const int e = gf_check_entry(scene, geometry, [&](const GenGeom& gg) { return gen_fused_bwd_plan(gg, &pl); },
+                                 natural && x && d_out && (workspace || !d_natural), GF_FULL, GenFusedList{nullptr, nullptr, 0}, P, &g, &sc);
+    if (e != GF_LAUNCH) return e;
+    GradPlanesN gp = {};
+    const bool planes = gfb_wanted(d_planes, g.np, &gp);
+    if (!d_natural)       // nvsr_generic_decode_backward_fused_ext: nothing is recorded
+        return planes ? gfb_launch(sc, g, pl, (long)P, x, coord_noise, natural, d_out, gp, nullptr, (hipStream_t)stream) : NVSR_OK;
+    long woff[2][65];
+    gen_blob_offsets(g, woff);
+    hipStream_t s = (hipStream_t)stream;
+    for (int64_t a = 0; a < P; a += GEN_BWD_CHUNK) {
+        const long n = (long)((P - a) < GEN_BWD_CHUNK ? (P - a) : GEN_BWD_CHUNK);
+        const GenRecord rec = gfr_carve(workspace, g, n, planes);
+        const float* da = d_out + a * 4;
+        if (int err = gfb_launch(sc, g, pl, n, x + a * 6, coord_noise ? coord_noise + a * 3 : nullptr, natural, da, gp, &rec, s)) return err;
+        // the layered route's contractions (gen_decode_backward) on the record: the same slabs, the same operands' bits, dZ already gated
+        for (int dec = 0; dec < 2; ++dec) {
+            const int k0 = dec ? g.Kr : g.Kd, nl = dec ? g.nr : g.nd, Mh = dec ? 3 : 1, hoff = dec ? 0 : 3;
+            const float* in0 = dec ? rec.Xr : rec.Xd;
+            const float* Hs = rec.H + (dec ? (long)g.nd * n * g.hidden : 0);
+            const float* dZs = rec.dZ + (dec ? (long)g.nd * n * g.hidden : 0);
+            const float* last = Hs + (long)(nl - 1) * n * g.hidden;
+            float* gh = d_natural + woff[dec][nl];
+            if (int err = gen_wgrad_launch(n, Mh, g.hidden, 0, da, 4, hoff, nullptr, last, last, gh, gh + (long)Mh * g.hidden, s)) return err;
+            for (int l = nl - 1; l >= 0; --l) {
+                const bool skip = l > 0 && gen_skip_layer(l - 1, g.skip);
+                const int K1 = l == 0 ? k0 : g.hidden, K2 = skip ? k0 : 0;
+                const float* X1 = l == 0 ? in0 : Hs + (long)(l - 1) * n * g.hidden;
+                float* gw = d_natural + woff[dec][l];
+                if (int err = gen_wgrad_launch(n, g.hidden, K1, K2, dZs + (long)l * n * g.hidden, g.hidden, 0, nullptr, X1, in0, gw,
+                                               gw + (long)g.hidden * (K1 + K2), s))
+                    return err;
+            }
+        }
+    }
+    return NVSR_OK;
 }
 
 }  // extern "C"

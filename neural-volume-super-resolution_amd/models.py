@@ -743,6 +743,30 @@ class TwoDimPlanesModel(nn.Module):
             return "layered"
         return "fused" if self._generic_held("f32", "backward") else "layered"
 
+    # dec_channels (lowest, highest) at which training WITH decoder gradients takes the fused route (generic_decoder_train_route) without
+    # NVSR_GENERIC_TRAIN_DECODER_FUSED=1: the widths at which it beat the parent commit's layered route by more than the larger spread in both
+    # timed shapes (tools/generic_train_decoder_time.py -> profiles/generic_train_decoder_ab.txt; DESIGN 3.10 has the table).  None: nowhere, the
+    # route is opt-in.  Measured at 64 ('avg' / 'concat_pos'), 128 ('sum') and 256 ('concat' over 4 planes): 0.99 / 1.07 / 0.36 x per forward +
+    # backward of 2^19 points, 0.92 / 0.96 / 0.36 x per iteration of 4 096 rays -- no width wins both shapes, so none enters.
+    GENERIC_TRAIN_DECODER_FUSED_DEFAULT_HIDDEN = None
+
+    def generic_decoder_train_route(self):
+        """'fused' or 'layered': how a forward through the generic kernels that records a graph WITH DECODER GRADIENTS trains if called now.
+        'fused' = the forward in one launch (torch.ops.nvsr.triplane_decode_generic_fused: the layered forward's bits) and a backward that records
+        the weight-gradient operands from the fused plane-gradient launch and contracts them with the layered route's own launches
+        (csrc/generic_fused_bwd.hip, torch.ops.nvsr.triplane_decode_generic_fused_backward_record), exact f32.  It is taken when gradients are
+        enabled and a graph is recorded, at least one decoder parameter requires a gradient, the deterministic mode is off, both kernels hold the
+        geometry (nvsr_generic_fused_supported, nvsr_generic_backward_fused_supported) and NVSR_GENERIC_TRAIN_DECODER_FUSED (read at every
+        call) allows it: 0 never, 1 wherever the capacity allows, unset at the widths of GENERIC_TRAIN_DECODER_FUSED_DEFAULT_HIDDEN.  'layered' =
+        csrc/generic.hip layer by layer.  The decision touches no GPU and changes no other predicate."""
+        handle = self._generic_handle("NVSR_GENERIC_TRAIN_DECODER_FUSED")
+        if handle == "0" or not torch.is_grad_enabled() or capi.deterministic():
+            return "layered"
+        dec, _, graph = self._generic_graph()
+        if not dec or not graph or (handle != "1" and not self._generic_width_in(self.GENERIC_TRAIN_DECODER_FUSED_DEFAULT_HIDDEN)):
+            return "layered"
+        return "fused" if self._generic_held("f32", "backward") else "layered"
+
     # dec_channels (lowest, highest) at which planes-only training in 'f16x2' (generic_train_arithmetic) is taken without
     # NVSR_GENERIC_TRAIN_FUSED=1 once train_arithmetic names it: the widths at which it was measured faster than the better f32 route of the
     # parent commit by more than the larger spread, in both timed shapes (tools/generic_train_limb_time.py -> profiles/generic_train_limb_ab.txt;
@@ -759,7 +783,8 @@ class TwoDimPlanesModel(nn.Module):
         being recorded, NO decoder parameter requires a gradient, the deterministic mode is off, NVSR_GENERIC_TRAIN_FUSED is not 0, both limb
         kernels hold the geometry (nvsr_generic_fused_supported_arith, nvsr_generic_backward_fused_supported_arith) and
         NVSR_GENERIC_TRAIN_FUSED is 1 or dec_channels lies in GENERIC_TRAIN_LIMB_DEFAULT_HIDDEN.  'f32': what generic_train_route() says --
-        training with decoder gradients stays exact f32 on the layered route.  The decision touches no GPU and changes no other predicate."""
+        training with decoder gradients stays exact f32 (generic_decoder_train_route() picks its route).  The decision touches no GPU and changes
+        no other predicate."""
         if not (isinstance(self.train_arithmetic, str) and self.train_arithmetic == "f16x2"):
             return "f32"
         handle = self._generic_handle("NVSR_GENERIC_TRAIN_FUSED")
@@ -845,6 +870,8 @@ class TwoDimPlanesModel(nn.Module):
                     return _GenericFusedLimbTrainFn.apply(self, x, coord_noise, *planes)
                 if self.generic_train_route() == "fused":
                     return _GenericFusedTrainFn.apply(self, x, coord_noise, *planes)
+                if dec and self.generic_decoder_train_route() == "fused":
+                    return _GenericFusedDecoderTrainFn.apply(self, x, self.natural_blob(differentiable=True), coord_noise, *planes)
                 return _GenericDecodeFn.apply(self, x, self.natural_blob(differentiable=True) if dec else None, coord_noise, *planes)
         planes, consts, nat = self._generic_eval_args()
         if self.generic_arithmetic() == "f16x2":
@@ -1092,7 +1119,7 @@ class _DecodePointsFn(torch.autograd.Function):
 
 
 def _generic_forward_state(ctx, model, x, nat, coord_noise, plane_srcs):
-    """what the forwards of the three generic autograd functions share: the refusal in the deterministic mode (before any launch), the
+    """what the forwards of the four generic autograd functions share: the refusal in the deterministic mode (before any launch), the
     channel-last planes and the scene constants, the natural blob (nat, or the model's where the decoder does not train) -> the arguments of the
     forward operator, kept as ctx.state for the backward"""
     if capi.deterministic():
@@ -1147,6 +1174,30 @@ class _GenericFusedTrainFn(torch.autograd.Function):
         g = torch.ops.nvsr.triplane_decode_generic_fused_backward(planes_cl, consts, natural, geometry, x, capi.f32c(g_out), need_planes, align,
                                                                   coord_noise, bicubic)
         return (None, None, None) + tuple(from_channel_last(gp, like=p_) if n else None for gp, p_, n in zip(g, ctx.plane_srcs, need_planes))
+
+
+class _GenericFusedDecoderTrainFn(torch.autograd.Function):
+    """_GenericDecodeFn on the fused kernels for a decoder that DOES take gradients (TwoDimPlanesModel.generic_decoder_train_route() ==
+    'fused'): the forward is torch.ops.nvsr.triplane_decode_generic_fused (the layered forward's bits), the backward
+    torch.ops.nvsr.triplane_decode_generic_fused_backward_record (csrc/generic_fused_bwd.hip: per chunk one launch that scatters the planes'
+    gradients and records the weight gradients' operands, then the layered contractions on the record), exact f32.
+    inputs: model, x, the differentiable natural blob, jitter (None = none), then the planes of the scene."""
+
+    @staticmethod
+    def forward(ctx, model, x, nat, coord_noise, *plane_srcs):
+        return torch.ops.nvsr.triplane_decode_generic_fused(*_generic_forward_state(ctx, model, x, nat, coord_noise, plane_srcs))
+
+    @staticmethod
+    def backward(ctx, g_out):
+        planes_cl, consts, natural, geometry, x, align, coord_noise, bicubic = ctx.state
+        need = ctx.needs_input_grad
+        need_planes = [bool(n) for n in need[4:]]
+        if not any(need_planes) and not need[2]:
+            return (None,) * len(need)
+        g = torch.ops.nvsr.triplane_decode_generic_fused_backward_record(planes_cl, consts, natural, geometry, x, capi.f32c(g_out), bool(need[2]),
+                                                                         need_planes, align, coord_noise, bicubic)
+        return (None, None, g[0] if need[2] else None, None) + \
+               tuple(from_channel_last(gp, like=p_) if n else None for gp, p_, n in zip(g[1:], ctx.plane_srcs, need_planes))
 
 
 class _GenericFusedLimbTrainFn(torch.autograd.Function):

@@ -317,8 +317,9 @@ def triplane_decode_generic_fused(planes: Sequence[Tensor], consts: Sequence[flo
                                   align_corners: bool = True, coord_noise: Optional[Tensor] = None, bicubic: bool = False) -> Tensor:
     """triplane_decode_generic in ONE launch, for evaluation (csrc/generic_fused.hip): the input features, every layer of both decoders and both
     heads with the activations in LDS; same arguments, the same bits in the result, no workspace and no registered autograd (training with
-    decoder-weight gradients keeps triplane_decode_generic; planes-only training pairs this forward with
-    triplane_decode_generic_fused_backward, TwoDimPlanesModel.generic_train_route()).  Raises for a geometry beyond the kernel's capacity (nvsr_generic_fused_supported, include/nvsr.h: hidden <= 256,
+    decoder-weight gradients keeps triplane_decode_generic unless TwoDimPlanesModel.generic_decoder_train_route() pairs this forward with
+    triplane_decode_generic_fused_backward_record; planes-only training pairs it with triplane_decode_generic_fused_backward,
+    TwoDimPlanesModel.generic_train_route()).  Raises for a geometry beyond the kernel's capacity (nvsr_generic_fused_supported, include/nvsr.h: hidden <= 256,
     first-layer inputs <= 512 columns, 32 points' rows in 160 KB of LDS) -- TwoDimPlanesModel.generic_route() picks the operator."""
     s = _generic_call(planes, consts, natural, geometry, align_corners, bicubic, x, coord_noise, "fused")
     out = _f(s.P, 4, like=x)
@@ -560,6 +561,34 @@ def triplane_decode_generic_fused_backward(planes: Sequence[Tensor], consts: Seq
 @triplane_decode_generic_fused_backward.register_fake
 def _(planes, consts, natural, geometry, x, d_out, need_planes, align_corners=True, coord_noise=None, bicubic=False):
     return [pl.new_empty(pl.shape if w else (0,)) for pl, w in zip(planes, need_planes)]
+
+
+@custom_op("nvsr::triplane_decode_generic_fused_backward_record", mutates_args=(), device_types="cuda")
+def triplane_decode_generic_fused_backward_record(planes: Sequence[Tensor], consts: Sequence[float], natural: Tensor, geometry: Sequence[int],
+                                                  x: Tensor, d_out: Tensor, want_natural: bool, want_planes: Sequence[bool],
+                                                  align_corners: bool = True, coord_noise: Optional[Tensor] = None,
+                                                  bicubic: bool = False) -> List[Tensor]:
+    """triplane_decode_generic_backward on the fused backward (csrc/generic_fused_bwd.hip, nvsr_generic_decode_backward_fused_record_ext; the
+    reference: torch.autograd through models.py:381-421), exact f32: per chunk one launch that scatters the planes' gradients and records the
+    decoder inputs, every hidden activation and every gated dZ with the layered route's bits, then the layered route's weight-gradient
+    contractions on that record.  d_out [P,4] -> [d_natural, d_plane0 .. d_planeN] (a gradient that is not wanted comes back as an empty
+    tensor).  d_natural is the layered operator's up to the order of its float atomics (bit for bit for P <= 512).  Raises for a geometry
+    beyond the kernel's capacity (nvsr_generic_backward_fused_supported) -- TwoDimPlanesModel.generic_decoder_train_route() picks the operator."""
+    s = _generic_call(planes, consts, natural, geometry, align_corners, bicubic, x, coord_noise, "backward", grad=d_out)
+    g_pl, d_planes, any_plane = _gradient_planes(planes, want_planes)
+    g_nat = torch.zeros(s.n if want_natural else 0, dtype=torch.float32, device=x.device)
+    if s.P and (want_natural or any_plane):
+        ws = None
+        if want_natural:
+            ws = _f(capi.lib().nvsr_generic_backward_fused_record_workspace_floats_ext(C.byref(s.geo), s.n_pos, s.P), like=x)
+        capi.call("nvsr_generic_decode_backward_fused_record_ext", *s.head, capi.ptr(s.grad), capi.ptr(g_nat) if want_natural else None, d_planes,
+                  capi.ptr(ws), capi.stream())
+    return [g_nat] + g_pl
+
+
+@triplane_decode_generic_fused_backward_record.register_fake
+def _(planes, consts, natural, geometry, x, d_out, want_natural, want_planes, align_corners=True, coord_noise=None, bicubic=False):
+    return [natural.new_empty(natural.numel() if want_natural else 0)] + [pl.new_empty(pl.shape if w else (0,)) for pl, w in zip(planes, want_planes)]
 
 
 @custom_op("nvsr::pack_generic_decoder_bwd", mutates_args=(), device_types="cuda")

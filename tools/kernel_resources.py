@@ -46,6 +46,9 @@ BENCHMARKED = [
     "generic_backward_fused_kernel",
     # ... and that training in 'f16x2' by name (tools/generic_train_limb_time.py times it): <NT, LDS floats>, and the transposed blob's pack kernel
     "generic_backward_fused_limb_kernel", "generic_pack_limb_bwd_kernel",
+    # ... and their training with decoder gradients (tools/generic_train_decoder_time.py times it): the f32 kernel compiled to record the
+    # weight-gradient operands, <NT, LDS floats>, and the layered route's contraction, which runs on the record
+    "generic_backward_fused_record_kernel", "generic_wgrad_kernel",
 ]
 # The gate covers EVERY kernel of the library (round 4; round 3 covered the benchmarked ones): no scratch memory, no spilled VGPRs -- except:
 #   ALLOW  name substring -> spilled VGPRs tolerated.  What is listed is debt, with the round that recorded it:
