@@ -678,6 +678,36 @@ int64_t nvsr_decoder_weight_grad_det_workspace_floats(int64_t N, int S);
 int nvsr_decoder_weight_grad_det_arith(int64_t N, int S, const float* record, float* grad_natural, float* workspace, int arithmetic,
                                        nvsr_stream_t stream);
 
+/* ---- input gradients: sample positions and view directions (csrc/points_grad.hip) ---------------------------
+ * The last link behind the ROWS backward: rows[d][m][48] = dL/d(feature of position plane d) of point m = ray * S + s (what
+ * nvsr_render_pass_backward_rows_arith leaves) and view_rows[ray][48] (nvsr_view_rows_reduce) -> d_points[m][3] = dL/d(o + z d) and
+ * d_viewdir[ray][3] = dL/d(rays[ray][8..10]).  The positions' derivative is the TRUE one: the reference projects under torch.no_grad()
+ * and returns 0 there (an extension, like the occupancy grids); the view half is the reference's.
+ *   rows: 3 pointers or NULL; rows[d] == NULL: plane d adds nothing.  view_rows NULL: d_viewdir is 0.  d_points / d_viewdir: either may
+ *   be NULL (not computed); both are OVERWRITTEN.  rows[d] and view_rows are 16-byte aligned.  z is needed for d_points only.
+ *   Status: NVSR_ERR_NULL (scene, a plane of it, rays; z with d_points), NVSR_ERR_ALIGN, NVSR_ERR_SHAPE (N < 0, S < 1, S > 4096,
+ *   N * S >= 2^29), NVSR_OK with nothing launched for N == 0 or no output.  Never allocates, never synchronises, no atomics.
+ * Exactly, every operation one correctly rounded float operation (a b: __fmul_rn, +: __fadd_rn, /: __fdiv_rn), left to right:
+ *   slope(d, gx, gy, row) -> (Gx, Gy), W x H the plane, hx = (W - 1) / 2, hy = (H - 1) / 2:
+ *     x = (gx + 1) hx, y = (gy + 1) hy;  xc = min(W - 1, max(x, 0)), yc likewise (max(NaN, 0) = 0);
+ *     w = xc - floor(xc), e = 1 - w, n = yc - floor(yc), s = 1 - n;  the texels T00 = (floor yc, floor xc), T01 = its east, T10 = its south,
+ *     T11 neighbour, a neighbour beyond the border clamped onto it: the forward's cell (an integer coordinate takes the cell floor selects);
+ *     per channel c:  dx_c = s (T01 - T00)_c + n (T11 - T10)_c,   dy_c = e (T10 - T00)_c + w (T11 - T01)_c;
+ *     12 partial sums over 4 channels each, l = 0..11:  a_l = ((row[4l] dx_4l + row[4l+1] dx_4l+1) + row[4l+2] dx_4l+2) + row[4l+3] dx_4l+3;
+ *     a_12..15 = +0;  A = a balanced tree over neighbours: b_i = a_2i + a_2i+1, c_i = b_2i + b_2i+1, d_i = c_2i + c_2i+1, A = d_0 + d_1;
+ *     Gx = 0 if x <= 0 or x >= W - 1, else hx A;   Gy likewise from dy with y, H - 1, hy   (torch's clip_coordinates_set_grad).
+ *   d_points: p_k = o_k + d_k z (as the kernels form it), n_k = (2 (p_k - lo_k)) / range_k - 1; per plane d, M = proj[d] (3 x 2):
+ *     gx = (n_0 M[0][0] + n_1 M[1][0]) + n_2 M[2][0], gy with column 1 (ray_pos_taps);  (Gx, Gy) = slope(d, gx, gy, rows[d][m]);
+ *     dn_k = +0;  for d = 0, 1, 2 with rows[d] != NULL:  dn_k = dn_k + (M[k][0] Gx + M[k][1] Gy);     d_points[m][k] = (2 dn_k) / range_k.
+ *     A NaN among p_0..2 makes all three components NaN; no other row changes (its taps are in range: max(NaN, 0) = 0).
+ *   d_viewdir: q = vx vx + vy vy, r = sqrt(q), az = atan2f(vy, vx), el = atan2f(vz, r) (view_taps);
+ *     (Gx, Gy) = slope(3, (2 (az - lo_3)) / range_3 - 1, (2 (el - lo_4)) / range_4 - 1, view_rows[ray]);
+ *     d_az = (2 Gx) / range_3, d_el = (2 Gy) / range_4;  h = q + vz vz;  a = d_az / q, b = d_el / h, c = (b vz) / r;
+ *     d_viewdir[ray] = ((-vy) a - vx c,  vx a - vy c,  r b).   A NaN component makes the row NaN.  At a pole (vx = vy = 0) the result is
+ *     unspecified (torch's is not finite either). */
+int nvsr_triplane_points_grad(const nvsr_scene* scene, int64_t N, int S, const float* rays, const float* z, const float* const* rows,
+                              const float* view_rows, float* d_points, float* d_viewdir, nvsr_stream_t stream);
+
 
 /* ---- training: gradients of the super-resolution CNN ('SR' in nerf.train.what) -------------------------------------------
  * torch.autograd through EDSR.forward (models.py:818-822), _Residual_Block.forward (:777-786), PlanesSR.forward (:884-926). */

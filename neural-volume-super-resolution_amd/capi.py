@@ -282,6 +282,8 @@ _PROTOS_OPTIONAL = {   # feature-plane super-resolution (csrc/sr.hip)
     "nvsr_rows_scatter": ([_i64, _vp, _vp, _vp, _i, _i, _vp, _vp, _i64, _vp], _i),
     "nvsr_decoder_weight_grad_det_workspace_floats": ([_i64, _i], _i64),
     "nvsr_decoder_weight_grad_det_arith": ([_i64, _i, _vp, _vp, _vp, _i, _vp], _i),
+    # input gradients of the tri-plane model (csrc/points_grad.hip)
+    "nvsr_triplane_points_grad": ([C.POINTER(Scene), _i64, _i, _vp, _vp, C.POINTER(C.c_void_p), _vp, _vp, _vp, _vp], _i),
     # low-rank feature planes (csrc/lowrank.hip)
     "nvsr_lowrank_planes": ([LowrankPlanesArgs, _vp], _i),
     "nvsr_lowrank_planes_backward": ([LowrankPlanesArgs, _vp], _i),

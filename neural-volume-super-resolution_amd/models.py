@@ -1001,6 +1001,42 @@ class TwoDimPlanesModel(nn.Module):
             self.__dict__["_scene_consts"] = cache
         return list(planes), cache[4]
 
+    def _warn_no_points_grad(self, why):
+        """once per model: a point tensor that requires grad met a route that returns no gradient for it"""
+        if not self.__dict__.get("_points_grad_warned"):
+            import warnings
+            warnings.warn("TwoDimPlanesModel: the points require a gradient, but a model call with %s returns none for them (x.grad stays "
+                          "None); the shipped geometry in 'f16x2' / 'bf16x3' does" % why)
+            self.__dict__["_points_grad_warned"] = True
+
+    def density_gradient(self, points):
+        """d sigma_raw / d xyz of points [P,6] = [xyz, viewdir] -> [P,3], under no_grad (sigma_raw: column 3 of forward(), before the
+        activation).  One-sample rays through decode_rays with gates, the rows backward of g_raw = (0, 0, 0, 1) for the three position
+        planes (no view workspace, no record), torch.ops.nvsr.triplane_points_grad.  The TRUE derivative; a normal is -normalize(.) of it.
+        The shipped geometry in a limb arithmetic only."""
+        if not self.is_native_geometry():
+            raise NotImplementedError("density_gradient: the shipped decoder geometry only (this model runs a generic one)")
+        arith = capi.resolve_decoder_arithmetic(self.arithmetic)
+        if arith == capi.ARITHMETIC["f32"]:
+            raise NotImplementedError("density_gradient: the limb arithmetics 'f16x2' / 'bf16x3' only (this model resolves to 'f32')")
+        with torch.no_grad():
+            x = capi.f32c(points)
+            assert x.shape[-1] == 6, "TwoDimPlanesModel expects [xyz, viewdir] rows"
+            P = x.numel() // 6
+            x = x.reshape(P, 6)
+            if P == 0:
+                return torch.empty((0, 3), dtype=torch.float32, device=x.device)
+            rays = torch.zeros((P, 11), dtype=torch.float32, device=x.device)
+            rays[:, 0:3] = x[:, 0:3]
+            rays[:, 8:11] = x[:, 3:6]
+            z = torch.zeros((P, 1), dtype=torch.float32, device=x.device)
+            planes, consts = self.scene_args()
+            _, gates, _ = torch.ops.nvsr.decode_rays(planes, consts, self.packed_decoder(), rays, z, True, False, arith)
+            g_raw = torch.zeros((P, 1, 4), dtype=torch.float32, device=x.device)
+            g_raw[..., 3] = 1.0
+            rows = ops.decode_rays_backward_rows(planes, consts, self.packed_decoder(), self.packed_decoder_bwd(), rays, z, g_raw, gates, arith)
+            return torch.ops.nvsr.triplane_points_grad(planes, consts, rays, z, rows, rays.new_empty(0))[0]
+
     def native_scene(self, planes=None):
         """struct nvsr_scene for the current scene id (+ the tensors that must outlive the launch) for direct C-ABI calls"""
         planes, consts = self.scene_args(planes)
@@ -1056,13 +1092,19 @@ class TwoDimPlanesModel(nn.Module):
         P = x.numel() // 6
         if P == 0:
             return torch.empty(list(x.shape[:-1]) + [4], dtype=torch.float32, device=x.device)
+        x_grad = x.requires_grad and torch.is_grad_enabled()
         if not self.is_native_geometry():
+            if x_grad:
+                self._warn_no_points_grad("a generic decoder geometry")
             return self._generic_forward(x.reshape(P, 6), coord_noise).reshape(list(x.shape[:-1]) + [4])
         assert coord_noise is None, "a jitter for a forward that does not jitter (point_coords_noise == 0 or evaluation mode)"
+        if x_grad and capi.resolve_decoder_arithmetic(self.arithmetic) == capi.ARITHMETIC["f32"]:
+            self._warn_no_points_grad("the 'f32' arithmetic")
+            x_grad = False
         if self.training and torch.is_grad_enabled() and not (hasattr(self, "SR_model") and not self.skip_SR_):
             names = [get_plane_name(self.cur_id, d) for d in range(self.num_density_planes + 1)]
             dec = any(p.requires_grad for p in self.decoder_parameters())
-            if dec or any(self.planes_[n].requires_grad for n in names):
+            if dec or x_grad or any(self.planes_[n].requires_grad for n in names):
                 planes = [self.raw_plane(n) for n in names]
                 # run_network's differentiable model call (train_utils.py:15-64): gradients for the planes and the decoder
                 # models.py:393 `np.random.randint(len(self.density_dec))`: the reference picks an ensemble member on every training-mode
@@ -1078,9 +1120,12 @@ class TwoDimPlanesModel(nn.Module):
 
 
 class _DecodePointsFn(torch.autograd.Function):
-    """TwoDimPlanesModel.forward on a list of points with gradients for the planes and the decoder.  The points are handed to the
-    ray-tiled training kernels as one-sample rays (origin = point, direction = 0, depth = 0): decode with published ReLU gates (+ the
-    layer-input record when the decoder trains), gate-driven backward, weight-gradient contraction."""
+    """TwoDimPlanesModel.forward on a list of points with gradients for the planes, the decoder and -- in the limb arithmetics -- the
+    points themselves.  The points are handed to the ray-tiled training kernels as one-sample rays (origin = point, direction = 0,
+    depth = 0): decode with published ReLU gates (+ the layer-input record when the decoder trains), gate-driven backward, weight-gradient
+    contraction.  Points that require a gradient take the rows route once, whatever the deterministic mode says: the same
+    rows feed the ordered scatter into the planes and torch.ops.nvsr.triplane_points_grad.  The position columns are the TRUE derivative
+    (the reference projects under no_grad and returns 0 there)."""
 
     @staticmethod
     def forward(ctx, model, x, p0, p1, p2, pv, nat):
@@ -1107,15 +1152,22 @@ class _DecodePointsFn(torch.autograd.Function):
         P = rays.shape[0]
         need = ctx.needs_input_grad
         need_planes = [bool(n) for n in need[2:6]]
-        if not any(need_planes) and rec is None:
+        need_x = bool(need[1]) and arith != capi.ARITHMETIC["f32"]          # ('f32': x.grad stays None, forward() has warned)
+        if not any(need_planes) and rec is None and not need_x:
             return (None,) * 7
         g_raw = capi.f32c(g_out).reshape(P, 1, 4)
         nv = torch.ops.nvsr
         bwd, wgrad = ((nv.decode_rays_backward_det, lambda *a: nv.decoder_weight_grad_det(*a, None)) if ctx.det else
                       (nv.decode_rays_backward, nv.decoder_weight_grad))
-        gplanes = bwd(planes_cl, consts, model.packed_decoder(), model.packed_decoder_bwd(), rays, z, g_raw, gates, rec, need_planes, arith)
+        gx = None
+        if need_x:
+            gplanes, d_points, d_viewdir = ops.decode_rays_backward_with_points(planes_cl, consts, model.packed_decoder(), model.packed_decoder_bwd(),
+                                                                                rays, z, g_raw, gates, rec, need_planes, arith)
+            gx = torch.cat([d_points, d_viewdir], -1)
+        else:
+            gplanes = bwd(planes_cl, consts, model.packed_decoder(), model.packed_decoder_bwd(), rays, z, g_raw, gates, rec, need_planes, arith)
         gnat = wgrad(rec, P, 1, arith) if (rec is not None and need[6]) else None
-        return (None, None) + tuple(from_channel_last(g, like=p_) if n else None for g, p_, n in zip(gplanes, ctx.plane_srcs, need_planes)) + (gnat,)
+        return (None, gx) + tuple(from_channel_last(g, like=p_) if n else None for g, p_, n in zip(gplanes, ctx.plane_srcs, need_planes)) + (gnat,)
 
 
 def _generic_forward_state(ctx, model, x, nat, coord_noise, plane_srcs):

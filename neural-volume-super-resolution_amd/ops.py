@@ -963,6 +963,44 @@ def _(rows, texel, weight, g, workspace):
     return None
 
 
+def _rows_backward_launch(sc, packed, packed_bwd, rays, z, g_raw, gates, record, want, arithmetic):
+    """the ROWS variant of the gate-driven backward: -> (rows[3] of [N*S,48] or None, the view plane's workspace or None) for the planes
+    `want` names; with `record` the pre-activation gradients are added to it"""
+    N, S = z.shape
+    rows = [_f(N * S, PC, like=rays) if want[d] else None for d in range(3)]
+    rptrs = (C.c_void_p * 3)(*[None if r is None else r.data_ptr() for r in rows]) if any(want[:3]) else None
+    view_ws = _f(capi.lib().nvsr_view_grad_workspace_floats(N, S), like=rays) if want[3] else None
+    capi.call("nvsr_render_pass_backward_rows_arith", C.byref(sc), capi.ptr(packed), capi.ptr(packed_bwd), N, S, capi.ptr(rays), capi.ptr(z),
+              capi.ptr(g_raw), capi.ptr(gates), rptrs, capi.ptr(view_ws), capi.ptr(record), arithmetic, capi.stream())
+    return rows, view_ws
+
+
+def _rows_scatter_tail(sc, planes, rays, z, rows, view_ws, need, grads, want_view_rows=False):
+    """what follows the rows launch on the ordered route, ADDING into `grads`: per wanted position plane taps + ordered scatter, then the view
+    plane (reduce-only kernel, taps per ray, ordered scatter with M = N).  -> view_rows [N,48] (None unless the view plane needs its
+    gradient or want_view_rows asks for the rows alone)"""
+    N, S = z.shape
+    M, st = N * S, capi.stream()
+    if any(need):
+        texel = torch.empty((M, 4), dtype=torch.int32, device=rays.device)
+        weight = _f(M, 4, like=rays)
+        ws = rows_scatter_workspace(M, rays)
+    for d in range(3):
+        if need[d]:
+            capi.call("nvsr_internal_plane_taps", C.byref(sc), d, N, S, capi.ptr(rays), capi.ptr(z), capi.ptr(texel), capi.ptr(weight), st)
+            capi.call("nvsr_rows_scatter", M, capi.ptr(rows[d]), capi.ptr(texel), capi.ptr(weight), planes[d].shape[0], planes[d].shape[1],
+                      capi.ptr(grads[d]), capi.ptr(ws), ws.numel(), st)
+    view_rows = None
+    if need[3] or want_view_rows:
+        view_rows = _f(N, PC, like=rays)
+        capi.call("nvsr_view_rows_reduce", N, S, capi.ptr(view_ws), capi.ptr(view_rows), st)
+    if need[3]:
+        capi.call("nvsr_internal_plane_taps", C.byref(sc), 3, N, S, capi.ptr(rays), None, capi.ptr(texel), capi.ptr(weight), st)
+        capi.call("nvsr_rows_scatter", N, capi.ptr(view_rows), capi.ptr(texel), capi.ptr(weight), planes[3].shape[0], planes[3].shape[1],
+                  capi.ptr(grads[3]), capi.ptr(ws), ws.numel(), st)
+    return view_rows
+
+
 def _decode_rays_backward_det_launch(planes, consts, packed, packed_bwd, rays, z, g_raw, gates, record, need, arithmetic, grads):
     """the gate-driven backward ADDING into `grads` in a fixed order: rows backward, then per wanted position plane taps + ordered scatter,
     then the view plane (reduce-only kernel, taps per ray, ordered scatter with M = N).  One stream, in this order."""
@@ -972,28 +1010,8 @@ def _decode_rays_backward_det_launch(planes, consts, packed, packed_bwd, rays, z
     N, S = z.shape
     if N == 0 or (not any(need) and record is None):
         return
-    M, st = N * S, capi.stream()
-    rows = [_f(M, PC, like=rays) if need[d] else None for d in range(3)]
-    rptrs = (C.c_void_p * 3)(*[None if r is None else r.data_ptr() for r in rows]) if any(need[:3]) else None
-    view_ws = _f(capi.lib().nvsr_view_grad_workspace_floats(N, S), like=rays) if need[3] else None
-    capi.call("nvsr_render_pass_backward_rows_arith", C.byref(sc), capi.ptr(packed), capi.ptr(packed_bwd), N, S, capi.ptr(rays), capi.ptr(z),
-              capi.ptr(g_raw), capi.ptr(gates), rptrs, capi.ptr(view_ws), capi.ptr(record), arithmetic, st)
-    if not any(need):
-        return
-    texel = torch.empty((M, 4), dtype=torch.int32, device=rays.device)
-    weight = _f(M, 4, like=rays)
-    ws = rows_scatter_workspace(M, rays)
-    for d in range(3):
-        if need[d]:
-            capi.call("nvsr_internal_plane_taps", C.byref(sc), d, N, S, capi.ptr(rays), capi.ptr(z), capi.ptr(texel), capi.ptr(weight), st)
-            capi.call("nvsr_rows_scatter", M, capi.ptr(rows[d]), capi.ptr(texel), capi.ptr(weight), planes[d].shape[0], planes[d].shape[1],
-                      capi.ptr(grads[d]), capi.ptr(ws), ws.numel(), st)
-    if need[3]:
-        view_rows = _f(N, PC, like=rays)
-        capi.call("nvsr_view_rows_reduce", N, S, capi.ptr(view_ws), capi.ptr(view_rows), st)
-        capi.call("nvsr_internal_plane_taps", C.byref(sc), 3, N, S, capi.ptr(rays), None, capi.ptr(texel), capi.ptr(weight), st)
-        capi.call("nvsr_rows_scatter", N, capi.ptr(view_rows), capi.ptr(texel), capi.ptr(weight), planes[3].shape[0], planes[3].shape[1],
-                  capi.ptr(grads[3]), capi.ptr(ws), ws.numel(), st)
+    rows, view_ws = _rows_backward_launch(sc, packed, packed_bwd, rays, z, g_raw, gates, record, need, arithmetic)
+    _rows_scatter_tail(sc, planes, rays, z, rows, view_ws, need, grads)
 
 
 @custom_op("nvsr::decode_rays_backward_det", mutates_args=("record",), device_types="cuda")
@@ -1049,6 +1067,67 @@ def decoder_weight_grad_det(record: Tensor, N: int, S: int, arithmetic: int, wor
 @decoder_weight_grad_det.register_fake
 def _(record, N, S, arithmetic, workspace):
     return record.new_empty((capi.DECODER_NATURAL_FLOATS,))
+
+
+# =====================================================================================================================================
+# input gradients (csrc/points_grad.hip): the rows of the ordered route, chained to the sample positions and view directions
+# =====================================================================================================================================
+@custom_op("nvsr::triplane_points_grad", mutates_args=(), device_types="cuda")
+def triplane_points_grad(planes: Sequence[Tensor], consts: Sequence[float], rays: Tensor, z: Tensor, rows: Sequence[Tensor],
+                         view_rows: Tensor) -> Tuple[Tensor, Tensor]:
+    """include/nvsr.h, nvsr_triplane_points_grad: rays [N,11], z [N,S], rows = three tensors [N*S,48] f32 (dL/d feature of position plane d
+    per point; an EMPTY tensor: plane d adds nothing), view_rows [N,48] (or empty) -> (d_points [N*S,3], d_viewdir [N,3]).  Fixed
+    summation order, no atomics: the same inputs give the same bits."""
+    capi.require_cuda(rays, z, view_rows, *rows)
+    if not (rays.dtype == z.dtype == torch.float32 and rays.is_contiguous() and z.is_contiguous() and rays.dim() == 2 and rays.shape[1] == 11
+            and z.dim() == 2 and z.shape[0] == rays.shape[0] and z.shape[1] >= 1):
+        raise ValueError("triplane_points_grad: rays [N,11] f32, z [N,S >= 1] f32, both contiguous")
+    N, S = z.shape
+    if len(rows) != 3:
+        raise ValueError("triplane_points_grad: rows is a list of three tensors ([N*S,%d] f32 or empty)" % PC)
+    for name, t, shape in [("rows[%d]" % d, r, (N * S, PC)) for d, r in enumerate(rows)] + [("view_rows", view_rows, (N, PC))]:
+        if t.numel() == 0:
+            continue
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise ValueError("triplane_points_grad: %s must be a contiguous float32 tensor %s, or an empty one" % (name, list(shape)))
+    sc = _scene(planes, consts)
+    d_points, d_viewdir = _f(N * S, 3, like=rays), _f(N, 3, like=rays)
+    if N:
+        rptrs = (C.c_void_p * 3)(*[r.data_ptr() if r.numel() else None for r in rows])
+        capi.call("nvsr_triplane_points_grad", C.byref(sc), N, S, capi.ptr(rays), capi.ptr(z), rptrs, capi.ptr(_none_if_empty(view_rows)),
+                  capi.ptr(d_points), capi.ptr(d_viewdir), capi.stream())
+    return d_points, d_viewdir
+
+
+@triplane_points_grad.register_fake
+def _(planes, consts, rays, z, rows, view_rows):
+    N, S = z.shape
+    return rays.new_empty((N * S, 3)), rays.new_empty((N, 3))
+
+
+def decode_rays_backward_rows(planes, consts, packed, packed_bwd, rays, z, g_raw, gates, arithmetic):
+    """the ROWS backward alone, for the three position planes (no view workspace, no record): -> rows, three [N*S,48] tensors.  Limb
+    arithmetics only; N >= 1."""
+    _require_limb_arithmetic(arithmetic, "decode_rays_backward_rows")
+    rays, z, g_raw = _c(rays), _c(z), _c(g_raw)
+    return _rows_backward_launch(_scene(planes, consts), packed, packed_bwd, rays, z, g_raw, gates, None, (True, True, True, False), arithmetic)[0]
+
+
+def decode_rays_backward_with_points(planes, consts, packed, packed_bwd, rays, z, g_raw, gates, record, need, arithmetic):
+    """the gate-driven backward when the points need their gradient too: ONE rows launch feeds the ordered scatter into the planes `need`
+    names (_decode_rays_backward_det_launch's tail), the record, and triplane_points_grad.
+    -> (gradient planes as decode_rays_backward_det returns them, d_points [N*S,3], d_viewdir [N,3])"""
+    _require_limb_arithmetic(arithmetic, "the input gradient of a model call")
+    rays, z, g_raw = _c(rays), _c(z), _c(g_raw)
+    sc = _scene(planes, consts)
+    N, S = z.shape
+    grads = [torch.zeros_like(p) if need[d] else _f(0, like=rays) for d, p in enumerate(planes)]
+    if N == 0:
+        return grads, _f(0, 3, like=rays), _f(0, 3, like=rays)
+    rows, view_ws = _rows_backward_launch(sc, packed, packed_bwd, rays, z, g_raw, gates, record, (True,) * 4, arithmetic)
+    view_rows = _rows_scatter_tail(sc, planes, rays, z, rows, view_ws, need, grads, want_view_rows=True)
+    d_points, d_viewdir = torch.ops.nvsr.triplane_points_grad(planes, consts, rays, z, rows, view_rows)
+    return grads, d_points, d_viewdir
 
 
 @custom_op("nvsr::decoder_weight_grad", mutates_args=(), device_types="cuda")

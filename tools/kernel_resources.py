@@ -49,6 +49,8 @@ BENCHMARKED = [
     # ... and their training with decoder gradients (tools/generic_train_decoder_time.py times it): the f32 kernel compiled to record the
     # weight-gradient operands, <NT, LDS floats>, and the layered route's contraction, which runs on the record
     "generic_backward_fused_record_kernel", "generic_wgrad_kernel",
+    # the input gradient of a model call (tools/points_grad_time.py times it)
+    "points_grad_kernel", "viewdir_grad_kernel",
 ]
 # The gate covers EVERY kernel of the library (round 4; round 3 covered the benchmarked ones): no scratch memory, no spilled VGPRs -- except:
 #   ALLOW  name substring -> spilled VGPRs tolerated.  What is listed is debt, with the round that recorded it:
