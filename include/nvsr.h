@@ -230,6 +230,17 @@ int nvsr_internal_point_order(const int* entries, const float* lists, const floa
                               nvsr_stream_t stream);
 int nvsr_internal_point_bands(void);
 int nvsr_internal_copy_point_steps(int* dst, int64_t G, nvsr_stream_t stream);
+/* The density pass of the two-phase route on two f16 limbs has two implementations that write the same bits.  The tile-pair kernels
+ * render_pass3_density[_z]_kernel<2> (csrc/render3.hip): one 4-wave workgroup of 256 rays per CU, a wave owns two 32-ray tiles and issues one
+ * tile's gathers, bias + ReLU and heads in the gaps of the other tile's MFMAs.  The one-tile kernels density_tile[_z]_kernel
+ * (csrc/density_tile.hip): one 8-wave workgroup of 256 rays per CU, a wave owns one tile and runs it in program order, and the two waves of a
+ * SIMD are staggered -- waves 4..7 gather a sample's features a step ahead, behind the blocks of layers 0 and 1 -- so that one has the matrix
+ * pipe while the other waits for texels; 158 KB of LDS (a weight ring of two 32-KB slots, density layers 0 and 1 resident), at most 256
+ * registers per wave.  NVSR_DENSITY_ONE_TILE (read at every launch): 1 selects the one-tile kernels, 0 the tile-pair kernels; unset: the
+ * one-tile kernels (the measurement is in profiles/density_one_tile_ab.txt).  The kept-list density pass of the occupancy route, one and three limbs and the fused
+ * kernel are not affected.  nvsr_internal_density_kernel (test hook): which of the two the latest two-phase launch on `stream` ran -- 0 the
+ * tile-pair kernels (every limb count, the kept lists), 1 the one-tile kernels, -1 when no two-phase launch is on record for the stream. */
+int nvsr_internal_density_kernel(nvsr_stream_t stream);
 /* Occupancy grid (csrc/occupancy.hip; opt-in: a caller who builds no grid gets the launches and the bits described above).  A grid belongs to one
  * (scene planes, decoder) pair: G^3 bits over the scene's normalised box, 1 <= G <= 512.  Cell (ix, iy, iz) is bit i & 31 of 32-bit word
  * i >> 5, i = (iz G + iy) G + ix; nvsr_occupancy_words(G) = ceil(G^3 / 32) words, the unused bits of the last word 0.

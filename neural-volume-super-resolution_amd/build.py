@@ -45,7 +45,7 @@ def _stale():
 # Per-file flags.  render3.hip: the SLP vectorizer packs pairs of f32 operations out of different MFMA gaps into v_pk_* and, to do so,
 # re-schedules the whole block at IR level -- every pure instruction (the MFMAs included) sinks below the block's loads and
 # sched_barriers, the hand-placed interleave is gone and hundreds of registers spill.
-# decode_limb.hip: same blocks, same reason (250 spilled registers with the vectorizer, none without).
+# decode_limb.hip, density_tile.hip: same blocks, same reason (250 spilled registers with the vectorizer, none without).
 # -pragma-unroll-threshold: the blocks of the tile-pair kernels are `#pragma unroll` loops whose side work is selected by the (constant) slot
 # index; before the selection folds away the body counts every alternative, and beyond 16 k instructions LLVM ignores the pragma -- the slot
 # index then reaches an asm immediate ("constraint 'n' expects an integer constant expression") or a register index as a run-time value.
@@ -56,7 +56,7 @@ _PAIR_FLAGS = ["-fno-slp-vectorize", "-mllvm", "-pragma-unroll-threshold=1000000
 # kernels do not gain (fine pass 77.1 -> 77.5 ms, planes-only backward 0.58 -> 0.595 ms with the flag): they keep the default.  Other strategies
 # tried on these two files (max-ilp, max-memory-clause, no pre-RA scheduler): none better (scratch timings of the session, profiles/r05_README.md).
 _SR_FLAGS = ["-mllvm", "-enable-post-misched=0"]
-PER_FILE_FLAGS = {"render3.hip": _PAIR_FLAGS, "decode_pair.hip": _PAIR_FLAGS, "decode_limb.hip": ["-fno-slp-vectorize"], "render_bwd_limb.hip": ["-fno-slp-vectorize"],
+PER_FILE_FLAGS = {"render3.hip": _PAIR_FLAGS, "decode_pair.hip": _PAIR_FLAGS, "decode_limb.hip": ["-fno-slp-vectorize"], "density_tile.hip": ["-fno-slp-vectorize"], "render_bwd_limb.hip": ["-fno-slp-vectorize"],
                   "sr.hip": _SR_FLAGS, "sr_bwd.hip": _SR_FLAGS}
 OBJ_DIR = os.path.join(CSRC, "_obj")      # (of the product build; experiment variants use <out_path>.obj)
 

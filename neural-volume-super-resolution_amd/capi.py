@@ -227,6 +227,7 @@ _PROTOS_OPTIONAL = {   # feature-plane super-resolution (csrc/sr.hip)
     "nvsr_internal_occupancy_probes": ([C.POINTER(Scene), _i, _i, _vp, _vp], _i),
     "nvsr_internal_occupancy_cull": ([C.POINTER(Scene), _i64, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp], _i),
     "nvsr_internal_copy_kept_counts": ([_vp, _i64, _vp], _i),
+    "nvsr_internal_density_kernel": ([_vp], _i),
     "nvsr_set_sr_plane_interp": ([_i], _i),
     "nvsr_get_sr_plane_interp": ([], _i),
     "nvsr_set_sr_align_corners": ([_i], _i),

@@ -43,6 +43,9 @@ struct KeptLists { int* idx; int* n; int* slot; int* trip; };
 // (nvsr_internal_copy_kept_counts returns an error).  launch = false sizes the scratch and leaves no launch behind.
 enum class PassRoute { Fused, TwoPhase, Occupancy };
 PassRoute acquire_pass_scratch(int64_t N, int S, hipStream_t stream, bool raw_out, bool want_kept, bool launch, LiveLists& live, KeptLists& kept);
+// a two-phase pass whose density launch was not the tile-pair kernels' says so behind acquire_pass_scratch (1: the one-tile kernels of
+// density_tile.hip); nvsr_internal_density_kernel reads it back
+void note_density_kernel(hipStream_t stream, int which);
 // the ray order, then the order of dispatch: between the density and the colour launch
 void launch_colour_order(const LiveLists& ll, int64_t N, int S, hipStream_t stream);
 // the same two orders for the density pass over the kept lists (live_order_kernel and group_order_kernel on the kept counts)

@@ -249,7 +249,7 @@ struct Buffer { void* p; size_t bytes; };
 // Lifetime: any growth of any buffer forgets all of it (a new buffer holds no launch's lists or order); a pass that takes the two-phase
 // route assigns all of it -- a plain pass carries the kept counts over, an occupancy pass replaces them; an occupancy pass that declines
 // forgets the kept counts and leaves the rest to the route it falls back to; a reservation assigns nothing.
-struct Launch { int64_t N; int* n; int* steps; int64_t kept_N; int* kept; };
+struct Launch { int64_t N; int* n; int* steps; int64_t kept_N; int* kept; int density; };      // density: 0 the tile-pair density kernels, 1 the one-tile ones
 struct Scratch { int device; hipStream_t stream; Buffer buf[N_BUFFERS]; Launch last; };
 std::mutex g_live_mutex;
 std::vector<Scratch> g_live;
@@ -358,6 +358,13 @@ PassRoute acquire_pass_scratch(int64_t N, int S, hipStream_t stream, bool raw_ou
     return route;
 }
 
+void note_density_kernel(hipStream_t stream, int which) {
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) return;
+    std::lock_guard<std::mutex> lock(g_live_mutex);
+    if (Scratch* e = find_scratch(device, stream)) e->last.density = which;
+}
+
 // the ray order on the counts n (in place), then the order of dispatch on the trips it leaves
 static void launch_orders(int* n, int* trip, int* slot, int64_t N, int S, hipStream_t stream) {
     // NVSR_COLOUR_ORDER=0 makes the ray order the identity (bins = 0: the colour kernel groups its rays as the density kernel does)
@@ -385,6 +392,14 @@ extern "C" int nvsr_internal_live_order(int* live_n, int64_t N, int S, nvsr_stre
 }
 extern "C" int nvsr_internal_copy_live_counts(int* dst, int64_t N, nvsr_stream_t stream) {
     return copy_left_behind(dst, N, stream, [N](const Scratch& c) { return c.last.N == N ? c.last.n : nullptr; });
+}
+// which density kernels the latest two-phase launch on `stream` ran (include/nvsr.h); -1: no such launch is on record
+extern "C" int nvsr_internal_density_kernel(nvsr_stream_t stream) {
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) return -1;
+    std::lock_guard<std::mutex> lock(g_live_mutex);
+    const Scratch* c = find_scratch(device, (hipStream_t)stream);
+    return c && c->last.n ? c->last.density : -1;
 }
 // test hooks of the order of dispatch (include/nvsr.h)
 extern "C" int nvsr_internal_group_order(const int* trips, int64_t G, int S, int* out, nvsr_stream_t stream) {

@@ -78,23 +78,6 @@ __device__ __forceinline__ void ringl_sync() {
     __syncthreads();
 }
 
-// act = max(acc + bias, 0)   (bias packed in accumulator-register order: [group of 4 registers][lane half][4])
-// LF = 2: act 2^SX = relu(acc 2^-SW + bias 2^SX) with the NaN-propagating ReLU of render3.hip (negated-source FMA + integer max)
-template <int LF>
-__device__ __forceinline__ void bias_relu(const f32x16 (&acc)[4], const float* bias, int h, f32x16 (&act)[4], float nsc) {
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-        const f32x4 b = *reinterpret_cast<const f32x4*>(bias + g * 8 + h * 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if constexpr (LF == 2) {
-                float v;        // (one statement: hipcc pads an s_nop between an asm statement and a dependent instruction)
-                asm("v_fma_f32 %0, -%1, %2, %3\n\tv_max_i32 %0, 0, %0" : "=v"(v) : "v"(acc[g >> 2][4 * (g & 3) + j]), "s"(nsc), "v"(b[j]));
-                act[g >> 2][4 * (g & 3) + j] = v;
-            } else act[g >> 2][4 * (g & 3) + j] = fmaxf(acc[g >> 2][4 * (g & 3) + j] + b[j], 0.0f);
-        }
-    }
-}
 // the layer's ReLU gate in relu_publish's format: bit gate_bit(ib, r) of word ib >> 1  <=>  pre-activation > 0
 __device__ __forceinline__ void publish_gates(const f32x16 (&act)[4], unsigned* __restrict__ rec, int layer) {
     // act = max(., 0) is +0 or a positive number (never -0: v_max_f32 of (x, +0) returns +0 for x = -0): act > 0  <=>  its bits, read as

@@ -28,6 +28,11 @@ int nvsr_render_pass_backward_gates_limb_launch(int limbs, const nvsr_scene* sce
 int nvsr_render_pass_backward_rows_limb_launch(int limbs, const nvsr_scene* scene, const float* packed_decoder, const float* packed_bwd, int64_t N, int S, const float* rays,
                                                const float* z, const float* g_raw, const uint32_t* gates, float* const* rows, float* view_ws, float* record,
                                                nvsr_stream_t stream);
+// density_tile.hip: the density pass of the two-phase route on two f16 limbs, one 32-ray tile per wave, one 8-wave workgroup per CU
+// (z = NULL: depths in registers, `lindisp`); writes what render_pass3_density[_z]_kernel<2> writes
+int nvsr_density_tile_launch(const nvsr_scene* scene, const float* packed_decoder, int64_t N, int S, const float* rays, const float* z, int lindisp,
+                             const float* noise, float* disp, float* acc, float* weights, float* depth, float* live_z, float* live_w, int* live_n,
+                             nvsr_stream_t stream);
 // render.hip: NVSR_ARITH_INHERIT -> the process default, anything that is not a mode -> -1; the mode named by an environment variable (dflt if unset;
 // conv != 0: the variable of the convolutions, which also takes "f16")
 int nvsr_internal_resolve_decoder_arith(int arithmetic);

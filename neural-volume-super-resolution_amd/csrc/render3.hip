@@ -1111,6 +1111,14 @@ extern "C" int nvsr_pack_decoder_limbs_launch(const float* natural, float* packe
 struct PassArgs { const nvsr_scene* scene; const float* packed; int64_t N; int S; const float *rays, *z; int lindisp; const float* noise; int white;
                   float *rgb, *disp, *acc, *weights, *depth, *raw_out; hipStream_t stream; };
 struct OccLaunch { const uint32_t* grid; int G; KeptLists kept; };
+// NVSR_DENSITY_ONE_TILE, read at every launch like NVSR_COLOUR_POINTS: 1 = the plain density pass on two f16 limbs runs the one-tile kernels of
+// density_tile.hip, 0 = the tile-pair kernels above; unset: DENSITY_ONE_TILE_DEFAULT (the measurement that set it).  The
+// kept-list density pass, one and three limbs and the fused kernel have no one-tile form.
+constexpr bool DENSITY_ONE_TILE_DEFAULT = true;
+static bool density_one_tile() {
+    const char* e = getenv("NVSR_DENSITY_ONE_TILE");
+    return e && (e[0] == '0' || e[0] == '1') ? e[0] == '1' : DENSITY_ONE_TILE_DEFAULT;
+}
 // ll: the two-phase route (density pass, the colour pass's orders, colour pass on the lists), NULL: the fused kernel.  occ (with ll): the occupancy
 // route -- the cull kernel and the orders on its counts in front, the density pass over the kept lists.
 template <int LIMBS>
@@ -1133,6 +1141,11 @@ static int launch_pass3(const PassArgs& a, const LiveLists* ll, const OccLaunch*
                 if (a.z) launch(render_pass3_density_kept_kernel<LIMBS>, a.z, a.disp, a.acc, a.weights, a.depth, flag, ll->z, ll->w, ll->n, kl.slot, kl.idx, kl.n);
                 else launch(render_pass3_density_kept_z_kernel<LIMBS>, a.lindisp, a.disp, a.acc, a.weights, a.depth, flag, ll->z, ll->w, ll->n, kl.slot, kl.idx, kl.n);
             }
+        } else if (LIMBS == 2 && density_one_tile()) {
+            // two f16 limbs: the one-tile density kernels (density_tile.hip), same bits; NVSR_DENSITY_ONE_TILE=0 keeps the tile-pair kernels below
+            if (int e = nvsr_density_tile_launch(a.scene, a.packed, a.N, a.S, a.rays, a.z, a.lindisp, a.noise, a.disp, a.acc, a.weights, a.depth, ll->z, ll->w, ll->n,
+                                                 (nvsr_stream_t)a.stream)) return e;
+            note_density_kernel(a.stream, 1);
         } else if (a.z) launch(render_pass3_density_kernel<LIMBS>, a.z, a.noise, a.disp, a.acc, a.weights, a.depth, flag, ll->z, ll->w, ll->n);
         else launch(render_pass3_density_z_kernel<LIMBS>, a.lindisp, a.noise, a.disp, a.acc, a.weights, a.depth, flag, ll->z, ll->w, ll->n);
         launch_colour_order(*ll, a.N, a.S, a.stream);
