@@ -719,6 +719,78 @@ int nvsr_decoder_weight_grad_det_arith(int64_t N, int S, const float* record, fl
 int nvsr_triplane_points_grad(const nvsr_scene* scene, int64_t N, int S, const float* rays, const float* z, const float* const* rows,
                               const float* view_rows, float* d_points, float* d_viewdir, nvsr_stream_t stream);
 
+/* ---- ray and camera-pose gradients of a training render (csrc/ray_grad.hip) ----------------------------------
+ * What consumes d_points / d_viewdir: the packed rays' gradient, then the adjoints of nvsr_pack_rays, nvsr_ndc_rays and
+ * nvsr_get_ray_bundle[_at] down to the camera-to-world matrix.  None of these entries allocates, synchronises or uses atomics; each sum has
+ * the fixed order stated below, every operation is one correctly rounded float operation (a b: __fmul_rn, + -: __fadd_rn / __fsub_rn,
+ * /: __fdiv_rn), never contracted into an FMA, so the same inputs give the same bits.  N == 0: NVSR_OK with nothing launched.
+ * "tree(x)" below is a sum over the 64 lanes of a wave as a balanced tree over neighbouring lanes:
+ *   b_i = x_2i + x_2i+1, c_i = b_2i + b_2i+1, ... six levels down to one value.
+ *
+ * nvsr_rays_grad: one pass of one render -> d_rays [N,11] = d loss / d rays.  rays [N,11], z [N,S], d_points [N*S,3] or NULL (adds
+ *   nothing), d_viewdir [N,3] or NULL (adds nothing), raw [N,S,4] (the pass's decoder output), noise [N,S] or NULL (the density noise the
+ *   compositor added), g_raw [N,S,4] (d loss / d raw, what nvsr_composite_backward_rays returned).  Per ray, lane l = 0..63 of its wave:
+ *     A_k[l] = +0;  for s = l, l + 64, ... < S ascending:  A_k[l] = A_k[l] + d_points[s][k]            (k = 0..2; p = o + z d, z a constant
+ *     B_k[l] = +0;  likewise                                B_k[l] = B_k[l] + z[s] d_points[s][k]        of the backward: the coarse depths depend
+ *     T[l]   = +0;  likewise  sn = raw[s][3] + noise[s] (raw[s][3] without noise), sigma = sn < 0 ? 0 : sn,     on near / far only, the fine
+ *                             T[l] = T[l] + g_raw[s][3] sigma                                                    depths are detached)
+ *     d_rays[0..2] = tree(A_k);   rr = (rd_0 rd_0 + rd_1 rd_1) + rd_2 rd_2,  rd = rays[3..5];
+ *     d_rays[3 + k] = tree(B_k) + (tree(T) rd_k) / rr:  the compositor reads sigma and |rd| through their product sigma dist |rd| only, so
+ *                     d loss / d|rd| = sum_s sigma_s (d loss / d sigma_s) / |rd|  (nvsr_composite_backward_rays is unchanged and still
+ *                     treats |rd| as a constant; this is its missing term);
+ *     d_rays[6..7] = +0: near and far are constants of the scene, never differentiated;   d_rays[8..10] = d_viewdir.
+ *   accumulate != 0: columns 0..5 and 8..10 are ADDED onto what d_rays holds (one more rounding: old + value; the coarse pass writes, the
+ *   fine pass adds); columns 6..7 are written +0 either way.  A NaN among rays[0..5], rays[8..10] of a ray makes its columns 0..5 and 8..10
+ *   NaN; no other row changes.  A NaN density stays a NaN (the compositor's relu).
+ *   Roundings on the longest path, n = ceil(S / 64): columns 0..2: n + 6;  columns 3..5: the larger of (1 + n + 6) for B and
+ *   (2 + n + 6) + 1 + 3 + 1 for the T term (noise add, product, lane sum, tree; times rd_k; rr; the division), + 1 for the last addition:
+ *   n + 14;  + 1 each with accumulate.
+ *   Status: NVSR_ERR_NULL (rays, raw, g_raw, d_rays; z with d_points), NVSR_ERR_SHAPE (N < 0, S < 1, S > 4096, N * S >= 2^29).
+ *
+ * nvsr_pack_rays_backward: adjoint of nvsr_pack_rays.  d_rays [N,11], view_src [N,3] (the forward's) -> d_ro [N,3] = d_rays[0..2],
+ *   d_rd [N,3] = d_rays[3..5], and the chain through viewdir = v / |v|:  n = sqrt((v_0 v_0 + v_1 v_1) + v_2 v_2), u_k = v_k / n (the
+ *   forward's), dot = (u_0 g_8 + u_1 g_9) + u_2 g_10, c_k = (g_(8+k) - u_k dot) / n.  view_is_rd != 0 (the view source IS the direction
+ *   tensor): d_rd[k] = d_rays[3 + k] + c_k and d_view_src is not touched; otherwise d_view_src [N,3] (or NULL) = c.  Columns 6..7 are ignored.
+ *   Roundings (relative errors add under a product or a quotient, + 1 for its own rounding; a square root halves its operand's):
+ *   n: 3 / 2 + 1 = 2.5, u_k: 3.5, dot: 4.5 + 2 = 6.5, u_k dot: 11, g - .: 12, / n: 15.5: c_k lies within 16 2^-24 (|g_(8+k)| + |u_k| sum_j |u_j g_(8+j)|) / n
+ *   of the exact value; d_rd with view_is_rd: 17, |d_rays[3 + k]| joining the terms.
+ *   Status: NVSR_ERR_NULL (d_rays, view_src, d_ro, d_rd), NVSR_ERR_SHAPE (N < 0, N >= 2^31).
+ *
+ * nvsr_ndc_rays_backward: adjoint of nvsr_ndc_rays with respect to ro and rd (the focal length and near are constants).  With the forward's
+ *   t = (-(near + o_2)) / d_2, ox = o_0 + t d_0, oy, oz likewise, sx, sy as the forward forms them, go = d_ro_out, gd = d_rd_out:
+ *     h_0 = sx (go_0 - gd_0), h_1 = sy (go_1 - gd_1), h_2 = (2 near) (go_2 - gd_2);   g_ox = h_0 / oz, g_oy = h_1 / oz,
+ *     g_oz = -(((ox h_0 + oy h_1) + h_2) / (oz oz));   k_0 = sx gd_0, k_1 = sy gd_1;   g_t = (g_ox d_0 + g_oy d_1) + g_oz d_2,  q = g_t / d_2;
+ *     d_ro = (g_ox, g_oy, g_oz - q);   d_rd_0 = k_0 / d_2 + t g_ox,  d_rd_1 = k_1 / d_2 + t g_oy,
+ *     d_rd_2 = (t g_oz - (k_0 d_0 + k_1 d_1) / (d_2 d_2)) - t q.
+ *   Roundings: oz is a cancelling sum (its exact value is -near) that divides, twice in g_oz: its relative error is <= 4 kappa 2^-24 with
+ *   kappa = (|o_2| + |t d_2|) / |oz| >= 1 per ray, not a few roundings.  With A the same expressions on absolute values (every difference a
+ *   sum, t taken as (|near| + |o_2|) / |d_2|, the divisor |oz| exact) each component lies within (20 + 8 kappa) 2^-24 A of the exact value:
+ *   19 roundings on the longest path (d_rd_2: ox 4, ox h_0 7, the numerator 9, / (oz oz) 11, g_oz d_2 12, g_t 14, q 15, t q 18, the last
+ *   difference 19), one of slack for the second-order terms, 8 kappa for the two divisions by oz.
+ *   Status: NVSR_ERR_NULL (any pointer), NVSR_ERR_SHAPE (N < 0, N >= 2^31, H < 1, W < 1).
+ *
+ * nvsr_ray_bundle_backward: adjoint of nvsr_get_ray_bundle_at (row_col [N,2]) or, row_col NULL, of nvsr_get_ray_bundle's padded grid
+ *   (N == (H + 2 padding)(W + 2 padding), ray i = pixel (i / Wp, i % Wp); padding is ignored with row_col) -> d_c2w [16], row-major 4 x 4:
+ *   with dir exactly as the forward forms it,  d_c2w[k][j] = sum_rays d_rd[ray][k] dir_j (j < 3),  d_c2w[k][3] = sum_rays d_ro[ray][k],
+ *   row 3 = +0.  The focal lengths stay constants: their gradient is out of scope (in NDC scenes the focal length also enters the warp, and
+ *   half a gradient would mislead).
+ *   Two stages over `workspace` (nvsr_ray_bundle_backward_workspace_floats(N) floats, contents need not be initialised): slab w = rays
+ *   [256 w, 256 w + 256), a ray beyond N contributing +0; per entry the slab's 4 waves each form tree(x), x_l the entry's term of ray
+ *   256 w + 64 wave + l, and partials[w] = (t_0 + t_1) + (t_2 + t_3); then ONE wave: lane l adds partials[l], partials[l + 64], ... in
+ *   ascending order from +0, and d_c2w's entry is the tree over the lanes.  The slab boundaries depend on N alone.
+ *   Roundings on the longest path: 2 (dir_j: a difference, a quotient) + 1 (product) + 6 + 2 + ceil(slabs / 64) + 6 = 17 + ceil(slabs / 64).
+ *   Status: NVSR_ERR_NULL (d_ro, d_rd, d_c2w; workspace with N > 0), NVSR_ERR_ALIGN (d_c2w not 16-byte aligned), NVSR_ERR_SHAPE (H, W < 1,
+ *   N < 0, N >= 2^31, padding < 0, a full grid whose N is not the padded grid's size). */
+int nvsr_rays_grad(int64_t N, int S, const float* rays, const float* z, const float* d_points, const float* d_viewdir, const float* raw,
+                   const float* noise, const float* g_raw, int accumulate, float* d_rays, nvsr_stream_t stream);
+int nvsr_pack_rays_backward(int64_t N, const float* d_rays, const float* view_src, int view_is_rd, float* d_ro, float* d_rd, float* d_view_src,
+                            nvsr_stream_t stream);
+int nvsr_ndc_rays_backward(int H, int W, double focal, double near_, int64_t N, const float* ro, const float* rd, const float* d_ro_out,
+                           const float* d_rd_out, float* d_ro, float* d_rd, nvsr_stream_t stream);
+int64_t nvsr_ray_bundle_backward_workspace_floats(int64_t N);
+int nvsr_ray_bundle_backward(int H, int W, double focal_x, double focal_y, double offset, int64_t N, const int32_t* row_col, int padding,
+                             const float* d_ro, const float* d_rd, float* d_c2w, float* workspace, nvsr_stream_t stream);
+
 
 /* ---- training: gradients of the super-resolution CNN ('SR' in nerf.train.what) -------------------------------------------
  * torch.autograd through EDSR.forward (models.py:818-822), _Residual_Block.forward (:777-786), PlanesSR.forward (:884-926). */

@@ -285,6 +285,12 @@ _PROTOS_OPTIONAL = {   # feature-plane super-resolution (csrc/sr.hip)
     "nvsr_decoder_weight_grad_det_arith": ([_i64, _i, _vp, _vp, _vp, _i, _vp], _i),
     # input gradients of the tri-plane model (csrc/points_grad.hip)
     "nvsr_triplane_points_grad": ([C.POINTER(Scene), _i64, _i, _vp, _vp, C.POINTER(C.c_void_p), _vp, _vp, _vp, _vp], _i),
+    # ray and camera-pose gradients of a training render (csrc/ray_grad.hip)
+    "nvsr_rays_grad": ([_i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp], _i),
+    "nvsr_pack_rays_backward": ([_i64, _vp, _vp, _i, _vp, _vp, _vp, _vp], _i),
+    "nvsr_ndc_rays_backward": ([_i, _i, _d, _d, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i),
+    "nvsr_ray_bundle_backward_workspace_floats": ([_i64], _i64),
+    "nvsr_ray_bundle_backward": ([_i, _i, _d, _d, _d, _i64, _vp, _i, _vp, _vp, _vp, _vp, _vp], _i),
     # low-rank feature planes (csrc/lowrank.hip)
     "nvsr_lowrank_planes": ([LowrankPlanesArgs, _vp], _i),
     "nvsr_lowrank_planes_backward": ([LowrankPlanesArgs, _vp], _i),

@@ -20,6 +20,10 @@ def get_ray_bundle(height: int, width: int, focal_length, tform_cam2world: torch
                    downsampling_offset: float = 0):
     """nerf_helpers.py:507-549 -> (ray_origins, ray_directions), each [H+2p, W+2p, 3]; directions are not normalised."""
     c2w = capi.f32c(tform_cam2world)
+    if torch.is_grad_enabled() and c2w.requires_grad:
+        # a pose that requires a gradient (camera-pose refinement, DESIGN.md 3.4): the same entry as a differentiable operator
+        return torch.ops.nvsr.ray_bundle(height, width, float(get_focal(focal_length, "H")), float(get_focal(focal_length, "W")), c2w,
+                                         padding_size, float(downsampling_offset))
     Hp, Wp = height + 2 * padding_size, width + 2 * padding_size
     ro = torch.empty((Hp, Wp, 3), dtype=torch.float32, device=c2w.device)
     rd = torch.empty_like(ro)
@@ -31,6 +35,8 @@ def get_ray_bundle(height: int, width: int, focal_length, tform_cam2world: torch
 def ndc_rays(H, W, focal, near, rays_o, rays_d):
     """nerf_helpers.py:578-605"""
     ro, rd = capi.f32c(rays_o), capi.f32c(rays_d)
+    if torch.is_grad_enabled() and (ro.requires_grad or rd.requires_grad):
+        return torch.ops.nvsr.ndc_rays(H, W, float(focal), float(near), ro, rd)      # (the same entry as a differentiable operator)
     o, d = torch.empty_like(ro), torch.empty_like(rd)
     if ro.numel() == 0:
         return o, d

@@ -1113,15 +1113,17 @@ def decode_rays_backward_rows(planes, consts, packed, packed_bwd, rays, z, g_raw
     return _rows_backward_launch(_scene(planes, consts), packed, packed_bwd, rays, z, g_raw, gates, None, (True, True, True, False), arithmetic)[0]
 
 
-def decode_rays_backward_with_points(planes, consts, packed, packed_bwd, rays, z, g_raw, gates, record, need, arithmetic):
+def decode_rays_backward_with_points(planes, consts, packed, packed_bwd, rays, z, g_raw, gates, record, need, arithmetic, grads=None):
     """the gate-driven backward when the points need their gradient too: ONE rows launch feeds the ordered scatter into the planes `need`
-    names (_decode_rays_backward_det_launch's tail), the record, and triplane_points_grad.
+    names (_decode_rays_backward_det_launch's tail), the record, and triplane_points_grad.  grads: existing gradient planes to ADD into, as
+    decode_rays_backward_det_ does (a second pass onto the first pass's planes); None: fresh zero-filled ones.
     -> (gradient planes as decode_rays_backward_det returns them, d_points [N*S,3], d_viewdir [N,3])"""
     _require_limb_arithmetic(arithmetic, "the input gradient of a model call")
     rays, z, g_raw = _c(rays), _c(z), _c(g_raw)
     sc = _scene(planes, consts)
     N, S = z.shape
-    grads = [torch.zeros_like(p) if need[d] else _f(0, like=rays) for d, p in enumerate(planes)]
+    if grads is None:
+        grads = [torch.zeros_like(p) if need[d] else _f(0, like=rays) for d, p in enumerate(planes)]
     if N == 0:
         return grads, _f(0, 3, like=rays), _f(0, 3, like=rays)
     rows, view_ws = _rows_backward_launch(sc, packed, packed_bwd, rays, z, g_raw, gates, record, (True,) * 4, arithmetic)
@@ -1945,9 +1947,251 @@ def _lowrank_bwd(ctx, grads):
 lowrank_planes.register_autograd(_lowrank_bwd, setup_context=_lowrank_setup)
 
 
+# =====================================================================================================================================
+# ray and camera-pose gradients of a training render (csrc/ray_grad.hip): the four backward entries, then the differentiable
+# forms of the ray generator, the NDC warp and the packer -- today's entries with today's arguments, their backward registered on top
+# =====================================================================================================================================
+def _check_f32(who, **named):
+    """every named (tensor, shape) is a contiguous float32 CUDA tensor of exactly that shape (None passes)"""
+    for name, (t, shape) in named.items():
+        if t is None:
+            continue
+        capi.require_cuda(t)
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+            raise ValueError("%s: %s must be a contiguous float32 tensor %s" % (who, name, list(shape)))
+
+
+@custom_op("nvsr::rays_grad", mutates_args=("d_rays",), device_types="cuda")
+def rays_grad(rays: Tensor, z: Tensor, d_points: Optional[Tensor], d_viewdir: Optional[Tensor], raw: Tensor, noise: Optional[Tensor],
+              g_raw: Tensor, d_rays: Tensor, accumulate: bool) -> None:
+    """include/nvsr.h, nvsr_rays_grad: one pass's share of d loss / d rays, WRITTEN into d_rays [N,11] (accumulate: added onto it; columns
+    6..7 are +0 either way).  rays [N,11], z [N,S], d_points [N*S,3] or None, d_viewdir [N,3] or None, raw / g_raw [N,S,4], noise [N,S] or
+    None.  Fixed summation order, no atomics."""
+    if not (z.dim() == 2 and z.shape[1] >= 1):
+        raise ValueError("rays_grad: z is [N,S >= 1]")
+    N, S = z.shape
+    _check_f32("rays_grad", rays=(rays, (N, 11)), z=(z, (N, S)), d_points=(d_points, (N * S, 3)), d_viewdir=(d_viewdir, (N, 3)),
+               raw=(raw, (N, S, 4)), noise=(noise, (N, S)), g_raw=(g_raw, (N, S, 4)), d_rays=(d_rays, (N, 11)))
+    if N:
+        capi.call("nvsr_rays_grad", N, S, capi.ptr(rays), capi.ptr(z), capi.ptr(d_points), capi.ptr(d_viewdir), capi.ptr(raw), capi.ptr(noise),
+                  capi.ptr(g_raw), int(bool(accumulate)), capi.ptr(d_rays), capi.stream())
+
+
+@rays_grad.register_fake
+def _(rays, z, d_points, d_viewdir, raw, noise, g_raw, d_rays, accumulate):
+    return None
+
+
+@custom_op("nvsr::pack_rays_backward", mutates_args=(), device_types="cuda")
+def pack_rays_backward(d_rays: Tensor, view_src: Tensor, view_is_rd: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """include/nvsr.h, nvsr_pack_rays_backward: d_rays [N,11], the forward's view source [N,3] -> (d_ro, d_rd, d_view_src), each [N,3];
+    view_is_rd: the view chain is added to d_rd and d_view_src comes back empty"""
+    if d_rays.dim() != 2:
+        raise ValueError("pack_rays_backward: d_rays is [N,11]")
+    N = d_rays.shape[0]
+    _check_f32("pack_rays_backward", d_rays=(d_rays, (N, 11)), view_src=(view_src, (N, 3)))
+    d_ro, d_rd = _f(N, 3, like=d_rays), _f(N, 3, like=d_rays)
+    d_vs = _f(0, like=d_rays) if view_is_rd else _f(N, 3, like=d_rays)
+    if N:
+        capi.call("nvsr_pack_rays_backward", N, capi.ptr(d_rays), capi.ptr(view_src), int(bool(view_is_rd)), capi.ptr(d_ro), capi.ptr(d_rd),
+                  capi.ptr(_none_if_empty(d_vs)), capi.stream())
+    return d_ro, d_rd, d_vs
+
+
+@pack_rays_backward.register_fake
+def _(d_rays, view_src, view_is_rd):
+    N = d_rays.shape[0]
+    return d_rays.new_empty((N, 3)), d_rays.new_empty((N, 3)), d_rays.new_empty((0,) if view_is_rd else (N, 3))
+
+
+@custom_op("nvsr::ndc_rays_backward", mutates_args=(), device_types="cuda")
+def ndc_rays_backward(H: int, W: int, focal: float, near: float, ro: Tensor, rd: Tensor, d_ro_out: Tensor, d_rd_out: Tensor) -> Tuple[Tensor, Tensor]:
+    """include/nvsr.h, nvsr_ndc_rays_backward: the forward's inputs ro, rd [N,3] and the gradients of its outputs -> (d_ro, d_rd)"""
+    if ro.dim() != 2:
+        raise ValueError("ndc_rays_backward: ro is [N,3]")
+    N = ro.shape[0]
+    _check_f32("ndc_rays_backward", ro=(ro, (N, 3)), rd=(rd, (N, 3)), d_ro_out=(d_ro_out, (N, 3)), d_rd_out=(d_rd_out, (N, 3)))
+    if H < 1 or W < 1:
+        raise ValueError("ndc_rays_backward: H, W >= 1")
+    d_ro, d_rd = _f(N, 3, like=ro), _f(N, 3, like=ro)
+    if N:
+        capi.call("nvsr_ndc_rays_backward", H, W, float(focal), float(near), N, capi.ptr(ro), capi.ptr(rd), capi.ptr(d_ro_out), capi.ptr(d_rd_out),
+                  capi.ptr(d_ro), capi.ptr(d_rd), capi.stream())
+    return d_ro, d_rd
+
+
+@ndc_rays_backward.register_fake
+def _(H, W, focal, near, ro, rd, d_ro_out, d_rd_out):
+    return ro.new_empty(ro.shape), ro.new_empty(ro.shape)
+
+
+@custom_op("nvsr::ray_bundle_backward", mutates_args=(), device_types="cuda")
+def ray_bundle_backward(H: int, W: int, focal_x: float, focal_y: float, offset: float, row_col: Optional[Tensor], padding: int, d_ro: Tensor,
+                        d_rd: Tensor) -> Tensor:
+    """include/nvsr.h, nvsr_ray_bundle_backward: d_ro, d_rd [N,3] of the rays of row_col [N,2] int32 (None: of the whole padded grid,
+    N = (H + 2 padding)(W + 2 padding)) -> d_c2w [4,4], row 3 zero.  Two stages in a fixed order over a workspace allocated here."""
+    if d_ro.dim() != 2:
+        raise ValueError("ray_bundle_backward: d_ro is [N,3]")
+    N = d_ro.shape[0]
+    _check_f32("ray_bundle_backward", d_ro=(d_ro, (N, 3)), d_rd=(d_rd, (N, 3)))
+    if H < 1 or W < 1 or padding < 0:
+        raise ValueError("ray_bundle_backward: H, W >= 1, padding >= 0")
+    if row_col is None:
+        if N != (H + 2 * padding) * (W + 2 * padding):
+            raise ValueError("ray_bundle_backward: without row_col the gradients cover the whole padded grid, %d rays" % ((H + 2 * padding) * (W + 2 * padding)))
+    else:
+        capi.require_cuda(row_col)
+        if row_col.dtype != torch.int32 or not row_col.is_contiguous() or tuple(row_col.shape) != (N, 2):
+            raise ValueError("ray_bundle_backward: row_col must be a contiguous int32 tensor [N,2]")
+    d_c2w = torch.zeros((4, 4), dtype=torch.float32, device=d_ro.device) if N == 0 else _f(4, 4, like=d_ro)
+    if N:
+        ws = _f(capi.lib().nvsr_ray_bundle_backward_workspace_floats(N), like=d_ro)
+        capi.call("nvsr_ray_bundle_backward", H, W, float(focal_x), float(focal_y), float(offset), N, capi.ptr(row_col), padding, capi.ptr(d_ro),
+                  capi.ptr(d_rd), capi.ptr(d_c2w), capi.ptr(ws), capi.stream())
+    return d_c2w
+
+
+@ray_bundle_backward.register_fake
+def _(H, W, focal_x, focal_y, offset, row_col, padding, d_ro, d_rd):
+    return d_ro.new_empty((4, 4))
+
+
+def _c2w_check(who, c2w):
+    capi.require_cuda(c2w)
+    if c2w.dtype != torch.float32 or not c2w.is_contiguous() or c2w.dim() != 2 or c2w.shape[1] != 4 or c2w.shape[0] not in (3, 4):
+        raise ValueError("%s: c2w must be a contiguous float32 tensor [3,4] or [4,4]" % who)
+
+
+@custom_op("nvsr::ray_bundle", mutates_args=(), device_types="cuda")
+def ray_bundle(H: int, W: int, focal_x: float, focal_y: float, c2w: Tensor, padding: int, offset: float) -> Tuple[Tensor, Tensor]:
+    """nvsr_get_ray_bundle as nerf_helpers.get_ray_bundle calls it, differentiable in c2w -> (ro, rd), each [H+2p, W+2p, 3]"""
+    _c2w_check("ray_bundle", c2w)
+    ro = _f(H + 2 * padding, W + 2 * padding, 3, like=c2w)
+    rd = torch.empty_like(ro)
+    capi.call("nvsr_get_ray_bundle", H, W, float(focal_x), float(focal_y), capi.ptr(c2w), padding, float(offset), capi.ptr(ro), capi.ptr(rd),
+              capi.stream())
+    return ro, rd
+
+
+@ray_bundle.register_fake
+def _(H, W, focal_x, focal_y, c2w, padding, offset):
+    return c2w.new_empty((H + 2 * padding, W + 2 * padding, 3)), c2w.new_empty((H + 2 * padding, W + 2 * padding, 3))
+
+
+@custom_op("nvsr::ray_bundle_at", mutates_args=(), device_types="cuda")
+def ray_bundle_at(H: int, W: int, focal_x: float, focal_y: float, c2w: Tensor, offset: float, row_col: Tensor) -> Tuple[Tensor, Tensor]:
+    """nvsr_get_ray_bundle_at as training.get_ray_bundle_at calls it, differentiable in c2w -> (ro, rd), each [N,3]"""
+    _c2w_check("ray_bundle_at", c2w)
+    capi.require_cuda(row_col)
+    if row_col.dtype != torch.int32 or not row_col.is_contiguous() or row_col.dim() != 2 or row_col.shape[1] != 2:
+        raise ValueError("ray_bundle_at: row_col must be a contiguous int32 tensor [N,2]")
+    N = row_col.shape[0]
+    ro = _f(N, 3, like=c2w)
+    rd = torch.empty_like(ro)
+    if N:
+        capi.call("nvsr_get_ray_bundle_at", H, W, float(focal_x), float(focal_y), capi.ptr(c2w), float(offset), N, capi.ptr(row_col), capi.ptr(ro),
+                  capi.ptr(rd), capi.stream())
+    return ro, rd
+
+
+@ray_bundle_at.register_fake
+def _(H, W, focal_x, focal_y, c2w, offset, row_col):
+    return c2w.new_empty((row_col.shape[0], 3)), c2w.new_empty((row_col.shape[0], 3))
+
+
+def _zeros_if_none(g, like):
+    return torch.zeros_like(like) if g is None else _c(g)
+
+
+def _ray_bundle_setup(ctx, inputs, output):
+    H, W, fx, fy, c2w, padding, offset = inputs
+    ctx.args, ctx.rows, ctx.row_col_saved = (H, W, fx, fy, offset, padding), c2w.shape[0], False
+
+
+def _ray_bundle_at_setup(ctx, inputs, output):
+    H, W, fx, fy, c2w, offset, row_col = inputs
+    ctx.args, ctx.rows, ctx.row_col_saved = (H, W, fx, fy, offset, 0), c2w.shape[0], True
+    ctx.save_for_backward(row_col)                   # (under autograd's version check: an in-place change before backward raises)
+
+
+def _ray_bundle_bwd(ctx, g_ro, g_rd):
+    H, W, fx, fy, offset, padding = ctx.args
+    row_col = ctx.saved_tensors[0] if ctx.row_col_saved else None
+    present = g_ro if g_ro is not None else g_rd      # (one of the two is: autograd does not call a backward without a gradient)
+    g = torch.ops.nvsr.ray_bundle_backward(H, W, fx, fy, offset, row_col, padding, _zeros_if_none(g_ro, present).reshape(-1, 3),
+                                           _zeros_if_none(g_rd, present).reshape(-1, 3))[:ctx.rows]
+    return (None, None, None, None, g, None, None)
+
+
+ray_bundle.register_autograd(_ray_bundle_bwd, setup_context=_ray_bundle_setup)
+ray_bundle_at.register_autograd(_ray_bundle_bwd, setup_context=_ray_bundle_at_setup)
+
+
+@custom_op("nvsr::ndc_rays", mutates_args=(), device_types="cuda")
+def ndc_rays(H: int, W: int, focal: float, near: float, ro: Tensor, rd: Tensor) -> Tuple[Tensor, Tensor]:
+    """nvsr_ndc_rays as nerf_helpers.ndc_rays calls it, differentiable in ro and rd (any leading shape, last axis 3)"""
+    _check_f32("ndc_rays", ro=(ro, ro.shape), rd=(rd, ro.shape))
+    o, d = torch.empty_like(ro), torch.empty_like(rd)
+    if ro.numel():
+        capi.call("nvsr_ndc_rays", H, W, float(focal), float(near), ro.numel() // 3, capi.ptr(ro), capi.ptr(rd), capi.ptr(o), capi.ptr(d), capi.stream())
+    return o, d
+
+
+@ndc_rays.register_fake
+def _(H, W, focal, near, ro, rd):
+    return torch.empty_like(ro), torch.empty_like(rd)
+
+
+def _ndc_setup(ctx, inputs, output):
+    ctx.args = inputs[:4]
+    ctx.save_for_backward(inputs[4], inputs[5])
+
+
+def _ndc_bwd(ctx, g_o, g_d):
+    ro, rd = ctx.saved_tensors
+    d_ro, d_rd = torch.ops.nvsr.ndc_rays_backward(*ctx.args, ro.reshape(-1, 3), rd.reshape(-1, 3), _zeros_if_none(g_o, ro).reshape(-1, 3),
+                                                  _zeros_if_none(g_d, rd).reshape(-1, 3))
+    return None, None, None, None, d_ro.reshape(ro.shape), d_rd.reshape(rd.shape)
+
+
+ndc_rays.register_autograd(_ndc_bwd, setup_context=_ndc_setup)
+
+
+@custom_op("nvsr::pack_rays", mutates_args=(), device_types="cuda")
+def pack_rays(ro: Tensor, rd: Tensor, view_src: Optional[Tensor], near: float, far: float) -> Tensor:
+    """nvsr_pack_rays as train_utils.pack_rays calls it, differentiable in ro, rd and the view source (None: the directions themselves)
+    -> rays [N,11]"""
+    N = ro.shape[0]
+    _check_f32("pack_rays", ro=(ro, (N, 3)), rd=(rd, (N, 3)), view_src=(view_src, (N, 3)))
+    rays = _f(N, 11, like=ro)
+    if N:
+        capi.call("nvsr_pack_rays", N, capi.ptr(ro), capi.ptr(rd), capi.ptr(rd if view_src is None else view_src), float(near), float(far),
+                  capi.ptr(rays), capi.stream())
+    return rays
+
+
+@pack_rays.register_fake
+def _(ro, rd, view_src, near, far):
+    return ro.new_empty((ro.shape[0], 11))
+
+
+def _pack_setup(ctx, inputs, output):
+    ro, rd, view_src, _, _ = inputs
+    ctx.view_is_rd = view_src is None
+    ctx.save_for_backward(rd if view_src is None else view_src)
+
+
+def _pack_bwd(ctx, g):
+    d_ro, d_rd, d_vs = torch.ops.nvsr.pack_rays_backward(_c(g), ctx.saved_tensors[0], ctx.view_is_rd)
+    return d_ro, d_rd, (None if ctx.view_is_rd else d_vs), None, None
+
+
+pack_rays.register_autograd(_pack_bwd, setup_context=_pack_setup)
+
+
 FORWARD_OPS = ["plane_to_channel_last", "plane_from_channel_last", "pack_decoder", "coarse_z", "importance_resample", "triplane_decode",
                "triplane_decode_generic", "triplane_decode_generic_fused", "pack_generic_decoder", "triplane_decode_generic_fused_arith",
-               "pack_generic_decoder_bwd", "ray_points", "lowrank_planes",
+               "pack_generic_decoder_bwd", "ray_points", "lowrank_planes", "ray_bundle", "ray_bundle_at", "ndc_rays", "pack_rays",
                "triplane_density_generic_fused_arith", "triplane_colour_generic_fused_arith", "generic_live_list",
                "generic_occupancy_build", "generic_occupancy_keep", "triplane_density_list_generic_fused_arith",
                "render_pass", "render_rays", "decode_rays", "composite", "composite_rays", "edsr", "planes_sr", "cumprod_exclusive"]

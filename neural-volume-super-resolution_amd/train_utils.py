@@ -89,12 +89,18 @@ class _RenderRaysFn(torch.autograd.Function):
                -> fine decode_rays + composite_rays (keeps raw);
     backward = per pass: composite_backward (wave per ray) -> decode_rays_backward (MFMA + plane scatter)
                [+ record of layer inputs / deltas -> decoder_weight_grad].
+    With cfg["rays_grad"] the packed rays are one more leaf, the last input (camera-pose refinement): each pass's backward
+    then takes the rows route once -- decode_rays_backward_with_points -> rays_grad, coarse first, fine accumulating.
     The arithmetic the forward ran in is stored with the context and handed to every backward operator."""
 
     @staticmethod
     def forward(ctx, cfg, p0, p1, p2, pv, nat_c, nat_f, *coarse_leaves):
         # coarse_leaves: the four planes the COARSE pass samples when they are other tensors than the fine pass's p0..pv -- the reference's default
         # SR training (train_nerf.py:554-561, apply_2_coarse False): only the fine model super-resolves, the coarse model samples the LR planes
+        # cfg["rays_grad"]: the packed rays need their gradient (camera-pose refinement, DESIGN.md 3.4): they are the LAST input, a leaf of
+        # the graph; the kernels read cfg["rays"], the same values detached
+        if cfg.get("rays_grad"):
+            coarse_leaves = coarse_leaves[:-1]
         N, Nc, Nf, rays = cfg["N"], cfg["Nc"], cfg["Nf"], cfg["rays"]
         nv = _NV()
         arith_c, arith_f = cfg["arith_c"], cfg["arith_f"]
@@ -157,6 +163,11 @@ class _RenderRaysFn(torch.autograd.Function):
         gplanes_f = [None, None, None, None]
         gplanes_c = [None, None, None, None] if sep else gplanes_f
         det = bool(cfg.get("det"))
+        # rays that need their gradient: each pass takes the rows route once, whatever the deterministic mode says (the rule of
+        # models._DecodePointsFn): ONE rows launch feeds the ordered scatter into the planes, the record and triplane_points_grad, then
+        # rays_grad reduces the points' gradient per ray -- coarse writes d_rays, fine adds, on one stream
+        need_rays = bool(cfg.get("rays_grad")) and bool(need[-1])
+        ray_out = []                                             # [d_rays] once a pass has written it
 
         def one_pass(S, z, raw, noise, planes, packed, packed_bwd, g_rgb, g_disp, g_acc, disp, acc, want_dec, gates, fwd_rec, arith, need_planes, gplanes):
             """-> decoder gradient of this pass (state-dict order) or None; plane gradients are added into `gplanes`"""
@@ -165,7 +176,7 @@ class _RenderRaysFn(torch.autograd.Function):
                     if need_planes[d]:
                         gplanes[d] = g if gplanes[d] is None else gplanes[d].add_(g)
 
-            if (g_rgb is None and g_acc is None and g_disp is None) or (not any(need_planes) and not want_dec):
+            if (g_rgb is None and g_acc is None and g_disp is None) or (not any(need_planes) and not want_dec and not need_rays):
                 return None
             g_rgb = torch.zeros((N, 3), dtype=torch.float32, device=dev) if g_rgb is None else capi.f32c(g_rgb)
             g_acc = None if g_acc is None else capi.f32c(g_acc)
@@ -186,7 +197,16 @@ class _RenderRaysFn(torch.autograd.Function):
                     have = [True] * len(have)
                 # deterministic mode (capi.deterministic, resolved by the forward): the ordered operators -- same arguments, no float atomics
                 bwd_, bwd, wgrad = ((nv.decode_rays_backward_det_, nv.decode_rays_backward_det, lambda *a: nv.decoder_weight_grad_det(*a, None))
-                                    if det else (nv.decode_rays_backward_, nv.decode_rays_backward, nv.decoder_weight_grad))
+                                    if det or need_rays else (nv.decode_rays_backward_, nv.decode_rays_backward, nv.decoder_weight_grad))
+                if need_rays:
+                    def with_rays(*a, grads=None):
+                        gs, d_points, d_viewdir = ops.decode_rays_backward_with_points(*a, grads=grads)
+                        first = not ray_out                     # the first pass writes d_rays, a later one adds onto it
+                        if first:
+                            ray_out.append(torch.empty((N, 11), dtype=torch.float32, device=dev))
+                        nv.rays_grad(rays, z, d_points, d_viewdir, raw, noise, g_raw, ray_out[0], not first)
+                        return gs
+                    bwd_, bwd = (lambda *a: with_rays(*a[:-1], grads=a[-1])), with_rays
                 if have and all(have) and all(gplanes[d].shape == planes[d].shape and gplanes[d].stride() == planes[d].stride()
                                               for d in range(4) if need_planes[d]):
                     # a second pass over the same planes scatters into the first pass's gradient planes (no second zero-fill, no add)
@@ -214,7 +234,7 @@ class _RenderRaysFn(torch.autograd.Function):
         # allocated on the second stream outlives the join.  Deterministic mode: ONE stream, coarse then fine -- the fine pass adds onto the
         # coarse pass's sums, and that order is part of the result's bits.
         need_planes, gplanes = need_planes_f, gplanes_f
-        two = (not det and os.environ.get("NVSR_BWD_STREAMS", "1") == "1" and not sep and cfg["coarse_grad"] and Nf > 0 and dev.type == "cuda" and any(need_planes)
+        two = (not det and not need_rays and os.environ.get("NVSR_BWD_STREAMS", "1") == "1" and not sep and cfg["coarse_grad"] and Nf > 0 and dev.type == "cuda" and any(need_planes)
                and not need[5] and not need[6] and sv["gates_c"] is not None and sv["gates_f"] is not None
                and all(a.shape == b.shape and a.stride() == b.stride() for a, b in zip(cfg["planes_c"], cfg["planes_f"])))
         if two:
@@ -249,6 +269,11 @@ class _RenderRaysFn(torch.autograd.Function):
                 if need_planes_c[d] and g is None:
                     g = torch.zeros(cfg["plane_shapes_c"][d], dtype=torch.float32, device=dev)
                 out_c.append(None if g is None else models.from_channel_last(g, like=src))
+        if cfg.get("rays_grad"):
+            d_rays = None
+            if need_rays:
+                d_rays = ray_out[0] if ray_out else torch.zeros((N, 11), dtype=torch.float32, device=dev)
+            out_c.append(d_rays)
         return tuple(out) + (gdec_c, gdec_f) + tuple(out_c)
 
 
@@ -274,6 +299,15 @@ def _decoder_needs_grad(model):
     return torch.is_grad_enabled() and any(p.requires_grad for p in model.decoder_parameters())
 
 
+def _warn_no_rays_grad(model, why):
+    """once per model: rays that require a gradient met a route that returns none for them (the precedent of models._warn_no_points_grad)"""
+    if not model.__dict__.get("_rays_grad_warned"):
+        import warnings
+        warnings.warn("the rays require a gradient, but a render with %s returns none for them (their .grad stays None); a training render of "
+                      "the shipped tri-plane geometry in 'f16x2' / 'bf16x3' does" % why)
+        model.__dict__["_rays_grad_warned"] = True
+
+
 def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, scene_id, mode="train", encode_position_fn=None,
                                 encode_direction_fn=None, randoms=None, force_arith=None):
     """train_utils.py:71-182 on packed rays [N,11].  `randoms` (extension) = dict(t_rand, u, noise_coarse, noise_fine) of
@@ -282,7 +316,11 @@ def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, sc
         raise NotImplementedError("Mip-NeRF baseline is outside the tri-plane hot path (SURVEY.md 2)")
     m = _cfg(options.nerf, mode)
     Nc, Nf = int(m.num_coarse), int(m.num_fine)
-    rays = capi.f32c(ray_batch)
+    rays_leaf = capi.f32c(ray_batch)
+    # rays that require a gradient: the training path of the shipped geometry in a limb arithmetic returns one; every other
+    # route warns once per model and leaves it None.  The kernels always read the detached values.
+    rays_ask = torch.is_grad_enabled() and rays_leaf.requires_grad
+    rays = rays_leaf.detach()
     N = rays.shape[0]
     dev = rays.device
     std = float(m.radiance_field_noise_std)
@@ -314,6 +352,8 @@ def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, sc
         if mode == "train" and torch.is_grad_enabled() and capi.deterministic() and any(
                 _planes_need_grad(mdl) or _decoder_needs_grad(mdl) for mdl in (model_coarse, model_fine)):
             capi.refuse_deterministic("training a generic decoder geometry (generic.hip)")
+        if rays_ask:
+            _warn_no_rays_grad(model_fine if Nf > 0 else model_coarse, "a generic decoder geometry")
         return _render_generic(rays, model_coarse, model_fine, m, Nc, Nf, t_rand, u, n_c, n_f, jit_c, jit_f)
     top = model_fine if Nf > 0 else model_coarse
     dec_c_grad = _decoder_needs_grad(model_coarse)
@@ -329,6 +369,21 @@ def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, sc
         capi.refuse_f16_training(model_coarse, model_fine)
     arith_c = capi.resolve_render_arithmetic(model_coarse.arithmetic if force_arith is None else force_arith)
     arith_f = capi.resolve_render_arithmetic(model_fine.arithmetic if force_arith is None else force_arith) if Nf > 0 else arith_c
+    rays_grad = False
+    if rays_ask:
+        if mode != "train":
+            _warn_no_rays_grad(top, "evaluation mode")
+        elif capi.ARITHMETIC["f32"] in (arith_c, arith_f):
+            _warn_no_rays_grad(top, "the 'f32' arithmetic")
+        elif N > 0:
+            rays_grad = True
+            _, fwd_max = _record_limits()
+            if (dec_c_grad and N * Nc > fwd_max) or (dec_f_grad and N * (Nc + Nf) > fwd_max):
+                # (such a pass publishes no gates: its backward recomputes the forward and leaves no rows behind)
+                raise NotImplementedError("rays that require a gradient need the recorded forward: a pass of %d rays x %d samples with decoder gradients "
+                                          "exceeds RECORD_FORWARD_MAX_POINTS = %d; at most %d rays per call fit"
+                                          % (N, Nc + Nf if dec_f_grad else Nc, fwd_max, fwd_max // (Nc + Nf if dec_f_grad else Nc)))
+            train_path = True
     det = train_path and capi.deterministic()
     if det:
         # what the deterministic mode does not cover is refused here, before anything is launched
@@ -381,6 +436,9 @@ def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, sc
                    plane_shapes=[tuple(k.shape) for k in planes_f], plane_leaves=leaves[:4], separate_coarse=bool(leaves_c),
                    plane_shapes_c=[tuple(k.shape) for k in planes_c], plane_leaves_c=leaves_c, coarse_grad=coarse_grad, dec_c_grad=dec_c_grad,
                    dec_f_grad=dec_f_grad, arith_c=arith_c, arith_f=arith_f, det=det)
+        if rays_grad:
+            cfg["rays_grad"] = True
+            leaves = leaves + [rays_leaf]
         outs = _RenderRaysFn.apply(cfg, *leaves)
         if Nf > 0:
             return outs[0], outs[1], outs[2], outs[3], outs[4], outs[5], None, None, None
@@ -597,6 +655,9 @@ def pack_rays(ray_origins, ray_directions, near, far, H=None, W=None, focal=None
     if no_ndc is False:
         from .nerf_helpers import ndc_rays
         ro, rd = ndc_rays(H, W, focal, 1.0, ro, rd)
+    if torch.is_grad_enabled() and (ro.requires_grad or rd.requires_grad or view_src.requires_grad):
+        # origins or directions that require a gradient (camera-pose refinement): the same entry as a differentiable operator
+        return torch.ops.nvsr.pack_rays(ro, rd, None if view_src is rd else view_src, float(near), float(far))
     rays = torch.empty((N, 11), dtype=torch.float32, device=ro.device)
     if N == 0:
         return rays
@@ -809,6 +870,9 @@ def _run_nerf_baseline(b, H, W, focal, model_coarse, model_fine, batch_rays, opt
     model_call = b.model_call(scene_id)
     rays = pack_rays(batch_rays[0], batch_rays[1], _cfg(scene_config, "near"), _cfg(scene_config, "far"), H, W, focal,
                      no_ndc=_cfg(scene_config, "no_ndc"))
+    if torch.is_grad_enabled() and rays.requires_grad:
+        _warn_no_rays_grad(model_fine, "the %s baseline" % b.name)
+    rays = rays.detach()
     N = rays.shape[0]
     m = _cfg(options.nerf, mode)
     Nc, Nf, std, x = int(m.num_coarse), int(m.num_fine), float(m.radiance_field_noise_std), b.extra

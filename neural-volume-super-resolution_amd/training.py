@@ -30,6 +30,10 @@ def get_ray_bundle_at(height, width, focal_length, tform_cam2world, rows_cols, d
     c2w = capi.f32c(tform_cam2world)
     rc = rows_cols.to(device=c2w.device, dtype=torch.int32).contiguous()
     N = rc.shape[0]
+    if torch.is_grad_enabled() and c2w.requires_grad:
+        # a pose that requires a gradient (camera-pose refinement): the same entry as a differentiable operator
+        return torch.ops.nvsr.ray_bundle_at(height, width, float(get_focal(focal_length, "H")), float(get_focal(focal_length, "W")), c2w,
+                                            float(downsampling_offset), rc)
     ro = torch.empty((N, 3), dtype=torch.float32, device=c2w.device)
     rd = torch.empty_like(ro)
     if N == 0:
@@ -460,7 +464,9 @@ class TrainStep:
         sr = getattr(mf, "SR_model", None) if mf is not None else None
         ahead = (self.prologue_ahead and sr is not None and not getattr(mf, "skip_SR_", False) and sr.training and isinstance(self.pixel_sampler, DevicePixelSampler)
                  and self.pixel_sampler.state is None and img_target.is_cuda and torch.is_tensor(pose_target) and pose_target.is_cuda
-                 and mf.is_native_geometry() and not getattr(mf, "point_coords_noise", 0))
+                 and mf.is_native_geometry() and not getattr(mf, "point_coords_noise", 0)
+                 # (a pose that requires a gradient draws in-stream: its rays' autograd nodes belong to the iteration's stream)
+                 and not pose_target.requires_grad)
         if not ahead:
             return draw()
         dev = img_target.device
@@ -602,6 +608,9 @@ class GraphedTrainStep:
         if step.grad_sync is not None:
             raise ValueError("GraphedTrainStep: a data-parallel step (grad_sync) would capture its all-reduces -- RCCL collectives, or the host-staged "
                              "gloo path, inside a HIP graph have never been run on this pool; launch the multi-rank iteration with TrainStep")
+        if torch.is_tensor(pose_target) and pose_target.requires_grad:
+            raise ValueError("GraphedTrainStep: a pose that requires a gradient takes the ordered rows route (DESIGN.md 3.4), which allocates its "
+                             "workspaces per iteration and has never been captured; refine poses with TrainStep")
         if step.vbs != 1:
             raise ValueError("GraphedTrainStep: virtual_batch_size > 1 alternates between two different iterations; capture needs one")
         for o in (step.optimizer, step.SR_optimizer, step.planes_optimizer):

@@ -51,6 +51,8 @@ BENCHMARKED = [
     "generic_backward_fused_record_kernel", "generic_wgrad_kernel",
     # the input gradient of a model call (tools/points_grad_time.py times it)
     "points_grad_kernel", "viewdir_grad_kernel",
+    # the ray / camera-pose gradient of a training render (tools/ray_grad_time.py times it)
+    "rays_grad_kernel", "pack_rays_backward_kernel", "ndc_rays_backward_kernel", "ray_bundle_backward_slab_kernel", "ray_bundle_backward_reduce_kernel",
 ]
 # The gate covers EVERY kernel of the library (round 4; round 3 covered the benchmarked ones): no scratch memory, no spilled VGPRs -- except:
 #   ALLOW  name substring -> spilled VGPRs tolerated.  What is listed is debt, with the round that recorded it:
