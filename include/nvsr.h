@@ -719,6 +719,42 @@ int nvsr_decoder_weight_grad_det_arith(int64_t N, int S, const float* record, fl
 int nvsr_triplane_points_grad(const nvsr_scene* scene, int64_t N, int S, const float* rays, const float* z, const float* const* rows,
                               const float* view_rows, float* d_points, float* d_viewdir, nvsr_stream_t stream);
 
+/* ---- surface normals of a rendered view (csrc/normals.hip) ------------------------------------------------------
+ * The density gradient on the LIVE samples of a pass only, composited per ray with the compositor's weights: normal[ray] = sum_s w_s n_s,
+ * n_s = -g_s / |g_s|, g_s = d sigma_raw / d p at p_s = o + z_s d.  A sample with w != 0 has sigma > 0, so relu' = 1 there and g is the
+ * gradient of sigma.  The sum is NOT renormalised: its length is at most about acc, background pixels go to 0; callers normalise if they want
+ * unit vectors.  The normals live in the coordinate system of the rays passed in (NDC space for an NDC scene).
+ * The route around the two entries (ops.normals_of_pass): nvsr_generic_live_list on weights [N,S] -> index (ascending) and its count;
+ * nvsr_live_ray_points; nvsr_decode_rays_arith with gates on the M one-sample rays; nvsr_render_pass_backward_rows_arith with
+ * g_raw = (0, 0, 0, 1) for the three position planes (no view workspace, no record); nvsr_normals_composite.
+ * Neither entry allocates, synchronises or uses atomics.  Status of both: NVSR_ERR_SHAPE (N < 0, M < 0, S < 1, S > 4096, N * S >= 2^31;
+ * M >= 2^31 for the points, M >= 2^29 for the compositor), then NVSR_OK with nothing launched for M == 0 or N == 0, then NVSR_ERR_NULL (any
+ * pointer; the scene and its planes are checked first by the compositor), NVSR_ERR_ALIGN (rows[d] not 16-byte aligned).
+ *
+ * nvsr_live_ray_points: for list entry i < M with p = index[i], ray = p / S (s = p % S):
+ *   live_rays[i] = [o_k + d_k z[p] (k = 0..2; one __fmul_rn, one __fadd_rn: nvsr_ray_points' position), 0, 0, 0, 0, 0, rays[ray][8..10]]
+ *   -- the one-sample ray (direction 0, near = far = 0; depth 0 is the caller's z) that TwoDimPlanesModel.density_gradient builds per point.
+ *   An index outside [0, N * S) is skipped: its row is not written.
+ *
+ * nvsr_normals_composite: index [M] ASCENDING (int32; entries outside [0, N * S) belong to no ray), live_rays [M,11] (what
+ *   nvsr_live_ray_points wrote for the same M entries), rows: 3 pointers, rows[d] [M][48] = d sigma_raw / d (feature of position plane d) of
+ *   entry i (16-byte aligned, all three required), weights [N,S], normal [N,3]: ACCUMULATED INTO.
+ *   Per ray, its run = the entries i with ray S <= index[i] < (ray + 1) S (two binary searches), in ascending i:
+ *     g = d_points of nvsr_triplane_points_grad above for the point p = live_rays[i][0..2] and the rows rows[d][i]: the same slope, the same
+ *         order, the same NaN rule (the kernels share the device functions, csrc/points_grad_core.h);
+ *     q = (g_0 g_0 + g_1 g_1) + g_2 g_2,  r = sqrt(q);   n_k = +0 if q == 0, else -(g_k / r);   w = weights[index[i]];
+ *     normal[ray][k] = normal[ray][k] + w n_k                        (one __fmul_rn, one __fadd_rn; a ray with an empty run is not touched)
+ *   Every operation is one correctly rounded float operation; NaN propagates: a NaN weight or gradient reaches its own ray and no other.
+ *   The fold is sequential and in place: cutting the live list into slabs at ANY position, mid-ray included -- index, live_rays and the rows
+ *   of entries [a, b) with the whole weights and normal -- and launching the slabs in ascending order on one stream gives the bits of one
+ *   launch over the whole list.
+ *   Roundings on the longest path of one term: g 18 (above), q: 2 g's relative error + 1 + 2 = 3 more on q, halved by the square root, + 1;
+ *   g_k / r: + 1; w n_k: + 1; one per addition of the fold (tests/normals_ref.py derives the bound the tests apply). */
+int nvsr_live_ray_points(int64_t N, int S, int64_t M, const int32_t* index, const float* rays, const float* z, float* live_rays,
+                         nvsr_stream_t stream);
+int nvsr_normals_composite(const nvsr_scene* scene, int64_t N, int S, int64_t M, const int32_t* index, const float* live_rays,
+                           const float* const* rows, const float* weights, float* normal, nvsr_stream_t stream);
+
 /* ---- ray and camera-pose gradients of a training render (csrc/ray_grad.hip) ----------------------------------
  * What consumes d_points / d_viewdir: the packed rays' gradient, then the adjoints of nvsr_pack_rays, nvsr_ndc_rays and
  * nvsr_get_ray_bundle[_at] down to the camera-to-world matrix.  None of these entries allocates, synchronises or uses atomics; each sum has

@@ -285,6 +285,9 @@ _PROTOS_OPTIONAL = {   # feature-plane super-resolution (csrc/sr.hip)
     "nvsr_decoder_weight_grad_det_arith": ([_i64, _i, _vp, _vp, _vp, _i, _vp], _i),
     # input gradients of the tri-plane model (csrc/points_grad.hip)
     "nvsr_triplane_points_grad": ([C.POINTER(Scene), _i64, _i, _vp, _vp, C.POINTER(C.c_void_p), _vp, _vp, _vp, _vp], _i),
+    # surface normals of a rendered view (csrc/normals.hip)
+    "nvsr_live_ray_points": ([_i64, _i, _i64, _vp, _vp, _vp, _vp, _vp], _i),
+    "nvsr_normals_composite": ([C.POINTER(Scene), _i64, _i, _i64, _vp, _vp, C.POINTER(C.c_void_p), _vp, _vp, _vp], _i),
     # ray and camera-pose gradients of a training render (csrc/ray_grad.hip)
     "nvsr_rays_grad": ([_i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp], _i),
     "nvsr_pack_rays_backward": ([_i64, _vp, _vp, _i, _vp, _vp, _vp, _vp], _i),

@@ -1132,6 +1132,120 @@ def decode_rays_backward_with_points(planes, consts, packed, packed_bwd, rays, z
     return grads, d_points, d_viewdir
 
 
+# =====================================================================================================================================
+# depth and surface-normal maps of a rendered view (csrc/normals.hip): opt-in, evaluation only
+# =====================================================================================================================================
+@custom_op("nvsr::render_pass_geometry", mutates_args=(), device_types="cuda")
+def render_pass_geometry(planes: Sequence[Tensor], consts: Sequence[float], packed: Tensor, rays: Tensor, z: Tensor, noise: Optional[Tensor],
+                         white: bool, arithmetic: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """render_pass's call with the compositor's weights AND its expected depth requested:
+    rays [N,11], z [N,S] -> rgb [N,3], disp [N], acc [N], weights [N,S], depth [N] (sum_s w_s z_s)"""
+    rays, z, noise = _c(rays), _c(z), _c(noise)
+    sc = _scene(planes, consts)
+    N, S = z.shape
+    rgb, disp, acc, w, depth = _f(N, 3, like=rays), _f(N, like=rays), _f(N, like=rays), _f(N, S, like=rays), _f(N, like=rays)
+    if N:
+        capi.call("nvsr_render_pass_arith", C.byref(sc), capi.ptr(packed), N, S, capi.ptr(rays), capi.ptr(z), capi.ptr(noise), int(white),
+                  capi.ptr(rgb), capi.ptr(disp), capi.ptr(acc), capi.ptr(w), capi.ptr(depth), None, arithmetic, capi.stream())
+    return rgb, disp, acc, w, depth
+
+
+@render_pass_geometry.register_fake
+def _(planes, consts, packed, rays, z, noise, white, arithmetic):
+    N, S = z.shape
+    return rays.new_empty((N, 3)), rays.new_empty((N,)), rays.new_empty((N,)), rays.new_empty((N, S)), rays.new_empty((N,))
+
+
+def _check_live(who, index, rays, z):
+    capi.require_cuda(index, rays, z)
+    if not (index.dtype == torch.int32 and index.dim() == 1 and index.is_contiguous() and rays.dtype == z.dtype == torch.float32
+            and rays.is_contiguous() and z.is_contiguous() and rays.dim() == 2 and rays.shape[1] == 11 and z.dim() == 2
+            and z.shape[0] == rays.shape[0] and z.shape[1] >= 1):
+        raise ValueError("%s: index [M] int32, rays [N,11] f32, z / weights [N,S >= 1] f32, all contiguous" % who)
+
+
+@custom_op("nvsr::live_ray_points", mutates_args=(), device_types="cuda")
+def live_ray_points(index: Tensor, rays: Tensor, z: Tensor) -> Tensor:
+    """include/nvsr.h, nvsr_live_ray_points: index [M] int32 (entries p = ray * S + s of a live list), rays [N,11], z [N,S] -> one-sample rays
+    [M,11] = [o + d z[p], 0 x 5, viewdir]; the row of an index outside [0, N * S) stays 0."""
+    _check_live("live_ray_points", index, rays, z)
+    N, S = z.shape
+    M = index.shape[0]
+    live = torch.zeros((M, 11), dtype=torch.float32, device=rays.device)
+    capi.call("nvsr_live_ray_points", N, S, M, capi.ptr(index), capi.ptr(rays), capi.ptr(z), capi.ptr(live), capi.stream())
+    return live
+
+
+@live_ray_points.register_fake
+def _(index, rays, z):
+    return rays.new_empty((index.shape[0], 11))
+
+
+@custom_op("nvsr::normals_composite", mutates_args=("normal",), device_types="cuda")
+def normals_composite(planes: Sequence[Tensor], consts: Sequence[float], index: Tensor, live_rays: Tensor, rows: Sequence[Tensor], weights: Tensor,
+                      normal: Tensor) -> None:
+    """include/nvsr.h, nvsr_normals_composite: index [M] int32 ASCENDING, live_rays [M,11] (live_ray_points of the same entries), rows = three
+    tensors [M,48] f32 (the ROWS backward of g_raw = (0, 0, 0, 1) on the one-sample rays), weights [N,S]; normal [N,3] is ADDED INTO, per ray
+    in ascending list order: slabs of one list launched in ascending order give the bits of one launch."""
+    N, S = weights.shape[0], (weights.shape[1] if weights.dim() == 2 else 0)
+    M = index.shape[0] if index.dim() == 1 else -1
+    capi.require_cuda(index, live_rays, weights, normal, *rows)
+    ok = (index.dtype == torch.int32 and M >= 0 and index.is_contiguous() and weights.dim() == 2 and S >= 1 and len(rows) == 3
+          and all(t.dtype == torch.float32 and t.is_contiguous() for t in (live_rays, weights, normal, *rows))
+          and tuple(live_rays.shape) == (M, 11) and tuple(normal.shape) == (N, 3) and all(tuple(r.shape) == (M, PC) for r in rows))
+    if not ok:
+        raise ValueError("normals_composite: index [M] int32, live_rays [M,11], rows three [M,%d], weights [N,S >= 1], normal [N,3]: f32, contiguous" % PC)
+    sc = _scene(planes, consts)
+    rptrs = (C.c_void_p * 3)(*[r.data_ptr() for r in rows])
+    capi.call("nvsr_normals_composite", C.byref(sc), N, S, M, capi.ptr(index), capi.ptr(live_rays), rptrs, capi.ptr(weights), capi.ptr(normal),
+              capi.stream())
+
+
+@normals_composite.register_fake
+def _(planes, consts, index, live_rays, rows, weights, normal):
+    return None
+
+
+def normals_of_pass(planes, consts, packed, packed_bwd, rays, z, weights, arith, slab_points=1 << 20, timers=None):
+    """normal [N,3] = sum_s w_s n_s of one pass (include/nvsr.h, "surface normals"): the live list of `weights` once, its count read on the
+    host once (the only host read), then per slab of slab_points list entries live_ray_points, decode_rays with gates on the one-sample rays,
+    the rows backward of g_raw = (0, 0, 0, 1) (three position planes, no view workspace, no record) and normals_composite.  A slab of 2^20
+    points holds 604 MB of rows; any slab size gives the same bits.  Limb arithmetics only.
+    timers: a dict of lists that receives (start, end) device events per stage ('decode', 'rows', 'composite'; tools/normals_time.py)."""
+    if capi.resolve_decoder_arithmetic(None if arith == capi.ARITH_INHERIT else arith) not in (capi.ARITHMETIC["f16x2"], capi.ARITHMETIC["bf16x3"]):
+        raise NotImplementedError("normals_of_pass: the limb arithmetics 'f16x2' / 'bf16x3' only")
+    rays, z, weights = _c(rays), _c(z), _c(weights)
+    N = z.shape[0]
+    normal = torch.zeros((N, 3), dtype=torch.float32, device=rays.device)
+    if N == 0:
+        return normal
+    nv = torch.ops.nvsr
+    index, count = nv.generic_live_list(weights)
+    M = int(count.item())
+
+    def timed(stage, fn):
+        if timers is None:
+            return fn()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        out = fn()
+        ev[1].record()
+        timers.setdefault(stage, []).append(ev)
+        return out
+
+    for a in range(0, M, int(slab_points)):
+        idx = index[a: min(a + int(slab_points), M)]
+        m = idx.shape[0]
+        live = nv.live_ray_points(idx, rays, z)
+        z0 = torch.zeros((m, 1), dtype=torch.float32, device=rays.device)
+        gates = timed("decode", lambda: nv.decode_rays(planes, consts, packed, live, z0, True, False, arith)[1])
+        g_raw = torch.zeros((m, 1, 4), dtype=torch.float32, device=rays.device)
+        g_raw[..., 3] = 1.0
+        rows = timed("rows", lambda: decode_rays_backward_rows(planes, consts, packed, packed_bwd, live, z0, g_raw, gates, arith))
+        timed("composite", lambda: nv.normals_composite(planes, consts, idx, live, rows, weights, normal))
+    return normal
+
+
 @custom_op("nvsr::decoder_weight_grad", mutates_args=(), device_types="cuda")
 def decoder_weight_grad(record: Tensor, N: int, S: int, arithmetic: int) -> Tensor:
     """one contraction over all points of the record -> weight / bias gradients in state-dict order"""
@@ -2194,7 +2308,7 @@ FORWARD_OPS = ["plane_to_channel_last", "plane_from_channel_last", "pack_decoder
                "pack_generic_decoder_bwd", "ray_points", "lowrank_planes", "ray_bundle", "ray_bundle_at", "ndc_rays", "pack_rays",
                "triplane_density_generic_fused_arith", "triplane_colour_generic_fused_arith", "generic_live_list",
                "generic_occupancy_build", "generic_occupancy_keep", "triplane_density_list_generic_fused_arith",
-               "render_pass", "render_rays", "decode_rays", "composite", "composite_rays", "edsr", "planes_sr", "cumprod_exclusive"]
+               "render_pass_geometry", "live_ray_points", "render_pass", "render_rays", "decode_rays", "composite", "composite_rays", "edsr", "planes_sr", "cumprod_exclusive"]
 
 
 class _Direct:

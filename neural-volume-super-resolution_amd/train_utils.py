@@ -962,6 +962,95 @@ def eval_nerf(height, width, focal_length, model_coarse, model_fine, ray_origins
     return rgb_coarse, None, None, rgb_fine, None, None, rgb_SR, None, None
 
 
+def _geometry_chunk(rays, model_coarse, model_fine, m, force_arith):
+    """depth [n], acc [n], normal [n,3] of the top pass of a ray chunk: coarse depths, the coarse pass with weights and depth, the importance
+    resampling, the fine pass likewise, then the normals of the top pass's live samples (ops.normals_of_pass)"""
+    nv = torch.ops.nvsr
+    Nc, Nf = int(m.num_coarse), int(m.num_fine)
+    white, lindisp = bool(m.white_background), bool(m.lindisp)
+    arith = lambda mdl: capi.resolve_render_arithmetic(mdl.arithmetic if force_arith is None else force_arith)
+    top = model_coarse
+    planes, consts = top.scene_args()            # (a model with SR planes renders its super-resolved planes)
+    z = nv.coarse_z(rays, Nc, lindisp, None)
+    _, _, acc, w, depth = nv.render_pass_geometry(planes, consts, top.packed_decoder(), rays, z, None, white, arith(top))
+    if Nf > 0:
+        z = nv.importance_resample(z, w, Nf, None)
+        top = model_fine
+        planes, consts = top.scene_args()
+        _, _, acc, w, depth = nv.render_pass_geometry(planes, consts, top.packed_decoder(), rays, z, None, white, arith(top))
+    normal = ops.normals_of_pass(planes, consts, top.packed_decoder(), top.packed_decoder_bwd(), rays, z, w, arith(top))
+    return depth, acc, normal
+
+
+def eval_geometry(height, width, focal_length, model_coarse, model_fine, ray_origins, ray_directions, options, scene_id,
+                  mode="validation", scene_config={}):
+    """Depth and surface-normal maps of a view (not in the reference) -> dict(depth [H,W], acc [H,W], normal [H,W,3]) of the
+    fine pass, of the coarse pass when num_fine == 0, rendered as an evaluation frame: no perturbation, no density noise.
+    depth = sum_s w_s z_s, acc = sum_s w_s, normal = sum_s w_s n_s with n_s = -normalize(d sigma / d p) on the samples of nonzero weight
+    (include/nvsr.h, "surface normals").  The normal is NOT renormalised: its length is at most about acc, so background pixels go to 0;
+    normalise it for unit vectors.  It lives in the coordinate system of the rays the passes march: NDC space for a scene with no_ndc False.
+    The shipped decoder geometry in 'f16x2' or 'bf16x3' only; an 'f16x2' chunk that leaves the limbs' range is rendered again in 'bf16x3'
+    like an evaluation render."""
+    m = _cfg(options.nerf, mode)
+    Nf = int(m.num_fine)
+    used = (model_coarse, model_fine) if Nf > 0 else (model_coarse,)
+    limb = (capi.ARITHMETIC["f16x2"], capi.ARITHMETIC["bf16x3"])
+    for mdl in used:
+        if not isinstance(mdl, models.TwoDimPlanesModel):
+            raise NotImplementedError("eval_geometry: the tri-plane model only (got a %s: the NeRF baselines have no density-gradient route)"
+                                      % type(mdl).__name__)
+        if not mdl.is_native_geometry():
+            raise NotImplementedError("eval_geometry: the shipped decoder geometry only (this model runs a generic one)")
+        code = capi.resolve_render_arithmetic(mdl.arithmetic)
+        if code not in limb:
+            name = {v: k for k, v in capi.RENDER_ARITHMETIC.items()}.get(code, code)
+            raise NotImplementedError("eval_geometry: the limb arithmetics 'f16x2' / 'bf16x3' only (this model resolves to %r)" % name)
+    if not options.nerf.use_viewdirs:
+        raise NotImplementedError("the decoder kernel expects use_viewdirs=True (all shipped configs)")
+    rays = pack_rays(ray_origins.reshape(-1, 3), ray_directions.reshape(-1, 3), _cfg(scene_config, "near"), _cfg(scene_config, "far"), height, width,
+                     focal_length, no_ndc=_cfg(scene_config, "no_ndc"))
+    N = rays.shape[0]
+    for mdl in used:
+        mdl.set_cur_scene_id(scene_id)
+    top = used[-1]
+    range_checked = N > 0 and _f16_in_play(*used)
+    key = _range_key(*used) if range_checked else None
+    flag = capi.range_flag(rays.device) if range_checked else None
+    outs, sr_changed, rendered = [], [], False
+    try:
+        with torch.no_grad():
+            for a in range(0, max(N, 1), MAX_RAYS_PER_LAUNCH):
+                sub = rays[a: min(a + MAX_RAYS_PER_LAUNCH, N)]
+                if range_checked and top.__dict__.get("_f16_unfit") == key:
+                    if not sr_changed and top.__dict__.get("_f16_unfit_bits", 3) & 2:
+                        sr_changed = _sr_fallback(*used)
+                    outs.append(_geometry_chunk(sub, model_coarse, model_fine, m, "bf16x3"))
+                    continue
+                if range_checked:
+                    flag.reset()
+                out = _geometry_chunk(sub, model_coarse, model_fine, m, None)
+                bits = capi.RangeFlag.raised(flag.read_async()) if range_checked else 0
+                if bits:
+                    if not top.__dict__.get("_f16_unfit_warned"):
+                        import warnings
+                        warnings.warn("weights, plane values or activations beyond NVSR_ARITH_F16X2's range (|W| < 255, |feature / activation| < 4094): "
+                                      "this model renders in 'bf16x3' while its parameters stay as they are (set model.arithmetic = 'bf16x3' to "
+                                      "render there in the first place)")
+                        top.__dict__["_f16_unfit_warned"] = True
+                    top.__dict__["_f16_unfit"] = key
+                    top.__dict__["_f16_unfit_bits"] = int(bits)
+                    if bits & 2:
+                        sr_changed = _sr_fallback(*used, redo=True)
+                    out = _geometry_chunk(sub, model_coarse, model_fine, m, "bf16x3")
+                    flag.reset()
+                outs.append(out)
+        rendered = True
+    finally:
+        _sr_restore(sr_changed, rendered)
+    depth, acc, normal = (torch.cat([o[i] for o in outs], 0) for i in range(3))
+    return dict(depth=depth.reshape(height, width), acc=acc.reshape(height, width), normal=normal.reshape(height, width, 3))
+
+
 def find_latest_checkpoint(ckpt_path, sr, find_best=False):
     """train_utils.py:333-345 (implemented with the rest of the store protocol in plane_store.py)"""
     from .plane_store import find_latest_checkpoint as impl

@@ -17,7 +17,7 @@ import torch
 
 from . import capi
 from .nerf_helpers import get_focal, img2mse, mse2psnr
-from .train_utils import _cfg, eval_nerf, pack_rays, run_one_iter_of_nerf
+from .train_utils import _cfg, eval_geometry, eval_nerf, pack_rays, run_one_iter_of_nerf
 
 
 def downsampling_offset(ds_factor):
@@ -721,9 +721,11 @@ class GraphedTrainStep:
 
 
 def evaluate_view(model_coarse, model_fine, options, scene_id, scene_config, img_target, pose_target, H, W, focal, cur_ds_factor=1,
-                  SR_model=None, sr_scene=False, ds_factor=1, im_inconsistency=False):
+                  SR_model=None, sr_scene=False, ds_factor=1, im_inconsistency=False, geometry=False):
     """One view of evaluate() (train_nerf.py:655-713): render; on an SR scene render again with the SR model bypassed as the
-    reference image, and report the SR PSNR gain.  -> dict of images and metrics (python floats)."""
+    reference image, and report the SR PSNR gain.  -> dict of images and metrics (python floats).
+    geometry (not in the reference): also attach eval_geometry's depth, acc and normal maps of the view as rendered first (with the SR model
+    when there is one) under res["geometry"]; False runs exactly the launches of a call without the argument."""
     for m in (model_coarse, model_fine, SR_model):
         if m is not None:
             m.eval()
@@ -737,6 +739,8 @@ def evaluate_view(model_coarse, model_fine, options, scene_id, scene_config, img
             return rgb_c, rgb_f, rgb_sr
 
         rgb_coarse, rgb_fine, rgb_SR = render_view()
+        geo = eval_geometry(H, W, focal, model_coarse, model_fine, ro, rd, options, scene_id, mode="validation",
+                            scene_config=scene_config) if geometry else None
         tgt = img_target[..., :3]
         res = dict(loss=img2mse(rgb_fine[..., :3], tgt).item())
         res["psnr"] = mse2psnr(res["loss"])
@@ -760,4 +764,6 @@ def evaluate_view(model_coarse, model_fine, options, scene_id, scene_config, img
         if SR_model is not None:
             SR_model.clear_SR_planes()       # evaluate() drops the cached super-resolved planes when it is done with a scene (:714-718)
         res.update(rgb_coarse=rgb_coarse, rgb_fine=rgb_fine, rgb_SR=rgb_SR)
+        if geo is not None:
+            res["geometry"] = geo
         return res

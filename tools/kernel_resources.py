@@ -51,6 +51,8 @@ BENCHMARKED = [
     "generic_backward_fused_record_kernel", "generic_wgrad_kernel",
     # the input gradient of a model call (tools/points_grad_time.py times it)
     "points_grad_kernel", "viewdir_grad_kernel",
+    # depth / normal maps of a view (tools/normals_time.py times it): the live samples as one-sample rays, the slope composited per ray
+    "live_ray_points_kernel", "normals_composite_kernel",
     # the ray / camera-pose gradient of a training render (tools/ray_grad_time.py times it)
     "rays_grad_kernel", "pack_rays_backward_kernel", "ndc_rays_backward_kernel", "ray_bundle_backward_slab_kernel", "ray_bundle_backward_reduce_kernel",
 ]
