@@ -1123,9 +1123,11 @@ class _DecodePointsFn(torch.autograd.Function):
     """TwoDimPlanesModel.forward on a list of points with gradients for the planes, the decoder and -- in the limb arithmetics -- the
     points themselves.  The points are handed to the ray-tiled training kernels as one-sample rays (origin = point, direction = 0,
     depth = 0): decode with published ReLU gates (+ the layer-input record when the decoder trains), gate-driven backward, weight-gradient
-    contraction.  Points that require a gradient take the rows route once, whatever the deterministic mode says: the same
-    rows feed the ordered scatter into the planes and torch.ops.nvsr.triplane_points_grad.  The position columns are the TRUE derivative
-    (the reference projects under no_grad and returns 0 there)."""
+    contraction.  The backward adds into one set of zero-filled gradient planes on the route ops.gate_route names (ops.gate_backward_, as
+    train_utils._RenderRaysFn does per pass): points that require a gradient take the rows route once, whatever the deterministic mode says
+     -- the same rows feed the ordered scatter into the planes and torch.ops.nvsr.triplane_points_grad -- and the record is
+    contracted by the mode's own weight-gradient operator.  The position columns are the TRUE derivative (the reference projects under
+    no_grad and returns 0 there)."""
 
     @staticmethod
     def forward(ctx, model, x, p0, p1, p2, pv, nat):
@@ -1157,16 +1159,13 @@ class _DecodePointsFn(torch.autograd.Function):
             return (None,) * 7
         g_raw = capi.f32c(g_out).reshape(P, 1, 4)
         nv = torch.ops.nvsr
-        bwd, wgrad = ((nv.decode_rays_backward_det, lambda *a: nv.decoder_weight_grad_det(*a, None)) if ctx.det else
-                      (nv.decode_rays_backward, nv.decoder_weight_grad))
-        gx = None
-        if need_x:
-            gplanes, d_points, d_viewdir = ops.decode_rays_backward_with_points(planes_cl, consts, model.packed_decoder(), model.packed_decoder_bwd(),
-                                                                                rays, z, g_raw, gates, rec, need_planes, arith)
-            gx = torch.cat([d_points, d_viewdir], -1)
-        else:
-            gplanes = bwd(planes_cl, consts, model.packed_decoder(), model.packed_decoder_bwd(), rays, z, g_raw, gates, rec, need_planes, arith)
-        gnat = wgrad(rec, P, 1, arith) if (rec is not None and need[6]) else None
+        gplanes = ops.zero_planes_like(planes_cl, need_planes, rays)
+        gx = ops.gate_backward_(nv, ops.gate_route(ctx.det, need_x), planes_cl, consts, model.packed_decoder(), model.packed_decoder_bwd(), rays, z, g_raw,
+                                gates, rec, need_planes, arith, gplanes)
+        gx = None if gx is None else torch.cat(gx, -1)
+        gnat = None
+        if rec is not None and need[6]:      # (the weight gradient contracts in the MODE's operator, also behind points that took the ordered route)
+            gnat = nv.decoder_weight_grad_det(rec, P, 1, arith, None) if ctx.det else nv.decoder_weight_grad(rec, P, 1, arith)
         return (None, gx) + tuple(from_channel_last(g, like=p_) if n else None for g, p_, n in zip(gplanes, ctx.plane_srcs, need_planes)) + (gnat,)
 
 

@@ -853,6 +853,16 @@ def zero_planes_like(planes, need, like):
     return out
 
 
+def _check_grads_layout(who, planes, need, grads, contiguous):
+    """the gradient planes an in-place backward adds into: float32 CUDA tensors shaped like the planes `need` names, with the planes' strides
+    (the atomic kernel indexes both alike) or, contiguous=True, dense (nvsr_rows_scatter's layout)"""
+    for d, (g, p) in enumerate(zip(grads, planes)):
+        if need[d] and (g.shape != p.shape or g.dtype != torch.float32 or not g.is_cuda
+                        or not (g.is_contiguous() if contiguous else g.stride() == p.stride())):
+            raise ValueError("%s: grads[%d] must be a %sfloat32 CUDA tensor %s planes[%d]"
+                             % (who, d, "contiguous " if contiguous else "", "shaped like" if contiguous else "laid out like", d))
+
+
 @custom_op("nvsr::decode_rays_backward", mutates_args=("record",), device_types="cuda")
 def decode_rays_backward(planes: Sequence[Tensor], consts: Sequence[float], packed: Tensor, packed_bwd: Tensor, rays: Tensor, z: Tensor,
                          g_raw: Tensor, gates: Tensor, record: Optional[Tensor], need: Sequence[bool], arithmetic: int) -> List[Tensor]:
@@ -876,9 +886,7 @@ def decode_rays_backward_(planes: Sequence[Tensor], consts: Sequence[float], pac
     """decode_rays_backward ACCUMULATING into existing gradient planes (`grads`: what the functional form returned for an earlier pass over
     the same planes): the fine pass of a training step scatters into the coarse pass's buffers instead of zero-filling a second set of
     full-size planes and adding the two (the reference's autograd accumulates into one .grad the same way)."""
-    for d, (g, p) in enumerate(zip(grads, planes)):
-        if need[d] and (g.shape != p.shape or g.stride() != p.stride() or g.dtype != torch.float32 or not g.is_cuda):
-            raise ValueError("decode_rays_backward_: grads[%d] must be a float32 CUDA tensor laid out like planes[%d]" % (d, d))
+    _check_grads_layout("decode_rays_backward_", planes, need, grads, contiguous=False)
     _decode_rays_backward_launch(planes, consts, packed, packed_bwd, rays, z, g_raw, gates, record, need, arithmetic, grads)
 
 
@@ -1001,28 +1009,13 @@ def _rows_scatter_tail(sc, planes, rays, z, rows, view_ws, need, grads, want_vie
     return view_rows
 
 
-def _decode_rays_backward_det_launch(planes, consts, packed, packed_bwd, rays, z, g_raw, gates, record, need, arithmetic, grads):
-    """the gate-driven backward ADDING into `grads` in a fixed order: rows backward, then per wanted position plane taps + ordered scatter,
-    then the view plane (reduce-only kernel, taps per ray, ordered scatter with M = N).  One stream, in this order."""
-    _require_limb_arithmetic(arithmetic, "the gate-driven backward")
-    rays, z, g_raw = _c(rays), _c(z), _c(g_raw)
-    sc = _scene(planes, consts)
-    N, S = z.shape
-    if N == 0 or (not any(need) and record is None):
-        return
-    rows, view_ws = _rows_backward_launch(sc, packed, packed_bwd, rays, z, g_raw, gates, record, need, arithmetic)
-    _rows_scatter_tail(sc, planes, rays, z, rows, view_ws, need, grads)
-
-
 @custom_op("nvsr::decode_rays_backward_det", mutates_args=("record",), device_types="cuda")
 def decode_rays_backward_det(planes: Sequence[Tensor], consts: Sequence[float], packed: Tensor, packed_bwd: Tensor, rays: Tensor, z: Tensor,
                              g_raw: Tensor, gates: Tensor, record: Optional[Tensor], need: Sequence[bool], arithmetic: int) -> List[Tensor]:
     """decode_rays_backward without float atomics: the same gradient planes, every texel summed in a fixed order (two calls on the same inputs
     return the same bits).  Limb arithmetics only ('f32' raises)."""
     _require_limb_arithmetic(arithmetic, "decode_rays_backward_det")
-    grads = [torch.zeros_like(p) if need[d] else _f(0, like=rays) for d, p in enumerate(planes)]
-    _decode_rays_backward_det_launch(planes, consts, packed, packed_bwd, rays, z, g_raw, gates, record, need, arithmetic, grads)
-    return grads
+    return decode_rays_backward_with_points(planes, consts, packed, packed_bwd, rays, z, g_raw, gates, record, need, arithmetic, points=False)[0]
 
 
 @decode_rays_backward_det.register_fake
@@ -1037,10 +1030,8 @@ def decode_rays_backward_det_(planes: Sequence[Tensor], consts: Sequence[float],
     """decode_rays_backward_det ACCUMULATING into existing gradient planes: every texel this pass touches receives g + s, s being the sum
     the functional form would have returned for it -- pass 2 onto pass 1's planes equals the sum of the two functional results bit for bit."""
     _require_limb_arithmetic(arithmetic, "decode_rays_backward_det_")
-    for d, (g, p) in enumerate(zip(grads, planes)):
-        if need[d] and (g.shape != p.shape or not g.is_contiguous() or g.dtype != torch.float32 or not g.is_cuda):
-            raise ValueError("decode_rays_backward_det_: grads[%d] must be a contiguous float32 CUDA tensor shaped like planes[%d]" % (d, d))
-    _decode_rays_backward_det_launch(planes, consts, packed, packed_bwd, rays, z, g_raw, gates, record, need, arithmetic, grads)
+    _check_grads_layout("decode_rays_backward_det_", planes, need, grads, contiguous=True)
+    decode_rays_backward_with_points(planes, consts, packed, packed_bwd, rays, z, g_raw, gates, record, need, arithmetic, grads, points=False)
 
 
 @decode_rays_backward_det_.register_fake
@@ -1113,23 +1104,48 @@ def decode_rays_backward_rows(planes, consts, packed, packed_bwd, rays, z, g_raw
     return _rows_backward_launch(_scene(planes, consts), packed, packed_bwd, rays, z, g_raw, gates, None, (True, True, True, False), arithmetic)[0]
 
 
-def decode_rays_backward_with_points(planes, consts, packed, packed_bwd, rays, z, g_raw, gates, record, need, arithmetic, grads=None):
-    """the gate-driven backward when the points need their gradient too: ONE rows launch feeds the ordered scatter into the planes `need`
-    names (_decode_rays_backward_det_launch's tail), the record, and triplane_points_grad.  grads: existing gradient planes to ADD into, as
-    decode_rays_backward_det_ does (a second pass onto the first pass's planes); None: fresh zero-filled ones.
-    -> (gradient planes as decode_rays_backward_det returns them, d_points [N*S,3], d_viewdir [N,3])"""
-    _require_limb_arithmetic(arithmetic, "the input gradient of a model call")
+def decode_rays_backward_with_points(planes, consts, packed, packed_bwd, rays, z, g_raw, gates, record, need, arithmetic, grads=None, points=True):
+    """the launcher of the ordered route, one stream, in this order: ONE rows launch (with `record` the pre-activation gradients are added to
+    it), then per position plane `need` names taps + ordered scatter, then the view plane (reduce-only kernel, taps per ray, ordered scatter
+    with M = N); points=True: the points need their gradient too -- the rows of all four planes, which also feed triplane_points_grad.
+    grads: existing gradient planes to ADD into (a second pass onto the first pass's planes); None: fresh zero-filled ones.
+    -> (gradient planes as decode_rays_backward_det returns them, d_points [N*S,3], d_viewdir [N,3]; both None without `points`)"""
+    _require_limb_arithmetic(arithmetic, "the input gradient of a model call" if points else "the gate-driven backward")
     rays, z, g_raw = _c(rays), _c(z), _c(g_raw)
     sc = _scene(planes, consts)
     N, S = z.shape
     if grads is None:
         grads = [torch.zeros_like(p) if need[d] else _f(0, like=rays) for d, p in enumerate(planes)]
+    if not points and (N == 0 or (not any(need) and record is None)):
+        return grads, None, None
     if N == 0:
         return grads, _f(0, 3, like=rays), _f(0, 3, like=rays)
-    rows, view_ws = _rows_backward_launch(sc, packed, packed_bwd, rays, z, g_raw, gates, record, (True,) * 4, arithmetic)
-    view_rows = _rows_scatter_tail(sc, planes, rays, z, rows, view_ws, need, grads, want_view_rows=True)
+    rows, view_ws = _rows_backward_launch(sc, packed, packed_bwd, rays, z, g_raw, gates, record, (True,) * 4 if points else need, arithmetic)
+    view_rows = _rows_scatter_tail(sc, planes, rays, z, rows, view_ws, need, grads, want_view_rows=points)
+    if not points:
+        return grads, None, None
     d_points, d_viewdir = torch.ops.nvsr.triplane_points_grad(planes, consts, rays, z, rows, view_rows)
     return grads, d_points, d_viewdir
+
+
+ATOMIC, ORDERED, ORDERED_POINTS = "atomic", "ordered", "ordered with points"
+
+
+def gate_route(det, points):
+    """the route of a gate-driven backward: points (or rays) that need a gradient take the ordered route once, whatever the deterministic mode
+    says; otherwise the mode decides between the ordered scatter and the float atomics"""
+    return ORDERED_POINTS if points else ORDERED if det else ATOMIC
+
+
+def gate_backward_(nv, route, planes, consts, packed, packed_bwd, rays, z, g_raw, gates, record, need, arithmetic, grads):
+    """the gate-driven backward of one pass on `route` (gate_route), ADDING into the gradient planes `grads` (zero_planes_like: entries of
+    planes that need no gradient are ignored) and, with `record`, the gradient half into it; nv: the operator namespace (torch.ops.nvsr, or
+    `direct`).  -> (d_points [N*S,3], d_viewdir [N,3]) on ORDERED_POINTS, else None"""
+    if route == ORDERED_POINTS:
+        return decode_rays_backward_with_points(planes, consts, packed, packed_bwd, rays, z, g_raw, gates, record, need, arithmetic, grads)[1:]
+    op = nv.decode_rays_backward_det_ if route == ORDERED else nv.decode_rays_backward_
+    op(planes, consts, packed, packed_bwd, rays, z, g_raw, gates, record, need, arithmetic, grads)
+    return None
 
 
 # =====================================================================================================================================

@@ -5,7 +5,7 @@ ray-chunk and point-chunk Python loops of the reference collapse into one `nvsr_
 depths -> fused coarse pass -> inverse-CDF resampling + sort -> fused fine pass, all on the current stream."""
 import ctypes as C
 import os
-from typing import Callable, NamedTuple
+from typing import Callable, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -80,201 +80,190 @@ def _NV():
     return torch.ops.nvsr if os.environ.get("NVSR_OPS_DISPATCH") == "1" else ops.direct
 
 
-class _RenderRaysFn(torch.autograd.Function):
-    """Differentiable predict_and_render_radiance, written against torch.ops.nvsr.*.  Leaves: the four planes of the current scene and
-    the decoder parameters of the coarse / fine model, the latter as flat blobs in state-dict order
-    (`TwoDimPlanesModel.natural_blob(differentiable=True)`; torch's own cat/reshape backward hands the slices to the parameters).
+class _Pass(NamedTuple):
+    """One pass (coarse or fine) of a training render, built once in predict_and_render_radiance: data only.  The host facts come first
+    (_pass_facts: known, and checked by _refuse_untrainable, before anything is launched); the tensors follow."""
+    S: int                          # samples per ray
+    arith: int                      # the arithmetic of its forward, handed to every backward operator
+    noise: Optional[torch.Tensor]
+    dec_grad: bool                  # its decoder takes a gradient
+    records: bool                   # ... and its forward records the layer inputs (9.2 KB per point): N * S <= RECORD_FORWARD_MAX_POINTS.
+    #                                 A pass with dec_grad that does not record publishes no gates: its backward recomputes the forward.
+    planes: Sequence = ()           # channel-last, detached
+    packed: Optional[torch.Tensor] = None
+    packed_bwd: Optional[torch.Tensor] = None
+    leaves: Sequence = ()           # the plane leaves its gradient planes go back to, and the planes' shapes
+    shapes: Sequence = ()
 
-    forward  = coarse_z -> decode_rays + composite_rays (keeps raw + weights) -> importance_resample (no gradient, train_utils.py:153)
-               -> fine decode_rays + composite_rays (keeps raw);
-    backward = per pass: composite_backward (wave per ray) -> decode_rays_backward (MFMA + plane scatter)
-               [+ record of layer inputs / deltas -> decoder_weight_grad].
-    With cfg["rays_grad"] the packed rays are one more leaf, the last input (camera-pose refinement): each pass's backward
-    then takes the rows route once -- decode_rays_backward_with_points -> rays_grad, coarse first, fine accumulating.
-    The arithmetic the forward ran in is stored with the context and handed to every backward operator."""
+
+def _pass_facts(N, S, arith, noise, dec_grad, fwd_max):
+    """the host facts of a pass; the ONE place that asks whether a pass of N x S points fits a forward record"""
+    return _Pass(S, arith, noise, dec_grad, dec_grad and N * S <= fwd_max)
+
+
+def _refuse_untrainable(models, N, passes, rays_grad, det, fwd_max):
+    """what a training render does not cover, refused before anything is launched: the 'f16' arithmetic; rays that need a gradient, or the
+    deterministic mode, with a pass whose backward would recompute the forward (it leaves no rows behind, and adds with float atomics); the
+    deterministic mode in 'f32'"""
+    capi.refuse_f16_training(*models)
+    recomputing = [p.S for p in passes if p.dec_grad and not p.records]
+    if rays_grad and recomputing:
+        raise NotImplementedError("rays that require a gradient need the recorded forward: a pass of %d rays x %d samples with decoder gradients "
+                                  "exceeds RECORD_FORWARD_MAX_POINTS = %d; at most %d rays per call fit"
+                                  % (N, recomputing[-1], fwd_max, fwd_max // recomputing[-1]))
+    if det and capi.ARITHMETIC["f32"] in [p.arith for p in passes]:
+        capi.refuse_deterministic("a training step in the 'f32' arithmetic")
+    if det and recomputing:
+        capi.refuse_deterministic("a pass of more than RECORD_FORWARD_MAX_POINTS points with decoder gradients (its backward recomputes the "
+                                  "forward: decode_rays_backward_recompute)")
+
+
+class _RenderRaysFn(torch.autograd.Function):
+    """Differentiable predict_and_render_radiance, written against torch.ops.nvsr.*.  Inputs: cfg (what the passes share), passes ([coarse] or
+    [coarse, fine], _Pass), then the leaves: the four planes the last pass samples, the decoder parameters of the coarse / fine model as flat
+    blobs in state-dict order (`TwoDimPlanesModel.natural_blob(differentiable=True)`; torch's own cat/reshape backward hands the slices to the
+    parameters), the four planes of the coarse pass where they are other tensors (passes[0].leaves is not passes[-1].leaves: the reference's
+    default SR training, train_nerf.py:554-561 with apply_2_coarse False -- only the fine model super-resolves, the coarse model samples the LR
+    planes) and, with cfg["rays_grad"], the packed rays (camera-pose refinement; the kernels read cfg["rays"], the same values
+    detached).
+
+    forward  = coarse_z, then per pass: [importance_resample (no gradient, train_utils.py:153) ->] decode_rays -> composite_rays;
+    backward = per pass: composite_backward (wave per ray) -> the gate-driven backward on the step's route (ops.gate_backward_: atomic,
+               ordered in deterministic mode, ordered with points when the rays need their gradient -> rays_grad, coarse first, fine
+               accumulating) [-> decoder_weight_grad on the forward's record]; a pass that published no gates recomputes its forward
+               (decode_rays_backward_recompute).  All passes over one set of plane leaves add into ONE set of zero-filled gradient planes."""
 
     @staticmethod
-    def forward(ctx, cfg, p0, p1, p2, pv, nat_c, nat_f, *coarse_leaves):
-        # coarse_leaves: the four planes the COARSE pass samples when they are other tensors than the fine pass's p0..pv -- the reference's default
-        # SR training (train_nerf.py:554-561, apply_2_coarse False): only the fine model super-resolves, the coarse model samples the LR planes
-        # cfg["rays_grad"]: the packed rays need their gradient (camera-pose refinement, DESIGN.md 3.4): they are the LAST input, a leaf of
-        # the graph; the kernels read cfg["rays"], the same values detached
-        if cfg.get("rays_grad"):
-            coarse_leaves = coarse_leaves[:-1]
-        N, Nc, Nf, rays = cfg["N"], cfg["Nc"], cfg["Nf"], cfg["rays"]
+    def forward(ctx, cfg, passes, p0, p1, p2, pv, nat_c, nat_f, *more_leaves):
+        rays, white = cfg["rays"], bool(cfg["white"])
         nv = _NV()
-        arith_c, arith_f = cfg["arith_c"], cfg["arith_f"]
         # an output the loss does not use hands None to backward() instead of a zero tensor: the disparity / opacity chain rules are
         # skipped for them (a dozen per-ray kernels per pass otherwise)
         ctx.set_materialize_grads(False)
-        _, fwd_max = _record_limits()
-        z_c = nv.coarse_z(rays, Nc, bool(cfg["lindisp"]), cfg["t_rand"])
         # training batches are a few thousand rays: the sample-parallel decoder + the wave-per-ray compositor fill the chip, the fused
         # per-ray kernel would run 32 workgroups; raw is needed by the backward anyway.  The forward publishes its ReLU gates (128 B per
         # point) so that the backward does not recompute it; when decoder gradients are wanted it also records every layer's input
-        # (9.2 KB per point) unless the pass is too large for that
-        def flags(S, dec_grad):
-            fwd_rec = dec_grad and N * S <= fwd_max
-            return (fwd_rec or not dec_grad), fwd_rec
-
-        def none_if_empty(t):
-            return t if t.numel() else None
-
-        want_g, want_r = flags(Nc, cfg["dec_c_grad"] and cfg["coarse_grad"])
-        raw_c, gates_c, rec_c = nv.decode_rays(cfg["planes_c"], cfg["consts"], cfg["packed_c"], rays, z_c, want_g, want_r, arith_c)
-        rgb_c, disp_c, acc_c, w_c = nv.composite_rays(raw_c, z_c, rays, cfg["noise_c"], bool(cfg["white"]), True)
-        outs = [rgb_c, disp_c, acc_c]
-        saved = dict(z_c=z_c, raw_c=raw_c, gates_c=none_if_empty(gates_c), rec_c=none_if_empty(rec_c))
-        if Nf > 0:
-            z_f = nv.importance_resample(z_c, w_c, Nf, cfg["u"])
-            want_g, want_r = flags(Nc + Nf, cfg["dec_f_grad"])
-            raw_f, gates_f, rec_f = nv.decode_rays(cfg["planes_f"], cfg["consts"], cfg["packed_f"], rays, z_f, want_g, want_r, arith_f)
-            rgb_f, disp_f, acc_f, _ = nv.composite_rays(raw_f, z_f, rays, cfg["noise_f"], bool(cfg["white"]), False)
-            outs += [rgb_f, disp_f, acc_f]
-            saved.update(z_f=z_f, raw_f=raw_f, gates_f=none_if_empty(gates_f), rec_f=none_if_empty(rec_f))
-        ctx.cfg, ctx.saved = cfg, saved          # (ctx.saved is also what the parity tests read the fine depths from)
-        # disp_map is differentiable like the reference's (volume_rendering_utils.py:46): its gradient is folded into those of depth / acc
-        # (detached views: the outputs themselves would close a reference cycle ctx -> saved -> output -> grad_fn -> ctx, and every step's
-        #  7 GB of forward record would wait for the cyclic garbage collector)
-        saved.update(disp_c=disp_c.detach(), acc_c=acc_c.detach())
-        if Nf > 0:
-            saved.update(disp_f=disp_f.detach(), acc_f=acc_f.detach())
+        # (9.2 KB per point) unless the pass is too large for that (_Pass.records)
+        z = nv.coarse_z(rays, passes[0].S, bool(cfg["lindisp"]), cfg["t_rand"])
+        outs, saved, guarded = [], {}, [rays]
+        for k, p in zip("cf", passes):
+            if k == "f":
+                z = nv.importance_resample(z, w, p.S - passes[0].S, cfg["u"])
+            raw, gates, rec = nv.decode_rays(p.planes, cfg["consts"], p.packed, rays, z, p.records or not p.dec_grad, p.records, p.arith)
+            rgb, disp, acc, w = nv.composite_rays(raw, z, rays, p.noise, white, k == "c")
+            outs += [rgb, disp, acc]
+            # disp_map is differentiable like the reference's (volume_rendering_utils.py:46): its gradient is folded into those of depth / acc
+            # (detached views: the outputs themselves would close a reference cycle ctx -> saved -> output -> grad_fn -> ctx, and every step's
+            #  7 GB of forward record would wait for the cyclic garbage collector)
+            saved.update({"z_" + k: z, "raw_" + k: raw, "gates_" + k: gates if gates.numel() else None, "rec_" + k: rec if rec.numel() else None,
+                          "disp_" + k: disp.detach(), "acc_" + k: acc.detach()})
+            guarded += [*p.planes, p.packed]
+        ctx.cfg, ctx.passes, ctx.saved = cfg, passes, saved          # (ctx.saved is also what the parity tests read the fine depths from)
         # autograd's version check: everything the backward reads -- the forward's intermediates and the channel-last planes (views of the
         # plane parameters, sharing their version counters) -- also goes through save_for_backward, so an in-place update of a plane or of a
         # saved tensor between forward and backward raises instead of producing the gradient of another function
-        guarded = [t for t in list(saved.values()) + list(cfg["planes_c"]) + list(cfg["planes_f"]) + [rays, cfg["packed_c"], cfg["packed_f"]]
-                   if isinstance(t, torch.Tensor)]
-        ctx.save_for_backward(*guarded)
-        if not cfg["coarse_grad"] and Nf > 0:
-            ctx.mark_non_differentiable(rgb_c, disp_c, acc_c)     # the coarse pass ran under the model's optional_no_grad (train_nerf.py:560)
+        ctx.save_for_backward(*[t for t in guarded + list(saved.values()) if isinstance(t, torch.Tensor)])
+        if not cfg["coarse_grad"] and len(passes) > 1:
+            ctx.mark_non_differentiable(*outs[:3])     # the coarse pass ran under the model's optional_no_grad (train_nerf.py:560)
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *grads):
         ctx.saved_tensors          # (raises if a tensor saved by the forward was modified in place since)
-        cfg, sv = ctx.cfg, ctx.saved
-        N, Nc, Nf, rays = cfg["N"], cfg["Nc"], cfg["Nf"], cfg["rays"]
+        cfg, passes, sv = ctx.cfg, ctx.passes, ctx.saved
+        N, rays, consts, white = cfg["N"], cfg["rays"], cfg["consts"], bool(cfg["white"])
         nv = _NV()
         dev = rays.device
-        need = ctx.needs_input_grad
-        sep = bool(cfg.get("separate_coarse"))                 # the coarse pass has plane leaves of its own (inputs 7..10)
-        need_planes_f = [bool(n) for n in need[1:5]]
-        need_planes_c = [bool(n) for n in need[7:11]] if sep else need_planes_f
-        gplanes_f = [None, None, None, None]
-        gplanes_c = [None, None, None, None] if sep else gplanes_f
-        det = bool(cfg.get("det"))
-        # rays that need their gradient: each pass takes the rows route once, whatever the deterministic mode says (the rule of
-        # models._DecodePointsFn): ONE rows launch feeds the ordered scatter into the planes, the record and triplane_points_grad, then
-        # rays_grad reduces the points' gradient per ray -- coarse writes d_rays, fine adds, on one stream
-        need_rays = bool(cfg.get("rays_grad")) and bool(need[-1])
-        ray_out = []                                             # [d_rays] once a pass has written it
+        need = ctx.needs_input_grad          # of: cfg, passes, p0..pv (2..5), nat_c, nat_f (6, 7), the coarse pass's own planes (8..11), the rays (last)
+        top = passes[-1]
+        # per set of plane leaves: which planes need a gradient, and their gradient planes (channel-last; every pass over the set ADDS into them)
+        sets = {id(top.leaves): ([bool(n) for n in need[2:6]], [None] * 4)}
+        sets.setdefault(id(passes[0].leaves), ([bool(n) for n in need[8:12]], [None] * 4))
+        need_rays = bool(cfg["rays_grad"]) and bool(need[-1])
+        # rays that need their gradient: ONE rows launch per pass feeds the ordered scatter into the planes, the record and
+        # triplane_points_grad, then rays_grad reduces the points' gradient per ray -- coarse writes d_rays, fine adds, on one stream
+        route = ops.gate_route(cfg["det"], need_rays)
+        d_rays = []                                              # [d_rays] once a pass has written it
 
-        def one_pass(S, z, raw, noise, planes, packed, packed_bwd, g_rgb, g_disp, g_acc, disp, acc, want_dec, gates, fwd_rec, arith, need_planes, gplanes):
-            """-> decoder gradient of this pass (state-dict order) or None; plane gradients are added into `gplanes`"""
-            def add_planes(gs):
-                for d, g in enumerate(gs):
-                    if need_planes[d]:
-                        gplanes[d] = g if gplanes[d] is None else gplanes[d].add_(g)
+        def zero_planes(p):
+            """the gradient planes of pass p's leaves, zero-filled in one allocation by the first pass that scatters into them"""
+            need_planes, gplanes = sets[id(p.leaves)]
+            if any(need_planes) and all(gplanes[d] is None for d in range(4) if need_planes[d]):
+                gplanes[:] = [g if need_planes[d] else None for d, g in enumerate(ops.zero_planes_like(p.planes, need_planes, rays))]
 
-            if (g_rgb is None and g_acc is None and g_disp is None) or (not any(need_planes) and not want_dec and not need_rays):
+        def backward_pass(k, p, g_rgb, g_disp, g_acc):
+            """-> decoder gradient of pass p (state-dict order) or None; plane gradients are added into its leaves' gradient planes"""
+            need_planes, gplanes = sets[id(p.leaves)]
+            if (g_rgb is None and g_acc is None and g_disp is None) or (not any(need_planes) and not p.dec_grad and not need_rays):
                 return None
+            z, raw = sv["z_" + k], sv["raw_" + k]
             g_rgb = torch.zeros((N, 3), dtype=torch.float32, device=dev) if g_rgb is None else capi.f32c(g_rgb)
             g_acc = None if g_acc is None else capi.f32c(g_acc)
             g_depth = None
             if g_disp is not None:
-                q = 1.0 / disp                      # disp = 1 / max(1e-10, q): q itself wherever the gradient is not zero (NaN stays NaN)
-                g_acc, g_depth = ops.fold_disp_grad(g_disp, q, acc, q * acc, g_acc, None)
-            g_raw = nv.composite_backward_rays(raw, z, rays, noise, bool(cfg["white"]), False, g_rgb, g_acc, g_depth)     # (directions read from the packed rays)
-            if gates is not None and (not want_dec or fwd_rec is not None):
-                # gate-driven backward (no recomputation); with the forward's record it adds the gradient half, then ONE contraction
-                rec = fwd_rec if want_dec else None
-                have = [gplanes[d] is not None for d in range(4) if need_planes[d]]
-                if have and not any(have):
-                    # first pass of the step: one zero-filled allocation holds all gradient planes
-                    for d, g in enumerate(ops.zero_planes_like(planes, need_planes, rays)):
-                        if need_planes[d]:
-                            gplanes[d] = g
-                    have = [True] * len(have)
-                # deterministic mode (capi.deterministic, resolved by the forward): the ordered operators -- same arguments, no float atomics
-                bwd_, bwd, wgrad = ((nv.decode_rays_backward_det_, nv.decode_rays_backward_det, lambda *a: nv.decoder_weight_grad_det(*a, None))
-                                    if det or need_rays else (nv.decode_rays_backward_, nv.decode_rays_backward, nv.decoder_weight_grad))
-                if need_rays:
-                    def with_rays(*a, grads=None):
-                        gs, d_points, d_viewdir = ops.decode_rays_backward_with_points(*a, grads=grads)
-                        first = not ray_out                     # the first pass writes d_rays, a later one adds onto it
-                        if first:
-                            ray_out.append(torch.empty((N, 11), dtype=torch.float32, device=dev))
-                        nv.rays_grad(rays, z, d_points, d_viewdir, raw, noise, g_raw, ray_out[0], not first)
-                        return gs
-                    bwd_, bwd = (lambda *a: with_rays(*a[:-1], grads=a[-1])), with_rays
-                if have and all(have) and all(gplanes[d].shape == planes[d].shape and gplanes[d].stride() == planes[d].stride()
-                                              for d in range(4) if need_planes[d]):
-                    # a second pass over the same planes scatters into the first pass's gradient planes (no second zero-fill, no add)
-                    bwd_(planes, cfg["consts"], packed, packed_bwd, rays, z, g_raw, gates, rec, need_planes, arith,
-                         [g if g is not None else rays.new_empty((0,)) for g in gplanes])
-                else:
-                    add_planes(bwd(planes, cfg["consts"], packed, packed_bwd, rays, z, g_raw, gates, rec, need_planes, arith))
-                return wgrad(fwd_rec, N, S, arith) if want_dec else None
-            # no gates published (pass too large for a forward record): recompute the forward in the backward, RECORD_RAYS rays at a time
-            if det:
-                capi.refuse_deterministic("the recomputing backward of a pass without a forward record (decode_rays_backward_recompute)")
-            _record_limits()
-            out = nv.decode_rays_backward_recompute(planes, cfg["consts"], packed, packed_bwd, rays, z, g_raw, need_planes, want_dec, arith)
-            add_planes(out[:4])
-            return out[4] if want_dec else None
+                q = 1.0 / sv["disp_" + k]           # disp = 1 / max(1e-10, q): q itself wherever the gradient is not zero (NaN stays NaN)
+                g_acc, g_depth = ops.fold_disp_grad(g_disp, q, sv["acc_" + k], q * sv["acc_" + k], g_acc, None)
+            g_raw = nv.composite_backward_rays(raw, z, rays, p.noise, white, False, g_rgb, g_acc, g_depth)     # (directions read from the packed rays)
+            if p.dec_grad and not p.records:
+                # no gates published (pass too large for a forward record): recompute the forward in the backward, RECORD_RAYS rays at a time
+                _record_limits()
+                out = nv.decode_rays_backward_recompute(p.planes, consts, p.packed, p.packed_bwd, rays, z, g_raw, need_planes, True, p.arith)
+                for d in range(4):
+                    if need_planes[d]:
+                        gplanes[d] = out[d] if gplanes[d] is None else gplanes[d].add_(out[d])
+                return out[4]
+            # gate-driven backward (no recomputation); with the forward's record it adds the gradient half, then ONE contraction
+            zero_planes(p)
+            rec = sv["rec_" + k]
+            inputs = ops.gate_backward_(nv, route, p.planes, consts, p.packed, p.packed_bwd, rays, z, g_raw, sv["gates_" + k], rec, need_planes, p.arith,
+                                        [g if g is not None else rays.new_empty((0,)) for g in gplanes])
+            if inputs is not None:
+                first = not d_rays                               # the first pass writes d_rays, a later one adds onto it
+                if first:
+                    d_rays.append(torch.empty((N, 11), dtype=torch.float32, device=dev))
+                nv.rays_grad(rays, z, inputs[0], inputs[1], raw, p.noise, g_raw, d_rays[0], not first)
+            if not p.dec_grad:
+                return None
+            return nv.decoder_weight_grad(rec, N, p.S, p.arith) if route == ops.ATOMIC else nv.decoder_weight_grad_det(rec, N, p.S, p.arith, None)
 
-        gdec_c = gdec_f = None
-        coarse = lambda: one_pass(Nc, sv["z_c"], sv["raw_c"], cfg["noise_c"], cfg["planes_c"], cfg["packed_c"], cfg["packed_bwd_c"], grads[0], grads[1],
-                                  grads[2], sv["disp_c"], sv["acc_c"], bool(need[5]), sv["gates_c"], sv["rec_c"], cfg["arith_c"], need_planes_c, gplanes_c)
-        fine = lambda: one_pass(Nc + Nf, sv["z_f"], sv["raw_f"], cfg["noise_f"], cfg["planes_f"], cfg["packed_f"], cfg["packed_bwd_f"], grads[3], grads[4],
-                                grads[5], sv["disp_f"], sv["acc_f"], bool(need[6]), sv["gates_f"], sv["rec_f"], cfg["arith_f"], need_planes_f, gplanes_f)
         # The two passes' backward kernels are independent (both ADD into the gradient planes with float atomics): the coarse pass runs on a
         # second stream, so that its workgroups fill the fine pass's partly empty rounds (same-box A/B of the planes-only iteration: eager
         # 1.683 -> 1.631 ms, replayed from a graph 1.728 -> 1.709 ms; NVSR_BWD_STREAMS=0 keeps one stream).  Planes-only passes: nothing
         # allocated on the second stream outlives the join.  Deterministic mode: ONE stream, coarse then fine -- the fine pass adds onto the
         # coarse pass's sums, and that order is part of the result's bits.
-        need_planes, gplanes = need_planes_f, gplanes_f
-        two = (not det and not need_rays and os.environ.get("NVSR_BWD_STREAMS", "1") == "1" and not sep and cfg["coarse_grad"] and Nf > 0 and dev.type == "cuda" and any(need_planes)
-               and not need[5] and not need[6] and sv["gates_c"] is not None and sv["gates_f"] is not None
-               and all(a.shape == b.shape and a.stride() == b.stride() for a, b in zip(cfg["planes_c"], cfg["planes_f"])))
+        two = (route == ops.ATOMIC and os.environ.get("NVSR_BWD_STREAMS", "1") == "1" and len(sets) == 1 and cfg["coarse_grad"] and len(passes) > 1
+               and dev.type == "cuda" and any(sets[id(top.leaves)][0]) and not need[6] and not need[7]
+               and all(a.shape == b.shape and a.stride() == b.stride() for a, b in zip(passes[0].planes, top.planes)))
+        gdec = [None, None]
         if two:
-            for d, g in enumerate(ops.zero_planes_like(cfg["planes_f"], need_planes, rays)):      # zero-filled before the fork
-                if need_planes[d]:
-                    gplanes[d] = g
+            zero_planes(top)                                     # zero-filled before the fork
             cur, side = torch.cuda.current_stream(dev), _side_stream(dev)
             side.wait_stream(cur)
             with torch.cuda.stream(side):
-                gdec_c = coarse()
-            gdec_f = fine()
+                gdec[0] = backward_pass("c", passes[0], *grads[0:3])
+            gdec[1] = backward_pass("f", top, *grads[3:6])
             cur.wait_stream(side)
         else:
-            if cfg["coarse_grad"]:
-                gdec_c = coarse()
-            if Nf > 0:
-                gdec_f = fine()
-        out = [None]
-        for d, src in enumerate(cfg["plane_leaves"]):
-            g = gplanes[d]
-            if need_planes[d] and g is None:
-                g = torch.zeros(cfg["plane_shapes"][d], dtype=torch.float32, device=dev)
-            out.append(None if g is None else models.from_channel_last(g, like=src))    # back to the reference's [1,C,H,W]
-        if need[5] and gdec_c is None:
-            gdec_c = torch.zeros(capi.DECODER_NATURAL_FLOATS, dtype=torch.float32, device=dev)
-        if need[6] and gdec_f is None and Nf > 0:
-            gdec_f = torch.zeros(capi.DECODER_NATURAL_FLOATS, dtype=torch.float32, device=dev)
-        out_c = []
-        if sep:
-            for d, src in enumerate(cfg["plane_leaves_c"]):
-                g = gplanes_c[d]
-                if need_planes_c[d] and g is None:
-                    g = torch.zeros(cfg["plane_shapes_c"][d], dtype=torch.float32, device=dev)
-                out_c.append(None if g is None else models.from_channel_last(g, like=src))
-        if cfg.get("rays_grad"):
-            d_rays = None
-            if need_rays:
-                d_rays = ray_out[0] if ray_out else torch.zeros((N, 11), dtype=torch.float32, device=dev)
-            out_c.append(d_rays)
-        return tuple(out) + (gdec_c, gdec_f) + tuple(out_c)
+            for i, p in enumerate(passes):
+                if i or cfg["coarse_grad"]:
+                    gdec[i] = backward_pass("cf"[i], p, *grads[3 * i: 3 * i + 3])
+
+        def to_leaves(p):
+            """the gradient planes of p's leaves back in the reference's [1,C,H,W]"""
+            out = []
+            for d, (wanted, g) in enumerate(zip(*sets[id(p.leaves)])):
+                if wanted and g is None:
+                    g = torch.zeros(p.shapes[d], dtype=torch.float32, device=dev)
+                out.append(None if g is None else models.from_channel_last(g, like=p.leaves[d]))
+            return out
+
+        for i in range(len(passes)):
+            if need[6 + i] and gdec[i] is None:
+                gdec[i] = torch.zeros(capi.DECODER_NATURAL_FLOATS, dtype=torch.float32, device=dev)
+        out = [None, None] + to_leaves(top) + gdec + (to_leaves(passes[0]) if len(sets) > 1 else [])
+        if cfg["rays_grad"]:
+            out.append(None if not need_rays else d_rays[0] if d_rays else torch.zeros((N, 11), dtype=torch.float32, device=dev))
+        return tuple(out)
 
 
 _SIDE_STREAMS = {}
@@ -365,8 +354,6 @@ def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, sc
     # (an evaluation render whose operands leave the f16 limbs' range is found by the library's range flag and rendered again with
     #  force_arith = bf16x3: run_one_iter_of_nerf; a training step raises: training.TrainStep)
     # ('f16', one f16 limb: evaluation renders only -- the fused passes of the two-decoder frame; no occupancy grid, no shared decoder)
-    if mode == "train":
-        capi.refuse_f16_training(model_coarse, model_fine)
     arith_c = capi.resolve_render_arithmetic(model_coarse.arithmetic if force_arith is None else force_arith)
     arith_f = capi.resolve_render_arithmetic(model_fine.arithmetic if force_arith is None else force_arith) if Nf > 0 else arith_c
     rays_grad = False
@@ -376,24 +363,16 @@ def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, sc
         elif capi.ARITHMETIC["f32"] in (arith_c, arith_f):
             _warn_no_rays_grad(top, "the 'f32' arithmetic")
         elif N > 0:
-            rays_grad = True
-            _, fwd_max = _record_limits()
-            if (dec_c_grad and N * Nc > fwd_max) or (dec_f_grad and N * (Nc + Nf) > fwd_max):
-                # (such a pass publishes no gates: its backward recomputes the forward and leaves no rows behind)
-                raise NotImplementedError("rays that require a gradient need the recorded forward: a pass of %d rays x %d samples with decoder gradients "
-                                          "exceeds RECORD_FORWARD_MAX_POINTS = %d; at most %d rays per call fit"
-                                          % (N, Nc + Nf if dec_f_grad else Nc, fwd_max, fwd_max // (Nc + Nf if dec_f_grad else Nc)))
-            train_path = True
+            rays_grad = train_path = True
     det = train_path and capi.deterministic()
-    if det:
-        # what the deterministic mode does not cover is refused here, before anything is launched
-        for a_ in {arith_c, arith_f}:
-            if a_ == capi.ARITHMETIC["f32"]:
-                capi.refuse_deterministic("a training step in the 'f32' arithmetic")
+    if mode == "train":
+        # the host facts of the passes, and what a training render does not cover -- before anything is launched
+        coarse_grad = not isinstance(model_coarse.optional_no_grad(), torch.no_grad) if hasattr(model_coarse, "optional_no_grad") else True
         _, fwd_max = _record_limits()
-        if (dec_c_grad and N * Nc > fwd_max) or (dec_f_grad and N * (Nc + Nf) > fwd_max):
-            capi.refuse_deterministic("a pass of more than RECORD_FORWARD_MAX_POINTS points with decoder gradients (its backward recomputes the "
-                                      "forward: decode_rays_backward_recompute)")
+        passes = [_pass_facts(N, Nc, arith_c, n_c, dec_c_grad and coarse_grad, fwd_max)]
+        if Nf > 0:
+            passes.append(_pass_facts(N, Nc + Nf, arith_f, n_f, dec_f_grad, fwd_max))
+        _refuse_untrainable((model_coarse, model_fine), N, passes, rays_grad, det, fwd_max)
     packed_c = model_coarse.packed_decoder()
     packed_f = model_fine.packed_decoder() if Nf > 0 else None
     if not (train_path and sr_on):       # (the SR training path builds its scene from the ROI planes below)
@@ -423,23 +402,22 @@ def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, sc
         else:
             names = [models.get_plane_name(scene_id, d) for d in range(4)]
             leaves = [top.raw_plane(n) for n in names]          # (a low-rank plane: generated once, shared by both passes; models.gen_plane)
+        plane_leaves = leaves[:4]
         leaves += [model_coarse.natural_blob(differentiable=True) if dec_c_grad else None,
                    model_fine.natural_blob(differentiable=True) if dec_f_grad else None]
         leaves += leaves_c
-        coarse_grad = not isinstance(model_coarse.optional_no_grad(), torch.no_grad) if hasattr(model_coarse, "optional_no_grad") else True
         # 'f16x2': the library runs the forward of a pass whose decoder is not trained (no weight-gradient record) and every gate-driven
         # backward on 2 f16 limbs, the recording forward and the weight-gradient contraction on 3 bf16 limbs (include/nvsr.h); the gates a
         # forward publishes are signs, valid for either backward
-        cfg = dict(N=N, Nc=Nc, Nf=Nf, rays=rays, lindisp=lindisp, white=white, t_rand=t_rand, u=u, noise_c=n_c, noise_f=n_f,
-                   planes_c=planes_c, planes_f=planes_f, consts=consts, packed_c=packed_c, packed_f=packed_f,
-                   packed_bwd_c=model_coarse.packed_decoder_bwd(), packed_bwd_f=model_fine.packed_decoder_bwd() if Nf > 0 else None,
-                   plane_shapes=[tuple(k.shape) for k in planes_f], plane_leaves=leaves[:4], separate_coarse=bool(leaves_c),
-                   plane_shapes_c=[tuple(k.shape) for k in planes_c], plane_leaves_c=leaves_c, coarse_grad=coarse_grad, dec_c_grad=dec_c_grad,
-                   dec_f_grad=dec_f_grad, arith_c=arith_c, arith_f=arith_f, det=det)
+        passes[0] = passes[0]._replace(planes=planes_c, packed=packed_c, packed_bwd=model_coarse.packed_decoder_bwd(),
+                                       leaves=leaves_c or plane_leaves, shapes=[tuple(k.shape) for k in planes_c])
+        if Nf > 0:
+            passes[1] = passes[1]._replace(planes=planes_f, packed=packed_f, packed_bwd=model_fine.packed_decoder_bwd(),
+                                           leaves=plane_leaves, shapes=[tuple(k.shape) for k in planes_f])
+        cfg = dict(N=N, rays=rays, consts=consts, lindisp=lindisp, white=white, t_rand=t_rand, u=u, det=det, rays_grad=rays_grad, coarse_grad=coarse_grad)
         if rays_grad:
-            cfg["rays_grad"] = True
             leaves = leaves + [rays_leaf]
-        outs = _RenderRaysFn.apply(cfg, *leaves)
+        outs = _RenderRaysFn.apply(cfg, passes, *leaves)
         if Nf > 0:
             return outs[0], outs[1], outs[2], outs[3], outs[4], outs[5], None, None, None
         return outs[0], outs[1], outs[2], None, None, None, None, None, None

@@ -226,7 +226,7 @@ def torch_ndc_rays(H, W, focal, near, ro, rd):
     return ro_out, rd_out
 
 
-# ---- scenarios shared by the GPU tests and the recording of tests/ray_grad_entry_table.json -----------------------------------------------------
+# ---- scenarios shared by the GPU tests and the recordings tests/ray_grad_entry_table.json, tests/training_entry_table.json ------------------------
 def g27_case(ci):
     """case ci of g27_ray_grad.npz -> (g, decoders as coarse.* / fine.* arrays: g11's with this case's entries written over them, planes)"""
     from conftest import load_golden
@@ -239,29 +239,88 @@ def g27_case(ci):
     return g, dec, [g["plane%d" % d] for d in range(4)]
 
 
-def train_step_entries(hip, deterministic, iterations=2, device="cuda:0"):
-    """`iterations` TrainStep iterations (planes + decoder, 256 rays, 8 + 8 samples, 32^2 planes, a pose that requires no gradient) with every
-    capi.call recorded -> (entry names in call order, sha256 of the planes and decoder parameters afterwards)"""
+def _entry_record(fn, name, args, streams):
+    """one capi.call as [name, arguments, stream]: every scalar argument by value, "ptr" / "null" per pointer argument (an array of pointers: one
+    per element), the stream -- the last argument of every launching entry -- as an ordinal by first appearance in `streams`"""
+    import ctypes as C
+    types = fn.argtypes or ()
+    rec, stream = [], None
+    for i, a in enumerate(args):
+        t = types[i] if i < len(types) else None
+        pointer = t is C.c_void_p or (isinstance(t, type) and issubclass(t, C._Pointer))
+        if pointer and i == len(args) - 1 and t is C.c_void_p:
+            stream = streams.setdefault(a.value if isinstance(a, C.c_void_p) else a, len(streams))
+        elif isinstance(a, C.Array):
+            rec.append(["ptr" if v else "null" for v in a])
+        elif pointer:
+            rec.append("null" if a is None or (isinstance(a, C.c_void_p) and not a.value) else "ptr")
+        else:
+            a = getattr(a, "value", a)                          # (a ctypes scalar)
+            rec.append(a if isinstance(a, (bool, int, float)) else float(a) if t in (C.c_float, C.c_double) else int(a))
+    return [name, rec, stream]
+
+
+def train_step_entries(hip, deterministic, iterations=2, device="cuda:0", what=("LR_planes", "decoder"), pose_grad=False, arithmetic=None,
+                       fwd_max=None, sr=False, detail=False):
+    """`iterations` TrainStep iterations (256 rays, 8 + 8 samples, 32^2 planes, seeded randoms) with every capi.call recorded
+    -> (entry names in call order, sha256 of the planes and decoder parameters afterwards).
+    what: TrainStep's what2train -- the planes / the decoders train as it names them;  pose_grad: the pose requires a gradient;  arithmetic: of
+    both models (None: the library's default);  fwd_max: train_utils.RECORD_FORWARD_MAX_POINTS during the iterations;  sr: only the fine model
+    super-resolves (EDSR 16 x 2 on 20^2 planes, the coarse pass under no_grad, what = {'SR'}, loss on the fine output: the construction of
+    tests/test_hip_round4.py::test_default_sr_refinement_steps; the digest then covers the SR network's parameters too).
+    detail: the entries as _entry_record states them instead of names, and a third result: the number of torch.zeros / zeros_like calls made
+    from train_utils and ops while a backward() ran."""
     import hashlib
+    import sys
     import torch
     from bench import make_synthetic_scene, render_options
-    calls, real = [], hip.capi.call
+    calls, streams, real = [], {}, hip.capi.call
+    zeros = {"n": 0, "backward": False}
 
     def spy(name, *a):
-        calls.append(name)
+        calls.append(_entry_record(getattr(hip.capi.lib(), name), name, a, streams) if detail else name)
         return real(name, *a)
 
-    mc, mf, sid, pose = make_synthetic_scene(device, plane_res=32, view_res=16, seed=27)
+    def counting(fn):
+        def wrapped(*a, **kw):
+            if zeros["backward"] and sys._getframe(1).f_globals.get("__name__", "").rsplit(".", 1)[-1] in ("train_utils", "ops"):
+                zeros["n"] += 1
+            return fn(*a, **kw)
+        return wrapped
+
+    real_backward, real_zeros, real_zeros_like = torch.Tensor.backward, torch.zeros, torch.zeros_like
+
+    def backward(self, *a, **kw):
+        zeros["backward"] = True
+        try:
+            return real_backward(self, *a, **kw)
+        finally:
+            zeros["backward"] = False
+
+    what = set(what)
+    mc, mf, sid, pose = make_synthetic_scene(device, plane_res=20 if sr else 32, view_res=8 if sr else 16, seed=27)
     for m in (mc, mf):
         for n, p in m.named_parameters():
-            p.requires_grad_("rot_mats" not in n)
+            p.requires_grad_("rot_mats" not in n and (("LR_planes" in what) if "planes_" in n else ("decoder" in what)))
         m.train()
+        if arithmetic is not None:
+            m.arithmetic = arithmetic
     opts, scfg = render_options(8, 8, perturb=True, noise=0.2)
     planes = list(mc.planes_.values())
     dec = list({id(p): p for m in (mc, mf) for p in m.decoder_parameters()}.values())
-    step = hip.training.TrainStep(mc, mf, opts, {"LR_planes", "decoder"}, optimizer=torch.optim.Adam(dec, lr=5e-3),
-                                  planes_optimizer=torch.optim.Adam(planes, lr=5e-2), pixel_sampler=hip.training.DevicePixelSampler(seed=5),
-                                  deterministic=deterministic)
+    extra, kw = [], {}
+    if sr:
+        torch.manual_seed(8)
+        net = hip.models.PlanesSR(hip.models.EDSR, 4, 48, 48, {"model": {"hidden_size": 16, "n_blocks": 2}}, "bilinear").to(device)
+        net.train()
+        mf.assign_SR_model(net, SR_viewdir=False)
+        mf.assign_LR_planes()
+        mc.optional_no_grad = torch.no_grad
+        extra = list(net.parameters())
+        kw = dict(SR_optimizer=torch.optim.Adam(extra, lr=2e-3), SR_model=net, sr_loss="fine")
+    step = hip.training.TrainStep(mc, mf, opts, what, optimizer=torch.optim.Adam(dec, lr=5e-3) if "decoder" in what else None,
+                                  planes_optimizer=torch.optim.Adam(planes, lr=5e-2) if "LR_planes" in what else None,
+                                  pixel_sampler=hip.training.DevicePixelSampler(seed=5), deterministic=deterministic, **kw)
     H = W = 24
     focal = 0.5 * W / np.tan(0.5 * 0.6911112)
     gen = torch.Generator(device=device).manual_seed(3)
@@ -269,17 +328,57 @@ def train_step_entries(hip, deterministic, iterations=2, device="cuda:0"):
     N, Nc, Nf = 256, 8, 8
     rnd = dict(t_rand=torch.rand(N, Nc, device=device, generator=gen), u=torch.rand(N, Nf, device=device, generator=gen),
                noise_coarse=0.2 * torch.randn(N, Nc, device=device, generator=gen), noise_fine=0.2 * torch.randn(N, Nc + Nf, device=device, generator=gen))
+    if pose_grad:
+        pose = pose.clone().requires_grad_(True)
     # (what a process does once, whichever call comes first, is done before the spy goes in: the registration of the library's range flag,
     #  nvsr_set_range_flag -- the sequence must not depend on what ran earlier in the process)
     hip.capi.range_flag(torch.device(device))
+    limit = hip.train_utils.RECORD_FORWARD_MAX_POINTS
     hip.capi.call = spy
+    torch.Tensor.backward, torch.zeros, torch.zeros_like = backward, counting(real_zeros), counting(real_zeros_like)
     try:
+        if fwd_max is not None:
+            hip.train_utils.RECORD_FORWARD_MAX_POINTS = fwd_max
         for it in range(iterations):
-            step(it, img, pose, H, W, focal, 1, sid, scfg, N, randoms=rnd)
+            step(it, img, pose, H, W, focal, 1, sid, scfg, N, randoms=rnd, sr_iter=sr)
         torch.cuda.synchronize()
     finally:
         hip.capi.call = real
+        torch.Tensor.backward, torch.zeros, torch.zeros_like = real_backward, real_zeros, real_zeros_like
+        hip.train_utils.RECORD_FORWARD_MAX_POINTS = limit
     h = hashlib.sha256()
-    for p in planes + dec:
+    for p in planes + dec + extra:
         h.update(p.detach().cpu().numpy().tobytes())
-    return calls, h.hexdigest()
+    return (calls, h.hexdigest(), zeros["n"]) if detail else (calls, h.hexdigest())
+
+
+# the cases of tests/training_entry_table.json (tools/training_entry_table.py records them, tests/test_ray_grad.py replays them): name ->
+# (environment, deterministic, the arguments of train_step_entries, is the digest reproducible)
+TRAINING_CASES = {
+    "a_planes_two_streams": ({}, False, dict(what=("LR_planes",)), False),
+    "b_planes_one_stream": ({"NVSR_BWD_STREAMS": "0"}, False, dict(what=("LR_planes",)), False),
+    "c_planes_decoder_atomic": ({}, False, dict(), False),
+    "d_planes_decoder_deterministic": ({}, True, dict(), True),
+    "e_decoder_only": ({}, False, dict(what=("decoder",)), False),
+    # 256 x 8 = 2048 < 3000 < 4096 = 256 x 16: the coarse pass records, the fine pass recomputes
+    "f_fine_pass_recomputes": ({}, False, dict(fwd_max=3000), False),
+    "g_pose_gradient_f16x2": ({}, False, dict(pose_grad=True, arithmetic="f16x2"), False),
+    "g_pose_gradient_f16x2_deterministic": ({}, True, dict(pose_grad=True, arithmetic="f16x2"), True),
+    "h_sr_fine_only": ({}, False, dict(what=("SR",), sr=True), False),
+}
+
+
+def training_case(hip, name):
+    """run case `name` of TRAINING_CASES under its environment -> {"entries", "sha256" (None where float atomics order the sums), "zeros"}"""
+    import os
+    env, det, kw, reproducible = TRAINING_CASES[name]
+    handles = ("NVSR_BWD_STREAMS", "NVSR_OPS_DISPATCH", "NVSR_DETERMINISTIC")
+    saved = {h: os.environ.get(h) for h in handles}
+    try:
+        for h in handles:
+            os.environ.pop(h, None) if h not in env else os.environ.__setitem__(h, env[h])
+        calls, digest, zeros = train_step_entries(hip, det, detail=True, **kw)
+    finally:
+        for h, v in saved.items():
+            os.environ.pop(h, None) if v is None else os.environ.__setitem__(h, v)
+    return {"entries": calls, "sha256": digest if reproducible else None, "zeros": zeros}

@@ -158,6 +158,51 @@ def test_host_side_refusals_name_the_mode(pkg, monkeypatch):
         T.GraphedTrainStep(step, torch.zeros(4, 4, 3), torch.eye(4), 4, 4, 1.0, 1, "s", None, 8)
 
 
+def test_the_host_decisions_of_a_training_pass_over_the_product_of_their_inputs():
+    """train_utils._pass_facts + _refuse_untrainable + ops.gate_route -- the one place that decides, per pass of a training render, what the
+    forward publishes, which backward follows and what is refused -- over (N, S, decoder gradient, rays need a gradient, deterministic,
+    arithmetic, RECORD_FORWARD_MAX_POINTS) with N S = limit - 1, limit, limit + 1, against the rules as the route had them scattered before:
+      forward (`flags`):   record = decoder gradient and N S <= limit;  gates = record or no decoder gradient
+      backward:            gate-driven where gates were published -- ordered with points when the rays need a gradient, else ordered in
+                           deterministic mode, else atomic -- and recomputing where not
+      refusals, in order:  rays that need a gradient with a recomputing pass (NotImplementedError); deterministic mode in 'f32';
+                           deterministic mode with a recomputing pass.
+    (Rays never need a gradient in 'f32': predict_and_render_radiance warns and drops the request before it decides anything.)
+    No GPU, no library call."""
+    import itertools
+    import nvsr_amd
+    tu, ops, capi = nvsr_amd.train_utils, nvsr_amd.ops, nvsr_amd.capi
+    f32 = capi.ARITHMETIC["f32"]
+    seen = set()
+    for (N, S), off, dec, rays, det, arith in itertools.product([(1, 5), (3, 4), (7, 1)], (1, 0, -1), (False, True), (False, True), (False, True),
+                                                                [capi.ARITHMETIC[a] for a in ("f32", "bf16x3", "f16x2")]):
+        if rays and arith == f32:
+            continue
+        limit = N * S + off
+        too_large = dec and N * S > limit
+        if rays and too_large:
+            want = (NotImplementedError, "at most %d rays" % (limit // S))
+        elif det and arith == f32:
+            want = (capi.DeterministicModeError, "a training step in the 'f32' arithmetic")
+        elif det and too_large:
+            want = (capi.DeterministicModeError, "a pass of more than RECORD_FORWARD_MAX_POINTS points with decoder gradients")
+        else:
+            record = dec and N * S <= limit
+            gates = record or not dec
+            want = (gates, record, "recompute" if not gates else "ordered with points" if rays else "ordered" if det else "atomic")
+        p = tu._pass_facts(N, S, arith, None, dec, limit)
+        try:
+            tu._refuse_untrainable((), N, [p], rays, det, limit)
+            gates = p.records or not p.dec_grad            # (as _RenderRaysFn.forward asks decode_rays for them)
+            got = (gates, p.records, ops.gate_route(det, rays) if gates else "recompute")
+        except (NotImplementedError, RuntimeError) as e:
+            got = (type(e), want[1] if isinstance(want[1], str) and want[1] in str(e) else str(e))
+        assert got == want, ((N, S, limit, dec, rays, det, arith), got, want)
+        seen.add(want if isinstance(want[0], bool) else want[0])
+    routes = ("atomic", "ordered", "ordered with points")          # every outcome occurred: both refusal types, recompute, each route with / without a record
+    assert seen == {NotImplementedError, capi.DeterministicModeError, (False, False, "recompute")} | {(True, r, k) for r in (False, True) for k in routes}
+
+
 @pytest.mark.parametrize("kind,M,H,W", [("random", 257, 5, 7), ("random", 4099, 16, 16), ("one_texel", 513, 5, 7), ("zero_weights", 257, 16, 16)])
 def test_float32_reference_against_a_float64_sum(kind, M, H, W):
     """the reference the GPU test demands bit equality with is itself right: every element within n * 2^-24 * sum |terms| of the float64

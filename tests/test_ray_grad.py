@@ -355,6 +355,31 @@ def test_a_step_whose_pose_needs_no_gradient_keeps_the_parents_entries_and_bits(
             assert digest == table[key]["sha256"]
 
 
+def test_every_training_route_keeps_its_recorded_entries(hip):
+    """two TrainStep iterations on every host route of a training render (ray_grad_ref.TRAINING_CASES: planes only on two streams and on one,
+    planes + decoder atomic and deterministic, decoder only, a fine pass that recomputes, a pose that requires a gradient in 'f16x2' in both
+    modes, SR training where only the fine model super-resolves) make the calls tests/training_entry_table.json records (recorded by
+    tools/training_entry_table.py at the parent of the change that last touched the route): per entry its name, every scalar argument, which
+    pointer arguments are null, and the stream.  Where the route is reproducible the parameters afterwards have the recorded bits; a
+    decoder-only step makes no more torch.zeros / zeros_like calls from train_utils and ops in its backward than recorded."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "training_entry_table.json")) as f:
+        table = json.load(f)
+    assert sorted(table) == sorted(R.TRAINING_CASES)
+    for name, want in table.items():
+        got = R.training_case(hip, name)
+        got["entries"] = json.loads(json.dumps(got["entries"]))
+        for i, (a, b) in enumerate(zip(got["entries"], want["entries"])):
+            assert a == b, (name, i, a, b)
+        assert len(got["entries"]) == len(want["entries"]), (name, got["entries"][len(want["entries"]):], want["entries"][len(got["entries"]):])
+        assert got["sha256"] == want["sha256"], name
+        assert (want["sha256"] is not None) == ("deterministic" in name)
+        print("%s: %d entries, %d zero fills in the backward (recorded %d)" % (name, len(got["entries"]), got["zeros"], want["zeros"]))
+        if name == "e_decoder_only":
+            assert got["zeros"] <= want["zeros"], (got["zeros"], want["zeros"])
+
+
 def test_five_adam_steps_refine_a_perturbed_pose(hip, monkeypatch):
     """TrainStep with a pose_target that requires a gradient, planes and decoder frozen: g27's camera rotated by 0.02 rad, the target rendered
     from the true one; five Adam steps on the pose: the rendering loss falls and the pose moves towards the true one"""
